@@ -7,15 +7,18 @@ resident in HBM when the timed region starts (rtk_batch_create is outside, rtk_b
 
 Workload at every N: the HG002-chr20-scale set BASELINE.json's target is written on (configs[2]'s graph: 60 Mb diploid random
 reference, 0.1 % heterozygous SNPs, 30x PE 150 bp short reads at 0.5 % substitutions, ONT-R9.4-profile long reads, k = 31 first
-pass; it fits one GPU). The index is built by the repo's own index producer (k-mers counted on the device), correction runs on
-the GPU. At N = 1 the same run also measures configs[1] (5 Mb haploid reference) as the extra leg `config1`.
+pass; it fits one GPU). The index is built by the repo's own index producer (short reads sampled inside it, k-mers counted on the
+device), correction runs on the GPU.
 
 N > 1 (torch.distributed.run, one rank per GPU, RCCL): rank 0 loads the flat graph and broadcasts its buffers once; long
-reads are sharded by batch ticket (rank r takes batches r, r+N, ...), no collective on the data path -> weak scaling. Before
-the sharded run rank 0 measures the one-GPU rate on this very graph in the same process (`config.n1_on_this_graph`).
+reads are sharded by batch ticket (rank r takes batches r, r+N, ...), no collective on the data path -> weak scaling.
 
-Prints ONE JSON line on rank 0 (see the driver contract), with `roofline` for the dominant kernel (algorithmic bytes /
-HIP-event duration measured here) and `cpu_baseline` (the oracle, multithreaded, on a bounded sample; N = 1 only).
+A plain run sets up, warms up, times --steps steps and prints ONE JSON line on rank 0 (see the driver contract), with `roofline`
+for the dominant kernel (algorithmic bytes / HIP-event duration of this run's steps). --dump-outputs DIR writes what the last timed
+step computed. --full adds everything else: configs[1] (5 Mb haploid reference) as the leg `config1` and configs[4] (3 Gb graph)
+as `config4`, the host-inclusive, ticket-size, lane-kernel, CLI and second-pass legs, `cpu_baseline` (the oracle, multithreaded,
+on a bounded sample, with a parity check) at N = 1, the one-GPU rate on this very graph before the sharded run at N > 1
+(`config.n1_on_this_graph`), and the serial per-kernel re-run of --overlap.
 """
 import argparse
 import ctypes as C
@@ -60,6 +63,9 @@ def parse():
     ap.add_argument("--config4-ref-mb", type=int, default=3000, help="reference length of the configs[4] leg in Mb (its stated size: 3000)")
     ap.add_argument("--config4-tickets", type=int, default=16, help="tickets of 64 Mb of distinct long reads of the configs[4] leg")
     ap.add_argument("--sim", action="store_true", help="CPU-only developer simulator + gloo (tests of the N>1 plumbing); never a benchmark")
+    ap.add_argument("--full", action="store_true", help="besides the headline: configs[1], configs[4], the host-inclusive / ticket-size / lane-kernel / CLI / second-pass legs, the CPU baseline "
+                                                        "with its parity check, the one-GPU point of the graph at N > 1 and the serial per-kernel re-run of --overlap (a plain run times the steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step computed (the corrected reads of its batch) as DIR/<name>.npy")
     a = ap.parse_args()
     a.serial = not a.overlap
     if a.config1_only:
@@ -71,24 +77,33 @@ def parse():
     return a
 
 
+SR_SPEC = "sample:%s.ref.fa?cov=30&len=150&insert=500&err=0.005&seed=2"  # the workload's short reads (30x PE150, 0.5 % substitutions), sampled inside the index tool
+
+
+def short_reads(pre):
+    """The short reads of a set made by make_dataset: a sample source of the index tool (common/sample_source.hpp), never a file on disk."""
+    return SR_SPEC % pre
+
+
 def make_dataset(workdir, ref_len, lr_bases, snps=True, het=0.0, fast="--gpu", name="c2"):
-    """Seeded synthetic inputs + index in the reference's file formats."""
+    """Seeded synthetic inputs + index in the reference's file formats. The 30x short reads are sampled on the fly inside the index
+    tool (like bench_config4.py): 1.8 Gb of FASTQ for a 60 Mb reference would take longer to write and read back than the whole index build."""
     bin_dir = os.path.join(ROOT, "ratatosk_amd", "bin")
     pre = os.path.join(workdir, name)
     lr_cov = max(1.0, float(lr_bases) / ref_len)
     # a --workdir that already holds this very set (same generator arguments) is reused: the profiling scripts run this file a dozen times
-    stamp, stamp_fn = json.dumps({"ref_len": ref_len, "lr_cov": "%.3f" % lr_cov, "snps": bool(snps), "het": "%g" % het, "name": name}, sort_keys=True), pre + ".stamp.json"
+    stamp, stamp_fn = json.dumps({"ref_len": ref_len, "lr_cov": "%.3f" % lr_cov, "snps": bool(snps), "het": "%g" % het, "name": name, "short_reads": SR_SPEC}, sort_keys=True), pre + ".stamp.json"
     try:
-        if open(stamp_fn).read() == stamp and all(os.path.exists(pre + e) for e in (".index.k31.fasta.gz", ".index.k31.rtsk", ".lr.fq", ".sr.fq")):
+        if open(stamp_fn).read() == stamp and all(os.path.exists(pre + e) for e in (".index.k31.fasta.gz", ".index.k31.rtsk", ".lr.fq", ".ref.fa")):
             return pre
     except OSError:
         pass
-    subprocess.check_call([os.path.join(bin_dir, "rtk_simulate"), "--prefix", pre, "--seed", "2", "--ref-len", str(ref_len), "--sr-cov", "30",
-                           "--sr-err", "0.005", "--lr-cov", "%.3f" % lr_cov, "--lr-len", "8000", "--lr-profile", "ont", "--lr-err", "0.07"] + (["--het", "%g" % het] if het > 0 else []), stderr=subprocess.DEVNULL)
+    subprocess.check_call([os.path.join(bin_dir, "rtk_simulate"), "--prefix", pre, "--seed", "2", "--ref-len", str(ref_len), "--sr-cov", "0",
+                           "--lr-cov", "%.3f" % lr_cov, "--lr-len", "8000", "--lr-profile", "ont", "--lr-err", "0.07"] + (["--het", "%g" % het] if het > 0 else []), stderr=subprocess.DEVNULL)
     # --snps: SNP annotations like the reference's default `index` step (detectSNPs runs unless -F, src/Ratatosk.cpp:1120-1127)
     # (--gpu: the k-mers of the short reads are counted on the device and the other heavy steps run on the host threads; the files are the plain
     # tool's byte for byte, tests/test_index_build.py. `fast` = "" under the CPU-only simulator, which has no device to count on.)
-    cmd = [os.path.join(bin_dir, "rtk_build_index"), "-s", pre + ".sr.fq", "-o", pre] + (["--snps"] if snps else [])
+    cmd = [os.path.join(bin_dir, "rtk_build_index"), "-s", short_reads(pre), "-o", pre] + (["--snps"] if snps else [])
     r = subprocess.run(cmd + ([fast] if fast else []), stderr=subprocess.PIPE, text=True)
     if r.returncode != 0 and fast:
         sys.stderr.write("rtk_build_index %s failed (%s); building with the plain tool\n" % (fast, r.stderr.strip()[-200:]))
@@ -100,6 +115,12 @@ def make_dataset(workdir, ref_len, lr_bases, snps=True, het=0.0, fast="--gpu", n
             sys.stderr.write(line + "\n")
     open(stamp_fn, "w").write(stamp)
     return pre
+
+
+def lr_bases_of(a, world, ref_len, steps, warmup):
+    """Long-read bases a workload reads in: distinct tickets, two per rank are enough to overlap consecutive steps; at N = 1 up to four (30x of a 60 Mb
+    reference would give 28)."""
+    return int(2.3 * a.batch_bases * world) + 200_000 if world > 1 else min(a.batch_bases * (steps + warmup), 30 * ref_len, int(4.3 * a.batch_bases) + 200_000)
 
 
 def read_long_reads(path, max_bases):
@@ -316,14 +337,18 @@ def lane_kernel_leg(a, api, graph, opts, mine):
         return {"error": str(e)[-300:]}
 
 
+FULL_BUDGET_S, FULL_C4_START_S = 570, 150
+
+
 def config4_leg(a, workdir, t_start):
     """configs[4] (BASELINE.json: whole-genome-scale graph resident in HBM, long reads, roofline report) as its own process once this one has released the device:
     bench_config4.py builds the 3 Gb index (short reads sampled inside the index tool), keeps the graph resident and corrects tickets of DISTINCT reads.
     Guarded: host memory / disk / HBM inside that script, time here -- every refusal is a {"skipped": reason}."""
-    # time budget: the leg starts ~4 min into a run and takes ~6.5 min (index build 5.6); it is not started later than 7.5 min in and is cut at 16 min (index build at 10),
-    # so that the whole run stays under 25 min whatever the box does
-    if time.time() - t_start > 450:
-        return {"skipped": "time: this bench run had already used %d s when the leg was due (limit 450 s; run `python bench_config4.py out.json` on its own)" % (time.time() - t_start)}
+    # time budget: the leg takes ~6.5 min (index build 5.6) and a --full run has to end within 10 min whatever the box does: it is not started later than
+    # FULL_C4_START_S into the run and is cut (with its whole process group) FULL_BUDGET_S into the run
+    if time.time() - t_start > FULL_C4_START_S:
+        return {"skipped": "time: this bench run had already used %d s when the leg was due (limit %d s; run `python bench_config4.py out.json` on its own)" % (time.time() - t_start, FULL_C4_START_S)}
+    budget = max(1.0, FULL_BUDGET_S - (time.time() - t_start))
     out_fn = os.path.join(workdir, "config4.json")
     try:
         os.remove(out_fn)
@@ -332,14 +357,14 @@ def config4_leg(a, workdir, t_start):
     cmd = [sys.executable, os.path.join(ROOT, "bench_config4.py"), out_fn, str(a.config4_ref_mb), "30", str(a.config4_tickets), "128", os.path.join(workdir, "c4")]
     try:
         import signal
-        pr = subprocess.Popen(cmd, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True, start_new_session=True, env=dict(os.environ, RTK_C4_INDEX_TIMEOUT=os.environ.get("RTK_C4_INDEX_TIMEOUT", "600")))
+        pr = subprocess.Popen(cmd, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True, start_new_session=True, env=dict(os.environ, RTK_C4_INDEX_TIMEOUT=os.environ.get("RTK_C4_INDEX_TIMEOUT", "%d" % max(60, budget - 60))))
         try:
-            _, err = pr.communicate(timeout=960)
+            _, err = pr.communicate(timeout=budget)
         except subprocess.TimeoutExpired:
             os.killpg(pr.pid, signal.SIGKILL)  # (the whole group: the index tool it started must not outlive it)
             pr.communicate()
             d = json.load(open(out_fn)) if os.path.exists(out_fn) else {}
-            d["skipped"] = "time: the leg was cut after 960 s"
+            d["skipped"] = "time: the leg was cut after %d s (the run's %d s budget)" % (budget, FULL_BUDGET_S)
             return d
         d = json.load(open(out_fn))
         if pr.returncode != 0 and "skipped" not in d:
@@ -401,7 +426,7 @@ def second_pass_leg(a, pre):
         if r1.returncode != 0:
             return {"error": (r1.stderr or r1.stdout)[-300:]}
         t0 = time.time()
-        subprocess.run([os.path.join(ROOT, "ratatosk_amd", "bin", "rtk_build_index"), "-s", pre + ".sr.fq", "--colour-reads", out + ".2.fastq", "-k", "63", "-o", out + ".p2"], stderr=subprocess.DEVNULL, check=True, timeout=600)
+        subprocess.run([os.path.join(ROOT, "ratatosk_amd", "bin", "rtk_build_index"), "-s", short_reads(pre), "--colour-reads", out + ".2.fastq", "-k", "63", "-o", out + ".p2"], stderr=subprocess.DEVNULL, check=True, timeout=600)
         t_idx = time.time() - t0
         # like the first-pass CLI leg: list files (the corrected reads and, in step, the uncorrected ones, 18 times each: 2.7 Gb, ~80 tickets for 8 in flight) so that the ticket
         # pipeline runs in steady state; the figure of ONE copy of the files (4 tickets: mostly pipeline fill and drain) is kept next to it
@@ -509,7 +534,30 @@ def pmc_issue(kernel, avg_ms):
         return None, None
 
 
-def run_workload(a, ctx, ref_len, het, name, steps, warmup, n1_first=False):
+def dump_outputs(d, reads, sample_bases=4 << 20):
+    """What the last timed step handed its caller: the corrected reads of its batch (sequence + qualities, in input order), as float64 / float32 arrays.
+    Every read: its length and CRC-32 of sequence and of qualities; a fixed, seeded sample of reads (~4 Mi bases) in full: ASCII codes of the bases,
+    Phred values of the qualities, concatenated in the order of sample_read_index."""
+    import zlib
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    arrs = {"corrected_length": np.array([len(s_) for s_, _ in reads], dtype=np.float64),
+            "corrected_seq_crc32": np.array([zlib.crc32(s_.encode()) for s_, _ in reads], dtype=np.float64),
+            "corrected_qual_crc32": np.array([zlib.crc32(q_.encode()) for _, q_ in reads], dtype=np.float64)}
+    pick, tot = [], 0
+    for i in np.random.RandomState(20240611).permutation(len(reads)):
+        if tot >= sample_bases:
+            break
+        pick.append(int(i)); tot += len(reads[i][0])
+    pick.sort()
+    arrs["sample_read_index"] = np.array(pick, dtype=np.float64)
+    arrs["sample_seq_ascii"] = np.frombuffer("".join(reads[i][0] for i in pick).encode(), dtype=np.uint8).astype(np.float32)
+    arrs["sample_qual_phred"] = np.frombuffer("".join(reads[i][1] for i in pick).encode(), dtype=np.uint8).astype(np.float32) - 33.0
+    for k_, v in arrs.items():
+        np.save(os.path.join(d, k_ + ".npy"), v)
+
+
+def run_workload(a, ctx, ref_len, het, name, steps, warmup, n1_first=False, dump_dir=None):
     """One workload through the timed loop: dataset + index (rank 0), graph replicated, batches resident in HBM, W warm-up steps, K timed
     steps bracketed by synchronize + barrier. Returns everything the JSON line is made of."""
     import torch
@@ -517,13 +565,15 @@ def run_workload(a, ctx, ref_len, het, name, steps, warmup, n1_first=False):
     from ratatosk_amd import api, dist as rdist
     rank, world, device, lib_path = ctx["rank"], ctx["world"], ctx["device"], ctx["lib_path"]
     n_batches = steps + warmup
-    # distinct tickets: two per rank are enough to overlap consecutive steps; at N = 1 up to four (30x of a 60 Mb reference would give 28)
-    lr_bases = int(2.3 * a.batch_bases * world) + 200_000 if world > 1 else min(a.batch_bases * n_batches, 30 * ref_len, int(4.3 * a.batch_bases) + 200_000)
+    lr_bases = lr_bases_of(a, world, ref_len, steps, warmup)
     if rank == 0:
-        workdir = ctx["workdir"]
-        t0 = time.time()
-        pre = make_dataset(workdir, ref_len, lr_bases, snps=not a.plain_index, het=het, fast="" if a.sim else "--gpu", name=name)
-        t_data = time.time() - t0
+        pending = ctx.pop("dataset", None)  # (main() starts the main workload's set before torch and the device are initialised)
+        if pending is not None:
+            pre, t_data = pending.result()
+        else:
+            t0 = time.time()
+            pre = make_dataset(ctx["workdir"], ref_len, lr_bases, snps=not a.plain_index, het=het, fast="" if a.sim else "--gpu", name=name)
+            t_data = time.time() - t0
     else:
         pre, t_data = None, 0.0
     if world > 1:
@@ -572,7 +622,7 @@ def run_workload(a, ctx, ref_len, het, name, steps, warmup, n1_first=False):
     api.run_pipelined([batches[w % len(batches)] for w in range(warmup)], opts)
     sync()
     n1 = None
-    if n1_first and world > 1:
+    if n1_first and world > 1 and a.full:
         # the N = 1 point of THIS graph, measured in this process before the sharded run: rank 0 runs K steps alone, the other ranks wait
         if rank == 0:
             seq_1 = [batches[(warmup + st) % len(batches)] for st in range(steps)]
@@ -592,7 +642,7 @@ def run_workload(a, ctx, ref_len, het, name, steps, warmup, n1_first=False):
     # per-kernel times of a step on an otherwise idle GPU (after the clock has stopped): in the timed region two batches overlap, and the
     # HIP-event span of the seed kernels of one then includes their wait for wave slots behind the other's persistent region kernel
     stats_serial = []
-    if not a.serial:
+    if not a.serial and a.full:
         for b in seq_b[:2]:
             b.run(opts); stats_serial.append(b.stats())
         sync()
@@ -607,6 +657,8 @@ def run_workload(a, ctx, ref_len, het, name, steps, warmup, n1_first=False):
     else:
         dt_all, bases_all = dt, float(done_bases)
         per_rank = [{"rank": 0, "device": device, "bases": int(done_bases), "seconds": round(dt, 4), "distinct_tickets": len(mine), "shared_tickets": shared_tickets}]
+    if dump_dir and rank == 0 and seq_b:
+        dump_outputs(dump_dir, seq_b[-1].fetch())
     for b in batches:
         b.close()
     return {"pre": pre, "fa": fa, "rt": rt, "graph": graph, "info": graph.info(), "opts": opts, "mine": mine, "repl": repl, "t_data": t_data, "t_graph": t_graph,
@@ -621,11 +673,25 @@ T_START = time.time()
 
 def main():
     a = parse()
+    rank = int(os.environ.get("RANK", "0")); world = int(os.environ.get("WORLD_SIZE", "1")); local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    workdir = (a.workdir or tempfile.mkdtemp(prefix="rtk_bench_")) if rank == 0 else None
+    diploid = a.het > 0
+    dataset = None
+    if rank == 0:
+        # the main workload's set (simulator + index tool, subprocesses) is made while this process imports torch and opens the device
+        import concurrent.futures
+        os.makedirs(workdir, exist_ok=True)
+
+        def timed_dataset():
+            t0 = time.time()
+            pre = make_dataset(workdir, a.ref_len, lr_bases_of(a, world, a.ref_len, a.steps, a.warmup), snps=not a.plain_index, het=a.het, fast="" if a.sim else "--gpu",
+                               name="c2" if diploid else "c1")
+            return pre, time.time() - t0
+        dataset = concurrent.futures.ThreadPoolExecutor(1).submit(timed_dataset)
     import torch
     import torch.distributed as dist
     from ratatosk_amd import api
 
-    rank = int(os.environ.get("RANK", "0")); world = int(os.environ.get("WORLD_SIZE", "1")); local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     lib_path = os.path.join(ROOT, "tests", "hostsim", "librtk_hostsim.so") if a.sim else None
     if not a.sim and not torch.cuda.is_available():
         raise SystemExit("bench.py: no GPU visible (the hot path has no CPU fallback)")
@@ -635,12 +701,9 @@ def main():
     if world > 1:
         dist.init_process_group(backend="gloo" if a.sim else "nccl")
     api.load_library(lib_path)
-    ctx = {"rank": rank, "world": world, "device": device, "lib_path": lib_path, "workdir": (a.workdir or tempfile.mkdtemp(prefix="rtk_bench_")) if rank == 0 else None}
-    if ctx["workdir"]:
-        os.makedirs(ctx["workdir"], exist_ok=True)
+    ctx = {"rank": rank, "world": world, "device": device, "lib_path": lib_path, "workdir": workdir, "dataset": dataset}
 
-    diploid = a.het > 0
-    w = run_workload(a, ctx, a.ref_len, a.het, "c2" if diploid else "c1", a.steps, a.warmup, n1_first=True)
+    w = run_workload(a, ctx, a.ref_len, a.het, "c2" if diploid else "c1", a.steps, a.warmup, n1_first=True, dump_dir=a.dump_outputs)
     stats, stats_serial, info = w["stats"], w["stats_serial"], w["info"]
 
     if rank == 0:
@@ -668,7 +731,7 @@ def main():
                     "alg_bytes_per_launch": int(alg[dom]), "avg_launch_ms": round(avg_ms, 3),
                     "kernel_ms_per_step": {k_: round(v / n_l, 3) for k_, v in tot.items()},
                     "kernel_ms_per_step_is": ("HIP-event spans inside the timed region, one step at a time (the default): every kernel has the machine to itself" if a.serial else "HIP-event spans inside the timed region with consecutive steps on two streams (--overlap): the spans of k_mask / k_inexact / k_finalize include waiting for wave slots behind the other step's persistent k_regions; kernel_ms_per_step_serial has the same kernels with one step at a time"),
-                    "kernel_ms_per_step_serial": ({k_: round(sum(s_[v] for s_ in stats_serial) / len(stats_serial), 3) for k_, v in kern.items()} if stats_serial else {k_: round(v / n_l, 3) for k_, v in tot.items()}), "regions_per_step": int(S("n_regions")), "aligns_per_step": int(S("n_align")), "align_word_columns_per_step": int(S("n_align_cells")), "expansions_per_step": int(S("n_expand")), "colour_ids_per_step": int(S("n_colour_elem")), "path_bases_per_step": int(S("n_path_base")),
+                    "kernel_ms_per_step_serial": ({k_: round(sum(s_[v] for s_ in stats_serial) / len(stats_serial), 3) for k_, v in kern.items()} if stats_serial else ({k_: round(v / n_l, 3) for k_, v in tot.items()} if a.serial else None)), "regions_per_step": int(S("n_regions")), "aligns_per_step": int(S("n_align")), "align_word_columns_per_step": int(S("n_align_cells")), "expansions_per_step": int(S("n_expand")), "colour_ids_per_step": int(S("n_colour_elem")), "path_bases_per_step": int(S("n_path_base")),
                     "index_lookups_inexact_per_step": int(S("n_probes_inexact")), "index_slots_inexact_per_step": int(S("n_slots_inexact")),
                     "k_regions_wave_cycle_share": {k_: round(S(k_) / max(1.0, S("cyc_total")), 3) for k_ in ("cyc_colour", "cyc_paths", "cyc_consensus", "cyc_myers", "cyc_sets", "cyc_tostring", "cyc_pathqual", "cyc_walk")},
                     "alignment_moves_per_step": int(S("n_moves")), "k_regions_wave_ticks_per_step": int(S("cyc_total")), "regions_redone_bigger_arena": int(S("n_arena_overflow"))}
@@ -687,7 +750,7 @@ def main():
             "ms_per_step": 1e3 * dt_all / max(1, a.steps), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "vs_baseline_note": "null: BASELINE.md holds no published number for this metric and the reference binary cannot be built here (Bifrost, its un-vendored submodule, is absent), so the north_star's '>= 10x the reference CPU' cannot be evaluated against the real binary; cpu_baseline is this repo's port of the path",
             "dtype": "u64", "data": "synthetic",
-            "config": {"workload": "%s, 30x PE150 short reads, ONT-R9.4-profile long reads, %d bases/step/GPU%s" % (set_name, a.batch_bases, (", sharded across %d MI355X, >= 2 distinct tickets per GPU" % world) if world > 1 else ", 1 MI355X"),
+            "config": {"workload": "%s, 30x PE150 short reads (sampled inside the index tool), ONT-R9.4-profile long reads, %d bases/step/GPU%s" % (set_name, a.batch_bases, (", sharded across %d MI355X, >= 2 distinct tickets per GPU" % world) if world > 1 else ", 1 MI355X"),
                        "graph_replication": w["repl"] or None,
                        "n1_on_this_graph": w["n1"],
                        "graph": {"unitigs": int(info.n_unitigs), "kmers": int(info.n_kmers), "hbm_bytes": int(info.hbm_bytes)}, "parallelism": "reads sharded by ticket x%d, graph replicated (one RCCL broadcast per flat buffer)" % world, "per_rank": w["per_rank"],
@@ -695,14 +758,14 @@ def main():
                        "alg_bytes_per_base": round(whole_alg, 1), "setup_s": {"data+index": round(w["t_data"], 1), "graph_load+upload": round(w["t_graph"], 1)}},
             "roofline": roofline,
         }
-        if world == 1 and not a.no_host_legs:
+        if world == 1 and a.full and not a.no_host_legs:
             out["host_inclusive"] = host_inclusive_leg(a, api, w["graph"], w["opts"], w["mine"])
             out["by_ticket_size"] = ticket_size_leg(a, api, w["graph"], w["opts"], w["mine"])
             out["lane_kernel"] = lane_kernel_leg(a, api, w["graph"], w["opts"], w["mine"])
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline_leg(a, api, w["graph"], w["opts"], w["fa"], w["rt"], w["mine"], whole_alg, out)
     w["graph"].close()
-    if rank == 0 and world == 1 and not a.no_host_legs:
+    if rank == 0 and world == 1 and a.full and not a.no_host_legs:
         # The executable's legs run once this process has released the device (its graph image, 83 GB of work areas, pools): `Ratatosk correct -2` sizes its tickets in flight by
         # the device memory that is free, and beside this process it ran with five or six instead of eight (6.1 x 10^8 in the line against 8.1-9.0 x 10^8 on its own, round 6)
         out["cli_file_to_file"] = cli_leg(a, w["pre"], w["fa"], w["rt"])
@@ -710,7 +773,7 @@ def main():
         out["value_correction_phase"] = out["cli_file_to_file"].get("value")
         out["value_correction_phase_is"] = "cli_file_to_file.value: `Ratatosk correct -1` file to file, input bases / wall time of the correction phase (parse + pack + H2D + kernels + D2H + format + ordered write); quote THIS when one number is quoted"
         out["second_pass"] = second_pass_leg(a, w["pre"])
-    if world == 1 and not a.no_config1_leg:
+    if world == 1 and a.full and not a.no_config1_leg:
         # the metric's other single-GPU configuration, in the same run: configs[1] (5 Mb haploid reference; its graph sits largely in the caches)
         w1 = run_workload(a, ctx, 5_000_000, 0.0, "c1", a.steps, a.warmup)
         n1_ = max(1, len(w1["stats"]))
@@ -721,7 +784,7 @@ def main():
                                                         else {k_: round(sum(s_[v] for s_ in w1["stats"]) / n1_, 3) for k_, v in KERN.items()}),  # (steps one at a time are the default: the spans above ARE serial)
                           "graph": {"unitigs": int(w1["info"].n_unitigs), "kmers": int(w1["info"].n_kmers), "hbm_bytes": int(w1["info"].hbm_bytes)}}
         w1["graph"].close()
-    if world == 1 and not (a.no_config4 or a.no_host_legs or a.config1_only or a.sim):  # (the developer runs that leave out the host legs leave this one out too)
+    if world == 1 and a.full and not (a.no_config4 or a.no_host_legs or a.config1_only or a.sim):  # (the developer runs that leave out the host legs leave this one out too)
         # (last: every graph and work area of this process is released by now -- the leg's own process needs the 288 GB)
         out["config4"] = config4_leg(a, ctx["workdir"], T_START)
     if rank == 0:

@@ -17,7 +17,7 @@ r1 = subprocess.run([exe, "correct", "-1", "-c", "16", "-g", pre + ".index.k31.f
 t_p1 = time.time() - t0
 assert r1.returncode == 0, r1.stderr
 t0 = time.time()
-subprocess.check_call([os.path.join(ROOT, "ratatosk_amd", "bin", "rtk_build_index"), "-s", pre + ".sr.fq", "--colour-reads", pre + ".2.fastq", "-k", str(k2), "-o", pre + ".p2"], stderr=subprocess.DEVNULL)
+subprocess.check_call([os.path.join(ROOT, "ratatosk_amd", "bin", "rtk_build_index"), "-s", bench.short_reads(pre), "--colour-reads", pre + ".2.fastq", "-k", str(k2), "-o", pre + ".p2"], stderr=subprocess.DEVNULL)
 t_idx2 = time.time() - t0
 t0 = time.time()
 r2 = subprocess.run([exe, "correct", "-2", "-K", str(k2), "-c", "16", "-g", pre + ".p2.index.k%d.fasta.gz" % k2, "-d", pre + ".p2.index.k%d.rtsk" % k2, "-l", pre + ".2.fastq", "-L", pre + ".lr.fq", "-o", pre] + extra2,

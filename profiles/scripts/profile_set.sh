@@ -31,5 +31,5 @@ mkdir -p $OUT1/calib_fetch $OUT1/calib_write
 python profiles/scripts/summarise.py $OUT1 $SUM ${R}_config1 > $OUT1/summarise.log 2>&1
 # the bench line itself (with the host legs, the configs[1] leg and the CPU baseline), after the counter summary it quotes
 cp $SUM/${R}_pmc_summary.json profiles/${R}_pmc_summary.json
-( time timeout 1500 python bench.py --workdir $WD > $SUM/${R}_bench.json 2> $OUT/bench.err ) 2> $SUM/${R}_bench_time.txt
+( time timeout 1500 python bench.py --full --workdir $WD > $SUM/${R}_bench.json 2> $OUT/bench.err ) 2> $SUM/${R}_bench_time.txt
 ls -la $SUM; tail -3 $SUM/${R}_bench_time.txt; tail -c 600 $SUM/${R}_bench.json

@@ -20,7 +20,7 @@ p1 = pre + ".pass1.fq"
 with open(p1, "w") as f:
     for n_, (s_, q_) in zip(names, out1):
         f.write("@%s\n%s\n+\n%s\n" % (n_, s_, q_))
-subprocess.check_call([os.path.join(ROOT, "ratatosk_amd", "bin", "rtk_build_index"), "-s", pre + ".sr.fq", "--colour-reads", p1, "-k", "63", "-o", pre + ".p2"], stderr=subprocess.DEVNULL)
+subprocess.check_call([os.path.join(ROOT, "ratatosk_amd", "bin", "rtk_build_index"), "-s", bench.short_reads(pre), "--colour-reads", p1, "-k", "63", "-o", pre + ".p2"], stderr=subprocess.DEVNULL)
 fa, rt = pre + ".p2.index.k63.fasta.gz", pre + ".p2.index.k63.rtsk"
 og, pg = op.Graph(fa, rt, 63), api.Graph(fa, rt, 63, device=0)
 s1, q1 = [o[0] for o in out1], [o[1] for o in out1]

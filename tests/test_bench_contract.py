@@ -24,8 +24,8 @@ def _check_common(d, n):
 
 
 def test_bench_line_single(tmp_path):
-    """N = 1: the main line is the chr20-scale (diploid) set -- here at a reduced --ref-len -- and the same run carries configs[1] as the extra leg."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + SMALL + ["--workdir", str(tmp_path)], capture_output=True, text=True, timeout=900)
+    """N = 1: the main line is the chr20-scale (diploid) set -- here at a reduced --ref-len -- and a --full run carries configs[1] as the extra leg."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + SMALL + ["--full", "--workdir", str(tmp_path)], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _line(r.stdout)
     _check_common(d, 1)
@@ -37,7 +37,7 @@ def test_bench_line_single(tmp_path):
 
 def test_bench_line_two_ranks(tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29533",
-           os.path.join(ROOT, "bench.py"), "--gpus", "2"] + SMALL + ["--workdir", str(tmp_path)]
+           os.path.join(ROOT, "bench.py"), "--gpus", "2"] + SMALL + ["--full", "--workdir", str(tmp_path)]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _line(r.stdout)
@@ -47,6 +47,29 @@ def test_bench_line_two_ranks(tmp_path):
     assert abs(d["value"] - sum(p["bases"] for p in pr) / max(p["seconds"] for p in pr)) / d["value"] < 0.05  # whole-job rate: all ranks' bases over the slowest rank's time
     n1 = d["config"]["n1_on_this_graph"]  # the one-GPU point of the same graph, measured in this very run on rank 0 (not read from a file)
     assert n1["value"] > 0 and n1["ms_per_step"] > 0 and n1["steps"] == 1 and "in this run" in n1["measured"] and "config1" not in d
+
+
+def test_plain_bench_line_times_the_steps_only_and_dumps_outputs(tmp_path):
+    """Without --full the line is the headline alone (no extra legs), --steps sets the timed steps, ms_per_step is their time, and --dump-outputs writes the
+    last timed step's corrected reads; the same arguments give the same outputs."""
+    dumps = []
+    for i in range(2):
+        d_out = os.path.join(str(tmp_path), "out%d" % i)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--sim", "--ref-len", "60000", "--batch-bases", "120000", "--steps", "3", "--warmup", "1",
+                            "--workdir", os.path.join(str(tmp_path), "wd%d" % i), "--dump-outputs", d_out], capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = _line(r.stdout)
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["dtype"] == "u64" and d["value"] > 0
+        assert abs(d["value"] - d["config"]["per_rank"][0]["bases"] / (3e-3 * d["ms_per_step"])) / d["value"] < 1e-3  # bases of the 3 timed steps over 3 x ms_per_step
+        assert not {"config1", "config4", "cpu_baseline", "host_inclusive", "by_ticket_size", "lane_kernel", "cli_file_to_file", "second_pass"} & set(d)
+        import numpy as np
+        names = sorted(f for f in os.listdir(d_out) if f.endswith(".npy"))
+        assert names and sum(os.path.getsize(os.path.join(d_out, f)) for f in names) <= 64 << 20
+        arrs = {f: np.load(os.path.join(d_out, f)) for f in names}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+        assert arrs["corrected_length.npy"].sum() > 0 and arrs["sample_seq_ascii.npy"].size == arrs["corrected_length.npy"][arrs["sample_read_index.npy"].astype(int)].sum()
+        dumps.append(arrs)
+    assert dumps[0].keys() == dumps[1].keys() and all(np.array_equal(dumps[0][k], dumps[1][k]) for k in dumps[0])
 
 
 def test_bench_line_eight_ranks_is_the_configs2_run(tmp_path):
