@@ -248,9 +248,11 @@ int rtk_myers_batch_lanes(uint32_t n, const char* const* query, const uint32_t* 
 void rtk_myers_lanes_last_routes(uint64_t* lane_route, uint64_t* wave_route);
 
 /* Index build, device side (the reference builds its index on the CPU: `Ratatosk index`, src/Ratatosk.cpp:1066-1067, Bifrost
- * build + addCoverage src/Graph.cpp:1561). rtk_index_count_kmers: the canonical k-mers (odd k <= 31, A=0 C=1 G=2 T=3, first base in the
+ * build + addCoverage src/Graph.cpp:1561). rtk_index_count_kmers: the canonical k-mers (odd k <= 63, A=0 C=1 G=2 T=3, first base in the
  * high bits) that the reads of `files` (plain or gzipped FASTA/FASTQ) hold at least min_count times, sorted ascending; *solid is freed
- * with rtk_free. The tool csrc/tools/build_index.cpp (--gpu) builds the same files with it as its CPU path does. */
+ * with rtk_free. The tool csrc/tools/build_index.cpp (--gpu) builds the same files with it as its CPU path does.
+ * K-mer layout of the index calls: k <= 31 one uint64_t per k-mer; 33 <= k <= 63 TWO uint64_t words per k-mer, low word first (the 2k-bit code
+ * as a little-endian unsigned 128-bit integer), in `solid`, `*solid`, `*seeds` and `*left`. Counts (n_solid, n_unitigs, n_left) are in k-mers. */
 int rtk_index_count_kmers(int device, int k, const char* const* files, int n_files, uint32_t min_count, int n_threads, uint64_t** solid, uint64_t* n_solid);
 /* rtk_index_unitigs: the unitigs of a sorted set of canonical solid k-mers (Bifrost's compaction behind CompactedDBG::build, src/Ratatosk.cpp:1100-1118):
  * the k-mers in a table in HBM with their eight edge bits, every maximal chain of mutually unique links walked from its ends by one thread each, written

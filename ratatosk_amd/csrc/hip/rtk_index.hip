@@ -1,13 +1,13 @@
 // GPU side of the index build (reference: `Ratatosk index`, src/Ratatosk.cpp:1066-1067 Bifrost build + src/Graph.cpp:1561 addCoverage).
-// The reference builds its graph with Bifrost on the CPU; the data-parallel step of an index build that touches every base of the 30x short
-// reads most often -- counting their k-mers -- is done here on the device, behind the C ABI (include/ratatosk_hip.h), for the index tool
-// (csrc/tools/build_index.cpp --gpu):
+// The reference builds its graph with Bifrost on the CPU; the data-parallel steps of an index build are done here on the device, behind the C ABI
+// (include/ratatosk_hip.h), for the index tool (csrc/tools/build_index.cpp --gpu):
 //   rtk_index_count_kmers   canonical k-mers of the reads seen >= min_count times: every read position spells its k-mer (one lane per position,
 //                           the window packed 2 bits per base without branches), the k-mers of the pass are radix-sorted (rocPRIM) and the first
-//                           element of every run of >= min_count equal keys is kept. HBM-bound: 1 byte read + 8 bytes written per base, then the sort.
-// (Mapping the reads back onto the unitigs for the colour sets and coverages -- what addCoverage computes -- runs on the host threads of the tool,
-// by byte ranges of the read files; it is the next candidate for the device.)
-// One-word k-mers (k <= 31) only; the tool keeps its CPU path for k = 63 and for gzip input. Own translation unit: rocPRIM's templates.
+//                           element of every run of >= min_count equal keys is kept. HBM-bound: 1 byte read + 8 (16) bytes written per base, then the sort.
+//   rtk_index_unitigs       the chains of the compacted graph walked, numbered and spelt (k_ut_*)
+//   rtk_index_colour_*      every read k-mer mapped onto its unitig: colour events and coverage (k_col_map)
+// Every step serves one-word k-mers (k <= 31, key type uint64_t) and two-word k-mers (33 <= k <= 63, key type unsigned __int128: the 2k-bit code,
+// first base in the most significant bits; in memory the low word first). Own translation unit: rocPRIM's templates.
 #include <string.h>
 #include <unistd.h>
 
@@ -39,8 +39,14 @@ namespace {
 
 #define RTK_IDX_SENTINEL 0xFFFFFFFFFFFFFFFFull
 
+typedef unsigned __int128 km2_t; // two-word k-mer (rocprim::uint128_t: radix-sortable)
 __device__ __forceinline__ uint64_t idx_revcomp(uint64_t x, int k) { return rtk_revcomp(x, k); }
 __device__ __forceinline__ uint64_t idx_hash(uint64_t x) { return rtk_hash64(x); }
+__device__ __forceinline__ RtkKm idx_words(km2_t x) { RtkKm r; r.hi = static_cast<uint64_t>(x >> 64); r.lo = static_cast<uint64_t>(x); return r; }
+__device__ __forceinline__ km2_t idx_km2(const RtkKm& x) { return (static_cast<km2_t>(x.hi) << 64) | static_cast<km2_t>(x.lo); }
+__device__ __forceinline__ km2_t idx_revcomp(km2_t x, int k) { return idx_km2(rtk_km_revcomp(idx_words(x), k)); }
+__device__ __forceinline__ uint64_t idx_hash(km2_t x) { return rtk_km_hash(idx_words(x)); } // (the hash of the wide k-mer table of rtk_graph_tables)
+template <class KM> __device__ __forceinline__ KM idx_kmask(int k) { return (static_cast<KM>(1) << (2 * k)) - static_cast<KM>(1); }
 
 // code of base c (A/a 0, C/c 1, G/g 2, T/t 3) or 4
 __device__ __forceinline__ uint32_t idx_code(unsigned char c) {
@@ -50,16 +56,17 @@ __device__ __forceinline__ uint32_t idx_code(unsigned char c) {
 
 // One lane per character position of the chunk: the canonical k-mer that starts there (all k characters A/C/G/T, the separator between reads is
 // not), kept when its hash falls into partition `part` of `n_part`. Survivors are appended to `keys` (wave-level compaction: one atomic per wave).
-__global__ void k_index_kmers(const char* __restrict__ chars, uint64_t n, int k, uint32_t part, uint32_t n_part, uint64_t* __restrict__ keys, unsigned long long* __restrict__ top, uint64_t cap) {
+template <class KM>
+__global__ void k_index_kmers(const char* __restrict__ chars, uint64_t n, int k, uint32_t part, uint32_t n_part, KM* __restrict__ keys, unsigned long long* __restrict__ top, uint64_t cap) {
     const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
     for (uint64_t i0 = static_cast<uint64_t>(blockIdx.x) * blockDim.x; i0 < n; i0 += stride) {
         const uint64_t i = i0 + threadIdx.x;
-        uint64_t km = 0; bool ok = i + static_cast<uint64_t>(k) <= n;
+        KM km = 0; bool ok = i + static_cast<uint64_t>(k) <= n;
         if (ok) {
-            for (int j = 0; j < k; ++j) { const uint32_t c = idx_code(static_cast<unsigned char>(chars[i + j])); ok = ok && c < 4u; km = (km << 2) | (c & 3u); }
+            for (int j = 0; j < k; ++j) { const uint32_t c = idx_code(static_cast<unsigned char>(chars[i + j])); ok = ok && c < 4u; km = (km << 2) | static_cast<KM>(c & 3u); }
         }
-        uint64_t can = 0;
-        if (ok) { const uint64_t rc = idx_revcomp(km, k); can = km <= rc ? km : rc; ok = n_part <= 1u || (idx_hash(can) >> 40) % n_part == part; }
+        KM can = 0;
+        if (ok) { const KM rc = idx_revcomp(km, k); can = km <= rc ? km : rc; ok = n_part <= 1u || (idx_hash(can) >> 40) % n_part == part; }
         const uint64_t bal = __ballot(ok ? 1 : 0);
         if (bal) {
             const int lane = threadIdx.x & 63;
@@ -73,15 +80,15 @@ __global__ void k_index_kmers(const char* __restrict__ chars, uint64_t n, int k,
 }
 
 // first element of every run of >= min_count equal keys of a sorted array
-struct SolidHead {
-    const uint64_t* keys; uint64_t n; uint32_t min_count;
+template <class KM> struct SolidHead {
+    const KM* keys; uint64_t n; uint32_t min_count;
     __device__ bool operator()(uint64_t i) const {
-        const uint64_t x = keys[i];
+        const KM x = keys[i];
         if (i != 0 && keys[i - 1] == x) return false;
         return i + min_count - 1 < n && keys[i + min_count - 1] == x;
     }
 };
-struct KeyAt { const uint64_t* keys; __device__ uint64_t operator()(uint64_t i) const { return keys[i]; } };
+template <class KM> struct KeyAt { const KM* keys; __device__ KM operator()(uint64_t i) const { return keys[i]; } };
 
 struct DevBuf { void* p = nullptr; ~DevBuf() { if (p) (void)hipFree(p); } void alloc(uint64_t bytes) { if (p) (void)hipFree(p); p = nullptr; rtk_check(hipMalloc(&p, bytes ? bytes : 8), "hipMalloc (index build)"); } };
 struct PinBuf { void* p = nullptr; ~PinBuf() { if (p) (void)hipHostFree(p); } void alloc(uint64_t bytes) { rtk_check(hipHostMalloc(&p, bytes, hipHostMallocDefault), "hipHostMalloc (index build)"); } };
@@ -146,79 +153,95 @@ bool for_each_sequence_chunk(const std::vector<std::string>& files, int n_thread
 
 
 // ------------------------------------------------------------------------------------------------ unitigs (rtk_index_unitigs)
-// The solid k-mers in a table of 16-byte slots {canonical k-mer, value}: value bits 0..3 = which of the four successors (x << 2 | b) of the canonical
+// The solid k-mers in a table of slots {canonical k-mer, value}: value bits 0..3 = which of the four successors (x << 2 | b) of the canonical
 // orientation are solid, bits 4..7 = which of the four predecessors (b in front), bit 8 = the k-mer lies on a unitig written here.
+// One-word k-mers: 16-byte slots {key, value}. Two-word k-mers: 32-byte slots {hi, lo, value, unused}; the high word of a 2k-bit code (k <= 63) is
+// never all ones, so it doubles as the state word: a slot is claimed by one 64-bit compare-and-swap on it (keys are distinct and the table is filled
+// by a kernel of its own, before anything reads it) and the low word is written afterwards. Every lookup compares both words.
 #define RTK_UT_CLAIMED 256ull
+template <class KM> struct UtSlot { static const int W = 2, V = 1; };         // words per slot, word of the value
+template <> struct UtSlot<km2_t> { static const int W = 4, V = 2; };
 __device__ __forceinline__ uint64_t ut_find(const uint64_t* __restrict__ T, uint64_t slots, uint64_t can) {
     uint64_t s = __umul64hi(idx_hash(can), slots);
     for (;;) { const uint64_t key = T[2 * s]; if (key == can) return s; if (key == RTK_IDX_SENTINEL) return RTK_IDX_SENTINEL; s = s + 1 == slots ? 0 : s + 1; }
 }
+__device__ __forceinline__ uint64_t ut_find(const uint64_t* __restrict__ T, uint64_t slots, km2_t can) {
+    const uint64_t hi = static_cast<uint64_t>(can >> 64), lo = static_cast<uint64_t>(can);
+    uint64_t s = __umul64hi(idx_hash(can), slots);
+    for (;;) { const uint64_t h = T[4 * s]; if (h == hi && T[4 * s + 1] == lo) return s; if (h == RTK_IDX_SENTINEL) return RTK_IDX_SENTINEL; s = s + 1 == slots ? 0 : s + 1; }
+}
+template <class KM> __device__ __forceinline__ uint64_t ut_vi(uint64_t s) { return UtSlot<KM>::W * s + UtSlot<KM>::V; } // word of slot s's value
 __device__ __forceinline__ uint32_t rev4(uint32_t n) { return ((n & 1u) << 3) | ((n & 2u) << 1) | ((n & 4u) >> 1) | ((n & 8u) >> 3); }
 // edge bits of an ORIENTED k-mer from those of its canonical form: the successor by base b of the reverse complement is the predecessor by base 3 - b
 __device__ __forceinline__ uint32_t ut_omask(uint32_t m, bool is_can) { return is_can ? (m & 255u) : (rev4((m >> 4) & 15u) | (rev4(m & 15u) << 4)); }
-__device__ __forceinline__ uint32_t ut_mask_of(const uint64_t* __restrict__ T, uint64_t slots, uint64_t x, int k, uint64_t* slot_out) {
-    const uint64_t rc = idx_revcomp(x, k), can = x <= rc ? x : rc;
+template <class KM> __device__ __forceinline__ uint32_t ut_mask_of(const uint64_t* __restrict__ T, uint64_t slots, KM x, int k, uint64_t* slot_out) {
+    const KM rc = idx_revcomp(x, k), can = x <= rc ? x : rc;
     const uint64_t s = ut_find(T, slots, can); if (slot_out) *slot_out = s;
-    return ut_omask(static_cast<uint32_t>(T[2 * s + 1]), x == can);
+    return ut_omask(static_cast<uint32_t>(T[ut_vi<KM>(s)]), x == can);
 }
 // the link the construction follows forwards from x (its oriented edge bits mx): the only successor of x, if x is its only predecessor
-__device__ __forceinline__ bool ut_next(const uint64_t* __restrict__ T, uint64_t slots, int k, uint64_t kmask, uint64_t x, uint32_t mx, uint64_t* y, uint32_t* my, uint64_t* slot_y) {
+template <class KM> __device__ __forceinline__ bool ut_next(const uint64_t* __restrict__ T, uint64_t slots, int k, KM kmask, KM x, uint32_t mx, KM* y, uint32_t* my, uint64_t* slot_y) {
     const uint32_t sc = mx & 15u; if (__popc(sc) != 1) return false;
-    const uint64_t yy = ((x << 2) | static_cast<uint64_t>(__ffs(sc) - 1)) & kmask;
+    const KM yy = ((x << 2) | static_cast<KM>(__ffs(sc) - 1)) & kmask;
     const uint32_t m = ut_mask_of(T, slots, yy, k, slot_y); if (__popc(m >> 4) != 1) return false;
     *y = yy; *my = m; return true;
 }
-__device__ __forceinline__ bool ut_prev(const uint64_t* __restrict__ T, uint64_t slots, int k, uint64_t x, uint32_t mx) {
+template <class KM> __device__ __forceinline__ bool ut_prev(const uint64_t* __restrict__ T, uint64_t slots, int k, KM x, uint32_t mx) {
     const uint32_t pc = mx >> 4; if (__popc(pc) != 1) return false;
-    const uint64_t yy = (x >> 2) | (static_cast<uint64_t>(__ffs(pc) - 1) << (2 * (k - 1)));
+    const KM yy = (x >> 2) | (static_cast<KM>(__ffs(pc) - 1) << (2 * (k - 1)));
     return __popc(ut_mask_of(T, slots, yy, k, nullptr) & 15u) == 1;
 }
 
-__global__ void k_ut_fill(uint64_t* __restrict__ T, uint64_t slots) {
+template <class KM> __global__ void k_ut_fill(uint64_t* __restrict__ T, uint64_t slots) {
     const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
-    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < slots; i += stride) { T[2 * i] = RTK_IDX_SENTINEL; T[2 * i + 1] = 0; }
-}
-__global__ void k_ut_insert(const uint64_t* __restrict__ solid, uint64_t n, uint64_t* __restrict__ T, uint64_t slots) {
-    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
-    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const uint64_t c = solid[i]; uint64_t s = __umul64hi(idx_hash(c), slots);
-        while (atomicCAS(reinterpret_cast<unsigned long long*>(T + 2 * s), static_cast<unsigned long long>(RTK_IDX_SENTINEL), static_cast<unsigned long long>(c)) != RTK_IDX_SENTINEL) s = s + 1 == slots ? 0 : s + 1;
+    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < slots; i += stride) {
+        T[UtSlot<KM>::W * i] = RTK_IDX_SENTINEL; for (int w = 1; w < UtSlot<KM>::W; ++w) T[UtSlot<KM>::W * i + w] = 0;
     }
 }
-__global__ void k_ut_edges(const uint64_t* __restrict__ solid, uint64_t n, int k, uint64_t* __restrict__ T, uint64_t slots) {
-    const uint64_t kmask = (1ull << (2 * k)) - 1ull, stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
+template <class KM> __global__ void k_ut_insert(const KM* __restrict__ solid, uint64_t n, uint64_t* __restrict__ T, uint64_t slots) {
+    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
     for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const uint64_t c = solid[i]; uint64_t m = 0;
+        const KM c = solid[i]; uint64_t s = __umul64hi(idx_hash(c), slots);
+        const uint64_t w0 = sizeof(KM) == 8 ? static_cast<uint64_t>(c) : static_cast<uint64_t>(c >> (sizeof(KM) == 8 ? 0 : 64)); // key word / high word
+        while (atomicCAS(reinterpret_cast<unsigned long long*>(T + UtSlot<KM>::W * s), static_cast<unsigned long long>(RTK_IDX_SENTINEL), static_cast<unsigned long long>(w0)) != RTK_IDX_SENTINEL) s = s + 1 == slots ? 0 : s + 1;
+        if (sizeof(KM) != 8) T[UtSlot<KM>::W * s + 1] = static_cast<uint64_t>(c); // the low word of a slot this lane owns
+    }
+}
+template <class KM> __global__ void k_ut_edges(const KM* __restrict__ solid, uint64_t n, int k, uint64_t* __restrict__ T, uint64_t slots) {
+    const KM kmask = idx_kmask<KM>(k); const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
+    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const KM c = solid[i]; uint64_t m = 0;
         for (uint64_t b = 0; b < 4; ++b) {
-            const uint64_t y = ((c << 2) | b) & kmask, yr = idx_revcomp(y, k); if (ut_find(T, slots, y <= yr ? y : yr) != RTK_IDX_SENTINEL) m |= 1ull << b;
-            const uint64_t z = (c >> 2) | (b << (2 * (k - 1))), zr = idx_revcomp(z, k); if (ut_find(T, slots, z <= zr ? z : zr) != RTK_IDX_SENTINEL) m |= 16ull << b;
+            const KM y = ((c << 2) | static_cast<KM>(b)) & kmask, yr = idx_revcomp(y, k); if (ut_find(T, slots, y <= yr ? y : yr) != RTK_IDX_SENTINEL) m |= 1ull << b;
+            const KM z = (c >> 2) | (static_cast<KM>(b) << (2 * (k - 1))), zr = idx_revcomp(z, k); if (ut_find(T, slots, z <= zr ? z : zr) != RTK_IDX_SENTINEL) m |= 16ull << b;
         }
-        T[2 * ut_find(T, slots, c) + 1] = m;
+        T[ut_vi<KM>(ut_find(T, slots, c))] = m;
     }
 }
 // Every maximal chain of mutually unique links is walked from both of its end k-mers; the end whose canonical k-mer is the smaller one owns it (tools/
 // build_index.cpp fast_unitigs: the same rules, so that the two produce the same unitigs). An owner reports the oriented k-mer it starts from, the number of
 // k-mers, the smallest canonical k-mer on the chain (its seed: unitigs are numbered by it) and whether that one reads backwards on the walk (the unitig is
 // then the reverse complement of the walk). record == nullptr: count the owners only.
-__global__ void k_ut_chains(const uint64_t* __restrict__ solid, uint64_t n, int k, const uint64_t* __restrict__ T, uint64_t slots,
-                            unsigned long long* __restrict__ n_chains, uint64_t cap, uint64_t* __restrict__ start, uint64_t* __restrict__ seed, uint32_t* __restrict__ len_rev, uint32_t* __restrict__ too_long) {
-    const uint64_t kmask = (1ull << (2 * k)) - 1ull, stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
+template <class KM>
+__global__ void k_ut_chains(const KM* __restrict__ solid, uint64_t n, int k, const uint64_t* __restrict__ T, uint64_t slots,
+                            unsigned long long* __restrict__ n_chains, uint64_t cap, KM* __restrict__ start, KM* __restrict__ seed, uint32_t* __restrict__ len_rev, uint32_t* __restrict__ too_long) {
+    const KM kmask = idx_kmask<KM>(k); const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
     for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const uint64_t s = solid[i];
+        const KM s = solid[i];
         const uint32_t ms = ut_mask_of(T, slots, s, k, nullptr);
-        uint64_t y = 0; uint32_t my = 0;
+        KM y = 0; uint32_t my = 0;
         const bool has_fw = ut_next(T, slots, k, kmask, s, ms, &y, &my, nullptr), has_bw = ut_prev(T, slots, k, s, ms);
         if (has_fw && has_bw) continue; // inside a chain (or on a closed loop)
-        uint64_t x = has_bw ? idx_revcomp(s, k) : s; uint32_t mx = has_bw ? ut_omask(ms, false) : ms; // walk inwards from this end
-        const uint64_t x0 = x;
-        uint64_t len = 1, mc = s; bool m_fw = (x == s);
+        KM x = has_bw ? idx_revcomp(s, k) : s; uint32_t mx = has_bw ? ut_omask(ms, false) : ms; // walk inwards from this end
+        const KM x0 = x;
+        uint64_t len = 1; KM mc = s; bool m_fw = (x == s);
         while (ut_next(T, slots, k, kmask, x, mx, &y, &my, nullptr)) {
             x = y; mx = my; ++len;
-            const uint64_t r = idx_revcomp(x, k), c = x <= r ? x : r;
+            const KM r = idx_revcomp(x, k), c = x <= r ? x : r;
             if (c < mc) { mc = c; m_fw = (x == c); }
             if (len > n) break;
         }
-        const uint64_t xr = idx_revcomp(x, k), end_c = x <= xr ? x : xr;
+        const KM xr = idx_revcomp(x, k), end_c = x <= xr ? x : xr;
         if (len > 1 && end_c == s) continue; // the chain comes back to its own first k-mer (hairpin): left to the plain construction
         if (end_c < s) continue;            // the other end owns the chain
         if (len > n) continue;
@@ -229,25 +252,26 @@ __global__ void k_ut_chains(const uint64_t* __restrict__ solid, uint64_t n, int 
 }
 struct ChainBases { const uint32_t* len_rev; const uint32_t* order; int k; __device__ uint64_t operator()(uint64_t j) const { return static_cast<uint64_t>(len_rev[order[j]] & 0x7FFFFFFFu) + static_cast<uint64_t>(k - 1); } };
 // chain order[j] written as unitig j at seq_off[j]: walked again from its start, every k-mer claimed (a k-mer claimed twice: *clash)
-__global__ void k_ut_write(uint64_t n_ch, const uint32_t* __restrict__ order, const uint64_t* __restrict__ start, const uint32_t* __restrict__ len_rev, const uint64_t* __restrict__ seq_off,
+template <class KM>
+__global__ void k_ut_write(uint64_t n_ch, const uint32_t* __restrict__ order, const KM* __restrict__ start, const uint32_t* __restrict__ len_rev, const uint64_t* __restrict__ seq_off,
                            int k, uint64_t* __restrict__ T, uint64_t slots, char* __restrict__ pool, uint32_t* __restrict__ clash) {
-    const uint64_t kmask = (1ull << (2 * k)) - 1ull, stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
+    const KM kmask = idx_kmask<KM>(k); const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
     for (uint64_t j = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; j < n_ch; j += stride) {
         const uint32_t c = order[j]; const uint64_t len = len_rev[c] & 0x7FFFFFFFu; const bool rev = (len_rev[c] >> 31) != 0;
         const uint64_t L = len + static_cast<uint64_t>(k - 1); char* out = pool + seq_off[j];
         auto put = [&](uint64_t pos, uint32_t b) { if (!rev) out[pos] = "ACGT"[b]; else out[L - 1 - pos] = "TGCA"[b]; }; // base b at position pos of the walk
-        uint64_t x = start[c], slot = 0; uint32_t mx = ut_mask_of(T, slots, x, k, &slot);
-        for (int q = 0; q < k; ++q) put(static_cast<uint64_t>(q), static_cast<uint32_t>((x >> (2 * (k - 1 - q))) & 3ull));
-        if (atomicOr(reinterpret_cast<unsigned long long*>(T + 2 * slot + 1), static_cast<unsigned long long>(RTK_UT_CLAIMED)) & RTK_UT_CLAIMED) atomicOr(clash, 1u);
+        KM x = start[c]; uint64_t slot = 0; uint32_t mx = ut_mask_of(T, slots, x, k, &slot);
+        for (int q = 0; q < k; ++q) put(static_cast<uint64_t>(q), static_cast<uint32_t>((x >> (2 * (k - 1 - q))) & static_cast<KM>(3)));
+        if (atomicOr(reinterpret_cast<unsigned long long*>(T + ut_vi<KM>(slot)), static_cast<unsigned long long>(RTK_UT_CLAIMED)) & RTK_UT_CLAIMED) atomicOr(clash, 1u);
         for (uint64_t q = 1; q < len; ++q) {
-            uint64_t y = 0; uint32_t my = 0;
+            KM y = 0; uint32_t my = 0;
             if (!ut_next(T, slots, k, kmask, x, mx, &y, &my, &slot)) { atomicOr(clash, 2u); break; }
-            x = y; mx = my; put(static_cast<uint64_t>(k - 1) + q, static_cast<uint32_t>(x & 3ull));
-            if (atomicOr(reinterpret_cast<unsigned long long*>(T + 2 * slot + 1), static_cast<unsigned long long>(RTK_UT_CLAIMED)) & RTK_UT_CLAIMED) atomicOr(clash, 1u);
+            x = y; mx = my; put(static_cast<uint64_t>(k - 1) + q, static_cast<uint32_t>(x & static_cast<KM>(3)));
+            if (atomicOr(reinterpret_cast<unsigned long long*>(T + ut_vi<KM>(slot)), static_cast<unsigned long long>(RTK_UT_CLAIMED)) & RTK_UT_CLAIMED) atomicOr(clash, 1u);
         }
     }
 }
-struct Unclaimed { const uint64_t* solid; const uint64_t* T; uint64_t slots; __device__ bool operator()(uint64_t i) const { return !(T[2 * ut_find(T, slots, solid[i]) + 1] & RTK_UT_CLAIMED); } };
+template <class KM> struct Unclaimed { const KM* solid; const uint64_t* T; uint64_t slots; __device__ bool operator()(uint64_t i) const { return !(T[ut_vi<KM>(ut_find(T, slots, solid[i]))] & RTK_UT_CLAIMED); } };
 struct Iota32 { __device__ uint32_t operator()(uint64_t i) const { return static_cast<uint32_t>(i); } };
 
 
@@ -264,20 +288,39 @@ __global__ void k_col_pack(const char* __restrict__ pool, uint64_t n_bases, uint
 // One lane per character position of a chunk of reads (sequences separated by '\n'): its k-mer looked up in the unitig table. A run of consecutive
 // positions of one read on one unitig is one EVENT (unitig << 32 | id of the read) and one addition of its length to the unitig's coverage, made by
 // the first lane of the run inside its wave (a run that crosses a wave boundary gives two events: duplicates go when the events are sorted).
+// the unitig of a one-word k-mer: 16-byte slots {canonical k-mer, unitig << 32 | ...}
+__device__ __forceinline__ uint32_t col_find(const GraphView& g, uint64_t km, int k) {
+    const uint64_t rc = idx_revcomp(km, k), can = km <= rc ? km : rc;
+    const uint64_t* __restrict__ ht = g.ht; const uint64_t slots = g.ht_slots;
+    uint64_t s = __umul64hi(idx_hash(can), slots);
+    for (;;) { const uint64_t key = ht[2 * s]; if (key == can) return static_cast<uint32_t>(ht[2 * s + 1] >> 32); if (key == RTK_IDX_SENTINEL) return 0xFFFFFFFFu; s = s + 1 == slots ? 0 : s + 1; }
+}
+// the unitig of a two-word k-mer: the slots keep a fingerprint of the canonical k-mer, a match is confirmed against the unitig's bases
+// (rtk_find_kmer_wide without the presence filters, which the index build's table does not have)
+__device__ __forceinline__ uint32_t col_find(const GraphView& g, km2_t km, int k) {
+    const RtkKm fw = idx_words(km), rc = rtk_km_revcomp(fw, k), can = rtk_km_less(fw, rc) ? fw : rc;
+    const uint64_t fp = rtk_km_fingerprint(can); const uint64_t* __restrict__ ht = g.ht; const uint64_t slots = g.ht_slots;
+    for (uint64_t s = rtk_ht_slot(rtk_km_hash(can), slots);; s = rtk_ht_next(s, slots)) {
+        const uint64_t key = ht[2 * s];
+        if (key == fp) {
+            const uint64_t v = ht[2 * s + 1]; const uint32_t u = static_cast<uint32_t>(v >> 32);
+            const RtkKm urc = rtk_km_rc_of_unitig(g, g.uoff[u] + ((v & 0xFFFFFFFFull) >> 1), k);
+            if (rtk_km_eq(urc, rc) || rtk_km_eq(urc, fw)) return u;
+        }
+        if (key == RTK_EMPTY_KEY) return 0xFFFFFFFFu;
+    }
+}
+template <class KM>
 __global__ void k_col_map(const char* __restrict__ chars, uint64_t n, int k, const uint64_t* __restrict__ starts, const uint32_t* __restrict__ ids, uint32_t n_reads,
-                          const uint64_t* __restrict__ ht, uint64_t slots, unsigned long long* __restrict__ cov, uint64_t* __restrict__ events, unsigned long long* __restrict__ top, uint64_t cap) {
+                          GraphView g, unsigned long long* __restrict__ cov, uint64_t* __restrict__ events, unsigned long long* __restrict__ top, uint64_t cap) {
     const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
     const int lane = threadIdx.x & 63;
     for (uint64_t i0 = static_cast<uint64_t>(blockIdx.x) * blockDim.x; i0 < n; i0 += stride) { // (whole waves take part in every round)
         const uint64_t i = i0 + threadIdx.x;
-        uint64_t km = 0; bool ok = i + static_cast<uint64_t>(k) <= n;
-        if (ok) for (int j = 0; j < k; ++j) { const uint32_t c = idx_code(static_cast<unsigned char>(chars[i + j])); ok = ok && c < 4u; km = (km << 2) | (c & 3u); }
+        KM km = 0; bool ok = i + static_cast<uint64_t>(k) <= n;
+        if (ok) for (int j = 0; j < k; ++j) { const uint32_t c = idx_code(static_cast<unsigned char>(chars[i + j])); ok = ok && c < 4u; km = (km << 2) | static_cast<KM>(c & 3u); }
         uint32_t u = 0xFFFFFFFFu;
-        if (ok) {
-            const uint64_t rc = idx_revcomp(km, k), can = km <= rc ? km : rc;
-            uint64_t s = __umul64hi(idx_hash(can), slots);
-            for (;;) { const uint64_t key = ht[2 * s]; if (key == can) { u = static_cast<uint32_t>(ht[2 * s + 1] >> 32); break; } if (key == RTK_IDX_SENTINEL) break; s = s + 1 == slots ? 0 : s + 1; }
-        }
+        if (ok) u = col_find(g, km, k);
         const bool hit = u != 0xFFFFFFFFu;
         const uint32_t pu = __shfl_up(u, 1, 64); // (position i - 1 with a k-mer on the same unitig: the same read, its k-mer holds no separator)
         const bool head = hit && (lane == 0 || pu != u);
@@ -298,7 +341,7 @@ __global__ void k_col_map(const char* __restrict__ chars, uint64_t n, int k, con
 }
 
 struct ColourJob {
-    int device = 0, k = 31; uint32_t n_unitigs = 0;
+    int device = 0, k = 31; uint32_t n_unitigs = 0; GraphView g; // g: the k-mer table and the packed unitigs (the only fields k_col_map reads)
     DevBuf useq, uoff, ht, cov, events, alt, top, tmp;
     uint64_t slots = 0, cap = 0, n_events = 0; // n_events: sorted, distinct events at the front of `events`
     DevBuf d_chars[2], d_starts[2], d_ids[2]; PinBuf h_chars[2], h_starts[2], h_ids[2]; uint64_t chunk_cap = 0, reads_cap = 0;
@@ -329,11 +372,9 @@ struct ColourJob {
 
 } // namespace
 
-extern "C" int rtk_index_count_kmers(int device, int k, const char* const* files, int n_files, uint32_t min_count, int n_threads, uint64_t** solid_out, uint64_t* n_solid) {
-    if (!files || n_files <= 0 || !solid_out || !n_solid) return rtk_fail(RTK_ERR_ARG, "rtk_index_count_kmers: null argument");
-    if (k < 3 || k > 31 || !(k & 1)) return rtk_fail(RTK_ERR_UNSUPPORTED, "rtk_index_count_kmers: one-word k-mers only (odd k <= 31)");
-    if (min_count < 1) min_count = 1;
-    if (rtk_device_count() <= device || device < 0) return rtk_fail(RTK_ERR_NO_DEVICE, "rtk_index_count_kmers: no such HIP device (no CPU fallback)");
+namespace {
+// KM: uint64_t (k <= 31) or km2_t (33 <= k <= 63); *solid_out holds n_solid keys of sizeof(KM) bytes
+template <class KM> int count_kmers(int device, int k, const char* const* files, int n_files, uint32_t min_count, int n_threads, uint64_t** solid_out, uint64_t* n_solid) {
     try {
         rtk_check(hipSetDevice(device), "hipSetDevice");
         std::vector<std::string> fl(files, files + n_files);
@@ -343,14 +384,14 @@ extern "C" int rtk_index_count_kmers(int device, int k, const char* const* files
         size_t fr = 0, tot = 0; rtk_check(hipMemGetInfo(&fr, &tot), "hipMemGetInfo");
         if (getenv("RTK_INDEX_TRACE")) fprintf(stderr, "rtk_index_count_kmers: inputs sized (%.1f GB), %.1f GB of device memory free\n", total_bytes / 1e9, fr / 1e9);
         const uint64_t est_kmers = total_bytes / 2 + (1u << 20); // FASTQ: half of the bytes are bases (gzip input: a multiple of it; the capacity test below catches that)
-        uint64_t cap = static_cast<uint64_t>(fr) / 10 * 7 / 16; // 70 % of the free memory for keys + their sort buffer (the rest: two chunks of text, the sort's histograms)
+        uint64_t cap = static_cast<uint64_t>(fr) / 10 * 7 / (2 * sizeof(KM)); // 70 % of the free memory for keys + their sort buffer (the rest: two chunks of text, the sort's histograms)
         { const char* e = getenv("RTK_INDEX_CAP"); if (e) cap = strtoull(e, nullptr, 10); }
         if (cap < (1u << 20)) cap = 1u << 20;
         uint32_t n_part = static_cast<uint32_t>((est_kmers + cap - 1) / cap); if (n_part < 1) n_part = 1;
         uint64_t chunk_bytes = 256ull << 20;
         { const char* e = getenv("RTK_INDEX_CHUNK"); if (e && strtoull(e, nullptr, 10) >= 1024) chunk_bytes = strtoull(e, nullptr, 10); } // developer / tests: small chunks, so that long records are cut into pieces
         const uint64_t chunk_slack = std::min<uint64_t>(64ull << 20, chunk_bytes / 4);
-        std::vector<uint64_t> solid;
+        std::vector<KM> solid;
         // Several partitions = several passes over the reads. The text of the first pass is kept in host memory when it fits into half of what is free there
         // (a 3 Gb x 30x set: 90 GB of sequences, sampled or parsed ONCE instead of once per partition -- 13 passes at 0.5 Gb/s of host-side sampling were 36 minutes)
         std::vector<std::string> kept; bool keep_text = false, kept_complete = false;
@@ -368,7 +409,7 @@ extern "C" int rtk_index_count_kmers(int device, int k, const char* const* files
             done = true; solid.clear(); run_start.clear(); if (!kept_complete) kept.clear(); // (a restart with more partitions keeps the text of the complete first pass)
             const uint64_t cap_p = n_part == 1 ? std::min<uint64_t>(cap, est_kmers + est_kmers / 8) : cap;
             DevBuf d_keys, d_alt, d_top, d_chars[2], d_sel, d_nsel;
-            d_keys.alloc(8 * cap_p); d_alt.alloc(8 * cap_p); d_top.alloc(8); d_nsel.alloc(8);
+            d_keys.alloc(sizeof(KM) * cap_p); d_alt.alloc(sizeof(KM) * cap_p); d_top.alloc(8); d_nsel.alloc(8);
             d_chars[0].alloc(chunk_bytes + chunk_slack); d_chars[1].alloc(chunk_bytes + chunk_slack);
             PinBuf h_chars[2]; h_chars[0].alloc(chunk_bytes + chunk_slack); h_chars[1].alloc(chunk_bytes + chunk_slack);
             hipStream_t st[2]; rtk_check(hipStreamCreate(&st[0]), "hipStreamCreate"); rtk_check(hipStreamCreate(&st[1]), "hipStreamCreate");
@@ -384,8 +425,8 @@ extern "C" int rtk_index_count_kmers(int device, int k, const char* const* files
                         rtk_check(hipStreamSynchronize(st[slot]), "hipStreamSynchronize");
                         memcpy(h_chars[slot].p, chars + off, piece);
                         rtk_check(hipMemcpyAsync(d_chars[slot].p, h_chars[slot].p, piece, hipMemcpyHostToDevice, st[slot]), "hipMemcpyAsync");
-                        hipLaunchKernelGGL(k_index_kmers, dim3(4096), dim3(256), 0, st[slot], static_cast<const char*>(d_chars[slot].p), static_cast<uint64_t>(piece), k, part, n_part,
-                                           static_cast<uint64_t*>(d_keys.p), static_cast<unsigned long long*>(d_top.p), cap_p);
+                        hipLaunchKernelGGL(k_index_kmers<KM>, dim3(4096), dim3(256), 0, st[slot], static_cast<const char*>(d_chars[slot].p), static_cast<uint64_t>(piece), k, part, n_part,
+                                           static_cast<KM*>(d_keys.p), static_cast<unsigned long long*>(d_top.p), cap_p);
                         rtk_check(hipGetLastError(), "kernel launch (k_index_kmers)");
                         slot ^= 1; off += (off + piece < n) ? piece - static_cast<size_t>(k - 1) : piece; // a cut inside a sequence: the next piece starts k - 1 characters back, so that every window is seen once
                     }
@@ -405,14 +446,14 @@ extern "C" int rtk_index_count_kmers(int device, int k, const char* const* files
                 if (n_keys == 0) continue;
                 if (trace) fprintf(stderr, "rtk_index_count_kmers:   %llu k-mers on the device at %.1f s; sorting\n", n_keys, since());
                 // sort, then the first key of every run of >= min_count
-                rocprim::double_buffer<uint64_t> db(static_cast<uint64_t*>(d_keys.p), static_cast<uint64_t*>(d_alt.p));
+                rocprim::double_buffer<KM> db(static_cast<KM*>(d_keys.p), static_cast<KM*>(d_alt.p)); // (two-word keys: bits [0, 2k) of the 128-bit value)
                 size_t tb = 0; rtk_check(rocprim::radix_sort_keys(nullptr, tb, db, static_cast<size_t>(n_keys), 0, 2 * k), "rocprim::radix_sort_keys");
                 DevBuf d_tmp; d_tmp.alloc(tb);
                 rtk_check(rocprim::radix_sort_keys(d_tmp.p, tb, db, static_cast<size_t>(n_keys), 0, 2 * k), "rocprim::radix_sort_keys");
                 if (trace) { rtk_check(hipDeviceSynchronize(), "radix sort"); fprintf(stderr, "rtk_index_count_kmers:   sorted at %.1f s\n", since()); }
-                const uint64_t* sorted = db.current(); uint64_t* other = db.alternate();
-                SolidHead pred; pred.keys = sorted; pred.n = n_keys; pred.min_count = min_count;
-                KeyAt at; at.keys = sorted;
+                const KM* sorted = db.current(); KM* other = db.alternate();
+                SolidHead<KM> pred; pred.keys = sorted; pred.n = n_keys; pred.min_count = min_count;
+                KeyAt<KM> at; at.keys = sorted;
                 auto idx = rocprim::make_counting_iterator<uint64_t>(0);
                 auto vals = rocprim::make_transform_iterator(idx, at);
                 size_t sb = 0; // select with a flag iterator: the flag of element i is the predicate on its index
@@ -424,13 +465,13 @@ extern "C" int rtk_index_count_kmers(int device, int k, const char* const* files
                 unsigned long long n_sel = 0; rtk_check(hipMemcpy(&n_sel, d_nsel.p, 8, hipMemcpyDeviceToHost), "hipMemcpy");
                 const size_t old = solid.size(); solid.resize(old + n_sel); run_start.push_back(old);
                 if (trace) fprintf(stderr, "rtk_index_count_kmers: partition %u of %u: %llu k-mers, %llu solid (at %.1f s%s)\n", part + 1, n_part, n_keys, n_sel, since(), kept_complete ? ", text kept in host memory" : "");
-                if (n_sel) rtk_check(hipMemcpy(solid.data() + old, other, 8ull * n_sel, hipMemcpyDeviceToHost), "hipMemcpy");
+                if (n_sel) rtk_check(hipMemcpy(solid.data() + old, other, sizeof(KM) * n_sel, hipMemcpyDeviceToHost), "hipMemcpy");
             }
             (void)hipStreamDestroy(st[0]); (void)hipStreamDestroy(st[1]);
         }
-        uint64_t* out = static_cast<uint64_t*>(malloc(8 * (solid.size() ? solid.size() : 1)));
+        KM* out = static_cast<KM*>(malloc(sizeof(KM) * (solid.size() ? solid.size() : 1)));
         if (!out) return rtk_fail(RTK_ERR_IO, "rtk_index_count_kmers: out of host memory");
-        if (run_start.size() <= 1) { if (!solid.empty()) memcpy(out, solid.data(), 8 * solid.size()); }
+        if (run_start.size() <= 1) { if (!solid.empty()) memcpy(out, solid.data(), sizeof(KM) * solid.size()); }
         else {
             // the partitions are sorted each and a k-mer lives in one of them: merged by ranges of the key space, one range per thread (every thread finds its
             // stretch of every partition by bisection; the ranges before it give it its place in the output)
@@ -440,21 +481,30 @@ extern "C" int rtk_index_count_kmers(int device, int k, const char* const* files
             const unsigned __int128 span = static_cast<unsigned __int128>(1) << (2 * k);
             for (int t = 0; t <= T; ++t) for (size_t r = 0; r < P; ++r) {
                 if (t == T) { cut[t][r] = run_start[r + 1]; continue; }
-                const uint64_t v = static_cast<uint64_t>(span * static_cast<unsigned __int128>(t) / static_cast<unsigned __int128>(T));
+                const KM v = sizeof(KM) == 8 ? static_cast<KM>(span * static_cast<unsigned __int128>(t) / static_cast<unsigned __int128>(T)) : static_cast<KM>(span / static_cast<unsigned __int128>(T) * static_cast<unsigned __int128>(t)); // (2^126 * t would not fit)
                 cut[t][r] = static_cast<size_t>(std::lower_bound(solid.begin() + static_cast<std::ptrdiff_t>(run_start[r]), solid.begin() + static_cast<std::ptrdiff_t>(run_start[r + 1]), v) - solid.begin());
             }
             std::vector<std::thread> th;
             for (int t = 0; t < T; ++t) th.emplace_back([&, t]() {
                 size_t at = 0; for (size_t r = 0; r < P; ++r) at += cut[t][r] - run_start[r];
                 std::vector<size_t> head(cut[t]); const std::vector<size_t>& end = cut[t + 1];
-                for (;;) { size_t best = P; uint64_t bv = 0; for (size_t r = 0; r < P; ++r) if (head[r] < end[r] && (best == P || solid[head[r]] < bv)) { best = r; bv = solid[head[r]]; } if (best == P) break; out[at++] = bv; ++head[best]; }
+                for (;;) { size_t best = P; KM bv = 0; for (size_t r = 0; r < P; ++r) if (head[r] < end[r] && (best == P || solid[head[r]] < bv)) { best = r; bv = solid[head[r]]; } if (best == P) break; out[at++] = bv; ++head[best]; }
             });
             for (size_t t = 0; t < th.size(); ++t) th[t].join();
         }
         if (trace) fprintf(stderr, "rtk_index_count_kmers: %zu solid k-mers from %u partition(s) in %.1f s\n", solid.size(), n_part, since());
-        *solid_out = out; *n_solid = solid.size();
+        *solid_out = reinterpret_cast<uint64_t*>(out); *n_solid = solid.size();
     } catch (const std::exception& e) { return rtk_fail(RTK_ERR_DEVICE, std::string("rtk_index_count_kmers: ") + e.what()); }
     return RTK_OK;
+}
+} // namespace
+
+extern "C" int rtk_index_count_kmers(int device, int k, const char* const* files, int n_files, uint32_t min_count, int n_threads, uint64_t** solid_out, uint64_t* n_solid) {
+    if (!files || n_files <= 0 || !solid_out || !n_solid) return rtk_fail(RTK_ERR_ARG, "rtk_index_count_kmers: null argument");
+    if (k < 3 || k > 63 || !(k & 1)) return rtk_fail(RTK_ERR_UNSUPPORTED, "rtk_index_count_kmers: odd k <= 63 only");
+    if (min_count < 1) min_count = 1;
+    if (rtk_device_count() <= device || device < 0) return rtk_fail(RTK_ERR_NO_DEVICE, "rtk_index_count_kmers: no such HIP device (no CPU fallback)");
+    return k <= 31 ? count_kmers<uint64_t>(device, k, files, n_files, min_count, n_threads, solid_out, n_solid) : count_kmers<km2_t>(device, k, files, n_files, min_count, n_threads, solid_out, n_solid);
 }
 
 
@@ -462,12 +512,8 @@ extern "C" int rtk_index_count_kmers(int device, int k, const char* const* files
 // forwards, in the order of those k-mers -- what tools/build_index.cpp fast_unitigs builds on the host threads (the rules are restated there and here;
 // tests/test_index_build.py holds both to the plain construction and to oracle/oracle_index.py). Chains that meet themselves (closed loops, hairpins through
 // a reverse complement) are not built: their k-mers come back in *left (sorted) for the caller's plain construction.
-extern "C" int rtk_index_unitigs(int device, int k, const uint64_t* solid, uint64_t n_solid, char** seq_pool, uint64_t** seq_off, uint64_t** seeds, uint64_t* n_unitigs, uint64_t** left, uint64_t* n_left) {
-    if (!solid || !seq_pool || !seq_off || !seeds || !n_unitigs || !left || !n_left) return rtk_fail(RTK_ERR_ARG, "rtk_index_unitigs: null argument");
-    if (k < 3 || k > 31 || !(k & 1)) return rtk_fail(RTK_ERR_UNSUPPORTED, "rtk_index_unitigs: one-word k-mers only (odd k <= 31)");
-    if (rtk_device_count() <= device || device < 0) return rtk_fail(RTK_ERR_NO_DEVICE, "rtk_index_unitigs: no such HIP device (no CPU fallback)");
-    if (n_solid >= (1ull << 32)) return rtk_fail(RTK_ERR_UNSUPPORTED, "rtk_index_unitigs: more than 2^32 solid k-mers");
-    *seq_pool = nullptr; *seq_off = nullptr; *seeds = nullptr; *left = nullptr; *n_unitigs = 0; *n_left = 0;
+namespace {
+template <class KM> int unitigs(int device, int k, const KM* solid, uint64_t n_solid, char** seq_pool, uint64_t** seq_off, uint64_t** seeds, uint64_t* n_unitigs, uint64_t** left, uint64_t* n_left) {
     const bool trace = getenv("RTK_INDEX_TRACE") != nullptr;
     try {
         rtk_check(hipSetDevice(device), "hipSetDevice");
@@ -476,37 +522,37 @@ extern "C" int rtk_index_unitigs(int device, int k, const uint64_t* solid, uint6
         const uint64_t n = n_solid, slots = n + n * 3 / 7 + 16;
         auto grid = [](uint64_t items) { const uint64_t b = (items + 255) / 256; return dim3(static_cast<unsigned>(b < 1 ? 1 : (b > 65536 ? 65536 : b))); };
         DevBuf d_solid, d_T, d_cnt, d_flag;
-        d_solid.alloc(8 * n); d_T.alloc(16 * slots); d_cnt.alloc(8); d_flag.alloc(8);
-        rtk_check(hipMemcpy(d_solid.p, solid, 8 * n, hipMemcpyHostToDevice), "hipMemcpy");
+        d_solid.alloc(sizeof(KM) * n); d_T.alloc(8 * UtSlot<KM>::W * slots); d_cnt.alloc(8); d_flag.alloc(8);
+        rtk_check(hipMemcpy(d_solid.p, solid, sizeof(KM) * n, hipMemcpyHostToDevice), "hipMemcpy");
         rtk_check(hipMemset(d_cnt.p, 0, 8), "hipMemset"); rtk_check(hipMemset(d_flag.p, 0, 8), "hipMemset");
-        const uint64_t* ds = static_cast<const uint64_t*>(d_solid.p); uint64_t* T = static_cast<uint64_t*>(d_T.p);
+        const KM* ds = static_cast<const KM*>(d_solid.p); uint64_t* T = static_cast<uint64_t*>(d_T.p);
         uint32_t* d_too_long = static_cast<uint32_t*>(d_flag.p); uint32_t* d_clash = d_too_long + 1;
-        hipLaunchKernelGGL(k_ut_fill, grid(slots), dim3(256), 0, 0, T, slots);
-        hipLaunchKernelGGL(k_ut_insert, grid(n), dim3(256), 0, 0, ds, n, T, slots);
-        hipLaunchKernelGGL(k_ut_edges, grid(n), dim3(256), 0, 0, ds, n, k, T, slots);
+        hipLaunchKernelGGL(k_ut_fill<KM>, grid(slots), dim3(256), 0, 0, T, slots);
+        hipLaunchKernelGGL(k_ut_insert<KM>, grid(n), dim3(256), 0, 0, ds, n, T, slots);
+        hipLaunchKernelGGL(k_ut_edges<KM>, grid(n), dim3(256), 0, 0, ds, n, k, T, slots);
         rtk_check(hipGetLastError(), "kernel launch (unitig table)"); rtk_check(hipDeviceSynchronize(), "unitig table");
         const double t_table = since();
         // owners counted, then recorded
-        hipLaunchKernelGGL(k_ut_chains, grid(n), dim3(256), 0, 0, ds, n, k, static_cast<const uint64_t*>(T), slots, static_cast<unsigned long long*>(d_cnt.p), 0ull, static_cast<uint64_t*>(nullptr), static_cast<uint64_t*>(nullptr), static_cast<uint32_t*>(nullptr), d_too_long);
+        hipLaunchKernelGGL(k_ut_chains<KM>, grid(n), dim3(256), 0, 0, ds, n, k, static_cast<const uint64_t*>(T), slots, static_cast<unsigned long long*>(d_cnt.p), 0ull, static_cast<KM*>(nullptr), static_cast<KM*>(nullptr), static_cast<uint32_t*>(nullptr), d_too_long);
         rtk_check(hipGetLastError(), "kernel launch (k_ut_chains)"); rtk_check(hipDeviceSynchronize(), "k_ut_chains");
         unsigned long long n_ch = 0; rtk_check(hipMemcpy(&n_ch, d_cnt.p, 8, hipMemcpyDeviceToHost), "hipMemcpy");
         uint32_t fl[2] = {0, 0}; rtk_check(hipMemcpy(fl, d_flag.p, 8, hipMemcpyDeviceToHost), "hipMemcpy");
         if (fl[0]) return rtk_fail(RTK_ERR_UNSUPPORTED, "rtk_index_unitigs: a unitig of more than 2^31 k-mers");
         if (n_ch >= (1ull << 32)) return rtk_fail(RTK_ERR_UNSUPPORTED, "rtk_index_unitigs: more than 2^32 unitigs");
         DevBuf d_start, d_seed, d_seed2, d_lr, d_ord, d_ord2, d_off, d_tmp;
-        d_start.alloc(8 * n_ch); d_seed.alloc(8 * n_ch); d_seed2.alloc(8 * n_ch); d_lr.alloc(4 * n_ch); d_ord.alloc(4 * n_ch); d_ord2.alloc(4 * n_ch); d_off.alloc(8 * (n_ch + 1));
+        d_start.alloc(sizeof(KM) * n_ch); d_seed.alloc(sizeof(KM) * n_ch); d_seed2.alloc(sizeof(KM) * n_ch); d_lr.alloc(4 * n_ch); d_ord.alloc(4 * n_ch); d_ord2.alloc(4 * n_ch); d_off.alloc(8 * (n_ch + 1));
         rtk_check(hipMemset(d_cnt.p, 0, 8), "hipMemset");
-        hipLaunchKernelGGL(k_ut_chains, grid(n), dim3(256), 0, 0, ds, n, k, static_cast<const uint64_t*>(T), slots, static_cast<unsigned long long*>(d_cnt.p), static_cast<uint64_t>(n_ch), static_cast<uint64_t*>(d_start.p), static_cast<uint64_t*>(d_seed.p), static_cast<uint32_t*>(d_lr.p), d_too_long);
+        hipLaunchKernelGGL(k_ut_chains<KM>, grid(n), dim3(256), 0, 0, ds, n, k, static_cast<const uint64_t*>(T), slots, static_cast<unsigned long long*>(d_cnt.p), static_cast<uint64_t>(n_ch), static_cast<KM*>(d_start.p), static_cast<KM*>(d_seed.p), static_cast<uint32_t*>(d_lr.p), d_too_long);
         rtk_check(hipGetLastError(), "kernel launch (k_ut_chains)"); rtk_check(hipDeviceSynchronize(), "k_ut_chains");
         const double t_chains = since();
-        std::vector<uint64_t> h_off(n_ch + 1, 0), h_seed(n_ch);
+        std::vector<uint64_t> h_off(n_ch + 1, 0); std::vector<KM> h_seed(n_ch);
         uint64_t total = 0;
         if (n_ch) {
             // the chains in the order of their seeds (one chain per seed: a k-mer lies on one chain)
             auto iota = rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint64_t>(0), Iota32());
-            size_t tb = 0; rtk_check(rocprim::radix_sort_pairs(nullptr, tb, static_cast<uint64_t*>(d_seed.p), static_cast<uint64_t*>(d_seed2.p), iota, static_cast<uint32_t*>(d_ord.p), static_cast<size_t>(n_ch), 0, 2 * k), "rocprim::radix_sort_pairs");
+            size_t tb = 0; rtk_check(rocprim::radix_sort_pairs(nullptr, tb, static_cast<KM*>(d_seed.p), static_cast<KM*>(d_seed2.p), iota, static_cast<uint32_t*>(d_ord.p), static_cast<size_t>(n_ch), 0, 2 * k), "rocprim::radix_sort_pairs");
             d_tmp.alloc(tb);
-            rtk_check(rocprim::radix_sort_pairs(d_tmp.p, tb, static_cast<uint64_t*>(d_seed.p), static_cast<uint64_t*>(d_seed2.p), iota, static_cast<uint32_t*>(d_ord.p), static_cast<size_t>(n_ch), 0, 2 * k), "rocprim::radix_sort_pairs");
+            rtk_check(rocprim::radix_sort_pairs(d_tmp.p, tb, static_cast<KM*>(d_seed.p), static_cast<KM*>(d_seed2.p), iota, static_cast<uint32_t*>(d_ord.p), static_cast<size_t>(n_ch), 0, 2 * k), "rocprim::radix_sort_pairs");
             ChainBases cb; cb.len_rev = static_cast<const uint32_t*>(d_lr.p); cb.order = static_cast<const uint32_t*>(d_ord.p); cb.k = k;
             auto lens = rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint64_t>(0), cb);
             size_t sb = 0; rtk_check(rocprim::exclusive_scan(nullptr, sb, lens, static_cast<uint64_t*>(d_off.p), 0ull, static_cast<size_t>(n_ch), rocprim::plus<uint64_t>()), "rocprim::exclusive_scan");
@@ -514,38 +560,49 @@ extern "C" int rtk_index_unitigs(int device, int k, const uint64_t* solid, uint6
             rtk_check(rocprim::exclusive_scan(d_tmp.p, sb, lens, static_cast<uint64_t*>(d_off.p), 0ull, static_cast<size_t>(n_ch), rocprim::plus<uint64_t>()), "rocprim::exclusive_scan");
             rtk_check(hipDeviceSynchronize(), "chain order");
             rtk_check(hipMemcpy(h_off.data(), d_off.p, 8 * n_ch, hipMemcpyDeviceToHost), "hipMemcpy");
-            rtk_check(hipMemcpy(h_seed.data(), d_seed2.p, 8 * n_ch, hipMemcpyDeviceToHost), "hipMemcpy");
+            rtk_check(hipMemcpy(h_seed.data(), d_seed2.p, sizeof(KM) * n_ch, hipMemcpyDeviceToHost), "hipMemcpy");
             uint32_t last_c = 0, last_lr = 0; rtk_check(hipMemcpy(&last_c, static_cast<uint32_t*>(d_ord.p) + (n_ch - 1), 4, hipMemcpyDeviceToHost), "hipMemcpy");
             rtk_check(hipMemcpy(&last_lr, static_cast<uint32_t*>(d_lr.p) + last_c, 4, hipMemcpyDeviceToHost), "hipMemcpy");
             total = h_off[n_ch - 1] + (last_lr & 0x7FFFFFFFu) + static_cast<uint64_t>(k - 1); h_off[n_ch] = total;
         }
         DevBuf d_pool; d_pool.alloc(total ? total : 8);
         if (n_ch) {
-            hipLaunchKernelGGL(k_ut_write, grid(n_ch), dim3(256), 0, 0, static_cast<uint64_t>(n_ch), static_cast<const uint32_t*>(d_ord.p), static_cast<const uint64_t*>(d_start.p), static_cast<const uint32_t*>(d_lr.p), static_cast<const uint64_t*>(d_off.p), k, T, slots, static_cast<char*>(d_pool.p), d_clash);
+            hipLaunchKernelGGL(k_ut_write<KM>, grid(n_ch), dim3(256), 0, 0, static_cast<uint64_t>(n_ch), static_cast<const uint32_t*>(d_ord.p), static_cast<const KM*>(d_start.p), static_cast<const uint32_t*>(d_lr.p), static_cast<const uint64_t*>(d_off.p), k, T, slots, static_cast<char*>(d_pool.p), d_clash);
             rtk_check(hipGetLastError(), "kernel launch (k_ut_write)"); rtk_check(hipDeviceSynchronize(), "k_ut_write");
         }
         rtk_check(hipMemcpy(fl, d_flag.p, 8, hipMemcpyDeviceToHost), "hipMemcpy");
         if (fl[1]) return rtk_fail(RTK_ERR_FORMAT, "rtk_index_unitigs: a k-mer ended up on two unitigs"); // (the tool then runs its plain construction)
         const double t_write = since();
         // the k-mers on no unitig written here, in sorted order
-        DevBuf d_left, d_nleft; d_left.alloc(8 * (n ? n : 1)); d_nleft.alloc(8);
-        Unclaimed un; un.solid = ds; un.T = T; un.slots = slots;
+        DevBuf d_left, d_nleft; d_left.alloc(sizeof(KM) * (n ? n : 1)); d_nleft.alloc(8);
+        Unclaimed<KM> un; un.solid = ds; un.T = T; un.slots = slots;
         { auto idx = rocprim::make_counting_iterator<uint64_t>(0); auto flags = rocprim::make_transform_iterator(idx, un);
-          size_t sb = 0; rtk_check(rocprim::select(nullptr, sb, ds, flags, static_cast<uint64_t*>(d_left.p), static_cast<unsigned long long*>(d_nleft.p), static_cast<size_t>(n)), "rocprim::select");
+          size_t sb = 0; rtk_check(rocprim::select(nullptr, sb, ds, flags, static_cast<KM*>(d_left.p), static_cast<unsigned long long*>(d_nleft.p), static_cast<size_t>(n)), "rocprim::select");
           d_tmp.alloc(sb);
-          rtk_check(rocprim::select(d_tmp.p, sb, ds, flags, static_cast<uint64_t*>(d_left.p), static_cast<unsigned long long*>(d_nleft.p), static_cast<size_t>(n)), "rocprim::select");
+          rtk_check(rocprim::select(d_tmp.p, sb, ds, flags, static_cast<KM*>(d_left.p), static_cast<unsigned long long*>(d_nleft.p), static_cast<size_t>(n)), "rocprim::select");
           rtk_check(hipDeviceSynchronize(), "left-over k-mers"); }
         unsigned long long nl = 0; rtk_check(hipMemcpy(&nl, d_nleft.p, 8, hipMemcpyDeviceToHost), "hipMemcpy");
-        char* o_pool = static_cast<char*>(malloc(total ? total : 1)); uint64_t* o_off = static_cast<uint64_t*>(malloc(8 * (n_ch + 1))); uint64_t* o_seed = static_cast<uint64_t*>(malloc(8 * (n_ch ? n_ch : 1))); uint64_t* o_left = static_cast<uint64_t*>(malloc(8 * (nl ? nl : 1)));
+        char* o_pool = static_cast<char*>(malloc(total ? total : 1)); uint64_t* o_off = static_cast<uint64_t*>(malloc(8 * (n_ch + 1))); KM* o_seed = static_cast<KM*>(malloc(sizeof(KM) * (n_ch ? n_ch : 1))); KM* o_left = static_cast<KM*>(malloc(sizeof(KM) * (nl ? nl : 1)));
         if (!o_pool || !o_off || !o_seed || !o_left) { free(o_pool); free(o_off); free(o_seed); free(o_left); return rtk_fail(RTK_ERR_IO, "rtk_index_unitigs: out of host memory"); }
         if (total) rtk_check(hipMemcpy(o_pool, d_pool.p, total, hipMemcpyDeviceToHost), "hipMemcpy");
-        memcpy(o_off, h_off.data(), 8 * (n_ch + 1)); if (n_ch) memcpy(o_seed, h_seed.data(), 8 * n_ch);
-        if (nl) rtk_check(hipMemcpy(o_left, d_left.p, 8 * nl, hipMemcpyDeviceToHost), "hipMemcpy");
-        *seq_pool = o_pool; *seq_off = o_off; *seeds = o_seed; *n_unitigs = n_ch; *left = o_left; *n_left = nl;
+        memcpy(o_off, h_off.data(), 8 * (n_ch + 1)); if (n_ch) memcpy(o_seed, h_seed.data(), sizeof(KM) * n_ch);
+        if (nl) rtk_check(hipMemcpy(o_left, d_left.p, sizeof(KM) * nl, hipMemcpyDeviceToHost), "hipMemcpy");
+        *seq_pool = o_pool; *seq_off = o_off; *seeds = reinterpret_cast<uint64_t*>(o_seed); *n_unitigs = n_ch; *left = reinterpret_cast<uint64_t*>(o_left); *n_left = nl;
         if (trace) fprintf(stderr, "rtk_index_unitigs: %llu unitigs, %llu bases, %llu k-mers left to the plain construction; table + edge bits %.2f s, chains %.2f s, order + sequences %.2f s, left-overs + copies %.2f s\n",
                            n_ch, static_cast<unsigned long long>(total), nl, t_table, t_chains - t_table, t_write - t_chains, since() - t_write);
     } catch (const std::exception& e) { return rtk_fail(RTK_ERR_DEVICE, std::string("rtk_index_unitigs: ") + e.what()); }
     return RTK_OK;
+}
+} // namespace
+
+extern "C" int rtk_index_unitigs(int device, int k, const uint64_t* solid, uint64_t n_solid, char** seq_pool, uint64_t** seq_off, uint64_t** seeds, uint64_t* n_unitigs, uint64_t** left, uint64_t* n_left) {
+    if (!solid || !seq_pool || !seq_off || !seeds || !n_unitigs || !left || !n_left) return rtk_fail(RTK_ERR_ARG, "rtk_index_unitigs: null argument");
+    if (k < 3 || k > 63 || !(k & 1)) return rtk_fail(RTK_ERR_UNSUPPORTED, "rtk_index_unitigs: odd k <= 63 only");
+    if (rtk_device_count() <= device || device < 0) return rtk_fail(RTK_ERR_NO_DEVICE, "rtk_index_unitigs: no such HIP device (no CPU fallback)");
+    if (n_solid >= (1ull << 32)) return rtk_fail(RTK_ERR_UNSUPPORTED, "rtk_index_unitigs: more than 2^32 solid k-mers");
+    *seq_pool = nullptr; *seq_off = nullptr; *seeds = nullptr; *left = nullptr; *n_unitigs = 0; *n_left = 0;
+    return k <= 31 ? unitigs<uint64_t>(device, k, solid, n_solid, seq_pool, seq_off, seeds, n_unitigs, left, n_left)
+                   : unitigs<km2_t>(device, k, reinterpret_cast<const km2_t*>(solid), n_solid, seq_pool, seq_off, seeds, n_unitigs, left, n_left); // (two words per k-mer, low word first)
 }
 
 
@@ -557,7 +614,7 @@ extern "C" int rtk_index_unitigs(int device, int k, const uint64_t* solid, uint6
 //   end    *events: n_events words unitig << 32 | id, ascending, distinct; *cov: n_unitigs counts. Freed with rtk_free. The job is gone afterwards (also on error).
 extern "C" int rtk_index_colour_begin(int device, int k, const char* seq_pool, const uint64_t* seq_off, uint64_t n_unitigs, void** job_out) {
     if (!seq_pool || !seq_off || !job_out || n_unitigs == 0) return rtk_fail(RTK_ERR_ARG, "rtk_index_colour_begin: null argument");
-    if (k < 3 || k > 31 || !(k & 1)) return rtk_fail(RTK_ERR_UNSUPPORTED, "rtk_index_colour_begin: one-word k-mers only (odd k <= 31)");
+    if (k < 3 || k > 63 || !(k & 1)) return rtk_fail(RTK_ERR_UNSUPPORTED, "rtk_index_colour_begin: odd k <= 63 only");
     if (rtk_device_count() <= device || device < 0) return rtk_fail(RTK_ERR_NO_DEVICE, "rtk_index_colour_begin: no such HIP device (no CPU fallback)");
     if (n_unitigs >= 0xFFFFFFFFull) return rtk_fail(RTK_ERR_UNSUPPORTED, "rtk_index_colour_begin: more than 2^32 - 1 unitigs");
     *job_out = nullptr;
@@ -574,6 +631,8 @@ extern "C" int rtk_index_colour_begin(int device, int k, const char* seq_pool, c
         J->uoff.alloc(8 * (n_unitigs + 1)); rtk_check(hipMemcpy(J->uoff.p, seq_off, 8 * (n_unitigs + 1), hipMemcpyHostToDevice), "hipMemcpy");
         void* ht = nullptr; rtk::device_kmer_table(static_cast<const uint64_t*>(J->useq.p), static_cast<const uint64_t*>(J->uoff.p), J->n_unitigs, n_bases, n_kmers, k, &ht, &J->slots);
         J->ht.p = ht;
+        memset(&J->g, 0, sizeof(J->g)); J->g.k = k; J->g.n_unitigs = J->n_unitigs; J->g.ht_slots = J->slots; J->g.ht = static_cast<const uint64_t*>(J->ht.p);
+        J->g.useq = static_cast<const uint64_t*>(J->useq.p); J->g.uoff = static_cast<const uint64_t*>(J->uoff.p);
         J->cov.alloc(8 * n_unitigs); rtk_check(hipMemset(J->cov.p, 0, 8 * n_unitigs), "hipMemset");
         J->top.alloc(8); rtk_check(hipMemset(J->top.p, 0, 8), "hipMemset");
         J->chunk_cap = 64ull << 20; J->reads_cap = J->chunk_cap / 16; // (a read of fewer than 15 characters per 16 bytes of chunk: the caller splits such chunks)
@@ -613,8 +672,12 @@ extern "C" int rtk_index_colour_chunk(void* job, const char* chars, uint64_t n_c
         rtk_check(hipMemcpyAsync(J->d_chars[sl].p, J->h_chars[sl].p, n_chars, hipMemcpyHostToDevice, J->st[sl]), "hipMemcpyAsync");
         rtk_check(hipMemcpyAsync(J->d_starts[sl].p, J->h_starts[sl].p, 8ull * n_reads, hipMemcpyHostToDevice, J->st[sl]), "hipMemcpyAsync");
         rtk_check(hipMemcpyAsync(J->d_ids[sl].p, J->h_ids[sl].p, 4ull * n_reads, hipMemcpyHostToDevice, J->st[sl]), "hipMemcpyAsync");
-        hipLaunchKernelGGL(k_col_map, dim3(4096), dim3(256), 0, J->st[sl], static_cast<const char*>(J->d_chars[sl].p), n_chars, J->k, static_cast<const uint64_t*>(J->d_starts[sl].p), static_cast<const uint32_t*>(J->d_ids[sl].p), n_reads,
-                           static_cast<const uint64_t*>(J->ht.p), J->slots, static_cast<unsigned long long*>(J->cov.p), static_cast<uint64_t*>(J->events.p), static_cast<unsigned long long*>(J->top.p), J->cap);
+        if (J->k <= 31)
+            hipLaunchKernelGGL(k_col_map<uint64_t>, dim3(4096), dim3(256), 0, J->st[sl], static_cast<const char*>(J->d_chars[sl].p), n_chars, J->k, static_cast<const uint64_t*>(J->d_starts[sl].p), static_cast<const uint32_t*>(J->d_ids[sl].p), n_reads,
+                               J->g, static_cast<unsigned long long*>(J->cov.p), static_cast<uint64_t*>(J->events.p), static_cast<unsigned long long*>(J->top.p), J->cap);
+        else
+            hipLaunchKernelGGL(k_col_map<km2_t>, dim3(4096), dim3(256), 0, J->st[sl], static_cast<const char*>(J->d_chars[sl].p), n_chars, J->k, static_cast<const uint64_t*>(J->d_starts[sl].p), static_cast<const uint32_t*>(J->d_ids[sl].p), n_reads,
+                               J->g, static_cast<unsigned long long*>(J->cov.p), static_cast<uint64_t*>(J->events.p), static_cast<unsigned long long*>(J->top.p), J->cap);
         rtk_check(hipGetLastError(), "kernel launch (k_col_map)");
         J->bases += n_chars; ++J->chunks;
     } catch (const std::exception& e) { return rtk_fail(RTK_ERR_DEVICE, std::string("rtk_index_colour_chunk: ") + e.what()); }

@@ -15,11 +15,14 @@
 // `correct -2 -g G2 -d D2 -l OUT.2.fastq -L raw_reads -o OUT` is the second pass (src/Ratatosk.cpp:1163-1262 with a pre-built second
 // index): the uncorrected reads are read in lock-step with the pass-1 reads (:774-802), qualities are kept, output goes to OUT.fastq
 // (:622), optionally gzipped (-G; one gzip member per ticket block, compressed by the workers) and trimmed / split at low-quality
-// bases (-t, :508-563). `-f` = fixSNPs() on the reads of the second pass (:828). Everything else (`index`, `-u`, `-p/-P`, `-a`) is out of scope.
+// bases (-t, :508-563). `-f` = fixSNPs() on the reads of the second pass (:828). `correct -s SHORT -l LONG -o OUT` without -g / -d builds the indexes
+// with rtk_build_index --gpu and runs the passes, each step a child process (correct_from_short_reads). Everything else (`index`, `-u`, `-p/-P`, `-a`) is out of scope.
 #include <getopt.h>
 #include <zlib.h>
 
+#include <algorithm>
 #include <atomic>
+#include <cerrno>
 #include <chrono>
 #include <condition_variable>
 #include <cstdio>
@@ -35,13 +38,17 @@
 #include <vector>
 
 #include <fcntl.h>
+#include <spawn.h>
+#include <sys/wait.h>
 #include <unistd.h>
 
 #include "../common/fastx.hpp"
 #include "ratatosk_hip.h"
 
 struct Opt {
-    std::vector<std::string> in_long, in_long_raw;
+    std::vector<std::string> in_long, in_long_raw, in_short; // in_short (-s): the index steps of `correct -s` (below)
+    std::vector<std::string> fwd1, fwd2; // the options given that the first / second correction step of `correct -s` passes on
+    bool no_snps = false;
     std::string out, graph, udata;
     bool workers_given = false;
     int cores = 1, gpus = 0, workers_per_gpu = 0, k1 = 31, k2 = 63, max_qual = 40, trim = 0, rounds = 1;
@@ -52,7 +59,11 @@ struct Opt {
 };
 
 static void usage() {
-    fprintf(stderr, "Ratatosk (MI355X hot-path build)\n\nUsage: Ratatosk correct -1 -g <graph.fasta.gz> -d <unitig_data.rtsk> -l <long_reads> -o <out_prefix> [options]\n"
+    fprintf(stderr, "Ratatosk (MI355X hot-path build)\n\nUsage: Ratatosk correct -s <short_reads> [-s ...] -l <long_reads> -o <out_prefix> [options]\n"
+                    "  both passes in one run: the index of each pass built from the short reads (rtk_build_index --gpu, k1 then k2), pass 1, pass 2;\n"
+                    "  writes <out_prefix>.fastq (-G: .fastq.gz). With -1 or -2 (-2: -l <out_prefix>.2.fastq -L <long_reads>) the index of that pass and that pass only.\n"
+                    "  -F, --no-snp-correction  build the indexes without SNP annotations\n\n"
+                    "       Ratatosk correct -1 -g <graph.fasta.gz> -d <unitig_data.rtsk> -l <long_reads> -o <out_prefix> [options]\n"
                     "  -c, --cores           number of host threads (default 1): index parsing, FASTQ formatting\n"
                     "      --gpus            number of GPUs to use (default: all visible)\n"
                     "      --workers-per-gpu tickets in flight per GPU (default 3; with -2 up to 8, as many as the device memory holds)\n"
@@ -97,6 +108,78 @@ static void append_trimmed(std::string& out, const char* name, size_t name_len, 
 // first-pass reader, bgzip, htslib) can inflate it on many threads. (Blocks are small, so zlib's 32-bit counters are never near their limit.)
 static bool gzip_member(const std::string& in, std::string& out) { out.clear(); return rtk::bgzf_compress(in.data(), in.size(), out); }
 
+// `correct -s SHORT -l LONG -o OUT` (no -g / -d): the reference's one-command run (src/Ratatosk.cpp:1040-1277) as a chain of fresh child processes --
+// this process never opens the GPU. Both passes (neither -1 nor -2): the k1 index of the short reads, pass 1 into OUT.2.fastq, the k2 index of the short
+// reads coloured by OUT.2.fastq, pass 2 into OUT.fastq[.gz]; the temporary index files and OUT.2.fastq are removed afterwards (src/Ratatosk.cpp:1268-1277).
+// -1 / -2: the index of that pass, then that pass. The first step that fails ends the run (non-zero exit, the step named); nothing is tried again.
+static int run_step(const char* what, const std::vector<std::string>& args, bool verbose) {
+    std::vector<char*> av; for (size_t i = 0; i < args.size(); ++i) av.push_back(const_cast<char*>(args[i].c_str())); av.push_back(nullptr);
+    if (verbose) { fprintf(stderr, "Ratatosk::correct: %s:", what); for (size_t i = 0; i < args.size(); ++i) fprintf(stderr, " %s", args[i].c_str()); fprintf(stderr, "\n"); }
+    pid_t pid = 0;
+    const int rc = posix_spawn(&pid, av[0], nullptr, nullptr, av.data(), environ);
+    if (rc != 0) { fprintf(stderr, "Ratatosk::correct: %s: cannot start %s (%s)\n", what, av[0], strerror(rc)); return 1; }
+    int st = 0;
+    while (waitpid(pid, &st, 0) < 0) if (errno != EINTR) { fprintf(stderr, "Ratatosk::correct: %s: waitpid failed (%s)\n", what, strerror(errno)); return 1; }
+    if (WIFEXITED(st) && WEXITSTATUS(st) == 0) return 0;
+    if (WIFEXITED(st)) fprintf(stderr, "Ratatosk::correct: %s failed (exit status %d)\n", what, WEXITSTATUS(st));
+    else fprintf(stderr, "Ratatosk::correct: %s failed (signal %d)\n", what, WIFSIGNALED(st) ? WTERMSIG(st) : 0);
+    return 1;
+}
+
+static int correct_from_short_reads(const Opt& opt, const char* argv0) {
+    const bool both = !opt.pass1 && !opt.pass2;
+    if (opt.pass1 && opt.pass2) { fprintf(stderr, "Ratatosk::correct: -1 and -2 exclude each other (neither: both passes)\n"); return 1; }
+    if (opt.in_long.empty() || opt.out.empty()) { fprintf(stderr, "Ratatosk::correct: -s, -l and -o are required\n"); return 1; }
+    if (opt.pass2 && opt.in_long_raw.empty()) { fprintf(stderr, "Ratatosk::correct: -2 needs the uncorrected long reads (-L) next to the pass-1 reads (-l)\n"); return 1; }
+    if (opt.k1 < 3 || opt.k1 > 31 || !(opt.k1 & 1) || opt.k2 < 3 || opt.k2 > 63 || !(opt.k2 & 1)) { fprintf(stderr, "Ratatosk::correct: k1 must be odd and <= 31, k2 odd and <= 63\n"); return 1; }
+    std::string self = argv0; // this executable and the index tool next to it
+    { char exe[4096]; const ssize_t n = readlink("/proc/self/exe", exe, sizeof(exe) - 1); if (n > 0) { exe[n] = 0; self = exe; } }
+    const std::string dir = self.find('/') == std::string::npos ? std::string(".") : self.substr(0, self.rfind('/')), tool = dir + "/rtk_build_index";
+    if (opt.cores > 0 && std::find(opt.fwd1.begin(), opt.fwd1.end(), std::string("-c")) != opt.fwd1.end()) setenv("RTK_INDEX_THREADS", std::to_string(opt.cores).c_str(), 1); // (else the tool sizes itself by the machine)
+    auto index_args = [&](int k, const std::string& prefix, const std::vector<std::string>& colour) {
+        std::vector<std::string> a; a.push_back(tool); a.push_back("--gpu"); a.push_back("-k"); a.push_back(std::to_string(k));
+        for (size_t i = 0; i < opt.in_short.size(); ++i) { a.push_back("-s"); a.push_back(opt.in_short[i]); }
+        for (size_t i = 0; i < colour.size(); ++i) { a.push_back("--colour-reads"); a.push_back(colour[i]); }
+        if (!opt.no_snps) a.push_back("--snps");
+        a.push_back("-o"); a.push_back(prefix); return a;
+    };
+    auto index_files = [&](int k, const std::string& prefix) { const std::string p = prefix + ".index.k" + std::to_string(k); return std::make_pair(p + ".fasta.gz", p + ".rtsk"); };
+    const std::string pre1 = opt.out + ".tmp.k1", pre2 = opt.out + ".tmp.k2", mid = opt.out + ".2.fastq";
+    const std::pair<std::string, std::string> f1 = index_files(opt.k1, pre1), f2 = index_files(opt.k2, pre2);
+    std::vector<std::string> tmp_files;
+    auto cleanup = [&]() { for (size_t i = 0; i < tmp_files.size(); ++i) unlink(tmp_files[i].c_str()); };
+    const auto t0 = std::chrono::steady_clock::now();
+    auto since = [&]() { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); };
+    const bool v = opt.verbose;
+    if (both || opt.pass1) {
+        if (v) fprintf(stderr, "Ratatosk::Ratatosk(): Building graph from short reads (1/2).\n");
+        tmp_files.push_back(f1.first); tmp_files.push_back(f1.second);
+        if (run_step("step 1 (k1 index, rtk_build_index)", index_args(opt.k1, pre1, std::vector<std::string>()), v)) { cleanup(); return 1; }
+        if (v) fprintf(stderr, "Ratatosk::Ratatosk(): Correcting long reads (1/2). [%.1f s]\n", since());
+        std::vector<std::string> a; a.push_back(self); a.push_back("correct"); a.push_back("-1"); a.push_back("-g"); a.push_back(f1.first); a.push_back("-d"); a.push_back(f1.second);
+        for (size_t i = 0; i < opt.in_long.size(); ++i) { a.push_back("-l"); a.push_back(opt.in_long[i]); }
+        a.push_back("-o"); a.push_back(opt.out); a.insert(a.end(), opt.fwd1.begin(), opt.fwd1.end());
+        if (run_step("step 2 (first correction pass)", a, v)) { cleanup(); return 1; }
+        cleanup(); tmp_files.clear();
+    }
+    if (both || opt.pass2) {
+        const std::vector<std::string> p1_reads = both ? std::vector<std::string>(1, mid) : opt.in_long, raw = both ? opt.in_long : opt.in_long_raw;
+        if (both) tmp_files.push_back(mid);
+        if (v) fprintf(stderr, "Ratatosk::Ratatosk(): Building graph from short reads (2/2). [%.1f s]\n", since());
+        tmp_files.push_back(f2.first); tmp_files.push_back(f2.second);
+        if (run_step("step 3 (k2 index, rtk_build_index)", index_args(opt.k2, pre2, p1_reads), v)) { cleanup(); return 1; }
+        if (v) fprintf(stderr, "Ratatosk::Ratatosk(): Correcting long reads (2/2). [%.1f s]\n", since());
+        std::vector<std::string> a; a.push_back(self); a.push_back("correct"); a.push_back("-2"); a.push_back("-g"); a.push_back(f2.first); a.push_back("-d"); a.push_back(f2.second);
+        for (size_t i = 0; i < p1_reads.size(); ++i) { a.push_back("-l"); a.push_back(p1_reads[i]); }
+        for (size_t i = 0; i < raw.size(); ++i) { a.push_back("-L"); a.push_back(raw[i]); }
+        a.push_back("-o"); a.push_back(opt.out); a.insert(a.end(), opt.fwd2.begin(), opt.fwd2.end());
+        if (run_step("step 4 (second correction pass)", a, v)) { cleanup(); return 1; }
+        cleanup();
+    }
+    if (v) fprintf(stderr, "Ratatosk::Ratatosk(): Done. [%.1f s]\n", since());
+    return 0;
+}
+
 int main(int argc, char** argv) {
     // Every ticket in flight owns a HIP stream (the phasing step of the second pass three), and their kernels are mostly narrow (one long read,
     // one big region): they only overlap if the runtime gives the streams hardware queues of their own. ROCm's default is 4 per process.
@@ -117,6 +200,15 @@ int main(int argc, char** argv) {
         {"batch-bases", required_argument, 0, 'B'}, {"strip-annotations", no_argument, 0, 1001}, {"gpus", required_argument, 0, 1002}, {"workers-per-gpu", required_argument, 0, 1003}, {"parse-only", no_argument, 0, 1004}, {"allow-tinybitmap", no_argument, 0, 1005}, {"verbose", no_argument, 0, 'v'}, {0, 0, 0, 0}};
     int c, idx = 0;
     while ((c = getopt_long(argc - 1, argv + 1, "s:l:o:c:g:d:i:k:w:Q:m:B:L:K:W:t:r:u:a:p:P:S:M:C:GFOIf12v", lo, &idx)) != -1) {
+        { // what `correct -s` hands on to its correction steps: the option as given (long options by their long name)
+            std::string flag; if (c == 1002) flag = "--gpus"; else if (c == 1003) flag = "--workers-per-gpu"; else if (c > 0 && c < 128) flag = std::string("-") + static_cast<char>(c);
+            const bool p1 = c > 0 && c < 128 && strchr("ckwrBiQmv", c) != nullptr, p2 = c > 0 && c < 128 && strchr("cKWBiQmtGfv", c) != nullptr;
+            if (c == 1002 || c == 1003 || p1 || p2) {
+                std::vector<std::string> a(1, flag); if (optarg) a.push_back(optarg);
+                if (c == 1002 || c == 1003 || p1) opt.fwd1.insert(opt.fwd1.end(), a.begin(), a.end());
+                if (c == 1002 || c == 1003 || p2) opt.fwd2.insert(opt.fwd2.end(), a.begin(), a.end());
+            }
+        }
         switch (c) {
             case 'l': opt.in_long.push_back(optarg); break;
             case 'o': opt.out = optarg; break;
@@ -130,7 +222,8 @@ int main(int argc, char** argv) {
             case 'm': opt.min_conf_snp = atof(optarg); break;
             case 'B': opt.batch_bases = strtoull(optarg, nullptr, 10); break;
             case 'r': opt.rounds = atoi(optarg); break;
-            case 'F': case 'I': case 'S': case 'M': case 'C': break; // only read by `index` (detectSNPs, .bfi, addCoverage: src/Ratatosk.cpp:1067,1124; src/Graph.cpp:1573,1796,2117)
+            case 'F': opt.no_snps = true; break; // only read by the index step (detectSNPs, src/Ratatosk.cpp:1067,1124): `correct -s` builds its indexes without --snps
+            case 'I': case 'S': case 'M': case 'C': break; // only read by `index` (detectSNPs, .bfi, addCoverage: src/Ratatosk.cpp:1067,1124; src/Graph.cpp:1573,1796,2117)
             case 'O': break; // output is in input order in both passes here (src/Ratatosk.cpp:919 re-orders only when asked in pass 2)
             case 'f': opt.force_snp = true; break; // fixSNPs() before phasing() in the second pass (src/Ratatosk.cpp:279,828); the first pass does not look at it
             case 'u': case 'a': case 'p': case 'P': fprintf(stderr, "Ratatosk::correct: -%c (unmapped-read rescue / helper long reads / phased input) is not in scope of this build\n", c); return 1;
@@ -147,13 +240,15 @@ int main(int argc, char** argv) {
             case 1003: opt.workers_per_gpu = atoi(optarg); opt.workers_given = true; break;
             case 1004: opt.parse_only = true; break;
             case 1005: setenv("RTK_ALLOW_TINYBITMAP", "1", 1); break; // the loader reads it (common/rtsk_io.hpp): colour sets written as Bifrost TinyBitmap streams are decoded under assumption [A8]
-            case 's': fprintf(stderr, "Ratatosk::correct: short reads are only needed by `index` (not in scope); ignored\n"); break;
+            case 's': opt.in_short.push_back(optarg); break; // (with -g / -d: ignored, said below)
             default: usage(); return 0; // the reference returns 0 on option errors too (src/Ratatosk.cpp:1018)
         }
     }
     // the reference drops arguments that belong to no option without a word (getopt_long permutes them to the end, src/Ratatosk.cpp:186-300):
     // `-l a.fq b.fq` corrects a.fq only. Same here, but said aloud.
     for (int i = optind; i < argc - 1; ++i) fprintf(stderr, "Ratatosk::correct: argument '%s' belongs to no option and is ignored (several input files: one -l each, or a text file of paths)\n", argv[1 + i]);
+    if (!opt.in_short.empty() && opt.graph.empty() && opt.udata.empty()) return correct_from_short_reads(opt, argv[0]);
+    for (size_t i = 0; i < opt.in_short.size(); ++i) fprintf(stderr, "Ratatosk::correct: short reads are only needed by `index` (not in scope); ignored\n");
     if (opt.pass1 == opt.pass2) { fprintf(stderr, "Ratatosk::correct: one pass per run with a pre-built index (-g, -d): give -1 or -2\n"); return 1; }
     const bool lrc = opt.pass2;
     // ticket size when -B is not given. First pass: 64 Mi (1.22 x 10^9 bases/s file to file against 1.19 at 32 Mi and 1.05-1.20 at 96 Mi, profiles/r06_split_and_cli_B.txt: a ticket's launches carry

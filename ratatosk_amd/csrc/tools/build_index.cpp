@@ -66,7 +66,7 @@ template <class KM> struct KTable { // open addressing: canonical k-mer -> 64-bi
 
 struct Unitig { std::string seq; std::vector<uint32_t> colours; uint64_t cov = 0; };
 
-// ---------------------------------------------------------------------------------------------- --fast / --gpu: thread-parallel steps (one-word k-mers)
+// ---------------------------------------------------------------------------------------------- --fast / --gpu: thread-parallel steps (one- and two-word k-mers)
 // They must produce what the plain path produces, byte for byte: the plain path stays the definition (and the fallback).
 template <class F> static void parallel_for(size_t n, unsigned n_thr, F f) { // f(begin, end, thread)
     if (n_thr < 1) n_thr = 1;
@@ -82,49 +82,51 @@ template <class F> static void parallel_for(size_t n, unsigned n_thr, F f) { // 
 // away from rc(x) (offset k-1-j, complemented base): a query scans the few entries that share a half with x, then with rc(x). Round 5: 8 bytes per
 // solid k-mer beside the k-mer set (26 GB at 3 Gb; the first version kept both orientations in both views, 103 GB + a sorting copy: `--snps` did not fit
 // a 3 Gb run). Used by the SNP search of --fast / --gpu (the plain path probes every variant in the k-mer table).
-struct NeighbourIndex {
-    int k = 0, hi_n = 0, lo_n = 0; uint64_t lomask = 0;
-    const uint64_t* a = nullptr; size_t n = 0; std::vector<uint64_t> b; std::vector<uint64_t> ia, ib; int shift = 0; // ia / ib: first entry of every value of the top 24 bits of the 2k-bit key
-    uint64_t rot(uint64_t x) const { return ((x & lomask) << (2 * hi_n)) | (x >> (2 * lo_n)); }
-    uint64_t unrot(uint64_t r) const { return ((r & ((1ULL << (2 * hi_n)) - 1ULL)) << (2 * lo_n)) | (r >> (2 * hi_n)); }
-    void build(const std::vector<uint64_t>& solid, int k_, unsigned n_thr) {
-        k = k_; hi_n = k / 2; lo_n = k - hi_n; lomask = (1ULL << (2 * lo_n)) - 1ULL;
+template <class KM> struct NeighbourIndex { // KM: uint64_t, or u128 for two-word k-mers (16 bytes per solid k-mer beside the k-mer set)
+    int k = 0, hi_n = 0, lo_n = 0; KM lomask = 0;
+    const KM* a = nullptr; size_t n = 0; std::vector<KM> b; std::vector<uint64_t> ia, ib; int shift = 0; // ia / ib: first entry of every value of the top 24 bits of the 2k-bit key
+    static int ctz(KM m) { const uint64_t lo = static_cast<uint64_t>(m); return lo ? __builtin_ctzll(lo) : 64 + __builtin_ctzll(static_cast<uint64_t>(m >> (sizeof(KM) > 8 ? 64 : 0))); }
+    KM rot(KM x) const { return ((x & lomask) << (2 * hi_n)) | (x >> (2 * lo_n)); }
+    KM unrot(KM r) const { return ((r & ((static_cast<KM>(1) << (2 * hi_n)) - 1)) << (2 * lo_n)) | (r >> (2 * hi_n)); }
+    void build(const std::vector<KM>& solid, int k_, unsigned n_thr) {
+        k = k_; hi_n = k / 2; lo_n = k - hi_n; lomask = (static_cast<KM>(1) << (2 * lo_n)) - 1;
         a = solid.data(); n = solid.size();
         // view two without a second copy: the rotated keys are counted by their top 12 bits per thread slice, scattered to their bucket's place, every bucket sorted by a thread
         const int bsh = 2 * k > 12 ? 2 * k - 12 : 0; const size_t nbk = static_cast<size_t>(1) << (2 * k - bsh);
         if (n_thr == 0) n_thr = 1;
         std::vector<std::vector<size_t> > cnt(n_thr, std::vector<size_t>(nbk, 0));
-        parallel_for(n, n_thr, [&](size_t bb, size_t ee, unsigned t) { for (size_t i = bb; i < ee; ++i) ++cnt[t][rot(a[i]) >> bsh]; });
+        parallel_for(n, n_thr, [&](size_t bb, size_t ee, unsigned t) { for (size_t i = bb; i < ee; ++i) ++cnt[t][static_cast<size_t>(rot(a[i]) >> bsh)]; });
         std::vector<size_t> start(nbk + 1, 0);
         { size_t at = 0; for (size_t q = 0; q < nbk; ++q) { start[q] = at; for (unsigned t = 0; t < n_thr; ++t) { const size_t c = cnt[t][q]; cnt[t][q] = at; at += c; } } start[nbk] = at; }
         b.resize(n);
-        parallel_for(n, n_thr, [&](size_t bb, size_t ee, unsigned t) { for (size_t i = bb; i < ee; ++i) { const uint64_t r = rot(a[i]); b[cnt[t][r >> bsh]++] = r; } });
+        parallel_for(n, n_thr, [&](size_t bb, size_t ee, unsigned t) { for (size_t i = bb; i < ee; ++i) { const KM r = rot(a[i]); b[cnt[t][static_cast<size_t>(r >> bsh)]++] = r; } });
         { std::atomic<size_t> nx(0); std::vector<std::thread> th;
           for (unsigned t = 0; t < n_thr; ++t) th.emplace_back([&]() { for (;;) { const size_t q = nx.fetch_add(1); if (q >= nbk) break; std::sort(b.begin() + start[q], b.begin() + start[q + 1]); } });
           for (size_t t = 0; t < th.size(); ++t) th[t].join(); }
         shift = 2 * k > 24 ? 2 * k - 24 : 0;
         const size_t nb = (static_cast<size_t>(1) << (2 * k - shift)) + 1;
-        auto index = [&](const uint64_t* v, std::vector<uint64_t>& ix) { ix.assign(nb, 0); for (size_t i = 0; i < n; ++i) ++ix[(v[i] >> shift) + 1]; for (size_t i = 0; i + 1 < nb; ++i) ix[i + 1] += ix[i]; };
+        auto index = [&](const KM* v, std::vector<uint64_t>& ix) { ix.assign(nb, 0); for (size_t i = 0; i < n; ++i) ++ix[static_cast<size_t>(v[i] >> shift) + 1]; for (size_t i = 0; i + 1 < nb; ++i) ix[i + 1] += ix[i]; };
         std::thread t2([&]() { index(b.data(), ib); }); index(a, ia); t2.join();
     }
     // the canonical k-mers one substitution away from x, as (offset << 2 | base) of the ORIENTED neighbour of the caller's k-mer (flipped: x is its reverse complement)
-    void scan(uint64_t x, bool flipped, uint32_t* found, int& nf) const {
-        auto put = [&](int bit, uint64_t y) { int j = k - 1 - bit / 2; uint32_t base = static_cast<uint32_t>((y >> bit) & 3ULL); if (flipped) { j = k - 1 - j; base = 3u - base; } if (nf < 192) found[nf++] = (static_cast<uint32_t>(j) << 2) | base; };
+    void scan(KM x, bool flipped, uint32_t* found, int& nf) const {
+        const KM m55 = ~static_cast<KM>(0) / 3; // 0101...01
+        auto put = [&](int bit, KM y) { int j = k - 1 - bit / 2; uint32_t base = static_cast<uint32_t>((y >> bit) & static_cast<KM>(3)); if (flipped) { j = k - 1 - j; base = 3u - base; } if (nf < 192) found[nf++] = (static_cast<uint32_t>(j) << 2) | base; };
         { // same first half: the differing base lies in the last lo_n bases
-            const uint64_t lo_key = x & ~lomask, hi_key = x | lomask;
-            size_t i = ia[lo_key >> shift]; const size_t e = ia[(hi_key >> shift) + 1];
+            const KM lo_key = x & ~lomask, hi_key = x | lomask;
+            size_t i = ia[static_cast<size_t>(lo_key >> shift)]; const size_t e = ia[static_cast<size_t>(hi_key >> shift) + 1];
             i = static_cast<size_t>(std::lower_bound(a + i, a + e, lo_key) - a);
-            for (; i < e && a[i] <= hi_key; ++i) { const uint64_t d = a[i] ^ x; if (d == 0) continue; const uint64_t m = (d | (d >> 1)) & 0x5555555555555555ULL; if (m & (m - 1)) continue; put(__builtin_ctzll(m), a[i]); }
+            for (; i < e && a[i] <= hi_key; ++i) { const KM d = a[i] ^ x; if (d == 0) continue; const KM m = (d | (d >> 1)) & m55; if (m & (m - 1)) continue; put(ctz(m), a[i]); }
         }
         { // same last half: the differing base lies in the first hi_n bases
-            const uint64_t r = rot(x), himask = (1ULL << (2 * hi_n)) - 1ULL; const uint64_t lo_key = r & ~himask, hi_key = r | himask;
-            size_t i = ib[lo_key >> shift]; const size_t e = ib[(hi_key >> shift) + 1];
+            const KM r = rot(x), himask = (static_cast<KM>(1) << (2 * hi_n)) - 1; const KM lo_key = r & ~himask, hi_key = r | himask;
+            size_t i = ib[static_cast<size_t>(lo_key >> shift)]; const size_t e = ib[static_cast<size_t>(hi_key >> shift) + 1];
             i = static_cast<size_t>(std::lower_bound(b.begin() + i, b.begin() + e, lo_key) - b.begin());
-            for (; i < e && b[i] <= hi_key; ++i) { const uint64_t y = unrot(b[i]); const uint64_t d = y ^ x; if (d == 0) continue; const uint64_t m = (d | (d >> 1)) & 0x5555555555555555ULL; if (m & (m - 1)) continue; put(__builtin_ctzll(m), y); }
+            for (; i < e && b[i] <= hi_key; ++i) { const KM y = unrot(b[i]); const KM d = y ^ x; if (d == 0) continue; const KM m = (d | (d >> 1)) & m55; if (m & (m - 1)) continue; put(ctz(m), y); }
         }
     }
     // calls f(offset j, substituted base) for every graph k-mer one substitution away from x, by (j, base) ascending
-    template <class F> void neighbours(uint64_t x, F f) const {
+    template <class F> void neighbours(KM x, F f) const {
         uint32_t found[192]; int nf = 0; // (j << 2 | base): at most 3 per offset, 3k <= 93 in all (a k-mer of a tandem repeat at small k has dozens: 16 slots lost some, found by tests/test_annotators.py)
         scan(x, false, found, nf); scan(kmer_revcomp(x, k), true, found, nf);
         std::sort(found, found + nf);
@@ -132,12 +134,7 @@ struct NeighbourIndex {
     }
 };
 
-static const std::vector<uint64_t>& solid64(const std::vector<uint64_t>& v) { return v; }
-static const std::vector<uint64_t>& solid64(const std::vector<u128>&) { static const std::vector<uint64_t> none; return none; }
-// (two-word k-mers take the plain path: these overloads are never reached)
-static void fast_table_fill(KTable<u128>&, const std::vector<u128>&, unsigned) {}
-struct DeviceUnitigs { const char* pool = nullptr; const uint64_t* off = nullptr; const uint64_t* seeds = nullptr; uint64_t n = 0; const uint64_t* left = nullptr; uint64_t n_left = 0; }; // what rtk_index_unitigs returns (--gpu)
-static bool fast_unitigs(KTable<u128>&, const std::vector<u128>&, int, unsigned, std::vector<Unitig>&, const DeviceUnitigs*) { return false; }
+struct DeviceUnitigs { const char* pool = nullptr; const uint64_t* off = nullptr; const uint64_t* seeds = nullptr; uint64_t n = 0; const uint64_t* left = nullptr; uint64_t n_left = 0; }; // what rtk_index_unitigs returns (--gpu; two-word k-mers: two words each)
 
 // every solid k-mer into the table with value 0 (slots claimed with a compare-and-swap on the key word; the table does not grow here)
 static void fast_table_fill(KTable<uint64_t>& km, const std::vector<uint64_t>& solid, unsigned n_thr) {
@@ -156,6 +153,23 @@ static void fast_table_fill(KTable<uint64_t>& km, const std::vector<uint64_t>& s
     });
     km.n = solid.size();
 }
+// two-word k-mers: the solid k-mers are distinct and the high word of a 2k-bit code (k <= 63) is never all ones, so a slot is claimed with a
+// 64-bit compare-and-swap on its high word and its low word written by the thread that owns it (nothing reads the table before the threads join)
+static void fast_table_fill(KTable<u128>& km, const std::vector<u128>& solid, unsigned n_thr) {
+    const uint64_t EMPTY = ~0ULL;
+    uint64_t* words = reinterpret_cast<uint64_t*>(km.keys.data()); const size_t mask = km.mask; // slot s: words[2 s] low, words[2 s + 1] high
+    parallel_for(solid.size(), n_thr, [&](size_t b, size_t e, unsigned) {
+        for (size_t i = b; i < e; ++i) {
+            const u128 key = solid[i]; const uint64_t hi = static_cast<uint64_t>(key >> 64); size_t s = hash_km(key) & mask;
+            while (true) {
+                uint64_t exp = EMPTY;
+                if (__atomic_compare_exchange_n(&words[2 * s + 1], &exp, hi, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) { __atomic_store_n(&words[2 * s], static_cast<uint64_t>(key), __ATOMIC_RELAXED); break; }
+                s = (s + 1) & mask;
+            }
+        }
+    });
+    km.n = solid.size();
+}
 
 // Unitigs by walking every maximal chain of mutually unique links from its ends, on all threads. The plain construction starts a unitig at the
 // first unvisited k-mer in sorted order, in its canonical orientation, and follows the links both ways: for a chain that never meets one of its
@@ -163,37 +177,37 @@ static void fast_table_fill(KTable<uint64_t>& km, const std::vector<uint64_t>& s
 // smallest k-mers. Chains that do meet themselves (closed loops, hairpins through a reverse complement) are left to the plain code, which
 // then only sees their k-mers; all unitigs are put in the order of their first k-mers at the end. Returns false (nothing kept) if a k-mer
 // ended up on two unitigs -- the caller then runs the plain construction.
-static bool fast_unitigs(KTable<uint64_t>& km, const std::vector<uint64_t>& solid, int k, unsigned n_thr, std::vector<Unitig>& U, const DeviceUnitigs* dev) {
-    const uint64_t mask = kmer_mask(k);
-    auto in_graph = [&](uint64_t oriented) -> bool { return km.slot(kmer_canonical(oriented, k), false) != nullptr; };
-    auto succs = [&](uint64_t x, uint64_t out[4]) -> int { int n = 0; for (uint64_t b = 0; b < 4; ++b) { const uint64_t y = ((x << 2) | b) & mask; if (in_graph(y)) out[n++] = y; } return n; };
-    auto preds = [&](uint64_t x, uint64_t out[4]) -> int { int n = 0; for (uint64_t b = 0; b < 4; ++b) { const uint64_t y = (x >> 2) | (b << (2 * (k - 1))); if (in_graph(y)) out[n++] = y; } return n; };
-    auto next = [&](uint64_t x, uint64_t* y) -> bool { uint64_t nb[4], nb2[4]; if (succs(x, nb) != 1) return false; if (preds(nb[0], nb2) != 1) return false; *y = nb[0]; return true; }; // the link the plain code follows forwards
-    auto prev = [&](uint64_t x, uint64_t* y) -> bool { uint64_t nb[4], nb2[4]; if (preds(x, nb) != 1) return false; if (succs(nb[0], nb2) != 1) return false; *y = nb[0]; return true; };
-    struct Rec { uint64_t seed; std::string seq; };
+template <class KM> static bool fast_unitigs(KTable<KM>& km, const std::vector<KM>& solid, int k, unsigned n_thr, std::vector<Unitig>& U, const DeviceUnitigs* dev) {
+    const KM mask = km_mask<KM>(k);
+    auto in_graph = [&](KM oriented) -> bool { return km.slot(kmer_canonical(oriented, k), false) != nullptr; };
+    auto succs = [&](KM x, KM out[4]) -> int { int n = 0; for (uint64_t b = 0; b < 4; ++b) { const KM y = ((x << 2) | static_cast<KM>(b)) & mask; if (in_graph(y)) out[n++] = y; } return n; };
+    auto preds = [&](KM x, KM out[4]) -> int { int n = 0; for (uint64_t b = 0; b < 4; ++b) { const KM y = (x >> 2) | (static_cast<KM>(b) << (2 * (k - 1))); if (in_graph(y)) out[n++] = y; } return n; };
+    auto next = [&](KM x, KM* y) -> bool { KM nb[4], nb2[4]; if (succs(x, nb) != 1) return false; if (preds(nb[0], nb2) != 1) return false; *y = nb[0]; return true; }; // the link the plain code follows forwards
+    auto prev = [&](KM x, KM* y) -> bool { KM nb[4], nb2[4]; if (preds(x, nb) != 1) return false; if (succs(nb[0], nb2) != 1) return false; *y = nb[0]; return true; };
+    struct Rec { KM seed; std::string seq; };
     std::vector<std::vector<Rec> > out(n_thr);
     std::atomic<bool> clash(false);
-    auto claim = [&](uint64_t canonical) { uint64_t* v = km.slot(canonical, false); if (__atomic_exchange_n(v, 1ULL, __ATOMIC_RELAXED) != 0) clash = true; };
+    auto claim = [&](KM canonical) { uint64_t* v = km.slot(canonical, false); if (__atomic_exchange_n(v, 1ULL, __ATOMIC_RELAXED) != 0) clash = true; };
     if (!dev) parallel_for(solid.size(), n_thr, [&](size_t b, size_t e, unsigned t) {
-        std::vector<uint64_t> path;
+        std::vector<KM> path;
         for (size_t i = b; i < e && !clash; ++i) {
-            const uint64_t s = solid[i]; uint64_t y;
+            const KM s = solid[i]; KM y;
             const bool has_fw = next(s, &y), has_bw = prev(s, &y);
             if (has_fw && has_bw) continue; // inside a chain (or on a closed loop)
             // walk inwards from this end: forwards from s if nothing links into it from behind, else forwards from its reverse complement
-            uint64_t x = has_bw ? kmer_revcomp(s, k) : s;
+            KM x = has_bw ? kmer_revcomp(s, k) : s;
             path.clear(); path.push_back(x);
             while (next(x, &y)) { path.push_back(y); x = y; if (path.size() > solid.size()) break; }
-            const uint64_t end_c = kmer_canonical(path.back(), k);
+            const KM end_c = kmer_canonical(path.back(), k);
             if (path.size() > 1 && end_c == s) continue;         // the chain comes back to its own first k-mer (hairpin): plain code
             if (end_c < s) continue;                              // the other end owns the chain
             if (path.size() > solid.size()) continue;
             // orient: the smallest canonical k-mer of the chain reads forwards
-            size_t m = 0; uint64_t mc = kmer_canonical(path[0], k);
-            for (size_t j = 1; j < path.size(); ++j) { const uint64_t c = kmer_canonical(path[j], k); if (c < mc) { mc = c; m = j; } }
+            size_t m = 0; KM mc = kmer_canonical(path[0], k);
+            for (size_t j = 1; j < path.size(); ++j) { const KM c = kmer_canonical(path[j], k); if (c < mc) { mc = c; m = j; } }
             bool dup = false; // a chain that holds a k-mer and its reverse complement without coming back to its first k-mer cannot exist (the links are symmetric); checked by the claims below
             if (path[m] != mc) { std::reverse(path.begin(), path.end()); for (size_t j = 0; j < path.size(); ++j) path[j] = kmer_revcomp(path[j], k); }
-            Rec r; r.seed = mc; r.seq = kmer_decode(path[0], k);
+            Rec r; r.seed = mc; r.seq = km_decode<KM>(path[0], k);
             for (size_t j = 1; j < path.size(); ++j) r.seq.push_back(bits2base(static_cast<int>(path[j] & 3)));
             for (size_t j = 0; j < path.size(); ++j) claim(kmer_canonical(path[j], k));
             (void)dup;
@@ -206,27 +220,27 @@ static bool fast_unitigs(KTable<uint64_t>& km, const std::vector<uint64_t>& soli
     {
         // (the k-mers no chain has claimed are looked for on all threads -- one table probe per solid k-mer, a cache miss each -- and come out in
         // sorted order, thread after thread; the plain construction then only visits those)
-        std::vector<uint64_t> left;
-        if (dev) left.assign(dev->left, dev->left + dev->n_left); // (--gpu: the chains were walked, written and claimed on the device)
+        std::vector<KM> left;
+        if (dev) { const KM* dl = reinterpret_cast<const KM*>(dev->left); left.assign(dl, dl + dev->n_left); } // (--gpu: the chains were walked, written and claimed on the device)
         else {
-            std::vector<std::vector<uint64_t> > left_t(n_thr);
+            std::vector<std::vector<KM> > left_t(n_thr);
             parallel_for(solid.size(), n_thr, [&](size_t b, size_t e, unsigned t) { for (size_t i = b; i < e; ++i) if (*km.slot(solid[i], false) == 0) left_t[t].push_back(solid[i]); });
             for (unsigned t = 0; t < n_thr; ++t) left.insert(left.end(), left_t[t].begin(), left_t[t].end());
         }
         size_t lcap = 16; while (lcap * 6 < left.size() * 10 + 16) lcap <<= 1; lcap <<= 1;
-        KTable<uint64_t> lt(lcap); // the left-over k-mers: 0 = free, 1 = on a unitig built below; a k-mer that is not in it lies on a chain built above
+        KTable<KM> lt(lcap); // the left-over k-mers: 0 = free, 1 = on a unitig built below; a k-mer that is not in it lies on a chain built above
         for (size_t li = 0; li < left.size(); ++li) *lt.slot(left[li], true) = 0;
-        auto taken = [&](uint64_t c) -> bool { const uint64_t* v = lt.slot(c, false); return !v || *v != 0; };
-        std::set<uint64_t> in_this;
+        auto taken = [&](KM c) -> bool { const uint64_t* v = lt.slot(c, false); return !v || *v != 0; };
+        std::set<KM> in_this;
         for (size_t li = 0; li < left.size(); ++li) {
-            const uint64_t seed_km = left[li];
+            const KM seed_km = left[li];
             if (taken(seed_km)) continue;
             in_this.clear(); in_this.insert(seed_km);
-            std::vector<uint64_t> fwd(1, seed_km), bwd; uint64_t nb[4], nb2[4];
-            for (uint64_t x = seed_km;;) { if (succs(x, nb) != 1) break; const uint64_t y = nb[0]; if (preds(y, nb2) != 1) break; const uint64_t cy = kmer_canonical(y, k); if (in_this.count(cy) || taken(cy)) break; in_this.insert(cy); fwd.push_back(y); x = y; }
-            for (uint64_t x = seed_km;;) { if (preds(x, nb) != 1) break; const uint64_t y = nb[0]; if (succs(y, nb2) != 1) break; const uint64_t cy = kmer_canonical(y, k); if (in_this.count(cy) || taken(cy)) break; in_this.insert(cy); bwd.push_back(y); x = y; }
-            std::vector<uint64_t> path(bwd.rbegin(), bwd.rend()); path.insert(path.end(), fwd.begin(), fwd.end());
-            Rec r; r.seed = seed_km; r.seq = kmer_decode(path[0], k);
+            std::vector<KM> fwd(1, seed_km), bwd; KM nb[4], nb2[4];
+            for (KM x = seed_km;;) { if (succs(x, nb) != 1) break; const KM y = nb[0]; if (preds(y, nb2) != 1) break; const KM cy = kmer_canonical(y, k); if (in_this.count(cy) || taken(cy)) break; in_this.insert(cy); fwd.push_back(y); x = y; }
+            for (KM x = seed_km;;) { if (preds(x, nb) != 1) break; const KM y = nb[0]; if (succs(y, nb2) != 1) break; const KM cy = kmer_canonical(y, k); if (in_this.count(cy) || taken(cy)) break; in_this.insert(cy); bwd.push_back(y); x = y; }
+            std::vector<KM> path(bwd.rbegin(), bwd.rend()); path.insert(path.end(), fwd.begin(), fwd.end());
+            Rec r; r.seed = seed_km; r.seq = km_decode<KM>(path[0], k);
             for (size_t j = 1; j < path.size(); ++j) r.seq.push_back(bits2base(static_cast<int>(path[j] & 3)));
             for (size_t j = 0; j < path.size(); ++j) *lt.slot(kmer_canonical(path[j], k), false) = 1;
             rest.push_back(r);
@@ -238,7 +252,7 @@ static bool fast_unitigs(KTable<uint64_t>& km, const std::vector<uint64_t>& soli
     std::vector<Rec> dev_recs;
     if (dev) { // (already in the order of their seeds; the sequences are cut out of the pool where the table values are set, below)
         dev_recs.resize(dev->n);
-        parallel_for(dev_recs.size(), n_thr, [&](size_t b, size_t e, unsigned) { for (size_t i = b; i < e; ++i) { dev_recs[i].seed = dev->seeds[i]; dev_recs[i].seq.assign(dev->pool + dev->off[i], dev->pool + dev->off[i + 1]); } });
+        parallel_for(dev_recs.size(), n_thr, [&](size_t b, size_t e, unsigned) { for (size_t i = b; i < e; ++i) { dev_recs[i].seed = reinterpret_cast<const KM*>(dev->seeds)[i]; dev_recs[i].seq.assign(dev->pool + dev->off[i], dev->pool + dev->off[i + 1]); } });
         for (size_t i = 0; i < dev_recs.size(); ++i) all.push_back(&dev_recs[i]);
     }
     for (unsigned t = 0; t < n_thr; ++t) for (size_t i = 0; i < out[t].size(); ++i) all.push_back(&out[t][i]);
@@ -248,11 +262,11 @@ static bool fast_unitigs(KTable<uint64_t>& km, const std::vector<uint64_t>& soli
     parallel_for(all.size(), n_thr, [&](size_t b, size_t e, unsigned) {
         for (size_t uid = b; uid < e; ++uid) {
             U[uid].seq.swap(all[uid]->seq);
-            const std::string& q = U[uid].seq; uint64_t fw = 0;
+            const std::string& q = U[uid].seq; KM fw = 0;
             for (size_t i = 0; i < q.size(); ++i) {
-                fw = ((fw << 2) | static_cast<uint64_t>(base2bits(q[i]))) & mask;
+                fw = ((fw << 2) | static_cast<KM>(base2bits(q[i]))) & mask;
                 if (i + 1 < static_cast<size_t>(k)) continue;
-                bool is_fw; const uint64_t c = kmer_canonical(fw, k, &is_fw);
+                bool is_fw; const KM c = kmer_canonical(fw, k, &is_fw);
                 *km.slot(c, false) = ((static_cast<uint64_t>(uid) + 1) << 32) | (static_cast<uint64_t>(i + 1 - k) << 1) | (is_fw ? 1ULL : 0ULL);
             }
         }
@@ -269,7 +283,7 @@ template <class KM> static int run(int argc, char** argv) { // KM: uint64_t for 
     size_t min_cov_vertices = 2;
     double global_cov_factor = 3.0, min_color_sharing = 0.5;
     bool detect_cycles = true, detect_snps = false;
-    bool fast = false, gpu = false; // --fast: the same files from thread-parallel counting-table build / compaction / adjacency / cycle search; --gpu: --fast with the k-mers counted on the device
+    bool fast = false, gpu = false; // --fast: the same files from thread-parallel counting-table build / compaction / adjacency / cycle search; --gpu: --fast with counting, unitigs and colours on the device (any odd k <= 63)
     std::string dump_input; // --dump-input FILE: the inputs (sample: sources included) written out as one FASTQ file, nothing else done
     std::vector<std::string> colour_files; // pass-2 index (`Ratatosk index -2`): colours = ids of these (pass-1 corrected long) reads, one id per read
     for (int i = 1; i < argc; ++i) {
@@ -288,7 +302,7 @@ template <class KM> static int run(int argc, char** argv) { // KM: uint64_t for 
         else if (a == "--dump-input") dump_input = need("--dump-input");
         else { fprintf(stderr, "rtk_build_index: unknown option %s\n", a.c_str()); return 2; }
     }
-    if (in_files.empty() || k < 3 || k > RTK_MAX_K || !(k & 1)) { fprintf(stderr, "usage: rtk_build_index -s reads.fq [-s ...] -o PREFIX [-k 31 (odd, <=63)] [--min-count 2] [--global-cov-factor 3.0] [--no-short-cycles] [--snps] [--fast | --gpu (k <= 31: same files, threads / the device for the heavy steps)] [--dump-input FILE] [--colour-reads corrected_long_reads.fq: second-pass index, the graph comes from -s, colours and coverage from these reads]\n"); return 2; }
+    if (in_files.empty() || k < 3 || k > RTK_MAX_K || !(k & 1)) { fprintf(stderr, "usage: rtk_build_index -s reads.fq [-s ...] -o PREFIX [-k 31 (odd, <=63)] [--min-count 2] [--global-cov-factor 3.0] [--no-short-cycles] [--snps] [--fast | --gpu (k <= 63: same files, threads / the device for the heavy steps)] [--dump-input FILE] [--colour-reads corrected_long_reads.fq: second-pass index, the graph comes from -s, colours and coverage from these reads]\n"); return 2; }
     if (!dump_input.empty()) { // what a `sample:` source stands for, as a file (tests compare the index built from either)
         FILE* fo = fopen(dump_input.c_str(), "wb"); if (!fo) { fprintf(stderr, "rtk_build_index: cannot write %s\n", dump_input.c_str()); return 1; }
         std::string name, seq, qual;
@@ -297,7 +311,6 @@ template <class KM> static int run(int argc, char** argv) { // KM: uint64_t for 
         fclose(fo); return 0;
     }
     const KM mask = km_mask<KM>(k);
-    if (fast && sizeof(KM) != 8) { fprintf(stderr, "rtk_build_index: --fast / --gpu serve one-word k-mers (k <= 31); k = %d takes the plain path\n", k); fast = false; gpu = false; }
     const auto t_start = std::chrono::steady_clock::now();
     auto lap = [&](const char* what) { if (getenv("RTK_INDEX_TRACE")) fprintf(stderr, "rtk_build_index: [%8.2f s] %s\n", std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count(), what); };
 
@@ -326,7 +339,7 @@ template <class KM> static int run(int argc, char** argv) { // KM: uint64_t for 
         uint64_t* sk = nullptr; uint64_t ns = 0;
         if (cf(0, k, fp.data(), static_cast<int>(fp.size()), min_count, static_cast<int>(n_thr), &sk, &ns) != 0) { fprintf(stderr, "rtk_build_index: --gpu: %s\n", ef()); return 1; }
         solid.resize(ns);
-        for (uint64_t i = 0; i < ns; ++i) solid[i] = static_cast<KM>(sk[i]);
+        if (ns) memcpy(solid.data(), sk, sizeof(KM) * ns); // (two-word k-mers: two words each, low word first)
         ff(sk);
     } else
     {
@@ -376,7 +389,7 @@ template <class KM> static int run(int argc, char** argv) { // KM: uint64_t for 
     bool fast_done = false;
     DeviceUnitigs dev_u; bool have_dev_u = false;
     char* du_pool = nullptr; uint64_t* du_off = nullptr; uint64_t* du_seeds = nullptr; uint64_t* du_left = nullptr;
-    if (gpu && gpu_unitigs_fn && sizeof(KM) == 8 && !getenv("RTK_INDEX_HOST_UNITIGS")) { // the chains walked and written on the device (csrc/hip/rtk_index.hip rtk_index_unitigs)
+    if (gpu && gpu_unitigs_fn && !getenv("RTK_INDEX_HOST_UNITIGS")) { // the chains walked and written on the device (csrc/hip/rtk_index.hip rtk_index_unitigs)
         uint64_t nu = 0, nl = 0;
         const int rc = gpu_unitigs_fn(0, k, reinterpret_cast<const uint64_t*>(solid.data()), solid.size(), &du_pool, &du_off, &du_seeds, &nu, &du_left, &nl);
         if (rc == 0) { dev_u.pool = du_pool; dev_u.off = du_off; dev_u.seeds = du_seeds; dev_u.n = nu; dev_u.left = du_left; dev_u.n_left = nl; have_dev_u = true; }
@@ -477,7 +490,7 @@ template <class KM> static int run(int argc, char** argv) { // KM: uint64_t for 
         // --gpu: the reads are handed to the device chunk by chunk (csrc/hip/rtk_index.hip rtk_index_colour_*: the k-mer table of the unitigs in HBM, one lane per
         // read position); this tool keeps what is its own -- reading, and the numbering of the reads. Every thread fills a chunk of its own.
         void* col_job = nullptr; std::atomic<int> col_failed(0);
-        if (gpu && gpu_col_begin && gpu_col_chunk && gpu_col_end && sizeof(KM) == 8 && !getenv("RTK_INDEX_HOST_COLOURS") && n_u > 0) {
+        if (gpu && gpu_col_begin && gpu_col_chunk && gpu_col_end && !getenv("RTK_INDEX_HOST_COLOURS") && n_u > 0) {
             std::vector<uint64_t> off(n_u + 1, 0); for (size_t u = 0; u < n_u; ++u) off[u + 1] = off[u] + U[u].seq.size();
             std::string pool(off[n_u], 'A');
             parallel_for(n_u, n_thr, [&](size_t b, size_t e, unsigned) { for (size_t u = b; u < e; ++u) memcpy(&pool[off[u]], U[u].seq.data(), U[u].seq.size()); });
@@ -817,9 +830,9 @@ template <class KM> static int run(int argc, char** argv) { // KM: uint64_t for 
             switch (c) { case 'A': return 1; case 'C': return 2; case 'G': return 4; case 'T': return 8; case 'M': return 3; case 'R': return 5; case 'S': return 6; case 'V': return 7;
                          case 'W': return 9; case 'Y': return 10; case 'H': return 11; case 'K': return 12; case 'D': return 13; case 'B': return 14; case 'N': return 15; default: return 0; } };
         static const char amb_char[16] = {'.', 'A', 'C', 'M', 'G', 'R', 'S', 'V', 'T', 'W', 'Y', 'H', 'K', 'D', 'B', 'N'}; // getAmbiguity
-        std::unique_ptr<NeighbourIndex> nbx_own;
-        if (fast) { nbx_own.reset(new NeighbourIndex()); nbx_own->build(solid64(solid), k, n_thr); lap("1-substitution neighbour index built"); }
-        const NeighbourIndex* const nbx = nbx_own.get();
+        std::unique_ptr<NeighbourIndex<KM> > nbx_own;
+        if (fast) { nbx_own.reset(new NeighbourIndex<KM>()); nbx_own->build(solid, k, n_thr); lap("1-substitution neighbour index built"); }
+        const NeighbourIndex<KM>* const nbx = nbx_own.get();
         auto annotate = [&](size_t u) {
             if (!(shared[u] & 0xffULL)) return; // hasSharedPids (src/Graph.cpp:500)
             const std::string& s = U[u].seq;
@@ -848,7 +861,7 @@ template <class KM> static int run(int argc, char** argv) { // KM: uint64_t for 
                         if (is_valid(lgt_fw, lgt_bw, u, w)) { seq_final[at] = cf; ok.insert(w); } else bad.insert(w);
                     }
                 };
-                if (nbx) nbx->neighbours(static_cast<uint64_t>(fw), candidate); // --fast: the neighbours from the two sorted views of the k-mer set, same order
+                if (nbx) nbx->neighbours(fw, candidate); // --fast: the neighbours from the two sorted views of the k-mer set, same order
                 else for (int j = 0; j < k; ++j) {
                     const uint64_t cur = static_cast<uint64_t>(fw >> (2 * (k - 1 - j))) & 3ULL;
                     for (uint64_t alt = 0; alt < 4; ++alt) if (alt != cur) candidate(j, alt);
