@@ -165,14 +165,14 @@ RTK_FN void rtk_fix_ambiguity(const RCtx& c_, char* query_, uint32_t query_len_,
         const uint32_t p = rtk_amb_pos(v[i]);
         if (quality[p] < q_min_conf_corr && rtk_amb_find(ms, nms, p) < 0) ms[nms++] = v[i]; // n_amb <= cap
     }
-    s.fine[10] += 1;
+    s.fine[RTK_FINE_FA_CALLS] += 1;
     if (nms == 0) {
         // every annotated base is confident: nothing enters the sets unless the alignment meets a non-ACGT character of the
         // corrected or the raw region (:630-678), and with both clean the whole call leaves query and quality as they are
         bool odd = false;
         for (uint32_t i = static_cast<uint32_t>(rtk_lane()); i < query_len; i += RTK_WAVE) odd |= !rtk_is_dna(query[i]);
         for (uint32_t i = static_cast<uint32_t>(rtk_lane()); i < ref_len; i += RTK_WAVE) odd |= !rtk_is_dna(ref[i]);
-        if (rtk_ballot(odd) == 0) { s.fine[11] += 1; return; }
+        if (rtk_ballot(odd) == 0) { s.fine[RTK_FINE_FA_ALL_CONFIDENT] += 1; return; }
     }
     char* qt = s.str[0]; // query_tmp
     rtk_wcopy(qt, query, query_len);
@@ -189,7 +189,7 @@ RTK_FN void rtk_fix_ambiguity(const RCtx& c_, char* query_, uint32_t query_len_,
 #define RTK_FA_LAP(i) { const unsigned long long tn_ = rtk_clock(); s.fine[i] += tn_ - tfa_; tfa_ = tn_; }
     RTK_SITE(17); rtk_align_path(c, qt, query_len, ref, ref_len, RTK_MODE_SHW, &nm); nm = rtk_u(nm);
     if (rtk_failed(s)) return;
-    RTK_FA_LAP(1)
+    RTK_FA_LAP(RTK_FINE_FA_ALIGN)
     { // walk of the alignment (:612-706); only moves touching a non-ACGT character on either side do anything
         const uint8_t* mv = rtk_ld(&s.my.moves);
         uint32_t qp = 0, rp = 0;
@@ -226,7 +226,7 @@ RTK_FN void rtk_fix_ambiguity(const RCtx& c_, char* query_, uint32_t query_len_,
             qp += static_cast<uint32_t>(rtk_popc(bq)); rp += static_cast<uint32_t>(rtk_popc(br));
         }
     }
-    RTK_FA_LAP(2)
+    RTK_FA_LAP(RTK_FINE_FA_WALK)
     // alleles of the other annotated positions of the unitig a decided SNP lies on (:713-768)
     for (uint32_t e = 0; e < nms; ++e) {
         const char pc = rtk_amb_chr(ms[e]);
@@ -295,7 +295,7 @@ RTK_FN void rtk_fix_ambiguity(const RCtx& c_, char* query_, uint32_t query_len_,
         }
         rtk_sync();
     }
-    RTK_FA_LAP(3)
+    RTK_FA_LAP(RTK_FINE_FA_LINKED)
     for (uint32_t i = 0; i < nsa; ++i) { // a linked position with exactly one candidate allele takes it, when compatible (:771-790)
         const uint32_t pos = rtk_amb_pos(sa[i]);
         uint32_t same = 0;
@@ -316,7 +316,7 @@ RTK_FN void rtk_fix_ambiguity(const RCtx& c_, char* query_, uint32_t query_len_,
     rtk_sync();
     rtk_wcopy(query, qt, query_len);
     rtk_sync();
-    RTK_FA_LAP(4)
+    RTK_FA_LAP(RTK_FINE_FA_APPLY)
 }
 
 #endif

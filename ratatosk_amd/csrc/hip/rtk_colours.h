@@ -202,7 +202,7 @@ RTK_FN uint32_t rtk_choose_colors_small(const RCtx& c_, const SideList& side_s_,
         if (t < T || !big) uni[t] = x;
     }
     RTK_WG_SYNC();
-    s.cnt[1] += T;
+    s.cnt[RTK_RC_COLOUR] += T;
     RTK_CS_LAP(3)
     { // sorted by id (radix, 8 bits per pass; the second buffer and the counters sit in the part of the LDS buffer the slot bit vectors take later)
         uint32_t mx = 0; for (uint32_t i2 = lane; i2 < T; i2 += RTK_WAVE) mx = uni[i2] > mx ? uni[i2] : mx;
@@ -356,7 +356,7 @@ RTK_FN uint32_t rtk_choose_colors_bits(const RCtx& c_, const SideList& side_s_, 
                        for (uint32_t x = static_cast<uint32_t>(rtk_lane()); x < ng; x += RTK_WAVE) gathered[at + x] = pg[x]; at += ng; }
       } }
     rtk_sync();
-    s.cnt[1] += T;
+    s.cnt[RTK_RC_COLOUR] += T;
     uint32_t U = 0;
 #ifdef RTK_SIM
     uint32_t* const uni = s.set[1] + RTK_CB_MAX_IDS; uint64_t* const scatter = nullptr;

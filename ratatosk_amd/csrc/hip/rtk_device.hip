@@ -75,12 +75,12 @@ struct rtk_graph {
         { std::lock_guard<std::mutex> h(pool_lock);
           std::multimap<uint64_t, void*>::iterator it = pool.lower_bound(bytes);
           if (it != pool.end() && it->first <= bytes + bytes / 4 + (1u << 20)) { void* p = it->second; *got = it->first; pool_bytes -= it->first; pool.erase(it); return p; } }
-        if (bytes >= (64u << 20) && getenv("RTK_TRACE")) { const auto t0 = std::chrono::steady_clock::now(); void* p = rtk_dmalloc(bytes); fprintf(stderr, "[rtk trace] pool_take: %.2f GB of new device memory in %.1f ms\n", bytes / 1073741824.0, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count()); *got = bytes; return p; }
+        if (bytes >= (64u << 20) && rtk_knob_trace()) { const auto t0 = std::chrono::steady_clock::now(); void* p = rtk_dmalloc(bytes); fprintf(stderr, "[rtk trace] pool_take: %.2f GB of new device memory in %.1f ms\n", bytes / 1073741824.0, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count()); *got = bytes; return p; }
         *got = bytes; return rtk_dmalloc(bytes);
     }
     void pool_give(void* p, uint64_t bytes) {
         std::lock_guard<std::mutex> h(pool_lock);
-        if (pool_bytes + bytes > (64ull << 30)) { if (bytes >= (64u << 20) && getenv("RTK_TRACE")) fprintf(stderr, "[rtk trace] pool_give: %.2f GB freed (64 GB parked already)\n", bytes / 1073741824.0); rtk_dfree(p); return; } // keep at most 64 GB parked (eleven second-pass tickets of ~5 GB: eight in flight, three being formatted)
+        if (pool_bytes + bytes > (64ull << 30)) { if (bytes >= (64u << 20) && rtk_knob_trace()) fprintf(stderr, "[rtk trace] pool_give: %.2f GB freed (64 GB parked already)\n", bytes / 1073741824.0); rtk_dfree(p); return; } // keep at most 64 GB parked (eleven second-pass tickets of ~5 GB: eight in flight, three being formatted)
         pool.insert(std::make_pair(bytes, p)); pool_bytes += bytes;
     }
     // work areas of the phasing step (second pass): one per ticket in flight, so that the hour-glass launches of several tickets (each as
@@ -101,7 +101,7 @@ struct rtk_graph {
         { std::lock_guard<std::mutex> h(pool_lock);
           std::multimap<uint64_t, void*>::iterator it = hpool.lower_bound(bytes);
           if (it != hpool.end() && it->first <= 2 * bytes + (4u << 20)) { void* p = it->second; *got = it->first; hpool_bytes -= it->first; hpool.erase(it); return p; } }
-        if (getenv("RTK_TRACE")) { const auto t0 = std::chrono::steady_clock::now(); void* p = rtk_hmalloc_pinned(bytes); fprintf(stderr, "[rtk trace] stage_take: %.1f MB of new pinned host memory in %.1f ms\n", bytes / 1048576.0, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count()); *got = bytes; return p; }
+        if (rtk_knob_trace()) { const auto t0 = std::chrono::steady_clock::now(); void* p = rtk_hmalloc_pinned(bytes); fprintf(stderr, "[rtk trace] stage_take: %.1f MB of new pinned host memory in %.1f ms\n", bytes / 1048576.0, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count()); *got = bytes; return p; }
         *got = bytes; return rtk_hmalloc_pinned(bytes);
     }
     void stage_give(void* p, uint64_t bytes) {
@@ -358,7 +358,7 @@ extern "C" int rtk_opts_default(const rtk_graph* g, rtk_opts* o) {
     o->max_km_cov = 128; if (g && g->info.max_km_cov_top > 128) o->max_km_cov = g->info.max_km_cov_top; // src/Ratatosk.cpp:625
     o->weak_region_len_factor = 0.25; o->large_k_factor = 1.5; o->min_score = 0.0; o->max_qual = 40; o->out_qual = 1; o->min_confidence_snp_corr = 0.9;
     o->long_read_correct = 0; o->force_unres_snp_corr = 0; o->max_len_weak_region2 = 5000; o->struct_size = static_cast<uint32_t>(sizeof(rtk_opts));
-    { const char* e = getenv("RTK_A2_XOR"); o->a2_exclusive = (e && !strcmp(e, "union")) ? 0 : ((e && !strcmp(e, "exclusive-ids")) ? 2 : 1); const char* e3 = getenv("RTK_A3_ORDER"); o->a3_strand_order = (e3 && !strcmp(e3, "strand")) ? 1 : 0;  const char* e4 = getenv("RTK_D1_ORDER"); o->d1_desc = (e4 && !strcmp(e4, "desc")) ? 1 : 0; } // [A2] switch, see rtk_opts
+    o->a2_exclusive = rtk_knob_a2_exclusive(); o->a3_strand_order = rtk_knob_a3_strand_order(); o->d1_desc = rtk_knob_d1_desc(); // [A2] switch, see rtk_opts
     return RTK_OK;
 }
 
@@ -385,7 +385,7 @@ void* rtk_graph::phase_take(uint64_t bytes, uint64_t* got) {
     bytes = (bytes + (2ull << 30) - 1) / (2ull << 30) * (2ull << 30);
     const auto t0 = std::chrono::steady_clock::now();
     void* p = rtk_dmalloc(bytes);
-    if (getenv("RTK_TRACE")) fprintf(stderr, "[rtk trace] phase_take: %.1f GB of new device memory in %.1f ms\n", bytes / 1073741824.0, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+    if (rtk_knob_trace()) fprintf(stderr, "[rtk trace] phase_take: %.1f GB of new device memory in %.1f ms\n", bytes / 1073741824.0, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
     *got = bytes; return p;
 }
 
@@ -577,12 +577,12 @@ extern "C" int rtk_myers_batch_waves(uint32_t n, const char* const* query, const
         uint8_t* dmoves = static_cast<uint8_t*>(held.get(static_cast<uint64_t>(n) * cap_moves + 8)); uint32_t* dnm = static_cast<uint32_t*>(held.get(4ull * n));
         rtk_h2d(dpool, pool.data(), pool.size()); rtk_h2d(dprobs, probs.data(), sizeof(MyersProb) * n);
         unsigned long long* dprof = nullptr; // RTK_MYERS_PROF=1: cycle counters of the Hirschberg drivers (developer)
-        if (getenv("RTK_MYERS_PROF")) { dprof = static_cast<unsigned long long*>(rtk_dmalloc(64)); const unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0}; rtk_h2d(dprof, z, 64); }
+        if (rtk_knob_myers_prof()) { dprof = static_cast<unsigned long long*>(rtk_dmalloc(64)); const unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0}; rtk_h2d(dprof, z, 64); }
 #ifndef RTK_SIM
         if (waves > 1) rtk_launch_myers_batch_waves(grid, waves, static_cast<const MyersProb*>(dprobs), n, static_cast<const char*>(dpool), want_path, use_iupac, dscr, stride, cfg, ddist, dnloc, dlocs, cap_locs, dmoves, dnm, cap_moves, dst, dprof);
         else
 #endif
-        { RtkTimer tk; const bool timed = getenv("RTK_MYERS_TIME") != nullptr && waves <= 1; if (timed) tk.start(0);
+        { RtkTimer tk; const bool timed = rtk_knob_myers_time() && waves <= 1; if (timed) tk.start(0);
           rtk_launch(k_myers_batch, grid, 0, static_cast<const MyersProb*>(dprobs), n, static_cast<const char*>(dpool), want_path, use_iupac, dscr, stride, cfg, grid, ddist, dnloc, dlocs, cap_locs, dmoves, dnm, cap_moves, dst, dprof);
           if (timed) { tk.stop(0); rtk_dsync(); fprintf(stderr, "[rtk myers time] one wave per problem: %u problems, %d waves, kernel %.3f ms\n", n, grid, tk.elapsed()); } }
         if (dprof) { rtk_dsync(); unsigned long long pc[8]; rtk_d2h(pc, dprof, 64); rtk_dfree(dprof);
@@ -672,7 +672,7 @@ extern "C" int rtk_myers_batch_lanes(uint32_t n, const char* const* query, const
         int32_t* dlocs = static_cast<int32_t*>(held.get(4ull * n * cap_locs + 8)); uint32_t* dst = static_cast<uint32_t*>(held.get(4ull * n));
         uint8_t* dmoves = static_cast<uint8_t*>(held.get(static_cast<uint64_t>(n) * cap_moves + 8)); uint32_t* dnm = static_cast<uint32_t*>(held.get(4ull * n));
         rtk_h2d(dpool, pool.data(), pool.size()); rtk_h2d(dprobs, probs.data(), sizeof(MyersProb) * n);
-        { RtkTimer tk; const bool timed = getenv("RTK_MYERS_TIME") != nullptr; if (timed) tk.start(0);
+        { RtkTimer tk; const bool timed = rtk_knob_myers_time(); if (timed) tk.start(0);
           rtk_launch(k_myers_batch_lanes, grid, 0, static_cast<const MyersProb*>(dprobs), n, static_cast<const char*>(dpool), want_path, use_iupac, dscr, stride, grid, ddist, dnloc, dlocs, cap_locs, dmoves, dnm, cap_moves, dst);
           if (timed) { tk.stop(0); rtk_dsync(); fprintf(stderr, "[rtk myers time] one lane per problem%s: %u problems, %d waves, kernel %.3f ms\n", want_path ? " (with paths)" : "", n, grid, tk.elapsed()); } }
         rtk_dsync();
@@ -697,7 +697,7 @@ extern "C" int rtk_myers_batch_lanes(uint32_t n, const char* const* query, const
         // the problems that are not for this route (query above 512 characters, target above 2048 or with a character outside ACGTN, a path table above 4096 word-columns): one wave each
         std::vector<uint32_t> rest; for (uint32_t i = 0; i < n; ++i) if (st[i]) rest.push_back(i);
         g_ml_routes[0] = n - rest.size(); g_ml_routes[1] = rest.size();
-        if (getenv("RTK_MYERS_TIME")) fprintf(stderr, "[rtk myers time] %zu of %u problems handed on to the wave route\n", rest.size(), n);
+        if (rtk_knob_myers_time()) fprintf(stderr, "[rtk myers time] %zu of %u problems handed on to the wave route\n", rest.size(), n);
         if (!rest.empty()) {
             const uint32_t nr = static_cast<uint32_t>(rest.size());
             std::vector<const char*> q2(nr), t2(nr); std::vector<uint32_t> ql2(nr), tl2(nr); std::vector<int32_t> k2(nr), m2(nr), d2(nr), nl2(nr), loc2(static_cast<size_t>(nr) * cap_locs + 1);

@@ -224,7 +224,7 @@ static void sync_check(const char* what) { rtk_check(hipGetLastError(), what); r
 namespace rtk {
 
 void device_tables_build(const uint64_t* d_useq, const uint64_t* d_uoff, uint32_t n_unitigs, uint64_t n_bases, uint64_t n_kmers, int k, DeviceTables* out) {
-    const bool trace = getenv("RTK_LOAD_TRACE") != nullptr;
+    const bool trace = rtk_knob_load_trace();
     const TableSizes tsz = table_sizes(k, n_kmers, n_bases);
     const uint64_t n_words = (n_bases + 31) / 32;
     const double t0 = now_s();
@@ -272,7 +272,7 @@ void device_tables_build(const uint64_t* d_useq, const uint64_t* d_uoff, uint32_
         const uint64_t later = 16 * tsz.ht_slots + 8 * tsz.bf_words + 8 * tsz.bf1_words + 32ull * n_unitigs + (1ull << 30);
         uint64_t cap = fr > later ? (static_cast<uint64_t>(fr) - later) / 2 / 16 : (1ull << 24); // (half of it: a caller may be reserving its work areas on another thread)
         if (cap > (1ull << 31)) cap = 1ull << 31;
-        { const char* e = getenv("RTK_HX_PART_KEYS"); if (e) cap = strtoull(e, nullptr, 10); }
+        cap = rtk_knob_hx_part_keys(cap);
         if (cap < 1024) cap = 1024;
         std::vector<std::pair<uint32_t, uint32_t> > parts; uint64_t max_part = 0;
         for (uint32_t b = 0; b < n_bins;) { uint64_t s = hh[b]; uint32_t e = b + 1; while (e < n_bins && s + hh[e] <= cap) { s += hh[e]; ++e; } parts.push_back(std::make_pair(b, e)); if (s > max_part) max_part = s; b = e; }

@@ -382,28 +382,27 @@ template <class KM> int count_kmers(int device, int k, const char* const* files,
         uint64_t total_bytes = 0;
         for (size_t f = 0; f < fl.size(); ++f) { if (rtk::SampleSource::is_spec(fl[f])) { std::string e_; std::shared_ptr<rtk::SampleSource> ss = rtk::SampleSource::get(fl[f], &e_); if (!ss) return rtk_fail(RTK_ERR_IO, "rtk_index_count_kmers: " + e_); total_bytes += 2 * ss->n_bases(); continue; } FILE* fp = fopen(fl[f].c_str(), "rb"); if (!fp) return rtk_fail(RTK_ERR_IO, "rtk_index_count_kmers: cannot open " + fl[f]); fseek(fp, 0, SEEK_END); total_bytes += static_cast<uint64_t>(ftell(fp)); fclose(fp); }
         size_t fr = 0, tot = 0; rtk_check(hipMemGetInfo(&fr, &tot), "hipMemGetInfo");
-        if (getenv("RTK_INDEX_TRACE")) fprintf(stderr, "rtk_index_count_kmers: inputs sized (%.1f GB), %.1f GB of device memory free\n", total_bytes / 1e9, fr / 1e9);
+        if (rtk_knob_index_trace()) fprintf(stderr, "rtk_index_count_kmers: inputs sized (%.1f GB), %.1f GB of device memory free\n", total_bytes / 1e9, fr / 1e9);
         const uint64_t est_kmers = total_bytes / 2 + (1u << 20); // FASTQ: half of the bytes are bases (gzip input: a multiple of it; the capacity test below catches that)
         uint64_t cap = static_cast<uint64_t>(fr) / 10 * 7 / (2 * sizeof(KM)); // 70 % of the free memory for keys + their sort buffer (the rest: two chunks of text, the sort's histograms)
-        { const char* e = getenv("RTK_INDEX_CAP"); if (e) cap = strtoull(e, nullptr, 10); }
+        cap = rtk_knob_index_cap(cap);
         if (cap < (1u << 20)) cap = 1u << 20;
         uint32_t n_part = static_cast<uint32_t>((est_kmers + cap - 1) / cap); if (n_part < 1) n_part = 1;
-        uint64_t chunk_bytes = 256ull << 20;
-        { const char* e = getenv("RTK_INDEX_CHUNK"); if (e && strtoull(e, nullptr, 10) >= 1024) chunk_bytes = strtoull(e, nullptr, 10); } // developer / tests: small chunks, so that long records are cut into pieces
+        const uint64_t chunk_bytes = rtk_knob_index_chunk(256ull << 20); // developer / tests: small chunks, so that long records are cut into pieces
         const uint64_t chunk_slack = std::min<uint64_t>(64ull << 20, chunk_bytes / 4);
         std::vector<KM> solid;
         // Several partitions = several passes over the reads. The text of the first pass is kept in host memory when it fits into half of what is free there
         // (a 3 Gb x 30x set: 90 GB of sequences, sampled or parsed ONCE instead of once per partition -- 13 passes at 0.5 Gb/s of host-side sampling were 36 minutes)
         std::vector<std::string> kept; bool keep_text = false, kept_complete = false;
         std::vector<size_t> run_start; // solid[run_start[p] ..): the sorted k-mers of partition p
-        const bool trace = getenv("RTK_INDEX_TRACE") != nullptr; const auto t_begin = std::chrono::steady_clock::now();
+        const bool trace = rtk_knob_index_trace(); const auto t_begin = std::chrono::steady_clock::now();
         auto since = [&]() { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count(); };
         { uint64_t avail = static_cast<uint64_t>(sysconf(_SC_AVPHYS_PAGES)) * static_cast<uint64_t>(sysconf(_SC_PAGE_SIZE));
           { // a container's memory limit is not what sysconf reports: what is left under the control group's limit, if there is one
             unsigned long long lim = 0, cur = 0; bool have = false;
             if (FILE* f1 = fopen("/sys/fs/cgroup/memory.max", "r")) { have = fscanf(f1, "%llu", &lim) == 1; fclose(f1); if (have) { if (FILE* f2 = fopen("/sys/fs/cgroup/memory.current", "r")) { if (fscanf(f2, "%llu", &cur) != 1) cur = 0; fclose(f2); } } }
             if (have && lim > cur && lim - cur < avail) avail = lim - cur; }
-          const char* e = getenv("RTK_INDEX_KEEP_TEXT"); keep_text = e ? atoi(e) != 0 : (est_kmers + est_kmers / 8 < avail / 2); // (the caller's own tables come on top of it later: half of what is left, no more)
+          const int kt = rtk_knob_index_keep_text(); keep_text = kt >= 0 ? kt != 0 : (est_kmers + est_kmers / 8 < avail / 2); // (the caller's own tables come on top of it later: half of what is left, no more)
           if (trace) fprintf(stderr, "rtk_index_count_kmers: %.1f GB of host memory to be had, text %s\n", avail / 1e9, keep_text ? "kept across partitions" : "read again for every partition"); }
         for (bool done = false; !done;) {
             done = true; solid.clear(); run_start.clear(); if (!kept_complete) kept.clear(); // (a restart with more partitions keeps the text of the complete first pass)
@@ -514,7 +513,7 @@ extern "C" int rtk_index_count_kmers(int device, int k, const char* const* files
 // a reverse complement) are not built: their k-mers come back in *left (sorted) for the caller's plain construction.
 namespace {
 template <class KM> int unitigs(int device, int k, const KM* solid, uint64_t n_solid, char** seq_pool, uint64_t** seq_off, uint64_t** seeds, uint64_t* n_unitigs, uint64_t** left, uint64_t* n_left) {
-    const bool trace = getenv("RTK_INDEX_TRACE") != nullptr;
+    const bool trace = rtk_knob_index_trace();
     try {
         rtk_check(hipSetDevice(device), "hipSetDevice");
         const auto t0 = std::chrono::steady_clock::now();
@@ -643,7 +642,7 @@ extern "C" int rtk_index_colour_begin(int device, int k, const char* seq_pool, c
         }
         size_t fr = 0, tot = 0; rtk_check(hipMemGetInfo(&fr, &tot), "hipMemGetInfo");
         J->cap = static_cast<uint64_t>(fr) / 10 * 6 / 16; // 60 % of what is left for the events and their sort buffer
-        { const char* e = getenv("RTK_INDEX_EVENTS"); if (e) J->cap = strtoull(e, nullptr, 10); }
+        J->cap = rtk_knob_index_events(J->cap);
         if (J->cap < 1024) J->cap = 1024;
         J->events.alloc(8 * J->cap); J->alt.alloc(8 * J->cap);
         J->t_table = std::chrono::duration<double>(std::chrono::steady_clock::now() - J->t0).count();
@@ -697,7 +696,7 @@ extern "C" int rtk_index_colour_end(void* job, uint64_t** events, uint64_t* n_ev
         if (J->n_events) rtk_check(hipMemcpy(ev, J->events.p, 8 * J->n_events, hipMemcpyDeviceToHost), "hipMemcpy");
         rtk_check(hipMemcpy(cv, J->cov.p, 8ull * J->n_unitigs, hipMemcpyDeviceToHost), "hipMemcpy");
         *events = ev; *n_events = J->n_events; *cov = cv;
-        if (getenv("RTK_INDEX_TRACE")) fprintf(stderr, "rtk_index_colour: %llu characters in %llu chunks -> %llu distinct (unitig, read) events (sorted and thinned out %llu times); table %.2f s, all %.2f s\n", static_cast<unsigned long long>(J->bases),
+        if (rtk_knob_index_trace()) fprintf(stderr, "rtk_index_colour: %llu characters in %llu chunks -> %llu distinct (unitig, read) events (sorted and thinned out %llu times); table %.2f s, all %.2f s\n", static_cast<unsigned long long>(J->bases),
                                                static_cast<unsigned long long>(J->chunks), static_cast<unsigned long long>(J->n_events), static_cast<unsigned long long>(J->compactions), J->t_table, std::chrono::duration<double>(std::chrono::steady_clock::now() - J->t0).count());
     } catch (const std::exception& e) { return rtk_fail(RTK_ERR_DEVICE, std::string("rtk_index_colour_end: ") + e.what()); }
     return RTK_OK;

@@ -447,9 +447,6 @@ __device__ __forceinline__ SweepStat rtk_myers_fast32(const char* __restrict__ q
         int j_full = n - c0; j_full = j_full < j_fill ? j_fill : (j_full > lim ? lim : j_full);
         int j = 0;
         for (; j < j_fill; ++j) RTK_STEP32(1)
-#ifdef RTK_MY_UNROLL
-        _Pragma("unroll 4")
-#endif
         for (; j < j_full; ++j) RTK_STEP32(0)
         for (; j < lim; ++j) RTK_STEP32(1)
     }
@@ -1446,8 +1443,6 @@ RTK_FN void rtk_myers_alignment(const MyersScratch& sc_, const char* q_, int m_,
     prof.hb_total += rtk_clock() - t_all0;
 }
 
-#include "variants/rtk_myers_lt.h"
-
 // edlibAlign(..., k = -1, NW or SHW, TASK_PATH): result and moves. When the whole table fits the in-memory traceback branch of
 // obtainAlignment (edlib.cpp:1191-1193) ONE stored sweep serves both the distance and the traceback: an SHW matrix restricted to
 // columns [0, end] IS the NW matrix of the truncated target edlib re-aligns (same top row, same left column), so the table
@@ -1459,25 +1454,6 @@ RTK_FN MyersResult rtk_myers_path(const MyersScratch& sc_, const char* q_, int m
     *n_moves = 0;
     { MyersScratch& msc = const_cast<MyersScratch&>(sc); msc.tb_gen = rtk_ld(&msc.tb_gen) + 1u; }
     MyersResult r; bool have = false;
-#ifdef RTK_HAVE_LT
-    if (rtk_lt_fits(sc, m, n)) { // small problem: the table lives in LDS, a chunk of steps at a time (rtk_myers_lt.h)
-        SweepStat st;
-        const bool ok = (mode == RTK_MODE_NW) ? rtk_lt_align<0>(sc, q, m, t, n, iupac, RTK_MODE_NW, &st, n_moves) : rtk_lt_align<1>(sc, q, m, t, n, iupac, RTK_MODE_SHW, &st, n_moves);
-        rtk_sync();
-        if (ok) {
-            r.dist = -1; r.first = -1; r.last = -1; r.nloc = 0;
-            if (mode == RTK_MODE_NW) { r.dist = st.final_score; r.first = r.last = n - 1; r.nloc = 1; return r; }
-            int best = st.best; const bool pseudo = (m & 63) != 0;
-            if (pseudo && m < best) best = m;
-            r.dist = best;
-            if (pseudo && m == best) { r.first = -1; r.last = (st.best == best) ? st.last : -1; r.nloc = 1 + ((st.best == best) ? st.cnt : 0); }
-            else { r.first = st.first; r.last = st.last; r.nloc = st.cnt; }
-            if (r.first + 1 <= 0) rtk_myers_alignment(sc, q, m, t, 0, r.dist, iupac, n_moves); // empty target prefix: m inserts (edlib.cpp:1171-1178)
-            return r;
-        }
-        *n_moves = 0;
-    }
-#endif
 #ifndef RTK_SIM
     const long long W = (m + 63) >> 6;
     if (m > 0 && n > 0 && m <= 4096 && static_cast<uint64_t>(4 * W * n) <= sc.tb_cap_words && static_cast<uint32_t>(m + n) <= sc.mv_cap && static_cast<uint32_t>(n) <= sc.t_cap &&
@@ -1521,26 +1497,6 @@ struct MyersSaved { uint32_t valid, gen; int32_t m, n, nw_dist; MyersResult shw;
 RTK_FN bool rtk_myers_nw_and_save(const MyersScratch& sc_, const char* q_, int m_, const char* t_, int n_, bool iupac_, MyersSaved* out_) {
     const MyersScratch& sc = *rtk_u(&sc_); RTK_ASSUME_LDS(&sc); const char* q = rtk_u(q_); const char* t = rtk_u(t_); const int m = rtk_u(m_), n = rtk_u(n_); const bool iupac = rtk_u(iupac_); MyersSaved* out = rtk_u(out_);
     out->valid = 0;
-#ifdef RTK_HAVE_LT
-    if (out->stash && rtk_lt_fits(sc, m, n) && static_cast<uint32_t>(m + n) <= out->stash_cap) {
-        // the SHW path alignment right away (its table lives in LDS and is gone when this call returns); the moves wait in the caller's stash
-        SweepStat st; uint32_t nm = 0;
-        MyersScratch& msc = const_cast<MyersScratch&>(sc); const uint32_t gen = rtk_ld(&msc.tb_gen) + 1u; msc.tb_gen = gen;
-        const bool ok = rtk_lt_align<1>(sc, q, m, t, n, iupac, RTK_MODE_SHW, &st, &nm);
-        rtk_sync();
-        if (ok) {
-            MyersResult r;
-            int best = st.best; const bool pseudo = (m & 63) != 0;
-            if (pseudo && m < best) best = m;
-            r.dist = best;
-            if (pseudo && m == best) { r.first = -1; r.last = (st.best == best) ? st.last : -1; r.nloc = 1 + ((st.best == best) ? st.cnt : 0); }
-            else { r.first = st.first; r.last = st.last; r.nloc = st.cnt; }
-            out->m = m; out->n = n; out->nw_dist = st.final_score; out->shw = r; out->gen = gen;
-            if (r.first + 1 > 0) { nm = rtk_u(nm); rtk_wcopy(out->stash, rtk_ld(&sc.moves), nm); out->stash_n = nm; out->valid = 2u; } // 2: moves in the stash
-            return true;
-        }
-    }
-#endif
 #ifndef RTK_SIM
     const long long W = (m + 63) >> 6;
     if (!(m > 0 && n > 0 && m <= 4096 && static_cast<uint64_t>(4 * W * n) <= sc.tb_cap_words && static_cast<uint32_t>(m + n) <= sc.mv_cap && static_cast<uint32_t>(n) <= sc.t_cap &&

@@ -44,11 +44,7 @@ __device__ __forceinline__ int rtk_gang_step64(uint64_t& Pv, uint64_t& Mv, uint6
     return hout;
 }
 
-#ifdef RTK_GANG_OLD_STEP
-#define RTK_GANG_STEP_CALL uint64_t Ph_, Mh_; const int hout = rtk_myers_step(nPv, nMv, Eq, hin, bit, Ph_, Mh_);
-#else
 #define RTK_GANG_STEP_CALL const int hout = rtk_gang_step64(nPv, nMv, Eq, hin, bit_hi, bit_pos);
-#endif
 template <int PLAIN>
 __device__ __forceinline__ void rtk_gang_sweep(const char* __restrict__ q, const char* __restrict__ stage, const uint64_t* __restrict__ peq, uint64_t* __restrict__ fin,
                                                const int32_t* __restrict__ nodes, bool iupac, int my_x, int side, int steps_max) {

@@ -89,7 +89,6 @@ struct rtk_batch {
     bool seeded = false, ran = false;
     rtk_stream_t stream = 0; bool has_stream = false;
     void (*on_region_slab)(void*) = nullptr; void* on_region_slab_arg = nullptr; // called once when the region stage of this batch has its work areas (the ticket coalescing of rtk_correct_batch paces its groups by it)
-    rtk_stream_t seed_stream = 0; bool has_seed_stream = false; // RTK_CU_SPLIT: the seed stage on its own compute units (rtk_mem.h); otherwise = stream
     rtk_stream_t stream2 = 0; bool has_stream2 = false; rtk_event_t ev[2]; // second stream of the region stage (the lane kernel beside the wave kernel) and the two events that order it
     rtk_stream_t lane_stream() { if (!has_stream2) { stream2 = rtk_stream_create_high(); ev[0] = rtk_event_create(); ev[1] = rtk_event_create(); has_stream2 = true; } return stream2; }
     RtkTimer t_all;
@@ -111,7 +110,7 @@ struct rtk_batch {
         bv.s_pos = alloc<uint32_t>(n_bases + 64); bv.n_solid = alloc<uint32_t>(n);
         bv.wk_cap = std::max<uint64_t>(4096, n_bases / 2); bv.wk_pos = alloc<uint32_t>(bv.wk_cap); bv.wk_hit = alloc<uint64_t>(bv.wk_cap); bv.wk_top = alloc<unsigned long long>(1);
         bv.w_off = alloc<uint64_t>(n); bv.w_cnt = alloc<uint32_t>(n);
-        bv.status = alloc<uint32_t>(n); bv.counters = alloc<unsigned long long>(224);
+        bv.status = alloc<uint32_t>(n); bv.counters = alloc<unsigned long long>(RTK_CNT_TOTAL);
     }
     rtk_batch() { memset(&bv, 0, sizeof(bv)); memset(&stats, 0, sizeof(stats)); memset(&rb, 0, sizeof(rb)); }
     // Round 6: a batch takes ONE buffer from the graph's pool, sized for everything it will ask for (rtk_batch_arena_bytes), and carves its ~45 arrays out of it; what does not
@@ -125,7 +124,7 @@ struct rtk_batch {
         if (arena && arena_top + bytes <= arena_bytes) { T* p = reinterpret_cast<T*>(arena + arena_top); arena_top += bytes; return p; }
         uint64_t got = 0; void* p = g->pool_take(bytes, &got); owned.push_back(std::make_pair(p, got)); return static_cast<T*>(p);
     }
-    ~rtk_batch() { if (has_seed_stream) { try { rtk_ssync(seed_stream); } catch (...) {} rtk_stream_destroy(seed_stream); } if (has_stream2) { try { rtk_ssync(stream2); } catch (...) {} rtk_stream_destroy(stream2); rtk_event_destroy(ev[0]); rtk_event_destroy(ev[1]); } if (has_stream) { try { rtk_ssync(stream); } catch (...) {} rtk_stream_destroy(stream); } if (g) { if (h_out) g->stage_give(h_out, h_out_bytes); for (size_t i = 0; i < owned.size(); ++i) g->pool_give(owned[i].first, owned[i].second); graph_release(g); } }
+    ~rtk_batch() { if (has_stream2) { try { rtk_ssync(stream2); } catch (...) {} rtk_stream_destroy(stream2); rtk_event_destroy(ev[0]); rtk_event_destroy(ev[1]); } if (has_stream) { try { rtk_ssync(stream); } catch (...) {} rtk_stream_destroy(stream); } if (g) { if (h_out) g->stage_give(h_out, h_out_bytes); for (size_t i = 0; i < owned.size(); ++i) g->pool_give(owned[i].first, owned[i].second); graph_release(g); } }
 };
 
 static bool opts_ok(const rtk_opts* o) { return o->struct_size == static_cast<uint32_t>(sizeof(rtk_opts)); }
@@ -140,7 +139,7 @@ static OptsView opts_view(const rtk_opts* o) {
 }
 
 // k_mask cuts the reads into segments of this many windows, one wave each (a multiple of 64 windows x the lanes of a wave; RTK_MASK_SEG: tests)
-static uint32_t mask_seg() { const uint32_t unit = 64u * RTK_WAVE; const char* e = getenv("RTK_MASK_SEG"); uint32_t v = e ? static_cast<uint32_t>(strtoul(e, nullptr, 10)) : 8192u; v = (v + unit - 1) / unit * unit; return v ? v : unit; }
+static uint32_t mask_seg() { const uint32_t unit = 64u * RTK_WAVE; uint32_t v = rtk_knob_mask_seg(); v = (v + unit - 1) / unit * unit; return v ? v : unit; }
 
 // what a batch of n reads / n_bases bases asks the pool for over its life (first pass: staging copy, seed-stage arrays, region arrays, segment and output pools; the raw-hit
 // pool holds one private chunk per resident wave: 268 MB whatever the ticket): ~62 B per base + 400 B per read + 280 MB, rounded up generously -- a short arena only means
@@ -196,8 +195,7 @@ extern "C" int rtk_batch_create(rtk_graph* g, uint32_t n, const char* const* seq
         rtk_set_device(g->device);
         std::unique_ptr<rtk_batch> b(new rtk_batch());
         b->g = g; b->n = n; g->refs.fetch_add(1);
-        if (rtk_cu_split(nullptr) > 0) { b->stream = rtk_stream_create_masked(false); b->has_stream = true; b->seed_stream = rtk_stream_create_masked(true); b->has_seed_stream = true; }
-        else { b->stream = rtk_stream_create(); b->has_stream = true; b->seed_stream = b->stream; }
+        b->stream = rtk_stream_create(); b->has_stream = true;
         b->roff.assign(n + 1, 0);
         for (uint32_t i = 0; i < n; ++i) b->roff[i + 1] = b->roff[i] + len[i];
         b->n_bases = b->roff[n];
@@ -250,14 +248,14 @@ extern "C" int rtk_batch_create(rtk_graph* g, uint32_t n, const char* const* seq
     return RTK_OK;
 }
 
-static int seed_waves() { const char* e = getenv("RTK_SEED_WAVES"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 4096; } // waves of the per-read seed kernels (one read each at a time, longest first): 16 per CU fit (LDS); 1024 -> 4096: k_mask 1.5 -> 1.0 ms, k_finalize 4.7 -> 3.0 ms per 64 Mb, 13 GB of work areas
+static int seed_waves() { return rtk_knob_seed_waves(); } // waves of the per-read seed kernels (one read each at a time, longest first): 16 per CU fit (LDS); 1024 -> 4096: k_mask 1.5 -> 1.0 ms, k_finalize 4.7 -> 3.0 ms per 64 Mb, 13 GB of work areas
 
 // anchors of every read (stage A of the pipeline): exact scan, mask, inexact scan, filters
 static void run_seed_stage(rtk_batch* b, const OptsView& ov, int attempt) {
     BatchView& bv = b->bv;
     const GraphView& g = b->g->dview;
-    const rtk_stream_t st = b->seed_stream;
-    rtk_dzero_s(bv.hitmap, 8ull * (b->n_bases / 64 + 4), st); rtk_dzero_s(bv.wdesc, 8ull * (b->n_bases + 64), st); rtk_dzero_s(bv.ipool_top, 8, st); rtk_dzero_s(bv.wk_top, 8, st); rtk_dzero_s(bv.status, 4ull * b->n, st); rtk_dzero_s(bv.counters, 8 * 224, st);
+    const rtk_stream_t st = b->stream;
+    rtk_dzero_s(bv.hitmap, 8ull * (b->n_bases / 64 + 4), st); rtk_dzero_s(bv.wdesc, 8ull * (b->n_bases + 64), st); rtk_dzero_s(bv.ipool_top, 8, st); rtk_dzero_s(bv.wk_top, 8, st); rtk_dzero_s(bv.status, 4ull * b->n, st); rtk_dzero_s(bv.counters, 8 * RTK_CNT_TOTAL, st);
     RtkTimer t0, t1, t2, t3;
     const int grid = default_grid();
     t0.start(st);
@@ -266,7 +264,7 @@ static void run_seed_stage(rtk_batch* b, const OptsView& ov, int attempt) {
     t0.stop(st);
     SeedScratchCfg cfg;
     cfg.set_cap = 32768u << (2 * attempt); cfg.v_cap = 32768u << (2 * attempt);
-    if (attempt == 0 && getenv("RTK_TEST_TINY_SCRATCH")) { cfg.set_cap = 48; cfg.v_cap = 64; } // test hook, see region_cfg
+    if (attempt == 0 && rtk_knob_test_tiny_scratch()) { cfg.set_cap = 48; cfg.v_cap = 64; } // test hook, see region_cfg
     uint32_t max_len = 0; for (uint32_t i = 0; i < b->n; ++i) max_len = std::max<uint32_t>(max_len, static_cast<uint32_t>(b->roff[i + 1] - b->roff[i]));
     { uint32_t q = 131072u; while (q < max_len) q <<= 1; cfg.s_cap = q + 64; } // coarse steps, see region_cfg
     const uint64_t stride = seed_scratch_bytes(cfg);
@@ -291,7 +289,7 @@ static void run_seed_stage(rtk_batch* b, const OptsView& ov, int attempt) {
     }
     t1.stop(st);
     t2.start(st);
-    if (!second_pass) { const char* e = getenv("RTK_INEXACT_ENUM"); if ((e && e[0] == '1') || g.hx_mask == 0) rtk_launch(k_inexact_enum, grid, st, L, bv, grid); else { const int sgrid = grid + grid / 2; rtk_launch(k_inexact, sgrid, st, L, bv, sgrid); } } // 76 VGPRs: six waves per SIMD (eight measured the same)
+    if (!second_pass) { if (rtk_knob_inexact_enum() || g.hx_mask == 0) rtk_launch(k_inexact_enum, grid, st, L, bv, grid); else { const int sgrid = grid + grid / 2; rtk_launch(k_inexact, sgrid, st, L, bv, sgrid); } } // 76 VGPRs: six waves per SIMD (eight measured the same)
     t2.stop(st);
     t3.start(st);
     rtk_launch(k_finalize, rgrid, st, L, bv, scratch, stride, cfg, rgrid);
@@ -305,14 +303,14 @@ static int seed_stage_checked(rtk_batch* b, const OptsView& ov) {
     for (int attempt = 0; attempt < 3; ++attempt) {
         const auto w0 = std::chrono::steady_clock::now();
         run_seed_stage(b, ov, attempt);
-        if (getenv("RTK_TRACE")) { unsigned long long c2[80]; rtk_d2h_s(c2, b->bv.counters, sizeof(c2), b->stream);
-            fprintf(stderr, "[rtk trace] finalize, slowest read: solid %.3g junction %.3g gather %.3g classify+sort %.3g groups %.3g conflicts %.3g write %.3g cycles\n", double(c2[72]), double(c2[73]), double(c2[74]), double(c2[75]), double(c2[76]), double(c2[77]), double(c2[78])); }
-        if (getenv("RTK_TRACE")) { unsigned long long c[32]; rtk_d2h_s(c, b->bv.counters, sizeof(c), b->stream);
-            fprintf(stderr, "[rtk trace] finalize wave-cycles: solid %.3g junction %.3g gather %.3g classify+sort %.3g groups %.3g conflicts %.3g write %.3g | slowest read %.3g cycles\n", double(c[24]), double(c[25]), double(c[26]), double(c[27]), double(c[28]), double(c[29]), double(c[30]), double(c[31])); }
-        if (getenv("RTK_TRACE")) fprintf(stderr, "[rtk trace] seeds attempt %d: %.2f ms (kernels %.2f)\n", attempt, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count(), b->stats.ms_lookup_exact + b->stats.ms_mask + b->stats.ms_lookup_inexact + b->stats.ms_seeds);
+        if (rtk_knob_trace()) { unsigned long long c2[RTK_CNT_FINALIZE_SLOWEST_PHASES_END]; rtk_d2h_s(c2, b->bv.counters, sizeof(c2), b->stream);
+            fprintf(stderr, "[rtk trace] finalize, slowest read: solid %.3g junction %.3g gather %.3g classify+sort %.3g groups %.3g conflicts %.3g write %.3g cycles\n", double(c2[RTK_CNT_FINALIZE_SLOWEST_PHASES + 0]), double(c2[RTK_CNT_FINALIZE_SLOWEST_PHASES + 1]), double(c2[RTK_CNT_FINALIZE_SLOWEST_PHASES + 2]), double(c2[RTK_CNT_FINALIZE_SLOWEST_PHASES + 3]), double(c2[RTK_CNT_FINALIZE_SLOWEST_PHASES + 4]), double(c2[RTK_CNT_FINALIZE_SLOWEST_PHASES + 5]), double(c2[RTK_CNT_FINALIZE_SLOWEST_PHASES + 6])); }
+        if (rtk_knob_trace()) { unsigned long long c[RTK_CNT_FINALIZE_END]; rtk_d2h_s(c, b->bv.counters, sizeof(c), b->stream);
+            fprintf(stderr, "[rtk trace] finalize wave-cycles: solid %.3g junction %.3g gather %.3g classify+sort %.3g groups %.3g conflicts %.3g write %.3g | slowest read %.3g cycles\n", double(c[RTK_CNT_FINALIZE + 0]), double(c[RTK_CNT_FINALIZE + 1]), double(c[RTK_CNT_FINALIZE + 2]), double(c[RTK_CNT_FINALIZE + 3]), double(c[RTK_CNT_FINALIZE + 4]), double(c[RTK_CNT_FINALIZE + 5]), double(c[RTK_CNT_FINALIZE + 6]), double(c[RTK_CNT_FINALIZE_SLOWEST])); }
+        if (rtk_knob_trace()) fprintf(stderr, "[rtk trace] seeds attempt %d: %.2f ms (kernels %.2f)\n", attempt, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count(), b->stats.ms_lookup_exact + b->stats.ms_mask + b->stats.ms_lookup_inexact + b->stats.ms_seeds);
         std::vector<uint32_t> st(b->n);
         rtk_d2h_s(st.data(), b->bv.status, 4ull * b->n, b->stream);
-        unsigned long long cnt[16]; rtk_d2h_s(cnt, b->bv.counters, sizeof(cnt), b->stream);
+        unsigned long long cnt[RTK_CNT_SEED_READBACK]; rtk_d2h_s(cnt, b->bv.counters, sizeof(cnt), b->stream);
         bool ovf = cnt[RTK_CNT_OVERFLOW] != 0;
         for (uint32_t i = 0; i < b->n; ++i) if (st[i]) ovf = true;
         if (!ovf) return RTK_OK;
@@ -484,7 +482,7 @@ static int phase_step(rtk_batch* b, const OptsView& ov) {
     BatchView& bv = b->bv;
     const rtk_stream_t st = b->stream;
     const int grid = default_grid();
-    rtk_dzero_s(bv.hitmap, 8ull * (b->n_bases / 64 + 4), st); rtk_dzero_s(bv.status, 4ull * b->n, st); rtk_dzero_s(bv.counters, 8 * 224, st);
+    rtk_dzero_s(bv.hitmap, 8ull * (b->n_bases / 64 + 4), st); rtk_dzero_s(bv.status, 4ull * b->n, st); rtk_dzero_s(bv.counters, 8 * RTK_CNT_TOTAL, st);
     { const int xgrid = 2 * grid; rtk_launch(k_lookup_exact, xgrid, st, g->dview, bv.seq, bv.roff, bv.n_reads, bv.n_bases, xgrid, bv.hits.get(), bv.hitmap.get(), reinterpret_cast<uint64_t*>(bv.counters + RTK_CNT_PROBES_EXACT)); }
     uint32_t max_len = b->raw_max_len; for (uint32_t i = 0; i < b->n; ++i) max_len = std::max<uint32_t>(max_len, static_cast<uint32_t>(b->roff[i + 1] - b->roff[i]));
     PhaseView pv;
@@ -496,7 +494,7 @@ static int phase_step(rtk_batch* b, const OptsView& ov) {
         auto fpp = [&](uint64_t h) { const double h_d = static_cast<double>(h); return std::pow(1.0 - std::exp(-(h_d / bpe)), h_d); };
         nb_h += static_cast<uint64_t>(fpp(nb_h) >= fpp(nb_h + 1));
         pv.tbf_nb_h = static_cast<uint32_t>(nb_h & 0xffull); }
-    { const char* e = getenv("RTK_PHASE_ALIGN_ALL"); pv.align_all = (e && e[0] == '1') ? 1u : 0u; }
+    pv.align_all = rtk_knob_phase_align_all() ? 1u : 0u;
     rtk_dzero_s(pv.out_top, 8, st);
     struct Slab { rtk_graph* g; void* p; uint64_t n; ~Slab() { if (p) g->phase_give(p, n); } } slab = {g, nullptr, 0}; // this ticket's own work area (no graph-wide lock)
     // Three classes of reads, longest first inside each. The whole-read alignment of phasing() is linear in the read length per Hirschberg level
@@ -507,7 +505,7 @@ static int phase_step(rtk_batch* b, const OptsView& ov) {
     //   long   (>  RTK_PHASE_LONG)     4 waves per read (k_phase_long; RTK_PHASE_LWAVES): gangs / row blocks of a level and the leaf tracebacks side by side
     std::vector<uint32_t> l_short, l_long, l_mid;
     {
-        uint32_t thr = 24576; { const char* e = getenv("RTK_PHASE_LONG"); if (e) thr = static_cast<uint32_t>(strtoul(e, nullptr, 10)); } // 0: no multi-wave class
+        const uint32_t thr = rtk_knob_phase_long(); // 0: no multi-wave class
         const uint32_t thr_s = 8192; (void)thr_s;
         std::vector<uint64_t> roff_raw(b->n + 1); rtk_d2h_s(roff_raw.data(), b->d_raw_off, 8ull * (b->n + 1), st);
         std::vector<uint32_t> ord(b->n); rtk_d2h_s(ord.data(), bv.order, 4ull * b->n, st);
@@ -539,14 +537,14 @@ static int phase_step(rtk_batch* b, const OptsView& ov) {
         // waves per workgroup of the long class. A second-pass run is bound by wave slots (128 VGPRs: 4096 waves on the chip, several tickets in flight) and
         // the helpers of a workgroup idle most of the time since the passes are banded: 4 waves x 192 workgroups instead of 16 x 64 is +15-20 % on the
         // file-to-file rate (profiles/scripts/p2_sweep.sh); the longest read of a ticket takes longer, other tickets fill the time
-        int lwaves = 4; { const char* e = getenv("RTK_PHASE_LWAVES"); if (e) lwaves = std::max(1, std::min(16, atoi(e))); }
+        const int lwaves = rtk_knob_phase_lwaves();
         const uint64_t stride_s = region_scratch_bytes(cfg_s), stride_l = rtk_phase_long_stride(cfg_l, lwaves), stride_m = region_scratch_bytes(cfg_m);
-        int pgrid = attempt == 0 ? (getenv("RTK_PHASE_PGRID") ? atoi(getenv("RTK_PHASE_PGRID")) : 1024) : (attempt == 1 ? 128 : 8);
+        int pgrid = attempt == 0 ? rtk_knob_phase_pgrid() : (attempt == 1 ? 128 : 8);
 #endif
         pgrid = static_cast<int>(std::min<uint32_t>(static_cast<uint32_t>(pgrid), l_short.empty() ? 1u : static_cast<uint32_t>(l_short.size())));
-        int lgrid = attempt == 0 ? (getenv("RTK_PHASE_LGRID") ? atoi(getenv("RTK_PHASE_LGRID")) : 192) : (attempt == 1 ? 16 : 4); // workgroups of `lwaves` waves
+        int lgrid = attempt == 0 ? rtk_knob_phase_lgrid() : (attempt == 1 ? 16 : 4); // workgroups of `lwaves` waves
         lgrid = static_cast<int>(std::min<uint32_t>(static_cast<uint32_t>(lgrid), l_long.empty() ? 1u : static_cast<uint32_t>(l_long.size())));
-        int mgrid = attempt == 0 ? (getenv("RTK_PHASE_MGRID") ? atoi(getenv("RTK_PHASE_MGRID")) : 768) : (attempt == 1 ? 64 : 4);
+        int mgrid = attempt == 0 ? rtk_knob_phase_mgrid() : (attempt == 1 ? 64 : 4);
         mgrid = static_cast<int>(std::min<uint32_t>(static_cast<uint32_t>(mgrid), l_mid.empty() ? 1u : static_cast<uint32_t>(l_mid.size())));
         const uint64_t off_l = stride_s * static_cast<uint64_t>(pgrid), off_m = off_l + (l_long.empty() ? 0u : stride_l * static_cast<uint64_t>(lgrid));
         const uint64_t need = off_m + (l_mid.empty() ? 0u : stride_m * static_cast<uint64_t>(mgrid));
@@ -567,14 +565,14 @@ static int phase_step(rtk_batch* b, const OptsView& ov) {
           if (!err.empty()) throw std::runtime_error(err); }
 #endif
         rtk_ssync(st);
-        if (getenv("RTK_TRACE")) fprintf(stderr, "[rtk trace] phase attempt %d: %.2f ms (k_phase %d waves for %zu reads <= 8 kb and %d waves for %zu longer ones, k_phase_long %d x %d for %zu reads, work areas %.1f GB), %llu + %llu bases\n", attempt, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tp0).count(), pgrid, l_short.size(), l_mid.empty() ? 0 : mgrid, l_mid.size(), lwaves, l_long.empty() ? 0 : lgrid, l_long.size(), need / 1073741824.0, static_cast<unsigned long long>(b->n_bases), static_cast<unsigned long long>(b->raw_bases));
+        if (rtk_knob_trace()) fprintf(stderr, "[rtk trace] phase attempt %d: %.2f ms (k_phase %d waves for %zu reads <= 8 kb and %d waves for %zu longer ones, k_phase_long %d x %d for %zu reads, work areas %.1f GB), %llu + %llu bases\n", attempt, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tp0).count(), pgrid, l_short.size(), l_mid.empty() ? 0 : mgrid, l_mid.size(), lwaves, l_long.empty() ? 0 : lgrid, l_long.size(), need / 1073741824.0, static_cast<unsigned long long>(b->n_bases), static_cast<unsigned long long>(b->raw_bases));
         { unsigned long long sk = 0; rtk_d2h_s(&sk, bv.counters + RTK_CNT_PHASE_SKIPPED, sizeof(sk), st); b->stats.n_phase_skipped = sk; b->stats.ms_phase = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tp0).count();
-          if (getenv("RTK_TRACE")) fprintf(stderr, "[rtk trace] phase: whole-read alignment skipped for %llu of %u reads (no unsupported stretch)\n", sk, b->n); }
-        if (getenv("RTK_TRACE")) { unsigned long long pc[5]; rtk_d2h_s(pc, bv.counters + 59, sizeof(pc), st);
+          if (rtk_knob_trace()) fprintf(stderr, "[rtk trace] phase: whole-read alignment skipped for %llu of %u reads (no unsupported stretch)\n", sk, b->n); }
+        if (rtk_knob_trace()) { unsigned long long pc[RTK_CNT_PHASE_TRACE_END - RTK_CNT_PHASE_TRACE]; rtk_d2h_s(pc, bv.counters + RTK_CNT_PHASE_TRACE, sizeof(pc), st);
             fprintf(stderr, "[rtk trace] k_phase_long wave-0 cycles: alignments %.3g, of which Hirschberg driver %.3g (half passes %.3g, columns + split %.3g, leaf tracebacks %.3g)\n", double(pc[0]), double(pc[4]), double(pc[1]), double(pc[2]), double(pc[3])); }
         std::vector<uint32_t> stt(b->n); rtk_d2h_s(stt.data(), bv.status, 4ull * b->n, st);
         bool ovf = false; for (uint32_t i = 0; i < b->n; ++i) if (stt[i]) ovf = true;
-        if (ovf && getenv("RTK_TRACE")) { std::map<uint32_t, std::pair<uint32_t, uint32_t> > hist; for (uint32_t i = 0; i < b->n; ++i) if (stt[i]) { auto& h = hist[stt[i]]; ++h.first; h.second = std::max<uint32_t>(h.second, static_cast<uint32_t>(b->roff[i + 1] - b->roff[i])); }
+        if (ovf && rtk_knob_trace()) { std::map<uint32_t, std::pair<uint32_t, uint32_t> > hist; for (uint32_t i = 0; i < b->n; ++i) if (stt[i]) { auto& h = hist[stt[i]]; ++h.first; h.second = std::max<uint32_t>(h.second, static_cast<uint32_t>(b->roff[i + 1] - b->roff[i])); }
             fprintf(stderr, "[rtk trace] phase attempt %d: reads to do again by status code:", attempt); for (auto& kv : hist) fprintf(stderr, " [code %u: %u reads, longest %u]", kv.first, kv.second.first, kv.second.second); fprintf(stderr, "\n"); }
         if (!ovf) break;
         if (attempt == 2) return rtk_fail(RTK_ERR_DEVICE, "phasing: scratch capacity exceeded after 3 attempts");

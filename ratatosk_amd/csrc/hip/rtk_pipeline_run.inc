@@ -206,7 +206,7 @@ RTK_GLOBAL void k_regions_lanes(const LaunchCtx* L, uint32_t* area, uint64_t* ta
 #endif
             rl_region_program(c, rd, &osl, &oql);
 #if defined(RTK_SIM) && defined(RTK_LANE_PROF)
-            if (getenv("RTK_LANE_COST")) { const uint32_t* sp_ = bv.s_pos + bv.roff[rd->read]; fprintf(stderr, "LANECOST gap %u cycles %llu expand %u align %u cells %llu fail %u\n", sp_[rd->i_solid + 1] - sp_[rd->i_solid], rtk_clock() - tr0_, c.c_expand - e0, c.c_align - e3, c.c_cells - e4, c.fail()); }
+            if (rtk_knob_lane_cost()) { const uint32_t* sp_ = bv.s_pos + bv.roff[rd->read]; fprintf(stderr, "LANECOST gap %u cycles %llu expand %u align %u cells %llu fail %u\n", sp_[rd->i_solid + 1] - sp_[rd->i_solid], rtk_clock() - tr0_, c.c_expand - e0, c.c_align - e3, c.c_cells - e4, c.fail()); }
 #endif
             if (c.fail()) { osl = 0; oql = 0; c.c_expand = e0; c.c_colour = e1; c.c_pathbase = e2; c.c_align = e3; c.c_cells = e4; } // (the wave kernel counts the region's events when it redoes it)
         }
@@ -239,7 +239,7 @@ RTK_GLOBAL void k_regions_lanes(const LaunchCtx* L, uint32_t* area, uint64_t* ta
 #ifndef RTK_SIM
       for (int o = 32; o > 0; o >>= 1) { v_ += __shfl_xor(v_, o, 64); w_ += __shfl_xor(w_, o, 64); }
 #endif
-      if (lane == 0 && v_) { rtk_atomic_add(bv.counters + 160 + x, v_); rtk_atomic_add(bv.counters + 184 + x, w_); } } }
+      if (lane == 0 && v_) { rtk_atomic_add(bv.counters + RTK_CNT_LANE_PROF + x, v_); rtk_atomic_add(bv.counters + RTK_CNT_LANE_PROF2 + x, w_); } } }
 #endif
     {
     // event counters: one atomic per wave and counter
@@ -250,7 +250,7 @@ RTK_GLOBAL void k_regions_lanes(const LaunchCtx* L, uint32_t* area, uint64_t* ta
     if (lane == 0) {
         if (v[0]) rtk_atomic_add(bv.counters + RTK_CNT_EXPAND, v[0]); if (v[1]) rtk_atomic_add(bv.counters + RTK_CNT_COLOUR, v[1]); if (v[2]) rtk_atomic_add(bv.counters + RTK_CNT_PATHBASE, v[2]);
         if (v[3]) rtk_atomic_add(bv.counters + RTK_CNT_ALIGN, v[3]); if (v[4]) rtk_atomic_add(bv.counters + RTK_CNT_CELLS, v[4]);
-        if (v[5]) rtk_atomic_add(bv.counters + 152, v[5]); if (v[6]) rtk_atomic_add(bv.counters + 153, v[6]); // lane kernel: regions handed on / done
+        if (v[5]) rtk_atomic_add(bv.counters + RTK_CNT_LANE_HANDED, v[5]); if (v[6]) rtk_atomic_add(bv.counters + RTK_CNT_LANE_DONE, v[6]); // lane kernel: regions handed on / done
     }
     }
 }
@@ -277,7 +277,7 @@ RTK_GLOBAL void k_regions(const LaunchCtx* L, GraphView g, OptsView o, BatchView
     unsigned long long nxt = 0;
     if (rtk_lane() == 0) nxt = rtk_atomic_add(rb.next_region, 1ull);
 #if !defined(RTK_SIM)
-    // developer figures of a traced run (counters 144..149): the longest single region, when the first wave started and the last one ended, the sum of the waves' lifetimes
+    // developer figures of a traced run (RTK_CNT_WAVE_TRACE): the longest single region, when the first wave started and the last one ended, the sum of the waves' lifetimes
     const unsigned long long wall0 = trace_class >= -1 ? 0ull : wall_clock64(); unsigned long long dt_max = 0, n_mine = 0, idx_of_max = 0;
 #endif
     int steal_sub = 0; // which & 4: own lists drained, the regions of the lane kernel's class one at a time, from the queue that kernel takes its rounds of 64 from
@@ -326,7 +326,7 @@ RTK_GLOBAL void k_regions(const LaunchCtx* L, GraphView g, OptsView o, BatchView
         const unsigned long long t0 = rtk_clock();
         const unsigned long long exp0 = RTK_HIST_GET(*sc, 31);
         rtk_region_program(c, rd);
-        { const unsigned long long dt = rtk_clock() - t0; sc->cnt[8] += dt;
+        { const unsigned long long dt = rtk_clock() - t0; sc->cnt[RTK_RC_CYC_TOTAL] += dt;
 #if !defined(RTK_SIM)
           if (trace_class < -1) { ++n_mine; if (dt > dt_max) { dt_max = dt; idx_of_max = idx; } }
 #endif
@@ -344,22 +344,22 @@ RTK_GLOBAL void k_regions(const LaunchCtx* L, GraphView g, OptsView o, BatchView
 #if !defined(RTK_SIM)
     if (trace_class < -1 && rtk_lane() == 0) {
         const unsigned long long wall1 = wall_clock64();
-        atomicMax(reinterpret_cast<unsigned long long*>(bv.counters + 144), dt_max); atomicMax(reinterpret_cast<unsigned long long*>(bv.counters + 145), ~wall0); atomicMax(reinterpret_cast<unsigned long long*>(bv.counters + 146), wall1);
-        rtk_atomic_add(bv.counters + 147, wall1 - wall0); rtk_atomic_add(bv.counters + 148, 1ull);
-        if (dt_max > 0 && atomicMax(reinterpret_cast<unsigned long long*>(bv.counters + 149), dt_max) < dt_max) bv.counters[150] = idx_of_max; // (racy on purpose: a hint of WHERE in the order the longest region sat)
+        atomicMax(reinterpret_cast<unsigned long long*>(bv.counters + RTK_CNT_WAVE_TRACE + 0), dt_max); atomicMax(reinterpret_cast<unsigned long long*>(bv.counters + RTK_CNT_WAVE_TRACE + 1), ~wall0); atomicMax(reinterpret_cast<unsigned long long*>(bv.counters + RTK_CNT_WAVE_TRACE + 2), wall1);
+        rtk_atomic_add(bv.counters + RTK_CNT_WAVE_TRACE + 3, wall1 - wall0); rtk_atomic_add(bv.counters + RTK_CNT_WAVE_TRACE + 4, 1ull);
+        if (dt_max > 0 && atomicMax(reinterpret_cast<unsigned long long*>(bv.counters + RTK_CNT_WAVE_TRACE + 5), dt_max) < dt_max) bv.counters[RTK_CNT_WAVE_TRACE + 6] = idx_of_max; // (racy on purpose: a hint of WHERE in the order the longest region sat)
         // when this wave took its last region off the queue, relative to the first start: waves that stop early leave their slots idle
-        atomicMax(reinterpret_cast<unsigned long long*>(bv.counters + 151), n_mine);
+        atomicMax(reinterpret_cast<unsigned long long*>(bv.counters + RTK_CNT_WAVE_TRACE + 7), n_mine);
     }
 #endif
     if (rtk_lane() == 0) {
-        rtk_atomic_add(bv.counters + RTK_CNT_EXPAND, sc->cnt[0]); rtk_atomic_add(bv.counters + RTK_CNT_COLOUR, sc->cnt[1]); rtk_atomic_add(bv.counters + RTK_CNT_PATHBASE, sc->cnt[2]);
-        rtk_atomic_add(bv.counters + RTK_CNT_ALIGN, sc->cnt[3]); rtk_atomic_add(bv.counters + RTK_CNT_CELLS, sc->cnt[4]);
-        for (int i = 0; i < 6; ++i) rtk_atomic_add(bv.counters + 16 + i, sc->cnt[5 + i]);
-        rtk_atomic_add(bv.counters + 21, sc->cnt[11]); rtk_atomic_add(bv.counters + 22, sc->cnt[12]); rtk_atomic_add(bv.counters + 23, sc->cnt[13]); rtk_atomic_add(bv.counters + 32, sc->my.walk_cycles); rtk_atomic_add(bv.counters + 33, sc->my.walk_moves); rtk_atomic_add(bv.counters + 34, sc->my.walk_reloads); rtk_atomic_add(bv.counters + 35, sc->my.walk_scalar); rtk_atomic_add(bv.counters + 36, sc->my.walk_calls); rtk_atomic_add(bv.counters + 37, sc->my.walk_tail_cycles); rtk_atomic_add(bv.counters + 38, sc->cnt[14]); rtk_atomic_add(bv.counters + 39, sc->cnt[15]);
-        for (int i = 0; i < 16; ++i) rtk_atomic_add(bv.counters + 40 + i, sc->fine[i]);
-        for (int i = 0; i < 32; ++i) rtk_atomic_add(bv.counters + 56 + i, static_cast<unsigned long long>(RTK_HIST_GET(*sc, i)));
+        rtk_atomic_add(bv.counters + RTK_CNT_EXPAND, sc->cnt[RTK_RC_EXPAND]); rtk_atomic_add(bv.counters + RTK_CNT_COLOUR, sc->cnt[RTK_RC_COLOUR]); rtk_atomic_add(bv.counters + RTK_CNT_PATHBASE, sc->cnt[RTK_RC_PATHBASE]);
+        rtk_atomic_add(bv.counters + RTK_CNT_ALIGN, sc->cnt[RTK_RC_ALIGN]); rtk_atomic_add(bv.counters + RTK_CNT_CELLS, sc->cnt[RTK_RC_CELLS]);
+        for (int i = 0; i < 6; ++i) rtk_atomic_add(bv.counters + RTK_CNT_CYC + i, sc->cnt[RTK_RC_CYC_COLOUR + i]);
+        rtk_atomic_add(bv.counters + RTK_CNT_CYC_SETS, sc->cnt[RTK_RC_CYC_PATHREC]); rtk_atomic_add(bv.counters + RTK_CNT_CYC_TOSTRING, sc->cnt[RTK_RC_CYC_TOSTRING]); rtk_atomic_add(bv.counters + RTK_CNT_CYC_PATHQUAL, sc->cnt[RTK_RC_CYC_PATHQUAL]); rtk_atomic_add(bv.counters + RTK_CNT_WALK_CYCLES, sc->my.walk_cycles); rtk_atomic_add(bv.counters + RTK_CNT_WALK_MOVES, sc->my.walk_moves); rtk_atomic_add(bv.counters + RTK_CNT_WALK_RELOADS, sc->my.walk_reloads); rtk_atomic_add(bv.counters + RTK_CNT_WALK_SCALAR, sc->my.walk_scalar); rtk_atomic_add(bv.counters + RTK_CNT_WALK_CALLS, sc->my.walk_calls); rtk_atomic_add(bv.counters + RTK_CNT_WALK_TAIL, sc->my.walk_tail_cycles); rtk_atomic_add(bv.counters + RTK_CNT_CYC_DFS, sc->cnt[RTK_RC_CYC_DFS]); rtk_atomic_add(bv.counters + RTK_CNT_CYC_COLOUR_OK, sc->cnt[RTK_RC_CYC_COLOUR_OK]);
+        for (int i = 0; i < RTK_FINE_N; ++i) rtk_atomic_add(bv.counters + RTK_CNT_FINE + i, sc->fine[i]);
+        for (int i = 0; i < 32; ++i) rtk_atomic_add(bv.counters + RTK_CNT_HIST + i, static_cast<unsigned long long>(RTK_HIST_GET(*sc, i)));
 #ifdef RTK_PROF
-        for (int i = 0; i < 48; ++i) rtk_atomic_add(bv.counters + 96 + i, static_cast<unsigned long long>(sc->prof[i]));
+        for (int i = 0; i < 48; ++i) rtk_atomic_add(bv.counters + RTK_CNT_PROF + i, static_cast<unsigned long long>(sc->prof[i]));
 #endif
     }
 }
@@ -371,30 +371,20 @@ RTK_GLOBAL void k_stitch_copy(const LaunchCtx* L, uint64_t n_regions, int grid) 
     for (uint64_t c0 = static_cast<uint64_t>(RTK_BLOCK_ID) * RTK_WAVE; c0 < n_regions; c0 += static_cast<uint64_t>(grid) * RTK_WAVE) rtk_stitch_copy(L->rb, c0, n_regions);
 }
 
-// the lane-per-region kernel: gaps under this many bases are its class (RTK_LANE_MAX_GAP; 0 = off); its resident waves (RTK_LANE_WAVES)
-// Off by default (round 5): the kernel is byte-identical to the wave kernel on every tier but not yet faster -- a lane's program is one long dependent chain, ~5 ms per
-// region on one lane (DESIGN_HISTORY.md section 3.8) -- so a run opts in with RTK_LANE_MAX_GAP=128 (the bench measures both ways and reports the pair).
-static uint32_t lane_max_gap() { const char* e = getenv("RTK_LANE_MAX_GAP"); return e ? static_cast<uint32_t>(strtoul(e, nullptr, 10)) : 0u; }
-static int lane_waves() { const char* e = getenv("RTK_LANE_WAVES"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 1024; }
-// Round 6, the decision the lane kernel was waiting for: it pays from ~10^6 lane-class regions per launch upwards (break-even at 253 Mb per ticket, -5.5 % of the region stage at
-// 989 Mb, one kernel after the other on 4 096 lane waves: DESIGN_HISTORY.md section 3.8), so a ticket of at least RTK_LANE_AUTO_BASES (512 Mi; 0 = never) bases -- `Ratatosk correct -B`
-// that large, or a caller's own -- takes it for gaps under 128 without being asked; smaller tickets (every ticket of the bench and of the CLI's default -B) never do.
-static uint64_t lane_auto_bases() { static const uint64_t v = [] { const char* e = getenv("RTK_LANE_AUTO_BASES"); return e ? strtoull(e, nullptr, 10) : (512ull << 20); }(); return v; }
-static bool region_compact() { const char* e = getenv("RTK_COMPACT"); return e && e[0] == '1'; } // measured on configs[1]: same kernel time as the full-size areas (78.4 vs 79.5 ms) plus a 19 ms redo launch; kept for graphs that leave little HBM
-static int region_waves() { const char* e = getenv("RTK_REGION_WAVES"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 4096; }
+static bool region_compact() { return rtk_knob_compact(); } // measured on configs[1]: same kernel time as the full-size areas (78.4 vs 79.5 ms) plus a 19 ms redo launch; kept for graphs that leave little HBM
 // resident waves of the region stage whose work areas (`stride` bytes each) fit next to a big graph: at most 70 % of what is free now plus what the
 // stage holds already (`held`); 4096 when there is room (a 5 Mb .. 60 Mb graph), never below 512
-static int region_waves_that_fit(uint64_t stride, uint64_t held) {
-    int w = region_waves();
+static int region_waves_that_fit(uint64_t stride, uint64_t held, bool trace) {
+    int w = rtk_knob_region_waves();
 #ifndef RTK_SIM
     size_t fr = 0, tot = 0;
     if (hipMemGetInfo(&fr, &tot) == hipSuccess && stride) {
         const uint64_t room = (static_cast<uint64_t>(fr) + held) / 10 * 7;
-        if (getenv("RTK_TRACE")) fprintf(stderr, "[rtk trace] region work areas: %.1f GB free + %.1f GB held of %.1f GB, %d waves x %.1f MB wanted\n", fr / 1073741824.0, held / 1073741824.0, tot / 1073741824.0, w, stride / 1048576.0);
+        if (trace) fprintf(stderr, "[rtk trace] region work areas: %.1f GB free + %.1f GB held of %.1f GB, %d waves x %.1f MB wanted\n", fr / 1073741824.0, held / 1073741824.0, tot / 1073741824.0, w, stride / 1048576.0);
         if (static_cast<uint64_t>(w) * stride > room) { uint64_t f = room / stride / 256 * 256; if (f < 512) f = 512; if (f < static_cast<uint64_t>(w)) w = static_cast<int>(f); }
     }
 #else
-    (void)stride; (void)held;
+    (void)stride; (void)held; (void)trace;
 #endif
     return w;
 }
@@ -402,7 +392,7 @@ static int region_waves_that_fit(uint64_t stride, uint64_t held) {
 static RegionScratchCfg region_cfg(uint32_t max_len_exact, int attempt) { // (declared in rtk_pipeline.inc for the phasing step)
     RegionScratchCfg c;
     uint32_t max_len = 131072u; while (max_len < max_len_exact) max_len <<= 1; // coarse steps: the per-wave slab (and the cached tens of GB behind it) keeps its size from batch to batch
-    if (attempt == 0 && getenv("RTK_TEST_TINY_SCRATCH")) { // test hook: start from a deliberately undersized work area so that the redo path runs
+    if (attempt == 0 && rtk_knob_test_tiny_scratch()) { // test hook: start from a deliberately undersized work area so that the redo path runs
         c.str_cap = 2048; c.my.w_cap = c.str_cap / 64 + 2; c.my.t_cap = c.str_cap; c.my.r_cap = c.str_cap; c.my.mv_cap = 2 * c.str_cap;
         c.my.tb_cap_words = 4ull * 52429 + 64; c.set_cap = 64; c.um_cap = 8; c.list_cap = 64; c.memo_cap = 16; c.bm_words = max_len / 64 + 8; c.arena_cap = 8192;
         return c;
@@ -452,208 +442,399 @@ extern "C" int rtk_batch_run_seeds(rtk_batch* b, const rtk_opts* opts) {
     return rc;
 }
 
+// ---- stage B, host side. rtk_batch_run_regions (below) calls these steps in order; what they hand on to each other lives in RegionRun.
+// the graph-wide work areas of the region stage (rtk_graph::region_slab_take): one half (what = 0 / 1) or both (2), given back when the stage leaves
+struct SlabHold {
+    rtk_graph* g; int what;
+    void take(bool half_ok) { what = g->region_slab_take(half_ok); }
+    void release() { if (what >= 0) { g->region_slab_give(what); what = -1; } }
+    ~SlabHold() { release(); }
+};
+// second pass: a work area of the ticket's own (no graph-wide lock, so that the tickets in flight overlap)
+struct OwnSlab {
+    rtk_graph* g; void* p; uint64_t n;
+    char* at_least(uint64_t bytes) { if (n < bytes) { if (p) { g->phase_give(p, n); p = nullptr; n = 0; } p = g->phase_take(bytes, &n); } return static_cast<char*>(p); }
+    ~OwnSlab() { if (p) g->phase_give(p, n); }
+};
+struct RegionRun {
+    rtk_batch* b; rtk_graph* g; OptsView ov; rtk_stream_t sm;
+    bool trace;     // RTK_TRACE, read once per call
+    // Second pass: a ticket has few, big regions (one per 3 kb of read, up to -W 5000 characters) and its launch lasts as long as its
+    // biggest one with most wave slots idle: it gets a work area of its own so that the tickets in flight overlap.
+    bool own_slab;
+    std::chrono::steady_clock::time_point w0;
+    int grid; uint32_t max_len; unsigned long long n_regions, n_ovf_total, out_top;
+    bool lane_auto, lanes_on, lanes_beside; int lane_waves_used;
+    RtkTimer t_enum, t_easy, t_lanes, t_reg, t_st; double ms_reg;
+    SlabHold hold; OwnSlab slab;
+    const LaunchCtx* ctx() const { return static_cast<const LaunchCtx*>(b->ctx()); }
+    void set_ctx() { rtk_launch(k_set_ctx, 1, sm, b->ctx(), g->dview, ov, b->bv, b->rb); }
+    void lap(const char* what) const {
+        if (trace) fprintf(stderr, "[rtk trace] regions %-10s +%.2f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count());
+    }
+};
+
+// the lists that hold one entry per region
+static void region_alloc_lists(rtk_batch* b, uint64_t cap) {
+    RegionBatch& rb = b->rb;
+    rb.regions_cap = cap;
+    rb.regions = b->alloc<RegionDesc>(cap); rb.rorder = b->alloc<uint32_t>(cap); rb.eorder = b->alloc<uint32_t>(cap);
+    rb.lorder = b->alloc<uint32_t>(4 * cap); rb.horder = b->alloc<uint32_t>(cap); rb.st_off = b->alloc<uint64_t>(cap);
+}
+
+// the per-batch buffers of the stage (first run of this batch only)
+static void region_alloc(RegionRun& R) {
+    rtk_batch* b = R.b; RegionBatch& rb = b->rb;
+    if (rb.seq_rc) return;
+    rb.seq_rc = b->alloc<char>(b->n_bases + 64);
+    rb.qual_rev = b->bv.qual.get() ? b->alloc<char>(b->n_bases + 64) : nullptr;
+    rb.r_first = b->alloc<uint64_t>(b->n); rb.r_count = b->alloc<uint32_t>(b->n);
+    rb.n_regions = b->alloc<unsigned long long>(1); rb.n_heavy = b->alloc<unsigned long long>(16); rb.seg_top = b->alloc<unsigned long long>(1);
+    rb.next_region = b->alloc<unsigned long long>(1); rb.n_overflow = b->alloc<unsigned long long>(1); rb.out_top = b->alloc<unsigned long long>(1);
+    rb.out_off = b->alloc<uint64_t>(b->n); rb.out_seq_len = b->alloc<uint32_t>(b->n); rb.out_qual_len = b->alloc<uint32_t>(b->n);
+    region_alloc_lists(b, std::max<uint64_t>(1024, b->n_bases / 8 + 4ull * b->n));
+    rb.next_lane = b->alloc<unsigned long long>(4);
+    rb.seg_cap = 6 * b->n_bases + (1ull << 20); rb.seg_pool = b->alloc<char>(rb.seg_cap);
+    rb.out_cap = 6 * b->n_bases + (1ull << 20); rb.out_pool = b->alloc<char>(rb.out_cap);
+}
+
+// Which regions the lane-per-region kernel gets (known before the views go to the device): gaps under RTK_LANE_MAX_GAP bases (0 = off); none in the second pass.
+// Off by default (round 5): the kernel is byte-identical to the wave kernel on every tier but not yet faster -- a lane's program is one long dependent chain, ~5 ms per
+// region on one lane (DESIGN_HISTORY.md section 3.8) -- so a run opts in with RTK_LANE_MAX_GAP=128 (the bench measures both ways and reports the pair).
+// Round 6, the decision the lane kernel was waiting for: it pays from ~10^6 lane-class regions per launch upwards (break-even at 253 Mb per ticket, -5.5 % of the region stage at
+// 989 Mb, one kernel after the other on 4 096 lane waves: DESIGN_HISTORY.md section 3.8), so a ticket of at least RTK_LANE_AUTO_BASES (512 Mi; 0 = never) bases -- `Ratatosk correct -B`
+// that large, or a caller's own -- takes it for gaps under 128 without being asked; smaller tickets (every ticket of the bench and of the CLI's default -B) never do.
+static void region_lane_class(RegionRun& R) {
+    const uint64_t auto_bases = rtk_knob_lane_auto_bases();
+    R.lane_auto = !R.own_slab && !rtk_knob_lane_max_gap_set() && auto_bases != 0 && R.b->n_bases >= auto_bases;
+    R.b->rb.lane_max_gap = R.own_slab ? 0u : (R.lane_auto ? 128u : rtk_knob_lane_max_gap());
+}
+
+// the regions of every read (k_enum; once more with bigger lists if there are more than expected), then their dequeue order: heavy regions first
+static void region_enumerate(RegionRun& R) {
+    rtk_batch* b = R.b; RegionBatch& rb = b->rb; const rtk_stream_t sm = R.sm;
+    const int eg = std::min<int>(R.grid, static_cast<int>(b->n) > 0 ? static_cast<int>(b->n) : 1);
+    for (int tries = 0; tries < 2; ++tries) {
+        rtk_dzero_s(rb.n_regions, 8, sm);
+        R.set_ctx();
+        R.t_enum.start(sm);
+        rtk_launch(k_enum, eg, sm, R.ctx(), b->bv, eg);
+        R.t_enum.stop(sm);
+        rtk_ssync(sm);
+        rtk_d2h_s(&R.n_regions, rb.n_regions, 8, sm);
+        if (R.n_regions <= rb.regions_cap) break;
+        region_alloc_lists(b, R.n_regions + 1024);
+    }
+    if (R.n_regions) {
+        rtk_dzero_s(rb.n_heavy, 128, sm);
+        R.set_ctx();
+        const unsigned long long per_wave = RTK_OQ * RTK_WAVE;
+        const int og = static_cast<int>(std::min<unsigned long long>(static_cast<unsigned long long>(R.grid), (R.n_regions + per_wave - 1ull) / per_wave));
+        rtk_launch(k_region_order, og, sm, R.ctx(), static_cast<uint64_t>(R.n_regions), og);
+    }
+}
+
+// the regions without a graph walk (first pass): written by a light kernel of their own, 8 waves per SIMD
+static void region_easy(RegionRun& R) {
+    rtk_dzero_s(R.b->rb.seg_top, 8, R.sm); rtk_dzero_s(R.b->rb.out_top, 8, R.sm);
+    if (!R.n_regions) return;
+    const int eg = static_cast<int>(std::min<unsigned long long>(static_cast<unsigned long long>(2 * R.grid), R.n_regions));
+    R.t_easy.start(R.sm);
+    rtk_launch(k_regions_easy, eg, R.sm, R.ctx(), eg);
+    R.t_easy.stop(R.sm);
+}
+
+// The light class, one region per lane (rtk_region_lane.h), on the batch's second stream BESIDE the wave kernel: its waves are few (64 regions each) and
+// bound by the latency of one lane's program, the wave kernel's persistent waves fill the rest of the machine. What it hands on is taken by a second
+// launch of the wave kernel when both are through. RTK_LANE_SERIAL=1: one after the other on the batch's stream (A/B).
+static void region_lanes(RegionRun& R) {
+    rtk_batch* b = R.b; RegionBatch& rb = b->rb; const rtk_stream_t sm = R.sm;
+    R.lane_waves_used = 0;
+    R.lanes_on = R.n_regions && rb.lane_max_gap;
+    R.lanes_beside = R.lanes_on && !R.lane_auto && !rtk_knob_lane_serial();
+    if (!R.lanes_on) return;
+    R.hold.take(false); // (the lane kernel's areas, slot 2, belong to whoever holds both halves of slot 1)
+#ifdef RTK_SIM
+    const int lgrid = 16;
+#else
+    const int lgrid = R.lane_auto ? 4096 : rtk_knob_lane_waves();
+#endif
+    R.lane_waves_used = lgrid;
+    const uint64_t a_bytes = rl_area_bytes(), t_bytes = rl_table_bytes();
+    char* ls = graph_scratch(R.g, 2, (a_bytes + t_bytes) * static_cast<uint64_t>(lgrid));
+    RlLimits lim;
+    lim.str = RL_STR_BYTES; lim.um = RL_UM_CAP; lim.list = RL_LIST_CAP; lim.arena0 = RL_A0_W; lim.arena1 = RL_A1_W; lim.arena2 = RL_A2_W; lim.tb = RL_TB_WORDCOLS;
+    if (rtk_knob_test_tiny_scratch()) { lim.str = 200; lim.um = 6; lim.list = 3; lim.arena0 = 160; lim.arena1 = 400; lim.arena2 = 400; lim.tb = 400; } // (most are handed on)
+    rtk_dzero_s(rb.next_lane, 32, sm);
+    rtk_stream_t sl = sm;
+    if (R.lanes_beside) { sl = b->lane_stream(); rtk_event_record(b->ev[0], sm); rtk_stream_wait(sl, b->ev[0]); }
+    R.t_lanes.start(sl);
+    rtk_launch(k_regions_lanes, lgrid, sl, R.ctx(), reinterpret_cast<uint32_t*>(ls), reinterpret_cast<uint64_t*>(ls + a_bytes * static_cast<uint64_t>(lgrid)),
+               static_cast<uint64_t>(R.n_regions), lim, lgrid, rtk_knob_lane_round());
+    R.t_lanes.stop(sl);
+    if (R.lanes_beside) rtk_event_record(b->ev[1], sl);
+}
+
+// The graph-wide work areas are taken here, not at the top: enumeration, ordering and the regions without a walk of one ticket run beside the region
+// kernel of another. Tickets up to RTK_HALF_SLAB_BASES share them two at a time: above ~8 Mi a launch fills the 4 096 wave slots by itself (at 24 Mi a
+// 16.8 Mb group took 18.9 ms on its half against 10-11 ms on both, profiles/r06_coalesce_trace.txt).
+static void region_take_areas(RegionRun& R) {
+    rtk_batch* b = R.b; rtk_graph* g = R.g;
+    if (!R.own_slab && R.hold.what < 0) {
+        const uint64_t half_max_bases = rtk_knob_half_slab_bases();
+        R.hold.take(half_max_bases != 0 && b->n_bases <= half_max_bases && !region_compact());
+        if (R.hold.what != 2) { // a half: only if the areas exist and half of them holds a useful number of waves of this ticket's size class; otherwise both after all
+            const uint64_t st0 = region_scratch_bytes(region_cfg(R.max_len, 0)), half_bytes = (g->scratch_bytes_[1] / 2) & ~255ull;
+            if (!g->scratch[1] || half_bytes / st0 < 512) { R.hold.release(); R.hold.take(false); }
+        }
+    }
+    if (b->on_region_slab) { b->on_region_slab(b->on_region_slab_arg); b->on_region_slab = nullptr; }
+}
+
+// Waves of one launch of k_regions, from plain values. 128 VGPRs -> 4 waves/SIMD -> 16 single-wave workgroups per CU.
+struct RegionGridIn {
+    int attempt; bool compact;          // attempt 0 or a redo launch (compact: attempt 0 ran on compact areas, the full-size ones start at attempt 1)
+    int waves_that_fit;                 // attempt 0: region_waves_that_fit
+    bool own_slab; int p2_cap;          // second pass: RTK_P2_RGRID
+    bool lanes_beside; int lane_waves;  // the lane kernel runs beside attempt 0 on that many waves
+    bool on_half; int half_waves; uint64_t half_fit; // one half of the work areas: RTK_HALF_WAVES, and the waves whose areas fit into it
+    unsigned long long n_regions;
+};
+static int region_grid(const RegionGridIn& in) {
+#ifdef RTK_SIM
+    int rgrid = 16;
+#else
+    const int big = in.attempt - (in.compact ? 1 : 0); // < 0: compact areas; 0, 1, 2: full-size areas x1, x8, x64
+    int rgrid = in.attempt == 0 ? in.waves_that_fit : (big == 0 ? 1024 : (big == 1 ? 256 : 8));
+#endif
+    if (in.own_slab && in.attempt == 0)
+        rgrid = static_cast<int>(std::min<unsigned long long>(static_cast<unsigned long long>(in.p2_cap), std::max<unsigned long long>(128ull, in.n_regions / 4ull)));
+    // the lane kernel's waves need their slots from the start: the persistent waves of this kernel only leave at the end
+    if (in.attempt == 0 && in.lanes_beside) rgrid = std::max(1024, rgrid - in.lane_waves);
+    rgrid = static_cast<int>(std::min<unsigned long long>(static_cast<unsigned long long>(rgrid), in.n_regions ? in.n_regions : 1ull));
+    // (measured: 1 536 / 1 024 waves per half, to leave the seed kernels of the ticket behind them wave slots, lose 4-20 %: profiles/r06_half_waves.txt)
+    if (in.on_half) rgrid = static_cast<int>(std::min<uint64_t>(static_cast<uint64_t>(std::min(rgrid, in.half_waves)), in.half_fit));
+    return rgrid;
+}
+
+// which capacity the flagged regions ran out of (status codes of rtk_fail_ovf), and the wave figures of a traced launch
+static void region_attempt_trace(RegionRun& R, int attempt, int rgrid, uint64_t stride) {
+    const BatchView& bv = R.b->bv; const rtk_stream_t sm = R.sm;
+    std::vector<RegionDesc> rds(R.n_regions); rtk_d2h_s(rds.data(), R.b->rb.regions, sizeof(RegionDesc) * R.n_regions, sm);
+    unsigned long long hist[16] = {0}; for (size_t i = 0; i < rds.size(); ++i) hist[rds[i].status & 15u]++;
+    fprintf(stderr, "[rtk trace] k_regions attempt %d: %.2f ms, %d waves, stride %.2f MB; status codes:", attempt, R.t_reg.elapsed(), rgrid, stride / 1048576.0);
+    for (int i = 1; i < 16; ++i) if (hist[i]) fprintf(stderr, " %d:%llu", i, hist[i]);
+    fprintf(stderr, "\n");
+    unsigned long long tc[RTK_CNT_WAVE_TRACE_END - RTK_CNT_WAVE_TRACE] = {0}; rtk_d2h_s(tc, bv.counters + RTK_CNT_WAVE_TRACE, sizeof(tc), sm);
+    const double span = static_cast<double>(tc[2] - ~tc[1]) / 100e6 * 1e3, avg_life = tc[4] ? static_cast<double>(tc[3]) / static_cast<double>(tc[4]) / 100e6 * 1e3 : 0.0;
+    fprintf(stderr, "[rtk trace] k_regions waves: first start to last end %.2f ms, average lifetime of a wave %.2f ms (%.0f %% of it), longest single region %.3g cycles "
+                    "(taken off the queue at place %llu of %llu), most regions on one wave %llu\n",
+            span, avg_life, span > 0 ? 100.0 * avg_life / span : 0.0, static_cast<double>(tc[0]), tc[6], static_cast<unsigned long long>(R.n_regions), tc[7]);
+}
+
+// k_regions until no region reports an overflow: any region that ran out of scratch is redone with a bigger arena (still on the device)
+static int region_attempts(RegionRun& R) {
+    rtk_batch* b = R.b; rtk_graph* g = R.g; RegionBatch& rb = b->rb; const rtk_stream_t sm = R.sm;
+    const int n_attempts = region_compact() ? 4 : 3;
+    R.ms_reg = 0; R.n_ovf_total = 0;
+    for (int attempt = 0; attempt < n_attempts; ++attempt) {
+        if (attempt != 0 && !R.own_slab && R.hold.what != 2) { R.hold.release(); R.hold.take(false); } // the redo launches may grow the areas: both halves
+        const RegionScratchCfg cfg = region_cfg(R.max_len, attempt);
+        const uint64_t stride = region_scratch_bytes(cfg);
+        if (R.trace) fprintf(stderr, "[rtk trace] region work area: %llu bytes per wave\n", static_cast<unsigned long long>(stride));
+        const bool on_half = !R.own_slab && R.hold.what != 2;
+        const uint64_t half_bytes = (g->scratch_bytes_[1] / 2) & ~255ull;
+        RegionGridIn gi;
+        gi.attempt = attempt; gi.compact = region_compact(); gi.n_regions = R.n_regions;
+#ifdef RTK_SIM
+        gi.waves_that_fit = 0;
+#else
+        gi.waves_that_fit = attempt == 0 ? region_waves_that_fit(stride, R.own_slab ? 0 : g->scratch_bytes_[1], R.trace) : 0;
+#endif
+        gi.own_slab = R.own_slab; gi.p2_cap = rtk_knob_p2_rgrid();
+        gi.lanes_beside = R.lanes_beside; gi.lane_waves = R.lane_waves_used;
+        gi.on_half = on_half; gi.half_waves = on_half ? rtk_knob_half_waves() : 0; gi.half_fit = on_half ? half_bytes / stride : 0;
+        const int rgrid = region_grid(gi);
+        char* scratch;
+        if (R.own_slab) scratch = R.slab.at_least(stride * rgrid);
+        else if (!on_half) scratch = graph_scratch(g, 1, stride * rgrid);
+        else scratch = static_cast<char*>(g->scratch[1]) + static_cast<uint64_t>(R.hold.what) * half_bytes;
+        rtk_dzero_s(rb.next_region, 8, sm); rtk_dzero_s(rb.n_overflow, 8, sm);
+        if (attempt != 0) R.set_ctx(); // (attempt 0: the views are in place since the order kernel, and the lane kernel may be reading them)
+        const int tcls = rtk_knob_trace_class(R.trace ? -2 : -1);
+        R.t_reg.start(sm);
+        rtk_launch(k_regions, rgrid, sm, R.ctx(), g->dview, R.ov, b->bv, rb, scratch, stride, cfg, static_cast<uint64_t>(R.n_regions), attempt == 0 ? 0 : 1, tcls,
+                   attempt == 0 ? (R.lanes_beside ? 5 : 1) : 3);
+        if (attempt == 0 && R.lanes_on) { // the regions the lane kernel handed on
+            if (R.lanes_beside) rtk_stream_wait(sm, b->ev[1]);
+            rtk_dzero_s(rb.next_region, 8, sm);
+            rtk_launch(k_regions, std::min(rgrid, 1024), sm, R.ctx(), g->dview, R.ov, b->bv, rb, scratch, stride, cfg, static_cast<uint64_t>(R.n_regions), 0, tcls, 2);
+        }
+        R.t_reg.stop(sm);
+        rtk_ssync(sm);
+        R.ms_reg += R.t_reg.elapsed();
+        if (R.trace) region_attempt_trace(R, attempt, rgrid, stride);
+        unsigned long long n_ovf = 0; rtk_d2h_s(&n_ovf, rb.n_overflow, 8, sm);
+        if (attempt == 0) R.n_ovf_total = n_ovf;
+        // the kernels that reserve pool space past the end skip their copies and raise nothing else (k_regions_easy, k_regions_lanes): looked at after EVERY attempt
+        unsigned long long seg_top = 0; rtk_d2h_s(&seg_top, rb.seg_top, 8, sm);
+        if (seg_top > rb.seg_cap) return rtk_fail(RTK_ERR_DEVICE, "region stage: segment pool exhausted");
+        if (n_ovf == 0) return RTK_OK;
+    }
+    return rtk_fail(RTK_ERR_DEVICE, "region stage: scratch capacity exceeded after " + std::to_string(n_attempts) + " attempts");
+}
+
+// the corrected reads put together from their regions' segments; ends the stage's clock
+static int region_stitch(RegionRun& R) {
+    rtk_batch* b = R.b; const rtk_stream_t sm = R.sm;
+    R.t_st.start(sm);
+    const int sg = std::min<int>(R.grid, static_cast<int>(b->n) > 0 ? static_cast<int>(b->n) : 1);
+    rtk_launch(k_stitch, sg, sm, R.ctx(), b->bv, sg);
+    if (R.n_regions) {
+        const int cg = static_cast<int>(std::min<unsigned long long>(static_cast<unsigned long long>(2 * R.grid), (R.n_regions + RTK_WAVE - 1ull) / RTK_WAVE));
+        rtk_launch(k_stitch_copy, cg, sm, R.ctx(), static_cast<uint64_t>(R.n_regions), cg);
+    }
+    R.t_st.stop(sm);
+    b->t_all.stop(sm);
+    rtk_ssync(sm);
+    R.out_top = 0; rtk_d2h_s(&R.out_top, b->rb.out_top, 8, sm);
+    if (R.out_top > b->rb.out_cap) return rtk_fail(RTK_ERR_DEVICE, "stitch: output pool exhausted");
+    return RTK_OK;
+}
+
+// everything that only RTK_TRACE prints at the end of the stage, from the copied counter block
+static void region_trace_report(const unsigned long long* cnt) {
+    const double total = double(cnt[RTK_CNT_CYC_TOTAL] ? cnt[RTK_CNT_CYC_TOTAL] : 1);
+    auto share = [&](int slot) { return double(cnt[slot]) / total; };
+#ifdef RTK_PROF
+    {
+        static const char* const pn[RTK_CNT_PROF_END - RTK_CNT_PROF] = {
+            "driver: dispatch + anchors", "driver: same-unitig shortcut", "region: prologue", "region: side lists", "region: chooseColors",
+            "semiweak: glue", "paths: prologue", "explore: prefix", "dfs: pop + adj", "dfs: nkm + colour_ok", "dfs T: load/extend",
+            "dfs T: to_string", "dfs T: NW sweep", "dfs T: commit", "dfs NT: load/extend", "dfs NT: commit/rest", "dfs post: nt scoring",
+            "dfs post: load + to_string", "dfs post: path qual", "dfs post: commit", "paths: after explore", "paths: final select",
+            "semiweak: merge", "region: restart/select", "region: assemble", "region: fixAmbiguity", "region: corrected? + trim",
+            "driver: between fw/bw", "consensus: rc + card", "consensus: fw NW path", "consensus: bw path / checks", "consensus: merge",
+            "consensus: final", "driver: emit prep", "dequeue", "emit", 0, 0, 0, 0, "probe: 4 dependent cold loads", "probe: 4 dependent warm loads",
+            "probe: slab store + load", 0};
+        const unsigned long long* pr = cnt + RTK_CNT_PROF; const int n = RTK_CNT_PROF_END - RTK_CNT_PROF;
+        if (pr[43]) fprintf(stderr, "[rtk trace] in-situ probes: cold load %.0f cycles, warm load %.0f cycles, slab store + load %.0f cycles "
+                                    "(per round trip, %llu samples)\n",
+                            double(pr[40]) / 4.0 / double(pr[43]), double(pr[41]) / 4.0 / double(pr[43]), double(pr[42]) / double(pr[43]), pr[43]);
+        unsigned long long tot = 0; for (int i = 0; i < n; ++i) tot += pr[i];
+        fprintf(stderr, "[rtk trace] k_regions lap profile (%.3g cycles):", double(tot));
+        for (int i = 0; i < n; ++i) if (pr[i] && pn[i]) fprintf(stderr, " [%d %s %.4f]", i, pn[i], double(pr[i]) / double(tot ? tot : 1));
+        fprintf(stderr, "\n");
+    }
+#endif
+    {
+        static const char* const hn[8] = {"gap<40", "gap<64", "gap<128", "gap<256", "gap<512", "gap<1024", "gap>=1024", "head/tail"};
+        const unsigned long long* h = cnt + RTK_CNT_HIST; // RegionScratch::hist: [b] cycles, [8 + b] regions, [16 + b] second strand too, [24 + b] DFS calls
+        fprintf(stderr, "[rtk trace] k_regions by size class (share of region time, regions, avg kcycles, second-strand share, DFS calls per region):");
+        for (int i = 0; i < 8; ++i) {
+            const unsigned long long cyc = h[i], n = h[8 + i];
+            if (n) fprintf(stderr, " [%s %.3f n=%llu %.0fk bw=%.2f dfs=%.1f]", hn[i], double(cyc) / total, n, 1e-3 * double(cyc) / double(n), double(h[16 + i]) / double(n),
+                           double(h[24 + i]) / double(n));
+        }
+        fprintf(stderr, "\n");
+    }
+    {
+        static const char* const fine_names[RTK_FINE_N] = {
+            "colour: class unions", "fixAmbiguity: path alignment", "fixAmbiguity: walk of the moves",
+            "fixAmbiguity: linked alleles (k-mer lookups)", "fixAmbiguity: apply", "colour small: bit vectors (or array: shared_with(all))",
+            "colour small: classes + selection (or array: set ops)", "region: side lists", "region: trim alignment", "region: fixAmbiguity",
+            "consensus: merge logic", "paths: explore_paths outside DFS", "colour: small path (cycles)", "colour: 4096-bit path (cycles)",
+            "colour: small path calls / total cycles", "colour: 4096-bit path calls / total cycles"};
+        const unsigned long long* f = cnt + RTK_CNT_FINE;
+        fprintf(stderr, "[rtk trace] chooseColors calls: small path %llu, 4096-bit path %llu; fixAmbiguity calls %llu, of which left by the all-confident way out %llu\n",
+                f[RTK_FINE_COL_S_CALLS], f[RTK_FINE_COL_B_CALLS], f[RTK_FINE_FA_CALLS], f[RTK_FINE_FA_ALL_CONFIDENT]);
+        fprintf(stderr, "[rtk trace] k_regions fine shares:");
+        for (int i = 0; i < RTK_FINE_N; ++i) if (f[i]) fprintf(stderr, " [%s %.3f]", fine_names[i], double(f[i]) / total);
+        fprintf(stderr, "\n");
+    }
+#ifdef RTK_LANE_PROF
+    {
+        static const char* const ln[RL_NPROF] = {
+            "driver", "side lists", "chooseColors", "search glue", "dfs walk", "colour_ok", "to_string", "peq build", "sweep", "walk",
+            "path records", "path qual", "select", "amb collect", "fixAmbiguity", "assemble", "trim", "revcomp", "consensus", "emit",
+            "idle at round end", "colours: universe", "colours: rows", 0};
+        static_assert(RL_NPROF == RTK_CNT_LANE_PROF2 - RTK_CNT_LANE_PROF, "counter map: the lane profile has RL_NPROF slots");
+        const unsigned long long* p1 = cnt + RTK_CNT_LANE_PROF; const unsigned long long* p2 = cnt + RTK_CNT_LANE_PROF2;
+        unsigned long long tot = 0; for (int i = 0; i < RL_NPROF; ++i) tot += p1[i];
+        fprintf(stderr, "[rtk trace] k_regions_lanes lap profile (%.3g lane cycles):", double(tot));
+        for (int i = 0; i < RL_NPROF; ++i) if (p1[i] && ln[i]) fprintf(stderr, " [%s %.4f]", ln[i], double(p1[i]) / double(tot ? tot : 1));
+        fprintf(stderr, "\n");
+        unsigned long long tw = 0; for (int i = 0; i < RL_NPROF; ++i) tw += p2[i];
+        fprintf(stderr, "[rtk trace] k_regions_lanes wave-time estimate by slot (share of %.3g, lanes together):", double(tw) / 64.0);
+        for (int i = 0; i < RL_NPROF; ++i)
+            if (p2[i] && ln[i]) fprintf(stderr, " [%s %.4f x%.1f]", ln[i], double(p2[i]) / double(tw ? tw : 1), 64.0 * double(p1[i]) / double(p2[i]));
+        fprintf(stderr, "\n");
+    }
+#endif
+    fprintf(stderr, "[rtk trace] k_regions shares of %.3g wave cycles: colour %.3f paths %.3f consensus %.3f myers %.3f sets %.3f tostring %.3f pathqual %.3f "
+                    "walk %.3f\n",
+            double(cnt[RTK_CNT_CYC_TOTAL]), share(RTK_CNT_CYC_COLOUR), share(RTK_CNT_CYC_PATHS), share(RTK_CNT_CYC_CONSENSUS), share(RTK_CNT_CYC_MYERS),
+            share(RTK_CNT_CYC_SETS),
+            share(RTK_CNT_CYC_TOSTRING), share(RTK_CNT_CYC_PATHQUAL), share(RTK_CNT_WALK_CYCLES));
+    fprintf(stderr, "[rtk trace] k_regions cycle shares: DFS bookkeeping %.3f (of which colour checks %.3f)\n", share(RTK_CNT_CYC_DFS), share(RTK_CNT_CYC_COLOUR_OK));
+    fprintf(stderr, "[rtk trace] walks %llu moves %llu reloads %llu scalar steps %llu cycles %.3g tail cycles %.3g\n", cnt[RTK_CNT_WALK_CALLS], cnt[RTK_CNT_WALK_MOVES],
+            cnt[RTK_CNT_WALK_RELOADS], cnt[RTK_CNT_WALK_SCALAR], double(cnt[RTK_CNT_WALK_CYCLES]), double(cnt[RTK_CNT_WALK_TAIL]));
+}
+
+// the stage's part of rtk_stats, from the timers and the copied counter block
+static void region_stats(RegionRun& R, const unsigned long long* cnt) {
+    rtk_batch* b = R.b; rtk_stats& st = b->stats;
+    st.cyc_colour = cnt[RTK_CNT_CYC_COLOUR]; st.cyc_paths = cnt[RTK_CNT_CYC_PATHS]; st.cyc_consensus = cnt[RTK_CNT_CYC_CONSENSUS]; st.cyc_total = cnt[RTK_CNT_CYC_TOTAL];
+    st.cyc_myers = cnt[RTK_CNT_CYC_MYERS]; st.cyc_sets = cnt[RTK_CNT_CYC_SETS]; st.cyc_tostring = cnt[RTK_CNT_CYC_TOSTRING]; st.cyc_pathqual = cnt[RTK_CNT_CYC_PATHQUAL];
+    st.cyc_walk = cnt[RTK_CNT_WALK_CYCLES]; st.n_moves = cnt[RTK_CNT_WALK_MOVES];
+    st.n_slots_exact = cnt[RTK_CNT_SLOTS_EXACT]; st.n_slots_inexact = cnt[RTK_CNT_SLOTS_INEXACT];
+    st.ms_regions = R.t_enum.elapsed() + (R.n_regions ? R.t_easy.elapsed() : 0.0); // (enumeration + the regions without a graph walk)
+    st.ms_lanes = R.lanes_on ? R.t_lanes.elapsed() : 0.0;
+    st.ms_correct = R.ms_reg + ((R.lanes_on && !R.lanes_beside) ? st.ms_lanes : 0.0); // (beside: the span of the wave kernel's two launches contains the lane kernel)
+    st.n_lane_handed = cnt[RTK_CNT_LANE_HANDED]; st.n_lane_regions = cnt[RTK_CNT_LANE_HANDED] + cnt[RTK_CNT_LANE_DONE];
+    st.ms_stitch = R.t_st.elapsed(); st.ms_total = b->t_all.elapsed();
+    st.n_windows = b->n_bases;
+    st.n_probes_exact = cnt[RTK_CNT_PROBES_EXACT]; st.n_probes_inexact = cnt[RTK_CNT_PROBES_INEXACT]; st.n_hits_inexact = cnt[RTK_CNT_HITS_INEXACT];
+    st.n_regions = R.n_regions; st.n_region_items = R.n_regions; st.n_arena_overflow = R.n_ovf_total;
+    st.n_expand = cnt[RTK_CNT_EXPAND]; st.n_colour_elem = cnt[RTK_CNT_COLOUR]; st.n_path_base = cnt[RTK_CNT_PATHBASE];
+    st.n_align = cnt[RTK_CNT_ALIGN]; st.n_align_cells = cnt[RTK_CNT_CELLS];
+    st.in_bases = b->n_bases; st.out_bases = R.out_top / 2;
+}
+
 // stage B: regions of every read (enumerate, correct, stitch) on the batch's stream; needs stage A of the same batch
 extern "C" int rtk_batch_run_regions(rtk_batch* b, const rtk_opts* opts) {
     int rc = batch_precheck(b, opts, "rtk_batch_run_regions");
     if (rc) return rc;
     if (!b->seeded) return rtk_fail(RTK_ERR_ARG, "rtk_batch_run_regions: rtk_batch_run_seeds has not completed for this batch");
-    if (opts->long_read_correct && !b->bv.qual.get()) return rtk_fail(RTK_ERR_ARG, "rtk_batch_run_regions: the second pass (long_read_correct) needs a batch created with quality strings");
+    if (opts->long_read_correct && !b->bv.qual.get())
+        return rtk_fail(RTK_ERR_ARG, "rtk_batch_run_regions: the second pass (long_read_correct) needs a batch created with quality strings");
     rtk_graph* g = b->g;
     try {
         rtk_set_device(g->device);
-        const OptsView ov = opts_view(opts);
-        const rtk_stream_t sm = b->stream;
-        RtkTimer& t_all = b->t_all;
-        // Second pass: a ticket has few, big regions (one per 3 kb of read, up to -W 5000 characters) and its launch lasts as long as its
-        // biggest one with most wave slots idle: it gets a work area of its own (no graph-wide lock) so that the tickets in flight overlap.
-        const bool own_slab = opts->long_read_correct != 0;
-        struct SlabHold { rtk_graph* g; int what; void take(bool half_ok) { what = g->region_slab_take(half_ok); } void release() { if (what >= 0) { g->region_slab_give(what); what = -1; } } ~SlabHold() { release(); } } hold = {g, -1};
-        static const uint64_t half_max_bases = [] { const char* e = getenv("RTK_HALF_SLAB_BASES"); return e ? strtoull(e, nullptr, 10) : (8ull << 20); }(); // tickets up to this size share the region stage's work areas two at a time (0: never). Above ~8 Mi a launch fills the 4 096 wave slots by itself: at 24 Mi a 16.8 Mb group took 18.9 ms on its half against 10-11 ms on both (profiles/r06_coalesce_trace.txt)
-        struct Slab { rtk_graph* g; void* p; uint64_t n; ~Slab() { if (p) g->phase_give(p, n); } } slab = {g, nullptr, 0};
-        const bool trace = getenv("RTK_TRACE") != nullptr;
-        const auto w0 = std::chrono::steady_clock::now();
-        auto lap = [&](const char* what) { if (trace) fprintf(stderr, "[rtk trace] regions %-10s +%.2f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count()); };
-        BatchView& bv = b->bv; RegionBatch& rb = b->rb;
-        uint32_t max_len = 0; for (uint32_t i = 0; i < b->n; ++i) max_len = std::max<uint32_t>(max_len, static_cast<uint32_t>(b->roff[i + 1] - b->roff[i]));
-        if (!rb.seq_rc) {
-            rb.seq_rc = b->alloc<char>(b->n_bases + 64);
-            rb.qual_rev = b->bv.qual.get() ? b->alloc<char>(b->n_bases + 64) : nullptr;
-            rb.r_first = b->alloc<uint64_t>(b->n); rb.r_count = b->alloc<uint32_t>(b->n);
-            rb.n_regions = b->alloc<unsigned long long>(1); rb.n_heavy = b->alloc<unsigned long long>(16); rb.seg_top = b->alloc<unsigned long long>(1); rb.next_region = b->alloc<unsigned long long>(1); rb.n_overflow = b->alloc<unsigned long long>(1); rb.out_top = b->alloc<unsigned long long>(1);
-            rb.out_off = b->alloc<uint64_t>(b->n); rb.out_seq_len = b->alloc<uint32_t>(b->n); rb.out_qual_len = b->alloc<uint32_t>(b->n);
-            rb.regions_cap = std::max<uint64_t>(1024, b->n_bases / 8 + 4ull * b->n); rb.regions = b->alloc<RegionDesc>(rb.regions_cap); rb.rorder = b->alloc<uint32_t>(rb.regions_cap); rb.eorder = b->alloc<uint32_t>(rb.regions_cap); rb.lorder = b->alloc<uint32_t>(4 * rb.regions_cap); rb.horder = b->alloc<uint32_t>(rb.regions_cap); rb.next_lane = b->alloc<unsigned long long>(4); rb.st_off = b->alloc<uint64_t>(rb.regions_cap);
-            rb.seg_cap = 6 * b->n_bases + (1ull << 20); rb.seg_pool = b->alloc<char>(rb.seg_cap);
-            rb.out_cap = 6 * b->n_bases + (1ull << 20); rb.out_pool = b->alloc<char>(rb.out_cap);
-        }
-        const bool lane_auto = !own_slab && !getenv("RTK_LANE_MAX_GAP") && lane_auto_bases() != 0 && b->n_bases >= lane_auto_bases();
-        rb.lane_max_gap = own_slab ? 0u : (lane_auto ? 128u : lane_max_gap()); // (second pass: the wave kernel alone)
-        lap("alloc");
-        const int grid = default_grid();
-        RtkTimer t_enum, t_reg, t_st, t_easy;
-        unsigned long long n_regions = 0;
-        for (int tries = 0; tries < 2; ++tries) {
-            rtk_dzero_s(rb.n_regions, 8, sm);
-            rtk_launch(k_set_ctx, 1, sm, b->ctx(), g->dview, ov, bv, rb);
-            t_enum.start(sm);
-            rtk_launch(k_enum, std::min<int>(grid, static_cast<int>(b->n) > 0 ? static_cast<int>(b->n) : 1), sm, static_cast<const LaunchCtx*>(b->ctx()), bv, std::min<int>(grid, static_cast<int>(b->n) > 0 ? static_cast<int>(b->n) : 1));
-            t_enum.stop(sm);
-            rtk_ssync(sm);
-            rtk_d2h_s(&n_regions, rb.n_regions, 8, sm);
-            if (n_regions <= rb.regions_cap) break;
-            rb.regions_cap = n_regions + 1024; rb.regions = b->alloc<RegionDesc>(rb.regions_cap); rb.rorder = b->alloc<uint32_t>(rb.regions_cap); rb.eorder = b->alloc<uint32_t>(rb.regions_cap); rb.lorder = b->alloc<uint32_t>(4 * rb.regions_cap); rb.horder = b->alloc<uint32_t>(rb.regions_cap); rb.st_off = b->alloc<uint64_t>(rb.regions_cap);
-        }
-        if (n_regions) { // dequeue order: heavy regions first
-            rtk_dzero_s(rb.n_heavy, 128, sm);
-            rtk_launch(k_set_ctx, 1, sm, b->ctx(), g->dview, ov, bv, rb);
-            const int og = static_cast<int>(std::min<unsigned long long>(static_cast<unsigned long long>(grid), (n_regions + RTK_OQ * RTK_WAVE - 1ull) / (RTK_OQ * RTK_WAVE)));
-            rtk_launch(k_region_order, og, sm, static_cast<const LaunchCtx*>(b->ctx()), static_cast<uint64_t>(n_regions), og);
-        }
-        lap("enum");
-        rtk_dzero_s(rb.seg_top, 8, sm); rtk_dzero_s(rb.out_top, 8, sm);
-        if (n_regions) { // the regions without a graph walk (first pass): written by a light kernel of their own, 8 waves per SIMD
-            const int eg = static_cast<int>(std::min<unsigned long long>(static_cast<unsigned long long>(2 * grid), n_regions));
-            t_easy.start(sm);
-            rtk_launch(k_regions_easy, eg, sm, static_cast<const LaunchCtx*>(b->ctx()), eg);
-            t_easy.stop(sm);
-        }
-        // The light class, one region per lane (rtk_region_lane.h), on the batch's second stream BESIDE the wave kernel: its waves are few (64 regions each) and
-        // bound by the latency of one lane's program, the wave kernel's persistent waves fill the rest of the machine. What it hands on is taken by a second
-        // launch of the wave kernel when both are through. RTK_LANE_SERIAL=1: one after the other on the batch's stream (A/B).
-        RtkTimer t_lanes; int lane_waves_used = 0;
-        const bool lanes_on = n_regions && rb.lane_max_gap;
-        const bool lanes_beside = lanes_on && !lane_auto && !(getenv("RTK_LANE_SERIAL") && getenv("RTK_LANE_SERIAL")[0] == '1');
-        if (lanes_on) {
-            hold.take(false); // (the lane kernel's areas, slot 2, belong to whoever holds both halves of slot 1)
-#ifdef RTK_SIM
-            const int lgrid = 16;
-#else
-            const int lgrid = lane_auto ? 4096 : lane_waves();
-#endif
-            lane_waves_used = lgrid;
-            const uint64_t a_bytes = rl_area_bytes(), t_bytes = rl_table_bytes();
-            char* ls = graph_scratch(g, 2, (a_bytes + t_bytes) * static_cast<uint64_t>(lgrid));
-            RlLimits lim; lim.str = RL_STR_BYTES; lim.um = RL_UM_CAP; lim.list = RL_LIST_CAP; lim.arena0 = RL_A0_W; lim.arena1 = RL_A1_W; lim.arena2 = RL_A2_W; lim.tb = RL_TB_WORDCOLS;
-            if (getenv("RTK_TEST_TINY_SCRATCH")) { lim.str = 200; lim.um = 6; lim.list = 3; lim.arena0 = 160; lim.arena1 = 400; lim.arena2 = 400; lim.tb = 400; } // test hook: most regions are handed on
-            rtk_dzero_s(rb.next_lane, 32, sm);
-            rtk_stream_t sl = sm;
-            if (lanes_beside) { sl = b->lane_stream(); rtk_event_record(b->ev[0], sm); rtk_stream_wait(sl, b->ev[0]); }
-            t_lanes.start(sl);
-            rtk_launch(k_regions_lanes, lgrid, sl, static_cast<const LaunchCtx*>(b->ctx()), reinterpret_cast<uint32_t*>(ls), reinterpret_cast<uint64_t*>(ls + a_bytes * static_cast<uint64_t>(lgrid)), static_cast<uint64_t>(n_regions), lim, lgrid, getenv("RTK_LANE_ROUND") ? atoi(getenv("RTK_LANE_ROUND")) : 64);
-            t_lanes.stop(sl);
-            if (lanes_beside) rtk_event_record(b->ev[1], sl);
-        }
-        double ms_reg = 0; unsigned long long n_ovf_total = 0;
-        const int n_attempts = region_compact() ? 4 : 3;
-        // the work areas are taken here, not at the top: enumeration, ordering and the regions without a walk of one ticket run beside the region kernel of another
-        if (!own_slab && hold.what < 0) {
-            hold.take(half_max_bases != 0 && b->n_bases <= half_max_bases && !region_compact());
-            if (hold.what != 2) { // a half: only if the areas exist and half of them holds a useful number of waves of this ticket's size class; otherwise both after all
-                const uint64_t st0 = region_scratch_bytes(region_cfg(max_len, 0)), half_bytes = (g->scratch_bytes_[1] / 2) & ~255ull;
-                if (!g->scratch[1] || half_bytes / st0 < 512) { hold.release(); hold.take(false); }
-            }
-        }
-        if (b->on_region_slab) { b->on_region_slab(b->on_region_slab_arg); b->on_region_slab = nullptr; }
-        for (int attempt = 0; attempt < n_attempts; ++attempt) {
-            if (attempt != 0 && !own_slab && hold.what != 2) { hold.release(); hold.take(false); } // the redo launches may grow the areas: both halves
-            const RegionScratchCfg cfg = region_cfg(max_len, attempt);
-            uint64_t stride = region_scratch_bytes(cfg);
-            { const char* e = getenv("RTK_STRIDE_SKEW"); if (e) stride += static_cast<uint64_t>(atoll(e)) / 256 * 256; } // developer knob: work areas of consecutive waves shifted against each other (memory-channel mapping of the areas' first lines)
-            if (trace) fprintf(stderr, "[rtk trace] region work area: %llu bytes per wave\n", static_cast<unsigned long long>(stride));
-#ifdef RTK_SIM
-            int rgrid = 16;
-#else
-            const int big = attempt - (region_compact() ? 1 : 0); // < 0: compact areas; 0, 1, 2: full-size areas x1, x8, x64
-            int rgrid = attempt == 0 ? region_waves_that_fit(stride, own_slab ? 0 : g->scratch_bytes_[1]) : (big == 0 ? 1024 : (big == 1 ? 256 : 8)); // 128 VGPRs -> 4 waves/SIMD -> 16 single-wave workgroups per CU
-#endif
-            if (own_slab && attempt == 0) rgrid = static_cast<int>(std::min<unsigned long long>(static_cast<unsigned long long>(getenv("RTK_P2_RGRID") ? atoi(getenv("RTK_P2_RGRID")) : 512), std::max<unsigned long long>(128ull, n_regions / 4ull)));
-            if (attempt == 0 && lanes_beside) rgrid = std::max(1024, rgrid - lane_waves_used); // the lane kernel's waves need their slots from the start: the persistent waves of this kernel only leave at the end
-            rgrid = static_cast<int>(std::min<unsigned long long>(static_cast<unsigned long long>(rgrid), n_regions ? n_regions : 1ull));
-            char* scratch;
-            if (own_slab) { if (slab.n < stride * rgrid) { if (slab.p) { g->phase_give(slab.p, slab.n); slab.p = nullptr; slab.n = 0; } slab.p = g->phase_take(stride * rgrid, &slab.n); } scratch = static_cast<char*>(slab.p); }
-            else if (hold.what == 2) scratch = graph_scratch(g, 1, stride * rgrid);
-            else { // one half of the areas, RTK_HALF_WAVES (2 048) persistent waves at most
-                const uint64_t half_bytes = (g->scratch_bytes_[1] / 2) & ~255ull;
-                static const int half_waves = [] { const char* e = getenv("RTK_HALF_WAVES"); const int v = e ? atoi(e) : 0; return v > 0 ? std::min(v, 2048) : 2048; }(); // (measured: 1 536 / 1 024 waves per half, to leave the seed kernels of the ticket behind them wave slots, lose 4-20 %: profiles/r06_half_waves.txt)
-                rgrid = static_cast<int>(std::min<uint64_t>(static_cast<uint64_t>(std::min(rgrid, half_waves)), half_bytes / stride));
-                scratch = static_cast<char*>(g->scratch[1]) + static_cast<uint64_t>(hold.what) * half_bytes;
-            }
-            rtk_dzero_s(rb.next_region, 8, sm); rtk_dzero_s(rb.n_overflow, 8, sm);
-            if (attempt != 0) rtk_launch(k_set_ctx, 1, sm, b->ctx(), g->dview, ov, bv, rb); // (attempt 0: the views are in place since the order kernel, and the lane kernel may be reading them)
-            const int tcls = getenv("RTK_TRACE_CLASS") ? atoi(getenv("RTK_TRACE_CLASS")) : (trace ? -2 : -1);
-            t_reg.start(sm);
-            rtk_launch(k_regions, rgrid, sm, static_cast<const LaunchCtx*>(b->ctx()), g->dview, ov, bv, rb, scratch, stride, cfg, static_cast<uint64_t>(n_regions), attempt == 0 ? 0 : 1, tcls, attempt == 0 ? (lanes_beside ? 5 : 1) : 3);
-            if (attempt == 0 && lanes_on) { // the regions the lane kernel handed on
-                if (lanes_beside) rtk_stream_wait(sm, b->ev[1]);
-                rtk_dzero_s(rb.next_region, 8, sm);
-                rtk_launch(k_regions, std::min(rgrid, 1024), sm, static_cast<const LaunchCtx*>(b->ctx()), g->dview, ov, bv, rb, scratch, stride, cfg, static_cast<uint64_t>(n_regions), 0, tcls, 2);
-            }
-            t_reg.stop(sm);
-            rtk_ssync(sm);
-            ms_reg += t_reg.elapsed();
-            if (trace) { // which capacity the flagged regions ran out of (status codes of rtk_fail_ovf)
-                std::vector<RegionDesc> rds(n_regions); rtk_d2h_s(rds.data(), rb.regions, sizeof(RegionDesc) * n_regions, sm);
-                unsigned long long hist[16] = {0}; for (size_t i = 0; i < rds.size(); ++i) hist[rds[i].status & 15u]++;
-                fprintf(stderr, "[rtk trace] k_regions attempt %d: %.2f ms, %d waves, stride %.2f MB; status codes:", attempt, t_reg.elapsed(), rgrid, stride / 1048576.0);
-                for (int i = 1; i < 16; ++i) if (hist[i]) fprintf(stderr, " %d:%llu", i, hist[i]);
-                fprintf(stderr, "\n");
-                { unsigned long long tc[8] = {0}; rtk_d2h_s(tc, bv.counters + 144, sizeof(tc), sm);
-                  const double span = static_cast<double>(tc[2] - ~tc[1]) / 100e6 * 1e3, avg_life = tc[4] ? static_cast<double>(tc[3]) / static_cast<double>(tc[4]) / 100e6 * 1e3 : 0.0;
-                  fprintf(stderr, "[rtk trace] k_regions waves: first start to last end %.2f ms, average lifetime of a wave %.2f ms (%.0f %% of it), longest single region %.3g cycles (taken off the queue at place %llu of %llu), most regions on one wave %llu\n",
-                          span, avg_life, span > 0 ? 100.0 * avg_life / span : 0.0, static_cast<double>(tc[0]), tc[6], static_cast<unsigned long long>(n_regions), tc[7]); }
-            }
-            // any region that ran out of scratch is redone with a bigger arena (still on the device)
-            unsigned long long n_ovf = 0; rtk_d2h_s(&n_ovf, rb.n_overflow, 8, sm);
-            const uint32_t worst = 0;
-            if (attempt == 0) n_ovf_total = n_ovf;
-            // the kernels that reserve pool space past the end skip their copies and raise nothing else (k_regions_easy, k_regions_lanes): looked at after EVERY attempt
-            unsigned long long seg_top = 0; rtk_d2h_s(&seg_top, rb.seg_top, 8, sm);
-            if (seg_top > rb.seg_cap) return rtk_fail(RTK_ERR_DEVICE, "region stage: segment pool exhausted");
-            if (n_ovf == 0) break;
-            if (attempt == n_attempts - 1) return rtk_fail(RTK_ERR_DEVICE, "region stage: scratch capacity exceeded after 3 attempts (code " + std::to_string(worst) + ")");
-        }
-        hold.release();
-        lap("regions");
-        t_st.start(sm);
-        { const int sg = std::min<int>(grid, static_cast<int>(b->n) > 0 ? static_cast<int>(b->n) : 1); rtk_launch(k_stitch, sg, sm, static_cast<const LaunchCtx*>(b->ctx()), bv, sg); }
-        if (n_regions) { const int cg = static_cast<int>(std::min<unsigned long long>(static_cast<unsigned long long>(2 * grid), (n_regions + RTK_WAVE - 1ull) / RTK_WAVE)); rtk_launch(k_stitch_copy, cg, sm, static_cast<const LaunchCtx*>(b->ctx()), static_cast<uint64_t>(n_regions), cg); }
-        t_st.stop(sm);
-        t_all.stop(sm);
-        rtk_ssync(sm);
-        unsigned long long out_top = 0; rtk_d2h_s(&out_top, rb.out_top, 8, sm);
-        if (out_top > rb.out_cap) return rtk_fail(RTK_ERR_DEVICE, "stitch: output pool exhausted");
-        unsigned long long cnt[224]; rtk_d2h_s(cnt, bv.counters, sizeof(cnt), sm);
-#ifdef RTK_PROF
-        if (getenv("RTK_TRACE")) { static const char* const pn[48] = {"driver: dispatch + anchors", "driver: same-unitig shortcut", "region: prologue", "region: side lists", "region: chooseColors", "semiweak: glue", "paths: prologue", "explore: prefix", "dfs: pop + adj", "dfs: nkm + colour_ok", "dfs T: load/extend", "dfs T: to_string", "dfs T: NW sweep", "dfs T: commit", "dfs NT: load/extend", "dfs NT: commit/rest", "dfs post: nt scoring", "dfs post: load + to_string", "dfs post: path qual", "dfs post: commit", "paths: after explore", "paths: final select", "semiweak: merge", "region: restart/select", "region: assemble", "region: fixAmbiguity", "region: corrected? + trim", "driver: between fw/bw", "consensus: rc + card", "consensus: fw NW path", "consensus: bw path / checks", "consensus: merge", "consensus: final", "driver: emit prep", "dequeue", "emit", 0, 0, 0, 0, "probe: 4 dependent cold loads", "probe: 4 dependent warm loads", "probe: slab store + load", 0};
-            if (cnt[96 + 43]) fprintf(stderr, "[rtk trace] in-situ probes: cold load %.0f cycles, warm load %.0f cycles, slab store + load %.0f cycles (per round trip, %llu samples)\n", double(cnt[96 + 40]) / 4.0 / double(cnt[96 + 43]), double(cnt[96 + 41]) / 4.0 / double(cnt[96 + 43]), double(cnt[96 + 42]) / double(cnt[96 + 43]), cnt[96 + 43]);
-            unsigned long long tot = 0; for (int i = 0; i < 48; ++i) tot += cnt[96 + i];
-            fprintf(stderr, "[rtk trace] k_regions lap profile (%.3g cycles):", double(tot)); for (int i = 0; i < 48; ++i) if (cnt[96 + i] && pn[i]) fprintf(stderr, " [%d %s %.4f]", i, pn[i], double(cnt[96 + i]) / double(tot ? tot : 1)); fprintf(stderr, "\n"); }
-#endif
-        if (getenv("RTK_TRACE")) { static const char* const hn[8] = {"gap<40", "gap<64", "gap<128", "gap<256", "gap<512", "gap<1024", "gap>=1024", "head/tail"};
-            fprintf(stderr, "[rtk trace] k_regions by size class (share of region time, regions, avg kcycles, second-strand share, DFS calls per region):");
-            for (int i = 0; i < 8; ++i) if (cnt[64 + i]) fprintf(stderr, " [%s %.3f n=%llu %.0fk bw=%.2f dfs=%.1f]", hn[i], double(cnt[56 + i]) / double(cnt[19] ? cnt[19] : 1), cnt[64 + i], 1e-3 * double(cnt[56 + i]) / double(cnt[64 + i]), double(cnt[72 + i]) / double(cnt[64 + i]), double(cnt[80 + i]) / double(cnt[64 + i]));
-            fprintf(stderr, "\n"); }
-        if (getenv("RTK_TRACE")) { static const char* const fine_names[16] = {"colour: class unions", "fixAmbiguity: path alignment", "fixAmbiguity: walk of the moves", "fixAmbiguity: linked alleles (k-mer lookups)", "fixAmbiguity: apply", "colour small: bit vectors (or array: shared_with(all))", "colour small: classes + selection (or array: set ops)", "region: side lists", "region: trim alignment", "region: fixAmbiguity", "consensus: merge logic", "paths: explore_paths outside DFS", "colour: small path (cycles)", "colour: 4096-bit path (cycles)", "colour: small path calls / total cycles", "colour: 4096-bit path calls / total cycles"};
-            fprintf(stderr, "[rtk trace] chooseColors calls: small path %llu, 4096-bit path %llu; fixAmbiguity calls %llu, of which left by the all-confident way out %llu\n", cnt[40 + 14], cnt[40 + 15], cnt[40 + 10], cnt[40 + 11]);
-            fprintf(stderr, "[rtk trace] k_regions fine shares:"); for (int i = 0; i < 16; ++i) if (cnt[40 + i]) fprintf(stderr, " [%s %.3f]", fine_names[i], double(cnt[40 + i]) / double(cnt[19] ? cnt[19] : 1)); fprintf(stderr, "\n"); }
-#ifdef RTK_LANE_PROF
-        if (getenv("RTK_TRACE")) { static const char* const ln[RL_NPROF] = {"driver", "side lists", "chooseColors", "search glue", "dfs walk", "colour_ok", "to_string", "peq build", "sweep", "walk", "path records", "path qual", "select", "amb collect", "fixAmbiguity", "assemble", "trim", "revcomp", "consensus", "emit", "idle at round end", "colours: universe", "colours: rows", 0};
-            unsigned long long tot = 0; for (int i = 0; i < RL_NPROF; ++i) tot += cnt[160 + i];
-            fprintf(stderr, "[rtk trace] k_regions_lanes lap profile (%.3g lane cycles):", double(tot)); for (int i = 0; i < RL_NPROF; ++i) if (cnt[160 + i] && ln[i]) fprintf(stderr, " [%s %.4f]", ln[i], double(cnt[160 + i]) / double(tot ? tot : 1)); fprintf(stderr, "\n");
-            unsigned long long tw = 0; for (int i = 0; i < RL_NPROF; ++i) tw += cnt[184 + i];
-            fprintf(stderr, "[rtk trace] k_regions_lanes wave-time estimate by slot (share of %.3g, lanes together):", double(tw) / 64.0); for (int i = 0; i < RL_NPROF; ++i) if (cnt[184 + i] && ln[i]) fprintf(stderr, " [%s %.4f x%.1f]", ln[i], double(cnt[184 + i]) / double(tw ? tw : 1), 64.0 * double(cnt[160 + i]) / double(cnt[184 + i])); fprintf(stderr, "\n"); }
-#endif
-        rtk_stats& st = b->stats;
-        st.cyc_colour = cnt[16]; st.cyc_paths = cnt[17]; st.cyc_consensus = cnt[18]; st.cyc_total = cnt[19]; st.cyc_myers = cnt[20]; st.cyc_sets = cnt[21]; st.cyc_tostring = cnt[22]; st.cyc_pathqual = cnt[23]; st.cyc_walk = cnt[32]; st.n_moves = cnt[33];
-        if (getenv("RTK_TRACE")) fprintf(stderr, "[rtk trace] k_regions shares of %.3g wave cycles: colour %.3f paths %.3f consensus %.3f myers %.3f sets %.3f tostring %.3f pathqual %.3f walk %.3f\n", double(cnt[19]), double(cnt[16]) / double(cnt[19] ? cnt[19] : 1), double(cnt[17]) / double(cnt[19] ? cnt[19] : 1), double(cnt[18]) / double(cnt[19] ? cnt[19] : 1), double(cnt[20]) / double(cnt[19] ? cnt[19] : 1), double(cnt[21]) / double(cnt[19] ? cnt[19] : 1), double(cnt[22]) / double(cnt[19] ? cnt[19] : 1), double(cnt[23]) / double(cnt[19] ? cnt[19] : 1), double(cnt[32]) / double(cnt[19] ? cnt[19] : 1));
-        if (getenv("RTK_TRACE")) fprintf(stderr, "[rtk trace] k_regions cycle shares: DFS bookkeeping %.3f (of which colour checks %.3f)\n", double(cnt[38]) / double(cnt[19] ? cnt[19] : 1), double(cnt[39]) / double(cnt[19] ? cnt[19] : 1));
-        if (getenv("RTK_TRACE")) fprintf(stderr, "[rtk trace] walks %llu moves %llu reloads %llu scalar steps %llu cycles %.3g tail cycles %.3g\n", cnt[36], cnt[33], cnt[34], cnt[35], double(cnt[32]), double(cnt[37]));
-        st.n_slots_exact = cnt[RTK_CNT_SLOTS_EXACT]; st.n_slots_inexact = cnt[RTK_CNT_SLOTS_INEXACT];
-        st.ms_regions = t_enum.elapsed() + (n_regions ? t_easy.elapsed() : 0.0); st.ms_lanes = lanes_on ? t_lanes.elapsed() : 0.0; st.ms_correct = ms_reg + ((lanes_on && !lanes_beside) ? st.ms_lanes : 0.0); /* (beside: the span of the wave kernel's two launches contains the lane kernel) */ st.n_lane_handed = cnt[152]; st.n_lane_regions = cnt[152] + cnt[153]; /* (ms_regions: enumeration + the regions without a graph walk) */ st.ms_stitch = t_st.elapsed(); st.ms_total = t_all.elapsed();
-        st.n_windows = b->n_bases; st.n_probes_exact = cnt[RTK_CNT_PROBES_EXACT]; st.n_probes_inexact = cnt[RTK_CNT_PROBES_INEXACT]; st.n_hits_inexact = cnt[RTK_CNT_HITS_INEXACT];
-        st.n_regions = n_regions; st.n_region_items = n_regions; st.n_arena_overflow = n_ovf_total;
-        st.n_expand = cnt[RTK_CNT_EXPAND]; st.n_colour_elem = cnt[RTK_CNT_COLOUR]; st.n_path_base = cnt[RTK_CNT_PATHBASE]; st.n_align = cnt[RTK_CNT_ALIGN]; st.n_align_cells = cnt[RTK_CNT_CELLS];
-        st.in_bases = b->n_bases; st.out_bases = out_top / 2;
-        lap("done");
+        RegionRun R = {};
+        R.b = b; R.g = g; R.ov = opts_view(opts); R.sm = b->stream; R.own_slab = opts->long_read_correct != 0;
+        R.hold.g = g; R.hold.what = -1; R.slab.g = g;
+        R.trace = rtk_knob_trace(); R.w0 = std::chrono::steady_clock::now();
+        for (uint32_t i = 0; i < b->n; ++i) R.max_len = std::max<uint32_t>(R.max_len, static_cast<uint32_t>(b->roff[i + 1] - b->roff[i]));
+        R.grid = default_grid();
+        region_alloc(R);
+        region_lane_class(R);
+        R.lap("alloc");
+        region_enumerate(R);
+        R.lap("enum");
+        region_easy(R);
+        region_lanes(R);
+        region_take_areas(R);
+        rc = region_attempts(R);
+        if (rc) return rc;
+        R.hold.release();
+        R.lap("regions");
+        rc = region_stitch(R);
+        if (rc) return rc;
+        unsigned long long cnt[RTK_CNT_TOTAL]; rtk_d2h_s(cnt, b->bv.counters, sizeof(cnt), R.sm);
+        if (R.trace) region_trace_report(cnt);
+        region_stats(R, cnt);
+        R.lap("done");
         if (b->h_out) { g->stage_give(b->h_out, b->h_out_bytes); b->h_out = nullptr; } // a re-run invalidates the fetched view
         b->ran = true; b->seeded = false;
     } catch (const std::exception& e) { return rtk_fail(RTK_ERR_DEVICE, e.what()); }
@@ -677,7 +858,7 @@ static int batch_fetch_host(rtk_batch* b) {
     b->h_off.resize(b->n); b->h_sl.resize(b->n); b->h_ql.resize(b->n);
     if (out_top) rtk_check_async_d2h(b->h_out, b->rb.out_pool, out_top, b->stream);
     rtk_d2h_s(b->h_off.data(), b->rb.out_off, 8ull * b->n, b->stream); rtk_d2h_s(b->h_sl.data(), b->rb.out_seq_len, 4ull * b->n, b->stream); rtk_d2h_s(b->h_ql.data(), b->rb.out_qual_len, 4ull * b->n, b->stream);
-    if (getenv("RTK_TRACE")) { auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b_) { return std::chrono::duration<double, std::milli>(b_ - a).count(); }; fprintf(stderr, "[rtk trace] fetch: wait for the stream %.2f ms, staging buffer %.2f ms, %.1f MB to the host %.2f ms\n", ms(tf0, tf1), ms(tf1, tf2), out_top / 1048576.0, ms(tf2, std::chrono::steady_clock::now())); }
+    if (rtk_knob_trace()) { auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b_) { return std::chrono::duration<double, std::milli>(b_ - a).count(); }; fprintf(stderr, "[rtk trace] fetch: wait for the stream %.2f ms, staging buffer %.2f ms, %.1f MB to the host %.2f ms\n", ms(tf0, tf1), ms(tf1, tf2), out_top / 1048576.0, ms(tf2, std::chrono::steady_clock::now())); }
     for (uint32_t i = 0; i < b->n; ++i) {
         const char* bad = nullptr;
         if (b->h_sl[i] != b->h_ql[i]) bad = "rtk_batch_fetch: sequence and quality lengths differ for a read";
@@ -750,8 +931,6 @@ struct CoTicket {
     const rtk_opts* opts; uint32_t n; const char* const* seq; const char* const* qual; const uint32_t* len; uint64_t bases;
     bool taken = false, done = false, alone_after_all = false; int rc = 0; std::string err; CoGroup* grp = nullptr; uint32_t first = 0;
 };
-static uint64_t coalesce_bases() { static const uint64_t v = [] { const char* e = getenv("RTK_COALESCE_BASES"); return e ? strtoull(e, nullptr, 10) : (16ull << 20); }(); return v; } // 0: every call runs on its own
-static long coalesce_wait_us() { static const long v = [] { const char* e = getenv("RTK_COALESCE_WAIT_US"); return e ? atol(e) : 1500L; }(); return v; }
 static bool co_compatible(const CoTicket& a, const CoTicket& b) { return (a.qual == nullptr) == (b.qual == nullptr) && memcmp(a.opts, b.opts, sizeof(rtk_opts)) == 0; }
 
 extern "C" int rtk_coalesce_stats(rtk_graph* g, uint64_t* n_groups, uint64_t* n_tickets) {
@@ -762,7 +941,7 @@ extern "C" int rtk_coalesce_stats(rtk_graph* g, uint64_t* n_groups, uint64_t* n_
 // one call on its own: the batch of one ticket
 static int correct_batch_alone(rtk_graph* g, const rtk_opts* opts, uint32_t n, const char* const* seq, const char* const* qual, const uint32_t* len, char** out_seq, char** out_qual, uint32_t* out_len) {
     rtk_batch* b = nullptr;
-    const bool trace = getenv("RTK_TRACE") != nullptr;
+    const bool trace = rtk_knob_trace();
     const auto t0 = std::chrono::steady_clock::now();
     auto ms = [&](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count(); };
     int rc = rtk_batch_create(g, n, seq, qual, len, &b);
@@ -784,7 +963,7 @@ extern "C" int rtk_correct_batch(rtk_graph* g, const rtk_opts* opts, uint32_t n,
     if (!g->on_device) return rtk_fail(RTK_ERR_NO_DEVICE, "rtk_correct_batch: graph is not resident on a device (call rtk_graph_upload); there is no CPU fallback");
     if (n == 0) return RTK_OK;
     uint64_t bases = 0; for (uint32_t i = 0; i < n; ++i) bases += len[i];
-    const uint64_t cap = coalesce_bases();
+    const uint64_t cap = rtk_knob_coalesce_bases();
     if (cap == 0 || bases >= cap || opts->long_read_correct) return correct_batch_alone(g, opts, n, seq, qual, len, out_seq, out_qual, out_len);
 
     CoTicket me; me.opts = opts; me.n = n; me.seq = seq; me.qual = qual; me.len = len; me.bases = bases;
@@ -796,7 +975,7 @@ extern "C" int rtk_correct_batch(rtk_graph* g, const rtk_opts* opts, uint32_t n,
         // ---- this caller gathers a group around its own ticket
         g->co_gathering = true;
         const bool alone = g->co_q.size() == 1 && g->co_running == 0 && g->co_last_group <= 1;
-        const auto deadline = std::chrono::steady_clock::now() + std::chrono::microseconds(alone ? 0L : coalesce_wait_us());
+        const auto deadline = std::chrono::steady_clock::now() + std::chrono::microseconds(alone ? 0L : rtk_knob_coalesce_wait_us());
         const bool cold = g->co_running == 0;
         while (true) {
             uint64_t sum = 0; for (size_t i = 0; i < g->co_q.size(); ++i) if (co_compatible(*g->co_q[i], me)) sum += g->co_q[i]->bases;
@@ -812,7 +991,7 @@ extern "C" int rtk_correct_batch(rtk_graph* g, const rtk_opts* opts, uint32_t n,
         // of everybody travelling in one group whose stages nothing overlaps (traced: 15 of 16 callers in one group, 37 ms per 16 Mb, profiles/r06_coalesce_trace.txt).
         uint64_t take_cap = cap; uint32_t take_n = 0xFFFFFFFFu;
         { uint32_t nw = 0; for (size_t i = 0; i < g->co_q.size(); ++i) if (co_compatible(*g->co_q[i], me)) ++nw;
-          static const uint32_t split = [] { const char* e = getenv("RTK_COALESCE_SPLIT"); const int v = e ? atoi(e) : 0; return static_cast<uint32_t>(v >= 1 ? v : 2); }();
+          const uint32_t split = rtk_knob_coalesce_split();
           const uint32_t around = nw + g->co_inflight_tickets; if (around >= 2 * split) take_n = (around + split - 1) / split; }
         (void)cold;
         std::vector<CoTicket*> grp; uint64_t sum = 0;
@@ -842,7 +1021,7 @@ extern "C" int rtk_correct_batch(rtk_graph* g, const rtk_opts* opts, uint32_t n,
             uint32_t tot = 0; for (size_t i = 0; i < grp.size(); ++i) { grp[i]->first = tot; tot += grp[i]->n; }
             std::vector<const char*> sa(tot), qa(qual ? tot : 0); std::vector<uint32_t> la(tot);
             for (size_t i = 0; i < grp.size(); ++i) for (uint32_t j = 0; j < grp[i]->n; ++j) { sa[grp[i]->first + j] = grp[i]->seq[j]; la[grp[i]->first + j] = grp[i]->len[j]; if (qual) qa[grp[i]->first + j] = grp[i]->qual[j]; }
-            const bool tr_ = getenv("RTK_TRACE") != nullptr; static const auto t_epoch = std::chrono::steady_clock::now();
+            const bool tr_ = rtk_knob_trace(); static const auto t_epoch = std::chrono::steady_clock::now();
             auto now_ms = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_epoch).count(); };
             const double tq0 = now_ms();
             rc = rtk_batch_create(g, tot, sa.data(), qual ? qa.data() : nullptr, la.data(), &cg->b);
@@ -855,7 +1034,7 @@ extern "C" int rtk_correct_batch(rtk_graph* g, const rtk_opts* opts, uint32_t n,
             if (rc == RTK_OK) rc = rtk_batch_fetch_view(cg->b, &cg->pool, &cg->off, &cg->len);
             if (tr_) fprintf(stderr, "[rtk trace] correct_batch group at %.1f ms: %zu tickets, %u reads, %.2f Mb; create %.2f seeds %.2f (kernels %.2f) regions %.2f (k_regions %.2f) fetch %.2f ms (rc %d)\n", tq0, grp.size(), tot, sum / 1e6, tq1 - tq0, tq2 - tq1,
                             cg->b ? cg->b->stats.ms_lookup_exact + cg->b->stats.ms_mask + cg->b->stats.ms_lookup_inexact + cg->b->stats.ms_seeds : 0.0, tq3 - tq2, cg->b ? cg->b->stats.ms_correct : 0.0, now_ms() - tq3, rc);
-            if (rc == RTK_OK && getenv("RTK_TEST_COALESCE_FAIL")) rc = rtk_fail(RTK_ERR_DEVICE, "test hook: the merged batch is reported as failed"); // (tests/test_coalesce.py: the members must come through on their own)
+            if (rc == RTK_OK && rtk_knob_test_coalesce_fail()) rc = rtk_fail(RTK_ERR_DEVICE, "test hook: the merged batch is reported as failed"); // (tests/test_coalesce.py: the members must come through on their own)
             if (rc) { err = rtk_last_error(); if (cg->b) rtk_batch_free(cg->b); delete cg; cg = nullptr; }
             else cg->left.store(static_cast<int>(grp.size()));
         }
@@ -927,13 +1106,13 @@ extern "C" int rtk_reserve_scratch(int device, uint32_t max_read_len) {
 #ifdef RTK_SIM
         const uint64_t n_seed_waves = 16, reg_waves = 16;
 #else
-        const uint64_t n_seed_waves = static_cast<uint64_t>(seed_waves()), reg_waves = static_cast<uint64_t>(region_waves());
+        const uint64_t n_seed_waves = static_cast<uint64_t>(seed_waves()), reg_waves = static_cast<uint64_t>(rtk_knob_region_waves());
 #endif
 #ifdef RTK_SIM
         uint64_t reg_bytes = region_scratch_bytes(region_cfg(max_read_len, 0)) * reg_waves;
 #else
         (void)reg_waves;
-        uint64_t reg_bytes = region_scratch_bytes(region_cfg(max_read_len, 0)) * static_cast<uint64_t>(region_waves_that_fit(region_scratch_bytes(region_cfg(max_read_len, 0)), 0));
+        uint64_t reg_bytes = region_scratch_bytes(region_cfg(max_read_len, 0)) * static_cast<uint64_t>(region_waves_that_fit(region_scratch_bytes(region_cfg(max_read_len, 0)), 0, rtk_knob_trace()));
 #endif
 #ifndef RTK_SIM
         if (region_compact()) reg_bytes = std::max<uint64_t>(reg_bytes, region_scratch_bytes(region_cfg(max_read_len, 1)) * 1024ull); // the full-size areas of the redo launch share the slab

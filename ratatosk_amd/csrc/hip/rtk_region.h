@@ -81,8 +81,8 @@ struct RegionScratch {
     U<uint64_t*> bm[3]; U<uint32_t> bm_words;
     UL<uint32_t*> overflow; U<uint32_t> ovf_word; // the flag itself, next to the header (same memory: LDS in the kernels)
     DriverLocals loc;
-    U<unsigned long long> cnt[16]; // expand, colour, pathbase, align, cells, then cycles: colour, paths, consensus, total, myers, sets
-    U<unsigned long long> fine[16]; // developer cycle counters printed with RTK_TRACE (RTK_FINE names in rtk_pipeline_run.inc)
+    U<unsigned long long> cnt[RTK_RC_N]; // event counts, then cycles: RtkRegionCnt (rtk_types.h)
+    U<unsigned long long> fine[RTK_FINE_N]; // developer cycle counters printed with RTK_TRACE: RtkRegionFine (rtk_types.h)
 #ifdef RTK_PROF
     U<unsigned long long> prof[48]; U<unsigned long long> prof_t; // developer build (-DRTK_PROF): lap profile of the region program, every cycle of a wave attributed to one slot (RTK_PL)
 #endif
@@ -217,7 +217,7 @@ RTK_FN_LEAF uint64_t rtk_wp_commit(RegionScratch& s_, const WPath& p_, int lvl_)
     PathHdr* h = reinterpret_cast<PathHdr*>(rec);
     h->n = pn; h->l = pl; h->qlen = pq; h->pad = 0;
     rtk_wcopy2(rec + sizeof(PathHdr), rtk_ld(&p.ums), sizeof(UMap) * pn, rec + sizeof(PathHdr) + sizeof(UMap) * pn, rtk_ld(&p.qual), pq);
-    s.cnt[11] += rtk_clock() - tc0;
+    s.cnt[RTK_RC_CYC_PATHREC] += rtk_clock() - tc0;
     return rtk_mk_handle(lvl, off);
 }
 
@@ -231,7 +231,7 @@ RTK_FN_LEAF void rtk_wp_load(RegionScratch& s_, WPath& p_, uint64_t h_) {
     const unsigned long long tc0 = rtk_clock();
     p.n = hn; p.l = hl; p.qlen = hq;
     rtk_wcopy2(rtk_ld(&p.ums), rec + sizeof(PathHdr), sizeof(UMap) * hn, rtk_ld(&p.qual), rec + sizeof(PathHdr) + sizeof(UMap) * hn, hq);
-    s.cnt[11] += rtk_clock() - tc0;
+    s.cnt[RTK_RC_CYC_PATHREC] += rtk_clock() - tc0;
 }
 
 RTK_DEV uint32_t rtk_rec_n(const RegionScratch& s, uint64_t h) { return rtk_ld(&rtk_path_hdr(s, rtk_h_lvl(h), rtk_h_off(h))->n); }
@@ -380,8 +380,8 @@ RTK_FN uint32_t rtk_ums_to_string(const RCtx& c, const UMap* ums_, uint32_t n_, 
         len += add;
     }
     rtk_sync();
-    s.cnt[2] += len;
-    s.cnt[12] += rtk_clock() - tc0;
+    s.cnt[RTK_RC_PATHBASE] += len;
+    s.cnt[RTK_RC_CYC_TOSTRING] += rtk_clock() - tc0;
     return len;
 }
 RTK_DEV uint32_t rtk_rec_to_string(const RCtx& c, uint64_t h, char* dst) {
@@ -409,11 +409,11 @@ static inline void rtk_site_note(uint32_t m, uint32_t n, int k, bool stored) {
 RTK_FN_HOT MyersResult rtk_align(const RCtx& c, const char* q_, uint32_t m_, const char* t_, uint32_t n_, int kk_, int mode_, bool iupac_ = true) {
     RegionScratch& s = *rtk_u(c.sc); const char* q = rtk_u(q_); const char* t = rtk_u(t_);
     const uint32_t m = rtk_u(m_), n = rtk_u(n_); const int kk = rtk_u(kk_), mode = rtk_u(mode_); const bool iupac = rtk_u(iupac_);
-    s.cnt[3] += 1; s.cnt[4] += static_cast<unsigned long long>((m + 63) / 64) * n;
+    s.cnt[RTK_RC_ALIGN] += 1; s.cnt[RTK_RC_CELLS] += static_cast<unsigned long long>((m + 63) / 64) * n;
     const unsigned long long t0 = rtk_clock();
     rtk_site_note(m, n, kk, false);
     const MyersResult r = rtk_myers_distance(s.my, q, static_cast<int>(m), t, static_cast<int>(n), kk, mode, iupac);
-    s.cnt[9] += rtk_clock() - t0;
+    s.cnt[RTK_RC_CYC_MYERS] += rtk_clock() - t0;
     return r;
 }
 
@@ -421,11 +421,11 @@ RTK_FN_HOT MyersResult rtk_align(const RCtx& c, const char* q_, uint32_t m_, con
 RTK_FN_HOT MyersResult rtk_align_path(const RCtx& c_, const char* q_, uint32_t m_, const char* t_, uint32_t n_, int mode_, uint32_t* n_moves_) {
     const RCtx& c = *rtk_u(&c_); RegionScratch& s = rtk_hdr(c); const char* q = rtk_u(q_); const char* t = rtk_u(t_);
     const uint32_t m = rtk_u(m_), n = rtk_u(n_); const int mode = rtk_u(mode_); uint32_t* n_moves = rtk_u(n_moves_);
-    s.cnt[3] += (m > 0 && n > 0) ? 2 : 1; s.cnt[4] += static_cast<unsigned long long>((m + 63) / 64) * n;
+    s.cnt[RTK_RC_ALIGN] += (m > 0 && n > 0) ? 2 : 1; s.cnt[RTK_RC_CELLS] += static_cast<unsigned long long>((m + 63) / 64) * n;
     const unsigned long long t0 = rtk_clock();
     rtk_site_note(m, n, -1, true);
     const MyersResult r = rtk_myers_path(s.my, q, static_cast<int>(m), t, static_cast<int>(n), mode, true, n_moves);
-    s.cnt[9] += rtk_clock() - t0;
+    s.cnt[RTK_RC_CYC_MYERS] += rtk_clock() - t0;
     return r;
 }
 
@@ -488,7 +488,7 @@ RTK_FN void rtk_score_path_qual(const RCtx& c, uint32_t sl_, const char* ref_, u
     if (saved && saved->valid && static_cast<uint32_t>(saved->m) == sl && static_cast<uint32_t>(saved->n) == ref_len) { // the sweep that scored this very path is still in the table
         MyersResult r0; const unsigned long long t0 = rtk_clock();
         resumed = rtk_myers_path_from_saved(s.my, *saved, &nm, &r0);
-        s.cnt[9] += rtk_clock() - t0;
+        s.cnt[RTK_RC_CYC_MYERS] += rtk_clock() - t0;
     }
     if (!resumed) { RTK_SITE(4); rtk_align_path(c, str1, sl, ref, ref_len, RTK_MODE_SHW, &nm); }
     nm = rtk_u(nm);
@@ -509,7 +509,7 @@ RTK_FN void rtk_score_path_qual(const RCtx& c, uint32_t sl_, const char* ref_, u
         qp += static_cast<uint32_t>(rtk_popc(bq)); rp += static_cast<uint32_t>(rtk_popc(br));
     }
     rtk_sync();
-    s.cnt[13] += rtk_clock() - tq0;
+    s.cnt[RTK_RC_CYC_PATHQUAL] += rtk_clock() - tq0;
 }
 
 // ------------------------------------------------------------------------------------------------ colour memo (src/GraphTraversal.cpp:485-487)
@@ -519,13 +519,13 @@ RTK_FN_HOT bool rtk_colour_ok(const RCtx& c, uint32_t u_, const uint32_t* all_pi
     for (uint32_t i0 = 0; i0 < mn; i0 += RTK_WAVE) { // 64 memo entries per step
         const uint32_t i = i0 + static_cast<uint32_t>(rtk_lane());
         const uint64_t hit = rtk_ballot(i < mn && mu[i] == u);
-        if (hit) { s.cnt[15] += rtk_clock() - tk0; return rtk_ld(mvv + i0 + static_cast<uint32_t>(rtk_ffs(hit) - 1)) != 0; }
+        if (hit) { s.cnt[RTK_RC_CYC_COLOUR_OK] += rtk_clock() - tk0; return rtk_ld(mvv + i0 + static_cast<uint32_t>(rtk_ffs(hit) - 1)) != 0; }
     }
     const uint32_t mcv = static_cast<uint32_t>(rtk_u(c.o.min_cov_vertices));
     const bool ok = (n_all == 0) || (rtk_u(rtk_shared_with_set(c.g, u, all_pids, n_all, mcv)) >= mcv);
-    s.cnt[1] += rtk_ld(c.g.card.get() + u) + n_all;
+    s.cnt[RTK_RC_COLOUR] += rtk_ld(c.g.card.get() + u) + n_all;
     if (mn < rtk_ld(&s.memo_cap)) { const_cast<uint32_t*>(mu)[mn] = u; mvv[mn] = ok ? 1 : 0; s.memo_n = mn + 1; rtk_sync(); }
-    s.cnt[15] += rtk_clock() - tk0;
+    s.cnt[RTK_RC_CYC_COLOUR_OK] += rtk_clock() - tk0;
     return ok;
 }
 
@@ -578,9 +578,9 @@ RTK_FN_SEARCH DfsOut rtk_explore_subgraph(const RCtx& c, const uint32_t* all_pid
     uint32_t n_nt_live = 0, n_t_scored = 0;
     MyersSaved& t_saved = s.loc.saved; t_saved.stash = reinterpret_cast<uint8_t*>(rtk_ld(&s.str[3])); t_saved.stash_cap = rtk_ld(&s.str_cap); t_saved.stash_n = 0; t_saved.valid = 0; t_saved.gen = 0; t_saved.m = 0; t_saved.n = 0; t_saved.nw_dist = 0; t_saved.shw.dist = -1; t_saved.shw.first = -1; t_saved.shw.last = -1; t_saved.shw.nloc = 0;
     unsigned long long n_exp = 0;
-    const unsigned long long td0 = rtk_clock(); const unsigned long long my0 = s.cnt[9];
+    const unsigned long long td0 = rtk_clock(); const unsigned long long my0 = s.cnt[RTK_RC_CYC_MYERS];
 #ifdef RTK_SIM
-    const unsigned long long dfs_al0 = s.cnt[3];
+    const unsigned long long dfs_al0 = s.cnt[RTK_RC_ALIGN];
 #endif
     // Walk 0 prunes (lazy mode only): an extension already longer than max_len_path can neither reach a terminal path that passes the
     // length test of :511 nor a non-terminal leaf that would ever be looked at again, so its subtree is skipped -- unless a LIVE
@@ -629,7 +629,7 @@ RTK_FN_SEARCH DfsOut rtk_explore_subgraph(const RCtx& c, const uint32_t* all_pid
                     double sco;
                     ++n_t_scored;
                     if (n_t_scored == 1 && sl != 0 && rtk_myers_nw_and_save(s.my, str1, static_cast<int>(sl), ref, static_cast<int>(ref_len), true, &t_saved)) {
-                        s.cnt[3] += 1; s.cnt[4] += static_cast<unsigned long long>((sl + 63) / 64) * ref_len;
+                        s.cnt[RTK_RC_ALIGN] += 1; s.cnt[RTK_RC_CELLS] += static_cast<unsigned long long>((sl + 63) / 64) * ref_len;
                         sco = 1.0 - (static_cast<double>(rtk_u(t_saved.nw_dist)) / static_cast<double>(sl));
                         sco = sco > 0.0 ? sco : 0.0; sco = sco < 1.0 ? sco : 1.0;
                     } else sco = rtk_u(rtk_score_path(c, sl, ref, ref_len, true));
@@ -684,11 +684,11 @@ RTK_FN_SEARCH DfsOut rtk_explore_subgraph(const RCtx& c, const uint32_t* all_pid
     }
     } // walk
 #ifdef RTK_SIM
-    { const unsigned long long na = s.cnt[3] - dfs_al0; const unsigned b = na > 15 ? 15 : static_cast<unsigned>(na); rtk_sim_site_stat[21][0] += 1; rtk_sim_site_stat[22 + (b >> 3)][b & 7] += 1; rtk_sim_site_stat[24 + (b >> 3)][b & 7] += na; }
+    { const unsigned long long na = s.cnt[RTK_RC_ALIGN] - dfs_al0; const unsigned b = na > 15 ? 15 : static_cast<unsigned>(na); rtk_sim_site_stat[21][0] += 1; rtk_sim_site_stat[22 + (b >> 3)][b & 7] += 1; rtk_sim_site_stat[24 + (b >> 3)][b & 7] += na; }
 #endif
     RTK_PL(s, 15);
-    s.cnt[0] += n_exp; RTK_HIST_ADD(s, 31, 1);
-    s.cnt[14] += (rtk_clock() - td0) - (s.cnt[9] - my0); // DFS bookkeeping: loop time minus the alignments inside it
+    s.cnt[RTK_RC_EXPAND] += n_exp; RTK_HIST_ADD(s, 31, 1);
+    s.cnt[RTK_RC_CYC_DFS] += (rtk_clock() - td0) - (s.cnt[RTK_RC_CYC_MYERS] - my0); // DFS bookkeeping: loop time minus the alignments inside it
     bool nt_score_deferred = false;
     if (lazy_nt && !rtk_failed(s)) {
         // whichever candidate survives the scoring is only re-queued; if none of them can pass the length test of the pop, the queue
@@ -1105,10 +1105,10 @@ RTK_DEV uint32_t rtk_choose_colors(const RCtx& c, const SideList& side_s, const 
     const unsigned long long tf = rtk_clock();
 #ifndef RTK_SIM
     { const uint32_t r0 = rtk_u(rtk_choose_colors_small(c, side_s, side_e, side_w));
-      if (r0 != RTK_NONE32) { const unsigned long long d_ = rtk_clock() - tf; s.fine[0] += d_; s.fine[12] += d_; s.fine[14] += 1; return rtk_failed(s) ? 0 : r0; } }
+      if (r0 != RTK_NONE32) { const unsigned long long d_ = rtk_clock() - tf; s.fine[RTK_FINE_COL_UNIONS] += d_; s.fine[RTK_FINE_COL_S_CYCLES] += d_; s.fine[RTK_FINE_COL_S_CALLS] += 1; return rtk_failed(s) ? 0 : r0; } }
 #endif
     const uint32_t r = rtk_u(rtk_choose_colors_bits(c, side_s, side_e, side_w));
-    if (r != RTK_NONE32) { const unsigned long long d_ = rtk_clock() - tf; s.fine[0] += d_; s.fine[13] += d_; s.fine[15] += 1; return rtk_failed(s) ? 0 : r; }
+    if (r != RTK_NONE32) { const unsigned long long d_ = rtk_clock() - tf; s.fine[RTK_FINE_COL_UNIONS] += d_; s.fine[RTK_FINE_COL_B_CYCLES] += d_; s.fine[RTK_FINE_COL_B_CALLS] += 1; return rtk_failed(s) ? 0 : r; }
     return rtk_u(rtk_choose_colors_general(c, side_s, side_e, side_w));
 }
 RTK_FN uint32_t rtk_choose_colors_general(const RCtx& c_, const SideList& side_s_, const SideList& side_e_, const SideList& side_w_) {
@@ -1131,7 +1131,7 @@ RTK_FN uint32_t rtk_choose_colors_general(const RCtx& c_, const SideList& side_s
             const int32_t gi = g.gid[u]; // G2: only the global set when there is one
             const uint32_t* src = gi >= 0 ? g.col + g.goff[gi] : g.col + g.loff[u];
             const uint32_t ns = gi >= 0 ? static_cast<uint32_t>(g.goff[gi + 1] - g.goff[gi]) : static_cast<uint32_t>(g.loff[u + 1] - g.loff[u]);
-            s.cnt[1] += ns;
+            s.cnt[RTK_RC_COLOUR] += ns;
             if (ns == 0) continue;
             // a class fed by ONE anchor set (the usual case: a region is flanked by a unitig or two) is that set: used where it lies in
             // the graph's colour pool, neither merged nor copied
@@ -1155,7 +1155,7 @@ RTK_FN uint32_t rtk_choose_colors_general(const RCtx& c_, const SideList& side_s
     { std::atomic<unsigned long long>* t = rtk_sim_site_stat[29]; t[0] += 1; t[1] += side_s.n; t[2] += side_e.n; t[3] += side_w.n; for (int i = 0; i < 6; ++i) rtk_sim_site_stat[30][i] += a_n[i];
       unsigned long long tot = 0; for (int i = 0; i < 6; ++i) tot += a_n[i]; int b = 0; while (b < 7 && (256ull << b) <= tot) ++b; rtk_sim_site_stat[31][b] += 1; }
 #endif
-    RTK_FINE_LAP(0)
+    RTK_FINE_LAP(RTK_FINE_COL_GENERAL + 0)
     auto A = [&](int i) -> const uint32_t* { return a_ptr[i]; };
     // candidate anchors: cardinality >= min_cov_vertices, ordered by (cardinality, unitig id) [D1]
     uint64_t* keys = s.list[4]; uint64_t* vals = s.list[3];
@@ -1169,7 +1169,7 @@ RTK_FN uint32_t rtk_choose_colors_general(const RCtx& c_, const SideList& side_s
         keys[nsp] = rtk_d1_key(g.card[u], u, c.o.d1_desc); vals[nsp] = 0; ++nsp; rtk_sync();
     }
     rtk_sort_pairs(keys, vals, nsp);
-    RTK_FINE_LAP(1)
+    RTK_FINE_LAP(RTK_FINE_COL_GENERAL + 1)
     const uint32_t cov = 30;
     for (uint32_t j = 0; j < nsp; ++j) { const uint32_t cd = static_cast<uint32_t>(keys[j] >> 32); vals[j] = cd < cov ? cd : cov; } // remaining quota (p_spid.second)
     // Set expressions of src/Correction.cpp:233-275,300-352 on immutable operands: a result is either one of its operands (union with
@@ -1197,7 +1197,7 @@ RTK_FN uint32_t rtk_choose_colors_general(const RCtx& c_, const SideList& side_s
     const SetRef a01 = In(pos0, pos1), a12 = In(pos1, pos2), a02 = In(pos0, pos2);
     const SetRef nobranch_all = Un(Un(a[3], a[4]), a[5]);
     if (rtk_failed(s)) return 0;
-    RTK_FINE_LAP(2)
+    RTK_FINE_LAP(RTK_FINE_COL_GENERAL + 2)
     uint32_t n_all = 0; int allb = 0; // all_pids lives in set[0] (while it is being built: in set[allb])
     uint32_t nb_unselected = nsp;
     SetRef nobranch = nobranch_all, branching = EMPTY, i3 = EMPTY, i2 = EMPTY, prev2 = EMPTY; // prev2: a_pid2 of the previous class
@@ -1216,7 +1216,7 @@ RTK_FN uint32_t rtk_choose_colors_general(const RCtx& c_, const SideList& side_s
         const uint32_t n2 = a2.n;
         if (rtk_failed(s)) break;
         prev2 = a2; // a_pid2[i] is needed by the next class
-        RTK_FINE_LAP(3)
+        RTK_FINE_LAP(RTK_FINE_COL_GENERAL + 3)
         if (n2 != 0) {
             nb_unselected = 0;
             const uint32_t* cur_p = a2.p; uint32_t ncur = n2; int curb = 8; // curr_pid: a_pid2[i] itself until the first selection, then set[7] / set[8] (ping-pong)
@@ -1224,14 +1224,14 @@ RTK_FN uint32_t rtk_choose_colors_general(const RCtx& c_, const SideList& side_s
                 const uint32_t u = rtk_d1_unitig(keys[j], c.o.d1_desc);
                 int quota = static_cast<int>(vals[j]);
                 bool touch = false;
-                if (quota > 0) { touch = (i == 0 || rtk_shared_with_set(g, u, cur_p, ncur, 1) >= 1); RTK_FINE_LAP(4) }
+                if (quota > 0) { touch = (i == 0 || rtk_shared_with_set(g, u, cur_p, ncur, 1) >= 1); RTK_FINE_LAP(RTK_FINE_COL_GENERAL + 4) }
 #ifdef RTK_SIM
                 rtk_sim_site_stat[29][5] += 1; if (touch) rtk_sim_site_stat[29][6] += 1;
 #endif
                 if (touch) {
                     const uint32_t min_cov = g.card[u] < cov ? g.card[u] : cov;
                     const uint32_t sh = rtk_shared_with_set(g, u, s.set[allb], n_all, min_cov);
-                    RTK_FINE_LAP(5)
+                    RTK_FINE_LAP(RTK_FINE_COL_GENERAL + 5)
                     quota = static_cast<int>(min_cov - (sh < min_cov ? sh : min_cov));
                     if (quota > 0) {
                         const uint32_t all_card = n_all;
@@ -1248,7 +1248,7 @@ RTK_FN uint32_t rtk_choose_colors_general(const RCtx& c_, const SideList& side_s
 #endif
                         const int gained = static_cast<int>(n_all - all_card);
                         quota -= gained < quota ? gained : quota;
-                        RTK_FINE_LAP(6)
+                        RTK_FINE_LAP(RTK_FINE_COL_GENERAL + 6)
                     }
                 }
                 vals[j] = static_cast<uint64_t>(quota);
@@ -1366,9 +1366,6 @@ RTK_DEV void rtk_scan_anchor_runs(const Anchors& a, int64_t start, int step, Con
 // s_read: read in the orientation of this call; v_s / v_w: anchors in that orientation. Result strings go to res.seq / res.qual.
 // q_read: pass 2 only, the quality string that goes with s_read in this call (the reference passes q_fw, q_bw or -- for the head region --
 // q_fw next to the reverse-complemented read, :787 G17); uncorrected stretches keep their qualities instead of getting q_min.
-#ifdef RTK_REGION_SPLIT
-#include "variants/rtk_region_split.h" // (measured and rejected: the call in three programs; not part of the default build)
-#endif
 
 RTK_FN_REGION void rtk_correct_region(const RCtx& c_, const char* s_read_, uint32_t s_len_, const Anchors& v_s_, const Anchors& v_w_, uint32_t i_s_, uint32_t i_w_, const ResCorr* rc_, ResCorr& res_, const char* q_read_ = nullptr) {
     const RCtx& c = *rtk_u(&c_); const char* s_read = rtk_u(s_read_); const char* q_read = rtk_u(q_read_);
@@ -1403,20 +1400,6 @@ RTK_FN_REGION void rtk_correct_region(const RCtx& c_, const char* s_read_, uint3
             lw_hi = rtk_u(rtk_an_first_ge(v_w, lw_lo, v_w_sz, pos_end));
         }
     }
-#ifdef RTK_REGION_SPLIT
-    {
-        RegionCall& st = s.loc.call;
-        st.s_read = s_read; st.q_read = q_read; st.s_len = s_len; st.p1 = p1; st.p2 = p2; st.um1 = um1; st.um2 = um2; st.first_pos = first_pos; st.len_weak_region = len_weak_region;
-        st.lw_lo = lw_lo; st.lw_hi = lw_hi; st.has_end_pt = has_end_pt ? 1u : 0u; st.lrc = lrc ? 1u : 0u; (void)u_min_start; (void)u_min_end; (void)q_min; (void)max_len_weak_anchors; (void)g;
-        uint32_t n_all_ = 0;
-        if (rc == nullptr) { n_all_ = rtk_u(rtk_region_colours(c, v_s, v_w, i_s, i_w)); if (rtk_failed(s)) return; } else n_all_ = rtk_u(rc->n_all);
-        st.n_all = n_all_; res.n_all = n_all_;
-        rtk_region_search(c, v_w, res);
-        if (rtk_failed(s)) return;
-        rtk_region_assemble(c, res);
-    }
-}
-#else
     uint32_t n_all = 0;
     RTK_PL(s, 2);
     if (rc == nullptr) {
@@ -1458,9 +1441,9 @@ RTK_FN_REGION void rtk_correct_region(const RCtx& c_, const char* s_read_, uint3
             rtk_scan_anchor_runs(v_w, static_cast<int64_t>(lw_lo), +1, [&](uint32_t p) { return p < pos_end_m; }, [&](const UMap& um) { const uint32_t u = um.unitig; if (g.kcov[u] < c.o.max_km_cov) rtk_side_insert(sm, u, !rtk_is_branching(g, u)); });
         }
         if (sl.n >= cap / 2 || sr.n >= cap / 2 || sm.n >= cap / 2) { rtk_fail_ovf(s, 8); return; }
-        s.fine[7] += rtk_clock() - t_side0;
+        s.fine[RTK_FINE_SIDE_LISTS] += rtk_clock() - t_side0;
         RTK_PL(s, 3);
-        { const unsigned long long t0 = rtk_clock(); n_all = rtk_u(rtk_choose_colors(c, sl, sr, sm)); s.cnt[5] += rtk_clock() - t0; }
+        { const unsigned long long t0 = rtk_clock(); n_all = rtk_u(rtk_choose_colors(c, sl, sr, sm)); s.cnt[RTK_RC_CYC_COLOUR] += rtk_clock() - t0; }
         RTK_PL(s, 4);
         if (rtk_failed(s)) return;
         // keep all_pids for the reverse-complement call (rc = &fw): set[0] is preserved by everything below
@@ -1482,7 +1465,7 @@ RTK_FN_REGION void rtk_correct_region(const RCtx& c_, const char* s_read_, uint3
     bool first_call = true, found_first = false, do_call = n_all >= c.o.min_cov_vertices;
     uint32_t i_w_s = 0;
     for (;;) {
-        if (do_call) { const unsigned long long t0 = rtk_clock(); complete = rtk_u(rtk_extract_semi_weak(c, s_read, s_len, all_pids, n_all, p1, um1, p2, um2, lvw, lw_lo, lw_hi, first_call ? 0u : i_w_s, &n_partial)); n_partial = rtk_u(n_partial); s.cnt[6] += rtk_clock() - t0; }
+        if (do_call) { const unsigned long long t0 = rtk_clock(); complete = rtk_u(rtk_extract_semi_weak(c, s_read, s_len, all_pids, n_all, p1, um1, p2, um2, lvw, lw_lo, lw_hi, first_call ? 0u : i_w_s, &n_partial)); n_partial = rtk_u(n_partial); s.cnt[RTK_RC_CYC_PATHS] += rtk_clock() - t0; }
         if (rtk_failed(s)) return;
         RTK_PL(s, 22);
         if (first_call && complete != ~0ull) found_first = true;
@@ -1551,7 +1534,7 @@ RTK_FN_REGION void rtk_correct_region(const RCtx& c_, const char* s_read_, uint3
     }
     if (rtk_failed(s)) return;
     RTK_PL(s, 24);
-    if (n_amb != 0) { const unsigned long long ta0 = rtk_clock(); rtk_fix_ambiguity(c, s_corr, sl_, q_corr, ql_, s_read + first_pos, res.old_len, n_amb); s.fine[9] += rtk_clock() - ta0; if (rtk_failed(s)) return; } // :716
+    if (n_amb != 0) { const unsigned long long ta0 = rtk_clock(); rtk_fix_ambiguity(c, s_corr, sl_, q_corr, ql_, s_read + first_pos, res.old_len, n_amb); s.fine[RTK_FINE_FIX_AMBIGUITY] += rtk_clock() - ta0; if (rtk_failed(s)) return; } // :716
     RTK_PL(s, 25);
     if (rtk_bm_card(res.bm, res.old_len) == res.old_len) { // :718-725 (G20): last k-mer of the WHOLE read vs last k-mer of the corrected region
         bool same = sl_ >= k && s_len >= k;
@@ -1561,7 +1544,7 @@ RTK_FN_REGION void rtk_correct_region(const RCtx& c_, const char* s_read_, uint3
     if (!res.is_corrected) { // :727-747 trim the corrected string to the largest SHW end location of the raw region
         const unsigned long long tt0 = rtk_clock();
         RTK_SITE(13); const MyersResult a = rtk_align(c, s_read + first_pos, p2 - first_pos + k, s_corr, sl_, -1, RTK_MODE_SHW);
-        s.fine[8] += rtk_clock() - tt0;
+        s.fine[RTK_FINE_TRIM] += rtk_clock() - tt0;
         if (a.dist >= 0) {
             const uint32_t keep = (a.first == -1) ? 0u : static_cast<uint32_t>(a.last + 1); // endLocations[0] == -1 wraps to SIZE_MAX in the reference
             if (keep < sl_) sl_ = keep;
@@ -1571,7 +1554,6 @@ RTK_FN_REGION void rtk_correct_region(const RCtx& c_, const char* s_read_, uint3
     res.seq_len = sl_; res.qual_len = ql_;
     RTK_PL(s, 26);
 }
-#endif
 
 // ------------------------------------------------------------------------------------------------ generateConsensus (src/Alignment.cpp:309-470)
 struct CigCur { const uint8_t* mv; uint32_t n, idx, qpos, rpos; }; // op-granular cursor over an alignment (moves 0/3 = M, 1 = I, 2 = D)
@@ -1722,7 +1704,7 @@ RTK_DEV RegionScratch* region_scratch_carve(char* base, const RegionScratchCfg& 
     t.str_cap = c.str_cap;
     t.memo_v = reinterpret_cast<uint8_t*>(p); p += c.memo_cap;
     t.ovf_word = 0; t.overflow = reinterpret_cast<uint32_t*>(&s->ovf_word); t.my.overflow = t.overflow;
-    for (int i = 0; i < 16; ++i) { t.cnt[i] = 0; t.fine[i] = 0; }
+    for (int i = 0; i < RTK_RC_N; ++i) { t.cnt[i] = 0; t.fine[i] = 0; }
 #ifdef RTK_PROF
     for (int i = 0; i < 48; ++i) t.prof[i] = 0;
     t.prof_t = rtk_clock();
@@ -1849,7 +1831,7 @@ RTK_FN_DRIVER void rtk_region_program(const RCtx& c_, RegionDesc* rd_) {
                     uint32_t& csl = s.loc.len[2]; uint32_t& cql = s.loc.len[3]; csl = 0; cql = 0;
                     const unsigned long long tc0 = rtk_clock();
                     const bool ok = rtk_generate_consensus(c, &fw, &bw, s_fw + pa, ref_len, c.o.weak_region_len_factor, s.rbuf[6], &csl, s.rbuf[7], &cql);
-                    s.cnt[7] += rtk_clock() - tc0;
+                    s.cnt[RTK_RC_CYC_CONSENSUS] += rtk_clock() - tc0;
                     RTK_PL(s, 32);
                     if (rtk_failed(s)) return;
                     if (!ok || csl == 0) { // raw region, k solid qualities then minimum quality (:898-904)
@@ -1927,15 +1909,8 @@ RTK_FN void rtk_enum_regions(const GraphView& g, const BatchView& bv, const Regi
     const uint64_t base = bv.roff[r];
     const uint32_t L = static_cast<uint32_t>(bv.roff[r + 1] - base);
     const uint32_t* sp = bv.s_pos + base; const uint32_t ns = bv.n_solid[r];
-    // reverse complement of the read (used by the head and backward corrections, src/Correction.cpp:175)
-#ifndef RTK_AB_ENUM_RC_REPS // (developer A/B builds: what the reverse complement / the anchor loops cost, by doing them several times)
-#define RTK_AB_ENUM_RC_REPS 1
-#endif
-#ifndef RTK_AB_ENUM_GAP_REPS
-#define RTK_AB_ENUM_GAP_REPS 1
-#endif
     // reverse complement of the read (used by the head and backward corrections, src/Correction.cpp:175); pass 2: the quality string reversed beside it
-    for (int rep_ = 0; rep_ < RTK_AB_ENUM_RC_REPS; ++rep_) {
+    {
         rtk_reverse_copy(rb.seq_rc.get() + base, bv.seq.get() + base, L, comp_tab);
         if (bv.qual.get() != nullptr && rb.qual_rev.get() != nullptr) rtk_reverse_copy(rb.qual_rev.get() + base, bv.qual.get() + base, L, nullptr);
     }
@@ -1944,7 +1919,9 @@ RTK_FN void rtk_enum_regions(const GraphView& g, const BatchView& bv, const Regi
     // (this program runs on ONE wave per read and the launch lasts as long as its longest read -- tens of thousands of solid anchors: the anchors are
     // read sixteen chunks of 64 at a time, and what the descriptors need from a neighbouring anchor comes out of the lanes' registers, not from memory)
     constexpr uint32_t EU = 16;
-    for (int rep_ = 0; rep_ < RTK_AB_ENUM_GAP_REPS; ++rep_) { n_gaps = 0;
+    // (what is left of a retired A/B build that counted the gaps several times: a loop of one trip. As a plain block the compiler allocates the
+    // registers of this function differently, so it stays until a change that touches this kernel anyway)
+    for (int once = 0; once < 1; ++once) { n_gaps = 0;
     if (!whole) for (uint32_t c0 = 0; c0 + 1 < ns; c0 += EU * RTK_WAVE) {
         uint32_t a[EU], b2[EU];
         for (uint32_t u = 0; u < EU; ++u) { const uint32_t i = c0 + u * RTK_WAVE + static_cast<uint32_t>(rtk_lane()); const bool in = i + 1 < ns; a[u] = in ? sp[i] : 0u; b2[u] = in ? sp[i + 1] : 1u; }

@@ -23,15 +23,10 @@
 
 #define RL_STRIDE RTK_WAVE
 // layout of a wave's work area and traceback table in device memory: RL_MS = 1: one contiguous slice per lane (a lane's walk over its own words stays in the
-// cache lines it has fetched: the lane programs are bound by the latency of their own dependent accesses, not by bandwidth); RL_MS = RL_STRIDE: words interleaved
-// by lane (the lanes' accesses to the same logical word coalesce; -DRL_INTERLEAVED, measured slower)
-#ifdef RL_INTERLEAVED
-#define RL_MS RL_STRIDE
-#define RL_LANE_WORDS(words) 1ull
-#else
+// cache lines it has fetched: the lane programs are bound by the latency of their own dependent accesses, not by bandwidth). The other layout, words interleaved
+// by lane (RL_MS = RL_STRIDE: the lanes' accesses to the same logical word coalesce), was measured slower and is gone
 #define RL_MS 1
 #define RL_LANE_WORDS(words) static_cast<uint64_t>(words)
-#endif
 
 // ---- capacities (compile-time layout; RlCtx::lim_* are the run-time limits the checks use: a test hook lowers them) ----
 #ifndef RL_STR_BYTES

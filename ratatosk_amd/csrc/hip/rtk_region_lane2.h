@@ -545,7 +545,7 @@ RTK_FN uint32_t rl_choose_colors(RlCtx& c, uint32_t n_side) {
     const uint32_t U = nu, vw = (U + 31u) >> 5;
     RL_LAP(c, 21);
 #if defined(RTK_SIM) && defined(RTK_LANE_PROF)
-    if (getenv("RTK_LANE_COST")) fprintf(stderr, "COLOURS slots %u T %llu U %u\n", n_slots, T, U);
+    if (rtk_knob_lane_cost()) fprintf(stderr, "COLOURS slots %u T %llu U %u\n", n_slots, T, U);
 #endif
     // ---- bit rows of every slot: local part, global part ----
     for (uint32_t s = 0; s < n_slots; ++s) {

@@ -47,7 +47,7 @@ struct BatchView {
     U<uint64_t*> w_off;          // [n_reads]
     U<uint32_t*> w_cnt;          // [n_reads]
     U<uint32_t*> status;         // [n_reads] non-zero: a scratch capacity was exceeded for this read
-    U<unsigned long long*> counters; // [16] event counters (see rtk_pipeline.inc)
+    U<unsigned long long*> counters; // [RTK_CNT_TOTAL] event and cycle counters: the map is RtkCounterSlot (rtk_types.h)
 };
 
 struct SeedScratch {
@@ -87,22 +87,6 @@ RTK_HD SeedScratch seed_scratch_carve(char* base, const SeedScratchCfg& c) {
     s.sflag = reinterpret_cast<uint8_t*>(p);
     return s;
 }
-
-#define RTK_CNT_WINDOWS 0
-#define RTK_CNT_PROBES_EXACT 1
-#define RTK_CNT_PROBES_INEXACT 2
-#define RTK_CNT_HITS_INEXACT 3
-#define RTK_CNT_REGIONS 4
-#define RTK_CNT_ITEMS 5
-#define RTK_CNT_OVERFLOW 6
-#define RTK_CNT_EXPAND 7
-#define RTK_CNT_COLOUR 8
-#define RTK_CNT_PATHBASE 9
-#define RTK_CNT_ALIGN 10
-#define RTK_CNT_CELLS 11
-#define RTK_CNT_SLOTS_EXACT 12
-#define RTK_CNT_SLOTS_INEXACT 13
-#define RTK_CNT_PHASE_SKIPPED 210 // second pass: reads whose whole-read alignment was skipped (rtk_phasing.h)
 
 RTK_DEV uint32_t rtk_hit_unitig(uint64_t h) { return static_cast<uint32_t>(h >> 33); }
 RTK_DEV bool rtk_is_branching(const GraphView& g, uint32_t u) { return (g.flags[u] & RTK_F_BRANCHING) != 0; }
@@ -1184,10 +1168,10 @@ static_assert(RTK_GQ % RTK_GH == 0, "a step is a whole number of halves");
     }
     RTK_PHASE();
     if (rtk_lane() == 0) { // phase profile of the stage (wave cycles), read back under RTK_TRACE
-        for (int i = 0; i < iph && i < 7; ++i) rtk_atomic_add(bv.counters + 24 + i, tph[i]);
+        for (int i = 0; i < iph && i < 7; ++i) rtk_atomic_add(bv.counters + RTK_CNT_FINALIZE + i, tph[i]);
 #ifndef RTK_SIM
-        { const unsigned long long mine = rtk_clock() - tstart; const unsigned long long was = atomicMax(bv.counters.get() + 31, mine);
-          if (mine > was) for (int i = 0; i < iph && i < 7; ++i) bv.counters[72 + i] = tph[i]; } // (developer trace: the phases of the slowest read so far; races between two record holders are harmless)
+        { const unsigned long long mine = rtk_clock() - tstart; const unsigned long long was = atomicMax(bv.counters.get() + RTK_CNT_FINALIZE_SLOWEST, mine);
+          if (mine > was) for (int i = 0; i < iph && i < 7; ++i) bv.counters[RTK_CNT_FINALIZE_SLOWEST_PHASES + i] = tph[i]; } // (developer trace: the phases of the slowest read so far; races between two record holders are harmless)
 #endif
     }
 #undef RTK_PHASE

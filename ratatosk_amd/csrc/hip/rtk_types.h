@@ -149,6 +149,68 @@ RTK_HD uint64_t rtk_revcomp(uint64_t x, int k) {
     return x >> (64 - 2 * k);
 }
 
+// ---- the map of BatchView::counters (rtk_seeds.h): every slot or range that any kernel or the host uses, with who writes it. The block is cleared at the start
+// of the seed stage and of the pass-2 phasing step (rtk_pipeline.inc) and copied back once at the end of the region stage. Slots outside a range are free.
+enum RtkCounterSlot {
+    RTK_CNT_WINDOWS = 0, RTK_CNT_PROBES_EXACT = 1, RTK_CNT_PROBES_INEXACT = 2, RTK_CNT_HITS_INEXACT = 3, RTK_CNT_REGIONS = 4, RTK_CNT_ITEMS = 5, // seed kernels -> rtk_stats
+    RTK_CNT_OVERFLOW = 6,           // seed kernels: a pool ran out (the host grows it and redoes the stage)
+    RTK_CNT_EXPAND = 7, RTK_CNT_COLOUR = 8, RTK_CNT_PATHBASE = 9, RTK_CNT_ALIGN = 10, RTK_CNT_CELLS = 11, // k_regions, k_regions_lanes -> rtk_stats
+    RTK_CNT_SLOTS_EXACT = 12, RTK_CNT_SLOTS_INEXACT = 13, // table slots read by the two scans -> rtk_stats
+    RTK_CNT_EVENTS_END = 14,        // (what the seed stage reads back after every attempt: [0, RTK_CNT_SEED_READBACK))
+    RTK_CNT_SEED_READBACK = 16,
+    RTK_CNT_CYC = 16,               // [8] k_regions wave cycles -> rtk_stats: colour, paths, consensus, total, myers, sets + path records, to_string, path quality
+    RTK_CNT_CYC_COLOUR = 16, RTK_CNT_CYC_PATHS = 17, RTK_CNT_CYC_CONSENSUS = 18, RTK_CNT_CYC_TOTAL = 19, RTK_CNT_CYC_MYERS = 20, RTK_CNT_CYC_SETS = 21, RTK_CNT_CYC_TOSTRING = 22, RTK_CNT_CYC_PATHQUAL = 23,
+    RTK_CNT_CYC_END = 24,
+    RTK_CNT_FINALIZE = 24,          // [7] k_finalize: wave cycles of its phases (trace)
+    RTK_CNT_FINALIZE_SLOWEST = 31,  // k_finalize: cycles of the slowest read (atomicMax; trace)
+    RTK_CNT_FINALIZE_END = 32,
+    RTK_CNT_WALK = 32,              // [6] k_regions, traceback walks: cycles, moves (both -> rtk_stats), reloads, scalar steps, calls, tail cycles (trace)
+    RTK_CNT_WALK_CYCLES = 32, RTK_CNT_WALK_MOVES = 33, RTK_CNT_WALK_RELOADS = 34, RTK_CNT_WALK_SCALAR = 35, RTK_CNT_WALK_CALLS = 36, RTK_CNT_WALK_TAIL = 37,
+    RTK_CNT_CYC_DFS = 38, RTK_CNT_CYC_COLOUR_OK = 39, // k_regions: DFS bookkeeping, of which colour checks (trace)
+    RTK_CNT_WALK_END = 40,
+    RTK_CNT_FINE = 40,              // [16] k_regions: RegionScratch::fine (RTK_FINE_*; trace)
+    RTK_CNT_FINE_END = 56,
+    RTK_CNT_HIST = 56,              // [32] k_regions: RegionScratch::hist, the size-class table (trace)
+    RTK_CNT_HIST_END = 88,
+    RTK_CNT_PHASE_TRACE = 59,       // [5] pass 2, k_phase_long: alignment cycles, then the Hirschberg driver's pass / split / leaf / total cycles (trace). INSIDE RTK_CNT_HIST
+    RTK_CNT_PHASE_TRACE_END = 64,
+    RTK_CNT_FINALIZE_SLOWEST_PHASES = 72, // [7] k_finalize: the phases of the slowest read (trace). INSIDE RTK_CNT_HIST
+    RTK_CNT_FINALIZE_SLOWEST_PHASES_END = 79,
+    RTK_CNT_PROF = 96,              // [48] k_regions of a -DRTK_PROF build: RegionScratch::prof (trace)
+    RTK_CNT_PROF_END = 144,
+    RTK_CNT_WAVE_TRACE = 144,       // [8] k_regions of a traced run: longest region, ~first start, last end, sum of lifetimes, waves, longest region again, its place, most regions on a wave
+    RTK_CNT_WAVE_TRACE_END = 152,
+    RTK_CNT_LANE_HANDED = 152, RTK_CNT_LANE_DONE = 153, // k_regions_lanes: regions handed on to the wave kernel / finished -> rtk_stats
+    RTK_CNT_LANE_END = 154,
+    RTK_CNT_LANE_PROF = 160,        // [24 = RL_NPROF] k_regions_lanes of a -DRTK_LANE_PROF build: lane cycles by slot (trace)
+    RTK_CNT_LANE_PROF2 = 184,       // [24] the same build: wave-time estimate by slot (trace)
+    RTK_CNT_LANE_PROF_END = 208,
+    RTK_CNT_PHASE_SKIPPED = 210,    // pass 2: reads whose whole-read alignment was skipped (rtk_phasing.h) -> rtk_stats
+    RTK_CNT_USED_END = RTK_CNT_PHASE_SKIPPED + 1,
+    RTK_CNT_TOTAL = (RTK_CNT_USED_END + 31) / 32 * 32 // words in the block: what is used, rounded up to 256 bytes (the tail is free)
+};
+static_assert(RTK_CNT_TOTAL == 224, "counter map: the size of the block changed (it is part of what the kernels and the host agree on)");
+// Two trace-only users sit INSIDE the size-class table today: RTK_CNT_PHASE_TRACE (written by the phasing step, which runs before the seed stage clears the block
+// -- so it is read back right there) and RTK_CNT_FINALIZE_SLOWEST_PHASES (written by k_finalize, read back by the seed stage; k_regions then adds its table on top).
+// Both only garble developer trace lines of the size-class table; renumbering them is a follow-up, because it changes device code. What reaches rtk_stats must
+// not share a slot with anything:
+constexpr bool rtk_cnt_apart(int a, int a_end, int b, int b_end) { return a_end <= b || b_end <= a; }
+static_assert(RTK_CNT_EVENTS_END <= RTK_CNT_CYC && RTK_CNT_CYC_END <= RTK_CNT_FINALIZE && RTK_CNT_FINALIZE_END <= RTK_CNT_WALK && RTK_CNT_WALK_END <= RTK_CNT_FINE, "counter map: the event, cycle, finalize and walk ranges overlap");
+static_assert(RTK_CNT_FINE_END <= RTK_CNT_HIST && RTK_CNT_HIST_END <= RTK_CNT_PROF && RTK_CNT_PROF_END <= RTK_CNT_WAVE_TRACE && RTK_CNT_WAVE_TRACE_END <= RTK_CNT_LANE_HANDED, "counter map: the trace ranges overlap");
+static_assert(RTK_CNT_LANE_END <= RTK_CNT_LANE_PROF && RTK_CNT_LANE_PROF2 - RTK_CNT_LANE_PROF == 24 && RTK_CNT_LANE_PROF_END <= RTK_CNT_PHASE_SKIPPED && RTK_CNT_PHASE_SKIPPED < RTK_CNT_TOTAL, "counter map: the lane ranges overlap");
+static_assert(rtk_cnt_apart(RTK_CNT_PHASE_TRACE, RTK_CNT_PHASE_TRACE_END, RTK_CNT_FINALIZE_SLOWEST_PHASES, RTK_CNT_FINALIZE_SLOWEST_PHASES_END), "counter map: the two guests of the size-class table overlap");
+static_assert(RTK_CNT_HIST <= RTK_CNT_PHASE_TRACE && RTK_CNT_FINALIZE_SLOWEST_PHASES_END <= RTK_CNT_HIST_END, "counter map: the guests of the size-class table left it (update the comment above)");
+
+// indices of RegionScratch::cnt (rtk_region.h): a wave's own accumulators, added to the block when its kernel ends
+enum RtkRegionCnt { RTK_RC_EXPAND = 0, RTK_RC_COLOUR = 1, RTK_RC_PATHBASE = 2, RTK_RC_ALIGN = 3, RTK_RC_CELLS = 4, // -> RTK_CNT_EXPAND .. RTK_CNT_CELLS
+    RTK_RC_CYC_COLOUR = 5, RTK_RC_CYC_PATHS = 6, RTK_RC_CYC_CONSENSUS = 7, RTK_RC_CYC_TOTAL = 8, RTK_RC_CYC_MYERS = 9, RTK_RC_CYC_SETS = 10, // [5, 11) -> RTK_CNT_CYC + 0 .. 5
+    RTK_RC_CYC_PATHREC = 11 /* -> RTK_CNT_CYC_SETS as well */, RTK_RC_CYC_TOSTRING = 12, RTK_RC_CYC_PATHQUAL = 13, RTK_RC_CYC_DFS = 14, RTK_RC_CYC_COLOUR_OK = 15, RTK_RC_N = 16 };
+// indices of RegionScratch::fine -> RTK_CNT_FINE + i (their names in the trace: region_trace_report, rtk_pipeline_run.inc)
+enum RtkRegionFine { RTK_FINE_COL_GENERAL = 0 /* [7] the laps of rtk_choose_colors_general: 1 .. 4 are ALSO the laps of rtk_fix_ambiguity (trace only) */, RTK_FINE_COL_UNIONS = 0, RTK_FINE_FA_ALIGN = 1, RTK_FINE_FA_WALK = 2, RTK_FINE_FA_LINKED = 3, RTK_FINE_FA_APPLY = 4, RTK_FINE_COL_S_VECTORS = 5, RTK_FINE_COL_S_SELECT = 6,
+    RTK_FINE_SIDE_LISTS = 7, RTK_FINE_TRIM = 8, RTK_FINE_FIX_AMBIGUITY = 9, RTK_FINE_FA_CALLS = 10, RTK_FINE_FA_ALL_CONFIDENT = 11, RTK_FINE_COL_S_CYCLES = 12, RTK_FINE_COL_B_CYCLES = 13,
+    RTK_FINE_COL_S_CALLS = 14, RTK_FINE_COL_B_CALLS = 15, RTK_FINE_N = 16 };
+static_assert(static_cast<int>(RTK_RC_N) == static_cast<int>(RTK_FINE_N), "region_scratch_carve clears cnt and fine in one loop");
+
 // Unitig mapping (restates the fields of Bifrost's const_UnitigMap the hot path reads).
 struct UMap {
     uint32_t unitig; // RTK_NONE32 == isEmpty

@@ -55,35 +55,16 @@ inline uint64_t rtk_brev64(uint64_t x) { uint64_t r = 0; for (int i = 0; i < 64;
 #define RTK_FN __device__ __noinline__ // large device functions are real calls: keeps hipcc compile time and code size bounded
 // The path search (extractSemiWeakPaths -> explorePathsBFS -> exploreSubGraph) is compiled into its caller: each of these programs
 // has ONE call site, and a call between two of them costs tens of 64-lane stack stores and reloads (register saves, by-reference
-// arguments) per region / hop / BFS step: k_regions 40.8 -> 38.5 ms per 64 Mb. -DRTK_SEARCH_CALLS restores the calls (A/B).
-#ifdef RTK_SEARCH_CALLS
-#define RTK_FN_SEARCH RTK_FN
-#else
+// arguments) per region / hop / BFS step: k_regions 40.8 -> 38.5 ms per 64 Mb (measured against a build that kept the calls; the
+// opposite builds, with the leaves, the region program or the driver inlined, lost: DESIGN_HISTORY.md).
 #define RTK_FN_SEARCH __device__ __forceinline__
-#endif
-#ifdef RTK_INLINE_LEAVES
-#define RTK_FN_LEAF __device__ __forceinline__
-#else
 #define RTK_FN_LEAF RTK_FN
-#endif
-#ifdef RTK_INLINE_REGION
-#define RTK_FN_REGION __device__ __forceinline__
-#else
 #define RTK_FN_REGION RTK_FN
-#endif
-#ifdef RTK_INLINE_DRIVER
-#define RTK_FN_DRIVER __device__ __forceinline__
-#else
 #define RTK_FN_DRIVER RTK_FN
-#endif
 // Thin wrappers and small leaves on the hot path (alignment entry, path scoring, path extension, colour memo, lane copies / fills).
 // A real call costs the callee-saved spills of the AMDGPU calling convention (one private-memory store and load of 64 lanes per
-// saved register, on every call): these are inlined; -DRTK_HOT_CALLS turns them back into calls for A/B measurements.
-#ifdef RTK_HOT_CALLS
-#define RTK_FN_HOT RTK_FN
-#else
+// saved register, on every call): these are inlined (a build that kept them as calls was slower).
 #define RTK_FN_HOT RTK_DEV
-#endif
 #define RTK_WAVE 64
 __device__ __forceinline__ int rtk_lane() { return static_cast<int>(threadIdx.x) & 63; }
 __device__ __forceinline__ uint64_t rtk_ballot(bool p) { return __ballot(p ? 1 : 0); }
@@ -108,11 +89,7 @@ __device__ __forceinline__ int rtk_popc(uint64_t x) { return __popcll(x); }
 __device__ __forceinline__ int rtk_ffs(uint64_t x) { return __ffsll(static_cast<unsigned long long>(x)); }
 template <class T> __device__ __forceinline__ T rtk_atomic_add_raw(T* p, T v) { return atomicAdd(p, v); }
 __device__ __forceinline__ uint32_t rtk_atomic_or(uint32_t* p, uint32_t v) { return atomicOr(p, v); }
-#ifdef RTK_NO_CLOCK // A/B build: what the cycle counters of the wave programs cost (measured in round 4: nothing, 30.93 against 30.90 ms)
-__device__ __forceinline__ unsigned long long rtk_clock() { return 0ull; }
-#else
-__device__ __forceinline__ unsigned long long rtk_clock() { return static_cast<unsigned long long>(clock64()); }
-#endif
+__device__ __forceinline__ unsigned long long rtk_clock() { return static_cast<unsigned long long>(clock64()); } // (a build without the cycle counters was no faster: 30.93 against 30.90 ms, round 4)
 __device__ __forceinline__ uint64_t rtk_brev64(uint64_t x) { return __builtin_bitreverse64(x); }
 
 #endif
