@@ -101,6 +101,11 @@ typedef struct rtk_stats {
      * (the walk over the CIGAR then returns the corrected read as it is, src/Graph.cpp:975-1069) */
     double ms_phase;
     uint64_t n_phase_skipped;
+    /* revision 7: routes of the region program's trims and consensus calls. A trim is read off the last column of one NW sweep of (corrected, raw), stored for
+     * the forward strand of a gap region (n_trim_stored) or not (n_trim_column), or made by the SHW distance call (n_trim_fallback: a raw byte other than
+     * A C G T, a corrected string above 4096 characters or an empty one). A consensus call takes the alignment of the forward strand's string from the stored
+     * sweep of its trim (n_consensus_resumed) or sweeps it anew (n_consensus_swept). */
+    uint64_t n_trim_stored, n_trim_column, n_trim_fallback, n_consensus_resumed, n_consensus_swept;
 } rtk_stats;
 
 /* dbg.read(G.fasta.gz) + readGraphData(G.rtsk) (reference: src/Ratatosk.cpp:1087-1089; src/Graph.cpp:722-784).
@@ -235,6 +240,19 @@ int rtk_myers_batch_waves(uint32_t n, const char* const* query, const uint32_t* 
                           const int32_t* k, const int32_t* mode, int want_path, int use_iupac,
                           int32_t* dist, int32_t* n_loc, int32_t* end_locs, uint32_t cap_locs, char* cigar, uint32_t cap_cigar, int waves);
 
+/* Test-only modes of rtk_myers_batch (revision 7; one wave per problem, not rtk_myers_batch_waves / _lanes): the routes by which the region program's trim
+ * and consensus share one sweep (csrc/hip/rtk_myers.h, rtk_myers_shw_by_column; csrc/hip/rtk_region.h, rtk_trim_by_column).
+ *   RTK_MYERS_MODE_SHW_BY_COLUMN: k < 0. The SHW distance of (query, target), read off the last column of ONE NW sweep of (target, query); n_loc = the number
+ *     of end locations, of which end_locs holds the first (slot 0) and the last (slot n_loc - 1) only: the route does not list the others. No path.
+ *   RTK_MYERS_MODE_NW_PREFIX: 0 <= k <= qlen. The NW distance and, with want_path, the path of (query[0, k), target), walked from row k of the stored NW sweep of
+ *     the WHOLE query; end_locs[0] = tlen - 1.
+ * A problem the route does not take (a target byte other than A C G T -- the sweep's target: the query in mode 3 --, more than 4096 characters in the swept
+ * query, a table or move list too big for the in-memory traceback, an empty string) is answered by the calls the route replaces. How the calling thread's last
+ * rtk_myers_batch call split its problems of these modes: rtk_myers_column_last_routes (a route that took nothing would pass on the fallback's results). */
+#define RTK_MYERS_MODE_SHW_BY_COLUMN 3
+#define RTK_MYERS_MODE_NW_PREFIX 4
+void rtk_myers_column_last_routes(uint64_t* column_route, uint64_t* fallback);
+
 /* rtk_myers_batch with ONE PROBLEM PER LANE: queries of up to 512 characters against targets of up to 2048 over A, C, G, T, N are computed column by column in a
  * lane's registers, 64 problems per wavefront (csrc/hip/rtk_myers_lane.h); with want_path the lane keeps the delta vectors of its columns (up to 4096
  * word-columns) and walks them back. What does not fit that takes the wave route of rtk_myers_batch. Same results
@@ -276,8 +294,9 @@ void rtk_free(void* p);
 void rtk_free_many(void** p, uint32_t n);
 const char* rtk_last_error(void);
 const char* rtk_version(void);
-/* Interface revision, raised whenever a struct of this header grows or a default changes (5: rtk_opts.struct_size, rtk_stats lane fields, a2_exclusive default 1). */
-#define RTK_API_REVISION 6
+/* Interface revision, raised whenever a struct of this header grows or a default changes (5: rtk_opts.struct_size, rtk_stats lane fields, a2_exclusive default 1;
+ * 7: rtk_stats route fields n_trim_* / n_consensus_*, the test-only rtk_myers_batch modes 3 and 4, rtk_myers_column_last_routes). */
+#define RTK_API_REVISION 7
 int rtk_api_revision(void);
 
 #ifdef __cplusplus

@@ -35,7 +35,8 @@ class RtkStats(C.Structure):
                [(n, C.c_uint64) for n in ("n_windows", "n_probes_exact", "n_probes_inexact", "n_hits_inexact", "n_regions", "n_region_items", "n_arena_overflow",
                                          "n_expand", "n_colour_elem", "n_path_base", "n_align", "n_align_cells", "in_bases", "out_bases",
                                          "cyc_colour", "cyc_paths", "cyc_consensus", "cyc_total", "cyc_myers", "cyc_sets", "cyc_tostring", "cyc_pathqual", "n_slots_exact", "n_slots_inexact", "cyc_walk", "n_moves")] + \
-               [("ms_lanes", C.c_double), ("n_lane_regions", C.c_uint64), ("n_lane_handed", C.c_uint64), ("ms_phase", C.c_double), ("n_phase_skipped", C.c_uint64)]
+               [("ms_lanes", C.c_double), ("n_lane_regions", C.c_uint64), ("n_lane_handed", C.c_uint64), ("ms_phase", C.c_double), ("n_phase_skipped", C.c_uint64)] + \
+               [(n, C.c_uint64) for n in ("n_trim_stored", "n_trim_column", "n_trim_fallback", "n_consensus_resumed", "n_consensus_swept")]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -293,6 +294,18 @@ def myers_batch(queries, targets, ks=None, modes=None, want_path=False, use_iupa
             c = cig.raw[i * cap_cig:(i + 1) * cap_cig].split(b"\0", 1)[0].decode()
         out.append((dist[i], el, c))
     return out
+
+
+MODE_SHW_BY_COLUMN, MODE_NW_PREFIX = 3, 4  # test-only modes of myers_batch (include/ratatosk_hip.h)
+
+
+def myers_column_last_routes(lib_path=None):
+    """(problems taken by the column route, problems answered by the calls it replaces) of this thread's last myers_batch call in modes 3 / 4."""
+    L = load_library(lib_path)
+    a, b = C.c_uint64(), C.c_uint64()
+    L.rtk_myers_column_last_routes.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]; L.rtk_myers_column_last_routes.restype = None
+    L.rtk_myers_column_last_routes(C.byref(a), C.byref(b))
+    return a.value, b.value
 
 
 def myers_lanes_last_routes(lib_path=None):

@@ -500,11 +500,48 @@ extern "C" int rtk_lookup_exact(rtk_graph* g, const char* seq, uint32_t len, int
 }
 
 // ------------------------------------------------------------------------------------------------ K6/K7: Myers batch
+// the test-only modes (include/ratatosk_hip.h): the trim's SHW read off the last column of an NW sweep of (target, query), and the consensus's NW path walked
+// from row k of the stored sweep of the whole query (rtk_trim_by_column). status: overflow | route << 16 (1: the column route, 2: the calls it replaces).
+RTK_FN void rtk_myers_column_item(const MyersScratch& sc, const MyersProb& p, uint32_t i, const char* q, const char* t, int use_iupac, int32_t* dist, int32_t* n_loc, int32_t* end_locs,
+                                  uint32_t cap_locs, uint8_t* moves_out, uint32_t* n_moves_out, uint32_t cap_moves, uint32_t* status) {
+    const int m = static_cast<int>(p.qlen), n = static_cast<int>(p.tlen); const bool iupac = use_iupac != 0;
+    uint32_t route = 2, nm = 0;
+    MyersResult r;
+    if (p.mode == RTK_MYERS_MODE_SHW_BY_COLUMN) {
+        if (rtk_myers_shw_by_column(sc, t, n, q, m, iupac, 0, 0, &r, nullptr)) route = 1;
+        else r = rtk_myers_distance(sc, q, m, t, n, -1, RTK_MODE_SHW, iupac);
+        if (cap_locs > 0) end_locs[static_cast<uint64_t>(i) * cap_locs] = r.first; // the first and the last location only: the route does not list the others
+        if (r.nloc > 1 && static_cast<uint32_t>(r.nloc) <= cap_locs) end_locs[static_cast<uint64_t>(i) * cap_locs + (r.nloc - 1)] = r.last;
+        n_loc[i] = r.nloc;
+    } else { // RTK_MYERS_MODE_NW_PREFIX: (q[0, k), t)
+        const int k = p.k;
+        int at = 0;
+        if (k > 0 && rtk_myers_shw_by_column(sc, q, m, t, n, iupac, 1, k, &r, &at)) {
+            const long long W = (k + 63) >> 6;
+            if (static_cast<uint32_t>(k) <= sc.r_cap && static_cast<uint32_t>(k + n) <= sc.mv_cap && (2LL * 8 + 4) * W * n + 8LL * n < 1024 * 1024) {
+                rtk_myers_walk(sc, k, n, n, at, &nm);
+                r.dist = at; route = 1;
+            }
+        }
+        if (route != 1) {
+            if (k > 0 && n > 0) r = rtk_myers_path(sc, q, k, t, n, RTK_MODE_NW, iupac, &nm);
+            else r = rtk_myers_distance(sc, q, k, t, n, -1, RTK_MODE_NW, iupac);
+        }
+        if (cap_locs > 0) end_locs[static_cast<uint64_t>(i) * cap_locs] = n - 1;
+        n_loc[i] = 1;
+    }
+    dist[i] = r.dist;
+    if (nm <= cap_moves) rtk_wcopy(moves_out + static_cast<uint64_t>(i) * cap_moves, sc.moves, nm);
+    n_moves_out[i] = nm;
+    status[i] = *sc.overflow | (route << 16);
+}
+
 // one problem of the batch on this wave (shared with the multi-wave variant of the kernel, rtk_phase_long.hip)
 RTK_FN void rtk_myers_batch_item(const MyersScratch& sc, const MyersProb& p, uint32_t i, const char* pool, int want_path, int use_iupac, int32_t* dist, int32_t* n_loc, int32_t* end_locs, uint32_t cap_locs,
                                  uint8_t* moves_out, uint32_t* n_moves_out, uint32_t cap_moves, uint32_t* status) {
     *sc.overflow = 0;
     const char* q = pool + p.q_off; const char* t = pool + p.t_off;
+    if (p.mode >= RTK_MYERS_MODE_SHW_BY_COLUMN) { rtk_myers_column_item(sc, p, i, q, t, use_iupac, dist, n_loc, end_locs, cap_locs, moves_out, n_moves_out, cap_moves, status); return; }
     const MyersResult r = rtk_myers_distance(sc, q, static_cast<int>(p.qlen), t, static_cast<int>(p.tlen), p.k, p.mode, use_iupac != 0, cap_locs ? end_locs + static_cast<uint64_t>(i) * cap_locs : nullptr, static_cast<int>(cap_locs)); // cap_locs == 0: no list of end locations (the route the region program takes)
     dist[i] = r.dist; n_loc[i] = r.nloc;
     uint32_t nm = 0;
@@ -539,6 +576,8 @@ RTK_GLOBAL void k_myers_batch(const MyersProb* probs, uint32_t n, const char* po
 void rtk_launch_myers_batch_waves(int grid, int waves, const MyersProb* probs, uint32_t n, const char* pool, int want_path, int use_iupac, char* scratch, uint64_t scratch_stride, const ScratchCfg& cfg,
                                   int32_t* dist, int32_t* n_loc, int32_t* end_locs, uint32_t cap_locs, uint8_t* moves_out, uint32_t* n_moves_out, uint32_t cap_moves, uint32_t* status, unsigned long long* prof);
 #endif
+static thread_local uint64_t g_col_routes[2] = {0, 0}; // problems of modes 3 and 4 of the calling thread's last rtk_myers_batch call: column route, fallback
+extern "C" void rtk_myers_column_last_routes(uint64_t* column_route, uint64_t* fallback) { if (column_route) *column_route = g_col_routes[0]; if (fallback) *fallback = g_col_routes[1]; }
 extern "C" int rtk_myers_batch(uint32_t n, const char* const* query, const uint32_t* qlen, const char* const* target, const uint32_t* tlen,
                                const int32_t* k, const int32_t* mode, int want_path, int use_iupac,
                                int32_t* dist, int32_t* n_loc, int32_t* end_locs, uint32_t cap_locs, char* cigar, uint32_t cap_cigar) {
@@ -560,8 +599,12 @@ extern "C" int rtk_myers_batch_waves(uint32_t n, const char* const* query, const
             probs[i].t_off = pool.size(); pool.append(target[i], tlen[i]);
             probs[i].qlen = qlen[i]; probs[i].tlen = tlen[i]; probs[i].k = k[i]; probs[i].mode = mode[i];
             if (mode[i] == RTK_MODE_HW && want_path) return rtk_fail(RTK_ERR_UNSUPPORTED, "rtk_myers_batch: HW path alignment is not on the hot path");
+            if (mode[i] < 0 || mode[i] > RTK_MYERS_MODE_NW_PREFIX || (mode[i] > RTK_MODE_HW && waves > 1)) return rtk_fail(RTK_ERR_ARG, "rtk_myers_batch: unknown mode (the test-only modes 3 and 4 run on one wave)");
+            if ((mode[i] == RTK_MYERS_MODE_SHW_BY_COLUMN && k[i] >= 0) || (mode[i] == RTK_MYERS_MODE_NW_PREFIX && (k[i] < 0 || static_cast<uint32_t>(k[i]) > qlen[i])))
+                return rtk_fail(RTK_ERR_ARG, "rtk_myers_batch: mode 3 takes k < 0, mode 4 a query row 0 <= k <= qlen");
             max_q = std::max(max_q, qlen[i]); max_t = std::max(max_t, tlen[i]);
         }
+        for (uint32_t i = 0; i < n; ++i) if (mode[i] > RTK_MODE_HW) { max_q = max_t = std::max(max_q, max_t); break; } // the column route sweeps (target, query) in mode 3
         ScratchCfg cfg;
         cfg.w_cap = (max_q + 63) / 64 + 1; cfg.t_cap = max_t + 64; cfg.r_cap = max_q + 64; cfg.mv_cap = max_q + max_t + 64;
         cfg.tb_cap_words = std::max<uint64_t>(4ull * 52429 + 64, 4ull * cfg.w_cap + 64);
@@ -592,7 +635,11 @@ extern "C" int rtk_myers_batch_waves(uint32_t n, const char* const* query, const
         rtk_d2h(dist, ddist, 4ull * n); rtk_d2h(n_loc, dnloc, 4ull * n); if (cap_locs) rtk_d2h(end_locs, dlocs, 4ull * n * cap_locs);
         rtk_d2h(st.data(), dst, 4ull * n); rtk_d2h(nm.data(), dnm, 4ull * n);
         int rc = RTK_OK;
-        for (uint32_t i = 0; i < n; ++i) if (st[i]) rc = rtk_fail(RTK_ERR_DEVICE, "rtk_myers_batch: scratch capacity exceeded on device");
+        g_col_routes[0] = 0; g_col_routes[1] = 0;
+        for (uint32_t i = 0; i < n; ++i) {
+            if (st[i] & 0xFFFFu) rc = rtk_fail(RTK_ERR_DEVICE, "rtk_myers_batch: scratch capacity exceeded on device");
+            if (mode[i] > RTK_MODE_HW) ++g_col_routes[(st[i] >> 16) == 1u ? 0 : 1];
+        }
         if (want_path && cigar && rc == RTK_OK) {
             std::vector<uint8_t> mv(static_cast<size_t>(n) * cap_moves);
             rtk_d2h(mv.data(), dmoves, mv.size());
@@ -656,6 +703,7 @@ extern "C" int rtk_myers_batch_lanes(uint32_t n, const char* const* query, const
             probs[i].t_off = pool.size(); pool.append(target[i], tlen[i]);
             probs[i].qlen = qlen[i]; probs[i].tlen = tlen[i]; probs[i].k = k[i]; probs[i].mode = mode[i];
             if (mode[i] == RTK_MODE_HW && want_path) return rtk_fail(RTK_ERR_UNSUPPORTED, "rtk_myers_batch_lanes: HW path alignment is not on the hot path");
+            if (mode[i] < 0 || mode[i] > RTK_MODE_HW) return rtk_fail(RTK_ERR_ARG, "rtk_myers_batch_lanes: unknown mode (the test-only modes 3 and 4 are rtk_myers_batch's)");
             max_q = std::max(max_q, qlen[i]); max_t = std::max(max_t, tlen[i]);
         }
         // the path table holds the word-columns the biggest problem of the call can ask for (words x (first end location + 1 <= tlen), never above the route's limit)

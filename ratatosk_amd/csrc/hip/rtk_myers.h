@@ -266,10 +266,36 @@ __device__ __forceinline__ void rtk_myers_sweep_acgt(int m, int n, int W, int to
 // Self-contained fast path for forward sequences with <= 64 query words: profile words built from 8 wide loads per lane,
 // branch-free sweep, running minimum kept in scalar registers (no per-column score array), A/C/G/T check folded into the
 // per-64-column target load. Returns plain == false (and no result) when the target holds another character.
-struct SweepStat { int final_score, best, first, last, cnt; bool plain; };
-template <int STORE>
-__device__ __forceinline__ SweepStat rtk_myers_fast(const char* __restrict__ qp, int m, const char* __restrict__ tp, int n, int top_h, bool iupac, uint64_t* __restrict__ tb) {
-    SweepStat st; st.final_score = m; st.best = 0x7fffffff; st.first = -1; st.last = -1; st.cnt = 0; st.plain = true;
+struct SweepStat { int final_score, best, first, last, cnt; bool plain; int at_score; };
+// The LAST COLUMN of a finished sweep, from the vertical deltas its words hold once the pipeline has drained (lane w: query rows [B w, B w + B) in a word
+// of B = 32 or 64 bits): D[i + 1][n] = n + the deltas of rows 0 .. i, a popcount prefix over the lanes as in rtk_myers_column. Reduced to its minimum
+// over the query rows, the first and the last row that hold it and their number (st.best / first / last / cnt), and st.at_score = D[at][n] (0 <= at <= m).
+__device__ __forceinline__ void rtk_last_column_stat(uint64_t pv, uint64_t mv, int B, int m, int n, int at, SweepStat& st) {
+    const int lane = rtk_lane();
+    const int row0 = B * lane;
+    int rows = m - row0; rows = rows < 0 ? 0 : (rows > B ? B : rows);
+    const uint64_t mask = rows >= 64 ? ~0ull : ((1ull << rows) - 1ull);
+    pv &= mask; mv &= mask;
+    int total;
+    int v = n + rtk_wave_excl_scan(rtk_popc(pv) - rtk_popc(mv), &total);
+    int best = 0x7fffffff, first = -1, last = -1, cnt = 0, atv = 0;
+    for (int b = 0; b < rows; ++b) {
+        v += static_cast<int>((pv >> b) & 1ull) - static_cast<int>((mv >> b) & 1ull);
+        const bool lt = v < best, eq = v == best;
+        best = lt ? v : best; first = lt ? row0 + b : first; last = (lt || eq) ? row0 + b : last; cnt = lt ? 1 : (cnt + (eq ? 1 : 0));
+        atv = (row0 + b + 1 == at) ? v : atv;
+    }
+    int gb = best;
+    for (int o = 32; o > 0; o >>= 1) { const int x = __shfl_xor(gb, o, 64); gb = x < gb ? x : gb; }
+    const uint64_t has = rtk_ballot(cnt > 0 && best == gb); // lanes in row order: the first row is in the lowest of them, the last in the highest
+    st.best = gb; st.first = __shfl(first, rtk_ffs(has) - 1, 64); st.last = __shfl(last, 63 - __builtin_clzll(has), 64);
+    st.cnt = rtk_wave_sum((cnt > 0 && best == gb) ? cnt : 0);
+    st.at_score = (at <= 0) ? n : __shfl(atv, (at - 1) / B, 64);
+}
+// COLUMN = 1: no last-row tracking; the last column is read once the sweep is done (rtk_last_column_stat, row `at`)
+template <int STORE, int COLUMN = 0>
+__device__ __forceinline__ SweepStat rtk_myers_fast(const char* __restrict__ qp, int m, const char* __restrict__ tp, int n, int top_h, bool iupac, uint64_t* __restrict__ tb, int at = 0) {
+    SweepStat st; st.final_score = m; st.best = 0x7fffffff; st.first = -1; st.last = -1; st.cnt = 0; st.plain = true; st.at_score = 0;
     const int lane = rtk_lane();
     const int W = (m + 63) >> 6, last_bit = (m - 1) & 63;
     const int w = lane;
@@ -320,7 +346,7 @@ __device__ __forceinline__ SweepStat rtk_myers_fast(const char* __restrict__ qp,
             score += (active && lane == W - 1) ? hout : 0;
             tc_prev = tc;
             const int tcol = s - (W - 1);
-            if (tcol >= 0) { // wave-uniform: last-row score of column tcol, tracked in scalar registers
+            if (!COLUMN && tcol >= 0) { // wave-uniform: last-row score of column tcol, tracked in scalar registers
                 const int sv = __builtin_amdgcn_readlane(score, W - 1);
                 fin = sv;
                 if (sv < best) { best = sv; first = tcol; last = tcol; cnt = 1; }
@@ -328,6 +354,7 @@ __device__ __forceinline__ SweepStat rtk_myers_fast(const char* __restrict__ qp,
             }
         }
     }
+    if (COLUMN) { rtk_last_column_stat(has_word ? Pv : 0ull, has_word ? Mv : 0ull, 64, m, n, at, st); return st; }
     st.final_score = fin; st.best = best; st.first = first; st.last = last; st.cnt = cnt;
     return st;
 }
@@ -351,10 +378,11 @@ RTK_DEV int rtk_myers_step32(uint32_t& Pv, uint32_t& Mv, uint32_t Eq, int hin, i
     return hout;
 }
 
-// TRACK = 0: only the final score is wanted (NW); 1: minimum of the last row with its first / last position and count (SHW, HW).
+// TRACK = 0: only the final score is wanted (NW); 1: minimum of the last row with its first / last position and count (SHW, HW);
+// 2: the same of the last COLUMN, read once the sweep is done (rtk_last_column_stat, row `at`).
 template <int STORE, int TRACK>
-__device__ __forceinline__ SweepStat rtk_myers_fast32(const char* __restrict__ qp, int m, const char* __restrict__ tp, int n, int top_h, bool iupac, uint64_t* __restrict__ tb) {
-    SweepStat st; st.final_score = m; st.best = 0x7fffffff; st.first = -1; st.last = -1; st.cnt = 0; st.plain = true;
+__device__ __forceinline__ SweepStat rtk_myers_fast32(const char* __restrict__ qp, int m, const char* __restrict__ tp, int n, int top_h, bool iupac, uint64_t* __restrict__ tb, int at = 0) {
+    SweepStat st; st.final_score = m; st.best = 0x7fffffff; st.first = -1; st.last = -1; st.cnt = 0; st.plain = true; st.at_score = 0;
     const int lane = rtk_lane();
     const int W = (m + 31) >> 5, W64 = (m + 63) >> 6, last_bit = (m - 1) & 31;
     const int w = lane;
@@ -426,7 +454,7 @@ __device__ __forceinline__ SweepStat rtk_myers_fast32(const char* __restrict__ q
             Pv = nPv; Mv = nMv; hout_prev = hout; score += hout;                                                                             \
         }                                                                                                                                    \
         m1_prev = m1; m2_prev = m2;                                                                                                          \
-        if (TRACK) {                                                                                                                         \
+        if (TRACK == 1) {                                                                                                                    \
             const int tcol = s - (W - 1);                                                                                                    \
             if (!(MASKED) || tcol >= 0) { /* every lane follows the minimum of ITS word's last row (selects, no branches); lane W - 1's is the one read at the end */ \
                 const bool lt_ = score < vbest, eq_ = score == vbest;                                                                        \
@@ -452,15 +480,16 @@ __device__ __forceinline__ SweepStat rtk_myers_fast32(const char* __restrict__ q
     }
 #undef RTK_STEP32
     st.final_score = __builtin_amdgcn_readlane(score, W - 1);
-    if (TRACK) { st.best = __builtin_amdgcn_readlane(vbest, W - 1); st.first = __builtin_amdgcn_readlane(vfirst, W - 1); st.last = __builtin_amdgcn_readlane(vlast, W - 1); st.cnt = __builtin_amdgcn_readlane(vcnt, W - 1); }
+    if (TRACK == 2) rtk_last_column_stat(has_word ? Pv : 0u, has_word ? Mv : 0u, 32, m, n, at, st);
+    if (TRACK == 1) { st.best = __builtin_amdgcn_readlane(vbest, W - 1); st.first = __builtin_amdgcn_readlane(vfirst, W - 1); st.last = __builtin_amdgcn_readlane(vlast, W - 1); st.cnt = __builtin_amdgcn_readlane(vcnt, W - 1); }
     return st;
 }
 
 // dispatcher: 32-bit words up to 2048 query characters, 64-bit words beyond
 template <int STORE, int TRACK>
-__device__ __forceinline__ SweepStat rtk_myers_fast_any(const char* __restrict__ qp, int m, const char* __restrict__ tp, int n, int top_h, bool iupac, uint64_t* __restrict__ tb) {
-    if (m <= 2048) return rtk_myers_fast32<STORE, TRACK>(qp, m, tp, n, top_h, iupac, tb);
-    return rtk_myers_fast<STORE>(qp, m, tp, n, top_h, iupac, tb);
+__device__ __forceinline__ SweepStat rtk_myers_fast_any(const char* __restrict__ qp, int m, const char* __restrict__ tp, int n, int top_h, bool iupac, uint64_t* __restrict__ tb, int at = 0) {
+    if (m <= 2048) return rtk_myers_fast32<STORE, TRACK>(qp, m, tp, n, top_h, iupac, tb, at);
+    return rtk_myers_fast<STORE, TRACK == 2 ? 1 : 0>(qp, m, tp, n, top_h, iupac, tb, at);
 }
 #endif
 
@@ -1145,6 +1174,52 @@ RTK_FN MyersResult rtk_myers_distance(const MyersScratch& sc_, const char* q_, i
     rtk_sync();
     r.first = first; r.last = last; r.nloc = cnt;
     return r;
+}
+
+// SHW by column: edlibAlign(raw, corr, SHW) with k = -1 -- the MyersResult rtk_myers_distance returns, end locations and the score-|raw| location
+// -1 included -- read off the LAST COLUMN of one NW sweep of (corr, raw). Equality is symmetric (rtk_eq_classes), so the SHW matrix of (raw, corr)
+// is the transpose of NW(corr, raw) and its score at end j is D[j + 1][|raw|]. Row i of the swept table only depends on rows <= i, so a stored
+// sweep (store != 0, table in sc.tb, ncols = |raw|) also holds NW(corr[0, r), raw) for every r <= |corr|: rtk_myers_walk(sc, r, |raw|, |raw|,
+// D[r][|raw|], ...) walks it. *at_score (optional) = D[at][|raw|]. The step is the plain NW step, without the last-row tracking of the
+// distance call. Returns false, with no result, where the route does not apply: an empty string, |corr| > 4096, a raw byte other than
+// A/C/G/T (the sweep's target), the capacities the distance call checks (the caller makes that call: it reports the overflow), and for a
+// stored sweep those of the table.
+RTK_FN bool rtk_myers_shw_by_column(const MyersScratch& sc_, const char* corr_, int m_, const char* raw_, int n_, bool iupac_, int store_, int at_, MyersResult* out_, int* at_score_) {
+    const MyersScratch& sc = *rtk_u(&sc_); RTK_ASSUME_LDS(&sc); const char* corr = rtk_u(corr_); const char* raw = rtk_u(raw_);
+    const int m = rtk_u(m_), n = rtk_u(n_), store = rtk_u(store_), at = rtk_u(at_); const bool iupac = rtk_u(iupac_);
+    MyersResult* out = rtk_u(out_); int* at_score = rtk_u(at_score_);
+    const long long W = (m + 63) >> 6;
+    if (m <= 0 || n <= 0 || m > 4096 || static_cast<uint32_t>((n + 63) >> 6) > sc.w_cap || static_cast<uint32_t>(m) > sc.t_cap) return false;
+    if (static_cast<uint32_t>(W) > sc.w_cap || static_cast<uint32_t>(n) > sc.t_cap) return false;
+    if (store && static_cast<uint64_t>(4 * W * n) > sc.tb_cap_words) return false;
+    if (store) { MyersScratch& msc = const_cast<MyersScratch&>(sc); msc.tb_gen = rtk_ld(&msc.tb_gen) + 1u; } // the table is written
+    int best, first, last, cnt, atv;
+#ifdef RTK_SIM
+    for (int j = 0; j < n; ++j) { const char ch = raw[j]; if (!(ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T')) return false; } // the device sweep's own test
+    uint64_t* fin = new uint64_t[2 * W];
+    rtk_myers_pass(sc, rtk_seq(corr, m), rtk_seq(raw, n), 1, iupac, store, fin, fin + W);
+    best = 0x7fffffff; first = -1; last = -1; cnt = 0; atv = n;
+    for (int i = 0, v = n; i < m; ++i) {
+        v += static_cast<int>((fin[i >> 6] >> (i & 63)) & 1ull) - static_cast<int>((fin[W + (i >> 6)] >> (i & 63)) & 1ull);
+        if (v < best) { best = v; first = last = i; cnt = 1; } else if (v == best) { last = i; ++cnt; }
+        if (i + 1 == at) atv = v;
+    }
+    delete[] fin;
+#else
+    const SweepStat st = store ? rtk_myers_fast_any<1, 2>(corr, m, raw, n, 1, iupac, rtk_ld(&sc.tb), at) : rtk_myers_fast_any<0, 2>(corr, m, raw, n, 1, iupac, nullptr, at);
+    rtk_sync();
+    if (!st.plain) return false;
+    best = st.best; first = st.first; last = st.last; cnt = st.cnt; atv = st.at_score;
+#endif
+    // the bookkeeping of rtk_myers_distance (SHW) with the query of that call, raw: location -1 has score |raw| when |raw| % 64 != 0
+    MyersResult r; const int colbest = best; const bool pseudo = (n & 63) != 0;
+    if (pseudo && n < best) best = n;
+    r.dist = best;
+    if (pseudo && n == best) { r.first = -1; r.last = (colbest == best) ? last : -1; r.nloc = 1 + ((colbest == best) ? cnt : 0); }
+    else { r.first = first; r.last = last; r.nloc = cnt; }
+    *out = r;
+    if (at_score) *at_score = atv;
+    return true;
 }
 
 // Canonical NW traceback over the stored table, preferring up (insert) > left (delete) > diagonal

@@ -67,7 +67,9 @@ struct ResCorr { char* seq; char* qual; uint32_t seq_len, qual_len; uint64_t* bm
 // header (LDS in the kernels) instead of the wave's stack, where every wave-uniform word is a 256-byte row per store and per load
 // state of one rtk_correct_region call that its three parts hand on (side lists + colours | path search | assembly + trim)
 struct RegionCall { const char* s_read; const char* q_read; uint64_t complete; UMap um1, um2; uint32_t s_len, p1, p2, first_pos, len_weak_region, lw_lo, lw_hi, n_all, n_partial, n_amb, has_end_pt, found_first, lrc; };
-struct DriverLocals { Anchors an[4]; ResCorr rc[2]; SideList side[3]; uint32_t len[6]; int best[2]; MyersSaved saved; RegionCall call; };
+// the forward trim of a gap region, kept for the consensus (rtk_trim_by_column): nm moves of NW(rbuf[0][0, len), raw region) parked in rbuf[7], distance dist; nm = 0: none
+struct TrimPark { uint32_t nm, len; int32_t dist; };
+struct DriverLocals { Anchors an[4]; ResCorr rc[2]; SideList side[3]; uint32_t len[6]; int best[2]; MyersSaved saved; RegionCall call; TrimPark park; MyersResult trim; };
 
 struct RegionScratch {
     MyersScratch my;
@@ -427,6 +429,35 @@ RTK_FN_HOT MyersResult rtk_align_path(const RCtx& c_, const char* q_, uint32_t m
     const MyersResult r = rtk_myers_path(s.my, q, static_cast<int>(m), t, static_cast<int>(n), mode, true, n_moves);
     s.cnt[RTK_RC_CYC_MYERS] += rtk_clock() - t0;
     return r;
+}
+
+// The trim of rtk_correct_region, edlibAlign(raw, corr, SHW), read off the last column of ONE NW sweep of (corr, raw) (rtk_myers_shw_by_column): a plain
+// NW step instead of the distance call's step with last-row tracking. park: the sweep is stored, and when the consensus's forward alignment -- NW path of the
+// trimmed string corr[0, keep) against this raw region (rtk_generate_consensus) -- would take the in-memory traceback of rtk_myers_path, its moves are walked
+// from row keep right away (D[keep][|raw|] is the minimum the trim found) and parked in rbuf[7], which only the consensus writes, after it has read them.
+// false: the route does not apply (no result, no alignment counted) and the caller makes the distance call.
+RTK_FN bool rtk_trim_by_column(const RCtx& c_, const char* raw_, uint32_t n_, const char* corr_, uint32_t m_, bool park_, MyersResult* out_) {
+    const RCtx& c = *rtk_u(&c_); RegionScratch& s = rtk_hdr(c); const char* raw = rtk_u(raw_); const char* corr = rtk_u(corr_);
+    const uint32_t n = rtk_u(n_), m = rtk_u(m_); const bool park = rtk_u(park_); MyersResult* out = rtk_u(out_);
+    const unsigned long long t0 = rtk_clock();
+    const bool ok = rtk_myers_shw_by_column(s.my, corr, static_cast<int>(m), raw, static_cast<int>(n), true, park ? 1 : 0, 0, out, nullptr);
+    s.cnt[RTK_RC_CYC_MYERS] += rtk_clock() - t0;
+    if (!ok) return false;
+    s.cnt[RTK_RC_ALIGN] += 1; s.cnt[RTK_RC_CELLS] += static_cast<unsigned long long>((m + 63) / 64) * n;
+    RTK_SITE(park ? 18 : 19); rtk_site_note(m, n, -1, park);
+    s.cnt[park ? RTK_RC_TRIM_STORED : RTK_RC_TRIM_COLUMN] += 1;
+    if (!park) return true;
+    // the conditions of rtk_myers_path's in-memory route for (corr[0, keep), raw) that the stored sweep of all of corr has not checked already
+    const uint32_t keep = (out->first == -1) ? 0u : static_cast<uint32_t>(out->last + 1);
+    const long long W = (keep + 63) >> 6;
+    if (keep == 0 || keep > s.my.r_cap || keep + n > s.my.mv_cap || !((2LL * 8 + 4) * W * n + 8LL * n < 1024 * 1024)) return true;
+    const unsigned long long t1 = rtk_clock();
+    uint32_t& nm = s.loc.park.nm; nm = 0;
+    rtk_myers_walk(s.my, static_cast<int>(keep), static_cast<int>(n), static_cast<int>(n), out->dist, &nm);
+    if (nm <= s.str_cap) { rtk_wcopy(s.rbuf[7], s.my.moves, nm); s.loc.park.len = keep; s.loc.park.dist = out->dist; }
+    else nm = 0;
+    s.cnt[RTK_RC_CYC_MYERS] += rtk_clock() - t1;
+    return true;
 }
 
 #include "rtk_ambiguity.h"
@@ -1367,8 +1398,9 @@ RTK_DEV void rtk_scan_anchor_runs(const Anchors& a, int64_t start, int step, Con
 // q_read: pass 2 only, the quality string that goes with s_read in this call (the reference passes q_fw, q_bw or -- for the head region --
 // q_fw next to the reverse-complemented read, :787 G17); uncorrected stretches keep their qualities instead of getting q_min.
 
-RTK_FN_REGION void rtk_correct_region(const RCtx& c_, const char* s_read_, uint32_t s_len_, const Anchors& v_s_, const Anchors& v_w_, uint32_t i_s_, uint32_t i_w_, const ResCorr* rc_, ResCorr& res_, const char* q_read_ = nullptr) {
-    const RCtx& c = *rtk_u(&c_); const char* s_read = rtk_u(s_read_); const char* q_read = rtk_u(q_read_);
+// park: the trim's sweep is stored and the consensus's forward alignment walked from it (rtk_trim_by_column): the forward strand of a gap region
+RTK_FN_REGION void rtk_correct_region(const RCtx& c_, const char* s_read_, uint32_t s_len_, const Anchors& v_s_, const Anchors& v_w_, uint32_t i_s_, uint32_t i_w_, const ResCorr* rc_, ResCorr& res_, const char* q_read_ = nullptr, bool park_ = false) {
+    const RCtx& c = *rtk_u(&c_); const char* s_read = rtk_u(s_read_); const char* q_read = rtk_u(q_read_); const bool park = rtk_u(park_);
     const bool lrc = rtk_u(c.o.long_read_correct) != 0 && q_read != nullptr; uint32_t s_len = rtk_u(s_len_); const Anchors& v_s = *rtk_u(&v_s_); const Anchors& v_w = *rtk_u(&v_w_); RTK_ASSUME_LDS(&v_s); RTK_ASSUME_LDS(&v_w); uint32_t i_s = rtk_u(i_s_); uint32_t i_w = rtk_u(i_w_); const ResCorr* rc = rtk_u(rc_); ResCorr& res = *rtk_u(&res_); RTK_ASSUME_LDS(&res);
     RegionScratch& s = rtk_hdr(c);
     const uint32_t k = static_cast<uint32_t>(c.k);
@@ -1543,7 +1575,11 @@ RTK_FN_REGION void rtk_correct_region(const RCtx& c_, const char* s_read_, uint3
     }
     if (!res.is_corrected) { // :727-747 trim the corrected string to the largest SHW end location of the raw region
         const unsigned long long tt0 = rtk_clock();
-        RTK_SITE(13); const MyersResult a = rtk_align(c, s_read + first_pos, p2 - first_pos + k, s_corr, sl_, -1, RTK_MODE_SHW);
+        MyersResult& a = s.loc.trim;
+        if (!rtk_trim_by_column(c, s_read + first_pos, p2 - first_pos + k, s_corr, sl_, park, &a)) {
+            s.cnt[RTK_RC_TRIM_FALLBACK] += 1;
+            RTK_SITE(13); a = rtk_align(c, s_read + first_pos, p2 - first_pos + k, s_corr, sl_, -1, RTK_MODE_SHW);
+        }
         s.fine[RTK_FINE_TRIM] += rtk_clock() - tt0;
         if (a.dist >= 0) {
             const uint32_t keep = (a.first == -1) ? 0u : static_cast<uint32_t>(a.last + 1); // endLocations[0] == -1 wraps to SIZE_MAX in the reference
@@ -1610,21 +1646,33 @@ RTK_FN bool rtk_generate_consensus(const RCtx& c_, const ResCorr* fw_, const Res
     else if (nfw == 0 && nbw != 0) return take(bw);
     else if (nfw + nbw == 0) return false;
     if (nbw > nfw) { const ResCorr* t = fw; fw = bw; bw = t; }
-    // NW path alignments of both corrections against the raw region; the moves are parked in str[3] (fw) and str[4] (bw)
+    // NW path alignments of both corrections against the raw region; the moves are parked in str[3] (fw) and str[4] (bw). The alignment of the
+    // forward strand's string was walked by its trim already (rtk_trim_by_column: s.loc.park, moves in rbuf[7], which is written below only).
+    const TrimPark pk = s.loc.park;
+    auto parked = [&](const ResCorr* x) { return pk.nm != 0 && x->seq_len == pk.len && (x->seq == s.rbuf[0].get() || rtk_str_equal(x->seq, s.rbuf[0], pk.len)); };
+    auto resume = [&](char* dst, uint32_t* nm) { MyersResult r; r.dist = pk.dist; r.first = r.last = static_cast<int32_t>(ref_len) - 1; r.nloc = 1; *nm = pk.nm; rtk_wcopy(dst, s.rbuf[7], pk.nm); return r; };
     uint32_t nm_fw = 0, nm_bw = 0;
-    RTK_SITE(14); const MyersResult afw = rtk_align_path(c, fw->seq, fw->seq_len, ref, ref_len, RTK_MODE_NW, &nm_fw);
-    if (rtk_failed(s) || nm_fw > s.str_cap) { rtk_fail_ovf(s, 7); return false; }
-    rtk_wcopy(s.str[3], s.my.moves, nm_fw);
+    MyersResult afw;
+    const bool fw_parked = parked(fw);
+    if (fw_parked) afw = resume(s.str[3], &nm_fw);
+    else {
+        RTK_SITE(14); afw = rtk_align_path(c, fw->seq, fw->seq_len, ref, ref_len, RTK_MODE_NW, &nm_fw);
+        if (rtk_failed(s) || nm_fw > s.str_cap) { rtk_fail_ovf(s, 7); return false; }
+        rtk_wcopy(s.str[3], s.my.moves, nm_fw);
+    }
     RTK_PL(s, 29);
     // Both directions usually arrive at the same corrected string: its alignment against the raw region is then the one just computed
     const bool same_strings = bw->seq_len == fw->seq_len && rtk_str_equal(bw->seq, fw->seq, fw->seq_len);
     MyersResult abw = afw;
+    bool bw_parked = false;
     if (same_strings) { nm_bw = nm_fw; rtk_wcopy(s.str[4], s.str[3], nm_fw); }
+    else if ((bw_parked = parked(bw))) abw = resume(s.str[4], &nm_bw);
     else {
         RTK_SITE(15); abw = rtk_align_path(c, bw->seq, bw->seq_len, ref, ref_len, RTK_MODE_NW, &nm_bw);
         if (rtk_failed(s) || nm_bw > s.str_cap) { rtk_fail_ovf(s, 7); return false; }
         rtk_wcopy(s.str[4], s.my.moves, nm_bw);
     }
+    s.cnt[(fw_parked || bw_parked) ? RTK_RC_CONS_RESUMED : RTK_RC_CONS_SWEPT] += 1;
     const double n_fw = static_cast<double>(afw.dist) / static_cast<double>(fw->seq_len > ref_len ? fw->seq_len : ref_len);
     const double n_bw = static_cast<double>(abw.dist) / static_cast<double>(bw->seq_len > ref_len ? bw->seq_len : ref_len);
     if (max_norm > 0.0 && (n_fw > max_norm || n_bw > max_norm)) {
@@ -1704,7 +1752,8 @@ RTK_DEV RegionScratch* region_scratch_carve(char* base, const RegionScratchCfg& 
     t.str_cap = c.str_cap;
     t.memo_v = reinterpret_cast<uint8_t*>(p); p += c.memo_cap;
     t.ovf_word = 0; t.overflow = reinterpret_cast<uint32_t*>(&s->ovf_word); t.my.overflow = t.overflow;
-    for (int i = 0; i < RTK_RC_N; ++i) { t.cnt[i] = 0; t.fine[i] = 0; }
+    for (int i = 0; i < RTK_RC_N; ++i) t.cnt[i] = 0;
+    for (int i = 0; i < RTK_FINE_N; ++i) t.fine[i] = 0;
 #ifdef RTK_PROF
     for (int i = 0; i < 48; ++i) t.prof[i] = 0;
     t.prof_t = rtk_clock();
@@ -1731,6 +1780,7 @@ RTK_FN void rtk_emit_segment(const RCtx& c_, RegionDesc* rd_, const char* sq_, u
 RTK_FN_DRIVER void rtk_region_program(const RCtx& c_, RegionDesc* rd_) {
     const RCtx& c = *rtk_u(&c_); RegionDesc* rd = rtk_u(rd_);
     RegionScratch& s = rtk_hdr(c);
+    s.loc.park.nm = 0; // nothing parked for this region yet
     const uint32_t r = rtk_u(rd->read), k = static_cast<uint32_t>(c.k);
     const uint64_t base = rtk_u(c.bv.roff[r]);
     const uint32_t L = rtk_u(static_cast<uint32_t>(c.bv.roff[r + 1] - base));
@@ -1803,7 +1853,7 @@ RTK_FN_DRIVER void rtk_region_program(const RCtx& c_, RegionDesc* rd_) {
             } else isUncorrected = true;
         } else if (pb >= pa + k) {
             RTK_PL(s, 0);
-            rtk_correct_region(c, s_fw, L, so, we, i, i_weak, nullptr, fw, q_fw);
+            rtk_correct_region(c, s_fw, L, so, we, i, i_weak, nullptr, fw, q_fw, /*park=*/true);
             if (rtk_failed(s)) return;
             const uint32_t l_solid = pa - prev_pos;
             auto emit_minus_k = [&](const char* seq, uint32_t sl, const char* q, uint32_t ql) { // (prefix + x).substr(0, len - k)

@@ -182,6 +182,8 @@ enum RtkCounterSlot {
     RTK_CNT_WAVE_TRACE_END = 152,
     RTK_CNT_LANE_HANDED = 152, RTK_CNT_LANE_DONE = 153, // k_regions_lanes: regions handed on to the wave kernel / finished -> rtk_stats
     RTK_CNT_LANE_END = 154,
+    RTK_CNT_ROUTES = 154,           // [5] k_regions: trims stored / by column / by the distance call, consensus calls resumed / swept (RTK_RC_TRIM_STORED ..) -> rtk_stats
+    RTK_CNT_ROUTES_END = 159,
     RTK_CNT_LANE_PROF = 160,        // [24 = RL_NPROF] k_regions_lanes of a -DRTK_LANE_PROF build: lane cycles by slot (trace)
     RTK_CNT_LANE_PROF2 = 184,       // [24] the same build: wave-time estimate by slot (trace)
     RTK_CNT_LANE_PROF_END = 208,
@@ -197,6 +199,7 @@ static_assert(RTK_CNT_TOTAL == 224, "counter map: the size of the block changed 
 constexpr bool rtk_cnt_apart(int a, int a_end, int b, int b_end) { return a_end <= b || b_end <= a; }
 static_assert(RTK_CNT_EVENTS_END <= RTK_CNT_CYC && RTK_CNT_CYC_END <= RTK_CNT_FINALIZE && RTK_CNT_FINALIZE_END <= RTK_CNT_WALK && RTK_CNT_WALK_END <= RTK_CNT_FINE, "counter map: the event, cycle, finalize and walk ranges overlap");
 static_assert(RTK_CNT_FINE_END <= RTK_CNT_HIST && RTK_CNT_HIST_END <= RTK_CNT_PROF && RTK_CNT_PROF_END <= RTK_CNT_WAVE_TRACE && RTK_CNT_WAVE_TRACE_END <= RTK_CNT_LANE_HANDED, "counter map: the trace ranges overlap");
+static_assert(RTK_CNT_LANE_END <= RTK_CNT_ROUTES && RTK_CNT_ROUTES_END <= RTK_CNT_LANE_PROF, "counter map: the route counters overlap the lane ranges");
 static_assert(RTK_CNT_LANE_END <= RTK_CNT_LANE_PROF && RTK_CNT_LANE_PROF2 - RTK_CNT_LANE_PROF == 24 && RTK_CNT_LANE_PROF_END <= RTK_CNT_PHASE_SKIPPED && RTK_CNT_PHASE_SKIPPED < RTK_CNT_TOTAL, "counter map: the lane ranges overlap");
 static_assert(rtk_cnt_apart(RTK_CNT_PHASE_TRACE, RTK_CNT_PHASE_TRACE_END, RTK_CNT_FINALIZE_SLOWEST_PHASES, RTK_CNT_FINALIZE_SLOWEST_PHASES_END), "counter map: the two guests of the size-class table overlap");
 static_assert(RTK_CNT_HIST <= RTK_CNT_PHASE_TRACE && RTK_CNT_FINALIZE_SLOWEST_PHASES_END <= RTK_CNT_HIST_END, "counter map: the guests of the size-class table left it (update the comment above)");
@@ -204,12 +207,15 @@ static_assert(RTK_CNT_HIST <= RTK_CNT_PHASE_TRACE && RTK_CNT_FINALIZE_SLOWEST_PH
 // indices of RegionScratch::cnt (rtk_region.h): a wave's own accumulators, added to the block when its kernel ends
 enum RtkRegionCnt { RTK_RC_EXPAND = 0, RTK_RC_COLOUR = 1, RTK_RC_PATHBASE = 2, RTK_RC_ALIGN = 3, RTK_RC_CELLS = 4, // -> RTK_CNT_EXPAND .. RTK_CNT_CELLS
     RTK_RC_CYC_COLOUR = 5, RTK_RC_CYC_PATHS = 6, RTK_RC_CYC_CONSENSUS = 7, RTK_RC_CYC_TOTAL = 8, RTK_RC_CYC_MYERS = 9, RTK_RC_CYC_SETS = 10, // [5, 11) -> RTK_CNT_CYC + 0 .. 5
-    RTK_RC_CYC_PATHREC = 11 /* -> RTK_CNT_CYC_SETS as well */, RTK_RC_CYC_TOSTRING = 12, RTK_RC_CYC_PATHQUAL = 13, RTK_RC_CYC_DFS = 14, RTK_RC_CYC_COLOUR_OK = 15, RTK_RC_N = 16 };
+    RTK_RC_CYC_PATHREC = 11 /* -> RTK_CNT_CYC_SETS as well */, RTK_RC_CYC_TOSTRING = 12, RTK_RC_CYC_PATHQUAL = 13, RTK_RC_CYC_DFS = 14, RTK_RC_CYC_COLOUR_OK = 15,
+    // routes of the trims and the consensus (rtk_trim_by_column, rtk_generate_consensus) -> RTK_CNT_ROUTES + 0 .. 4: trims by column with a stored sweep (forward
+    // strand of a gap region) / without, trims by the distance call; consensus calls whose forward-string alignment was resumed from the trim's sweep / swept
+    RTK_RC_TRIM_STORED = 16, RTK_RC_TRIM_COLUMN = 17, RTK_RC_TRIM_FALLBACK = 18, RTK_RC_CONS_RESUMED = 19, RTK_RC_CONS_SWEPT = 20, RTK_RC_N = 21 };
+static_assert(RTK_CNT_ROUTES_END - RTK_CNT_ROUTES == static_cast<int>(RTK_RC_N) - static_cast<int>(RTK_RC_TRIM_STORED), "counter map: one slot per route counter");
 // indices of RegionScratch::fine -> RTK_CNT_FINE + i (their names in the trace: region_trace_report, rtk_pipeline_run.inc)
 enum RtkRegionFine { RTK_FINE_COL_GENERAL = 0 /* [7] the laps of rtk_choose_colors_general: 1 .. 4 are ALSO the laps of rtk_fix_ambiguity (trace only) */, RTK_FINE_COL_UNIONS = 0, RTK_FINE_FA_ALIGN = 1, RTK_FINE_FA_WALK = 2, RTK_FINE_FA_LINKED = 3, RTK_FINE_FA_APPLY = 4, RTK_FINE_COL_S_VECTORS = 5, RTK_FINE_COL_S_SELECT = 6,
     RTK_FINE_SIDE_LISTS = 7, RTK_FINE_TRIM = 8, RTK_FINE_FIX_AMBIGUITY = 9, RTK_FINE_FA_CALLS = 10, RTK_FINE_FA_ALL_CONFIDENT = 11, RTK_FINE_COL_S_CYCLES = 12, RTK_FINE_COL_B_CYCLES = 13,
     RTK_FINE_COL_S_CALLS = 14, RTK_FINE_COL_B_CALLS = 15, RTK_FINE_N = 16 };
-static_assert(static_cast<int>(RTK_RC_N) == static_cast<int>(RTK_FINE_N), "region_scratch_carve clears cnt and fine in one loop");
 
 // Unitig mapping (restates the fields of Bifrost's const_UnitigMap the hot path reads).
 struct UMap {
