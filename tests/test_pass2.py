@@ -14,9 +14,12 @@ GPU_LIB = None  # default library of ratatosk_amd.api
 
 
 def _second_pass_set(tmpdir, name, sim_args):
-    """Pass 1 by the oracle (so the fixture needs no GPU), then the second-pass index: graph, coverage and colours from the
-    pass-1 reads, colour = read index (src/Ratatosk.cpp:1079-1101)."""
-    pre = make_dataset(tmpdir, name, sim_args)
+    return _second_pass_from(make_dataset(tmpdir, name, sim_args))
+
+
+def _second_pass_from(pre):
+    """PRE.sr.fq, PRE.lr.fq and the k = 31 index of a set that exists already. Pass 1 by the oracle (so the fixture needs no GPU), then the
+    second-pass index: graph, coverage and colours from the pass-1 reads, colour = read index (src/Ratatosk.cpp:1079-1101)."""
     og = op.Graph(pre + ".index.k31.fasta.gz", pre + ".index.k31.rtsk", 31)
     raw = op.read_fastq(pre + ".lr.fq")
     out, _ = og.correct_batch([r[1] for r in raw], [r[2] for r in raw], threads=8)

@@ -5,9 +5,9 @@ from oracle import oracle_py as op
 from ratatosk_amd import api
 
 
-def _check(prefix, n, lib_path):
-    fa, rt = prefix + ".index.k31.fasta.gz", prefix + ".index.k31.rtsk"
-    og, pg = op.Graph(fa, rt, 31), api.Graph(fa, rt, 31, device=0, lib_path=lib_path)
+def _check(prefix, n, lib_path, k=31):
+    fa, rt = prefix + ".index.k%d.fasta.gz" % k, prefix + ".index.k%d.rtsk" % k
+    og, pg = op.Graph(fa, rt, k), api.Graph(fa, rt, k, device=0, lib_path=lib_path)
     reads = op.read_fastq(prefix + ".lr.fq")
     tot_w = 0
     for name, s, q in reads[:n]:
