@@ -106,6 +106,10 @@ typedef struct rtk_stats {
      * A C G T, a corrected string above 4096 characters or an empty one). A consensus call takes the alignment of the forward strand's string from the stored
      * sweep of its trim (n_consensus_resumed) or sweeps it anew (n_consensus_swept). */
     uint64_t n_trim_stored, n_trim_column, n_trim_fallback, n_consensus_resumed, n_consensus_swept;
+    /* revision 8: fixAmbiguity's searches for the alleles of linked SNPs, one per decided entry of the safe set. A search can only append for a position whose
+     * entry is still undecided; when there is none the search is skipped (n_fa_linked_skipped), else it runs (n_fa_linked_run). n_fa_linked_entries: entries the
+     * searches produced. With RTK_FA_LINKED_ALWAYS=1 every search runs; the sum of run and skipped and the entries are the same either way. */
+    uint64_t n_fa_linked_run, n_fa_linked_skipped, n_fa_linked_entries;
 } rtk_stats;
 
 /* dbg.read(G.fasta.gz) + readGraphData(G.rtsk) (reference: src/Ratatosk.cpp:1087-1089; src/Graph.cpp:722-784).
@@ -295,8 +299,9 @@ void rtk_free_many(void** p, uint32_t n);
 const char* rtk_last_error(void);
 const char* rtk_version(void);
 /* Interface revision, raised whenever a struct of this header grows or a default changes (5: rtk_opts.struct_size, rtk_stats lane fields, a2_exclusive default 1;
- * 7: rtk_stats route fields n_trim_* / n_consensus_*, the test-only rtk_myers_batch modes 3 and 4, rtk_myers_column_last_routes). */
-#define RTK_API_REVISION 7
+ * 7: rtk_stats route fields n_trim_* / n_consensus_*, the test-only rtk_myers_batch modes 3 and 4, rtk_myers_column_last_routes;
+ * 8: rtk_stats fields n_fa_linked_*). */
+#define RTK_API_REVISION 8
 int rtk_api_revision(void);
 
 #ifdef __cplusplus

@@ -228,9 +228,20 @@ RTK_FN void rtk_fix_ambiguity(const RCtx& c_, char* query_, uint32_t query_len_,
     }
     RTK_FA_LAP(RTK_FINE_FA_WALK)
     // alleles of the other annotated positions of the unitig a decided SNP lies on (:713-768)
+    // Which searches run. The search for entry e appends to `sa` only at a position pos != p whose entry x of `ms` exists and holds a character outside
+    // A/C/G/T (:755-759 -- the two `continue`s in front of `uc` below); positions are unique in `ms`, so x != e, and `ms` is not written in this loop. An entry
+    // that is searched for is decided, so it is none of the undecided ones: with n_open == 0 no search of this call can append, whatever the graph holds, and
+    // `sa`, all that the loop hands on, stays empty. The reference runs those searches too, without effect. ('X', c_no, counts as undecided: rtk_is_dna('X')
+    // is false.) A skipped search cannot raise overflow code 11 (rtk_amb_of_um, the capacity of `sa`) either: such a region used to be redone with bigger
+    // work areas and then gave the same bytes; now it is done at once. RTK_FA_LINKED_ALWAYS=1 (rtk_knobs.h) runs every search.
+    uint32_t n_open = 0;
+    for (uint32_t e = 0; e < nms; ++e) n_open += rtk_is_dna(rtk_amb_chr(ms[e])) ? 0u : 1u;
+    const bool run_linked = n_open != 0 || c.o.fa_linked_always != 0;
     for (uint32_t e = 0; e < nms; ++e) {
         const char pc = rtk_amb_chr(ms[e]);
         if (!rtk_is_dna(pc)) continue;
+        if (!run_linked) { s.cnt[RTK_RC_FA_LINKED_SKIPPED] += 1; continue; }
+        s.cnt[RTK_RC_FA_LINKED_RUN] += 1;
         const uint32_t p = rtk_amb_pos(ms[e]);
         const uint32_t pos_buff = (p < k - 1) ? 0 : (p - k + 1);
         const uint32_t len_buff = ((p + k < query_len) ? (p + k) : query_len) - pos_buff;
@@ -295,6 +306,7 @@ RTK_FN void rtk_fix_ambiguity(const RCtx& c_, char* query_, uint32_t query_len_,
         }
         rtk_sync();
     }
+    s.cnt[RTK_RC_FA_LINKED_ENTRIES] += nsa;
     RTK_FA_LAP(RTK_FINE_FA_LINKED)
     for (uint32_t i = 0; i < nsa; ++i) { // a linked position with exactly one candidate allele takes it, when compatible (:771-790)
         const uint32_t pos = rtk_amb_pos(sa[i]);

@@ -761,3 +761,11 @@ extern "C" int rtk_myers_batch_lanes(uint32_t n, const char* const* query, const
 }
 
 #include "rtk_pipeline.inc"
+
+#ifdef RTK_SIM // the census of repeated alignments (rtk_region.h, rtk_pair_note; profiles/scripts/sim_pairs.py)
+thread_local std::vector<RtkSimPair> rtk_sim_pair_log;
+std::atomic<int> rtk_sim_pairs_on(0);
+std::atomic<unsigned long long> rtk_sim_pair_stat[32][10];
+extern "C" void rtk_sim_pairs(int on) { rtk_sim_pairs_on = on; }
+extern "C" void rtk_sim_pair_stats(unsigned long long* out, int reset) { for (int i = 0; i < 32; ++i) for (int j = 0; j < 10; ++j) { out[10 * i + j] = rtk_sim_pair_stat[i][j].load(); if (reset) rtk_sim_pair_stat[i][j] = 0; } }
+#endif

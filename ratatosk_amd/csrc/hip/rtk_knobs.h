@@ -54,6 +54,7 @@ inline int rtk_knob_lane_round() { return rtk_env_int("RTK_LANE_ROUND", 64); }  
 inline bool rtk_knob_compact() { return rtk_env_is1("RTK_COMPACT"); }              // '1': a first attempt with ~1.3 MB work areas (for graphs that leave little HBM)
 inline int rtk_knob_region_waves() { return rtk_env_pos_int("RTK_REGION_WAVES", 4096); } // int, 4096: persistent waves of k_regions
 inline int rtk_knob_p2_rgrid() { return rtk_env_int("RTK_P2_RGRID", 512); }        // int, 512: cap of the waves of a second-pass ticket's k_regions
+inline bool rtk_knob_fa_linked_always() { return rtk_env_is1("RTK_FA_LINKED_ALWAYS"); } // '1': fixAmbiguity runs every linked-allele search, also those that cannot append (same results; parity test, A/B traces)
 inline bool rtk_knob_test_coalesce_fail() { return rtk_env_set("RTK_TEST_COALESCE_FAIL"); } // flag, test hook: a merged batch is reported as failed (its members must come through on their own)
 
 // ---- region stage and rtk_correct_batch: read ONCE per process (the first call fixes the value)

@@ -306,6 +306,7 @@ RTK_GLOBAL void k_regions(const LaunchCtx* L, GraphView g, OptsView o, BatchView
             if (hb != trace_class) continue;
         }
         *sc->overflow = 0; sc->top[0] = 0; sc->top[1] = 0; sc->top[2] = 0; sc->memo_n = 0;
+        RTK_PAIR_REGION();
 #ifdef RTK_PROF
         { // in-situ latency probes (developer build): a chain of 4 dependent loads from random slots of the k-mer table (cold: HBM), one of 4 dependent
           // loads from the first words of the unitig offsets (warm: L2 / memory-side cache), one store + load of the wave's own slab
@@ -357,7 +358,8 @@ RTK_GLOBAL void k_regions(const LaunchCtx* L, GraphView g, OptsView o, BatchView
         for (int i = 0; i < 6; ++i) rtk_atomic_add(bv.counters + RTK_CNT_CYC + i, sc->cnt[RTK_RC_CYC_COLOUR + i]);
         rtk_atomic_add(bv.counters + RTK_CNT_CYC_SETS, sc->cnt[RTK_RC_CYC_PATHREC]); rtk_atomic_add(bv.counters + RTK_CNT_CYC_TOSTRING, sc->cnt[RTK_RC_CYC_TOSTRING]); rtk_atomic_add(bv.counters + RTK_CNT_CYC_PATHQUAL, sc->cnt[RTK_RC_CYC_PATHQUAL]); rtk_atomic_add(bv.counters + RTK_CNT_WALK_CYCLES, sc->my.walk_cycles); rtk_atomic_add(bv.counters + RTK_CNT_WALK_MOVES, sc->my.walk_moves); rtk_atomic_add(bv.counters + RTK_CNT_WALK_RELOADS, sc->my.walk_reloads); rtk_atomic_add(bv.counters + RTK_CNT_WALK_SCALAR, sc->my.walk_scalar); rtk_atomic_add(bv.counters + RTK_CNT_WALK_CALLS, sc->my.walk_calls); rtk_atomic_add(bv.counters + RTK_CNT_WALK_TAIL, sc->my.walk_tail_cycles); rtk_atomic_add(bv.counters + RTK_CNT_CYC_DFS, sc->cnt[RTK_RC_CYC_DFS]); rtk_atomic_add(bv.counters + RTK_CNT_CYC_COLOUR_OK, sc->cnt[RTK_RC_CYC_COLOUR_OK]);
         for (int i = 0; i < RTK_FINE_N; ++i) rtk_atomic_add(bv.counters + RTK_CNT_FINE + i, sc->fine[i]);
-        for (int i = RTK_RC_TRIM_STORED; i < RTK_RC_N; ++i) rtk_atomic_add(bv.counters + RTK_CNT_ROUTES + (i - RTK_RC_TRIM_STORED), sc->cnt[i]);
+        for (int i = RTK_RC_TRIM_STORED; i < RTK_RC_FA_LINKED_RUN; ++i) rtk_atomic_add(bv.counters + RTK_CNT_ROUTES + (i - RTK_RC_TRIM_STORED), sc->cnt[i]);
+        for (int i = RTK_RC_FA_LINKED_RUN; i < RTK_RC_N; ++i) rtk_atomic_add(bv.counters + RTK_CNT_FA_LINKED + (i - RTK_RC_FA_LINKED_RUN), sc->cnt[i]);
         for (int i = 0; i < 32; ++i) rtk_atomic_add(bv.counters + RTK_CNT_HIST + i, static_cast<unsigned long long>(RTK_HIST_GET(*sc, i)));
 #ifdef RTK_PROF
         for (int i = 0; i < 48; ++i) rtk_atomic_add(bv.counters + RTK_CNT_PROF + i, static_cast<unsigned long long>(sc->prof[i]));
@@ -780,6 +782,8 @@ static void region_trace_report(const unsigned long long* cnt) {
     fprintf(stderr, "[rtk trace] k_regions cycle shares: DFS bookkeeping %.3f (of which colour checks %.3f)\n", share(RTK_CNT_CYC_DFS), share(RTK_CNT_CYC_COLOUR_OK));
     fprintf(stderr, "[rtk trace] trims: by column %llu (of which stored %llu), by the distance call %llu, cycles %.3g; consensus calls: forward alignment resumed %llu, swept %llu\n",
             cnt[RTK_CNT_ROUTES + 0] + cnt[RTK_CNT_ROUTES + 1], cnt[RTK_CNT_ROUTES + 0], cnt[RTK_CNT_ROUTES + 2], double(cnt[RTK_CNT_FINE + RTK_FINE_TRIM]), cnt[RTK_CNT_ROUTES + 3], cnt[RTK_CNT_ROUTES + 4]);
+    fprintf(stderr, "[rtk trace] fixAmbiguity linked-allele searches: run %llu, skipped %llu, entries produced %llu, cycles %.3g\n", cnt[RTK_CNT_FA_LINKED + 0], cnt[RTK_CNT_FA_LINKED + 1],
+            cnt[RTK_CNT_FA_LINKED + 2], double(cnt[RTK_CNT_FINE + RTK_FINE_FA_LINKED]));
     fprintf(stderr, "[rtk trace] walks %llu moves %llu reloads %llu scalar steps %llu cycles %.3g tail cycles %.3g\n", cnt[RTK_CNT_WALK_CALLS], cnt[RTK_CNT_WALK_MOVES],
             cnt[RTK_CNT_WALK_RELOADS], cnt[RTK_CNT_WALK_SCALAR], double(cnt[RTK_CNT_WALK_CYCLES]), double(cnt[RTK_CNT_WALK_TAIL]));
 }
@@ -797,6 +801,7 @@ static void region_stats(RegionRun& R, const unsigned long long* cnt) {
     st.n_lane_handed = cnt[RTK_CNT_LANE_HANDED]; st.n_lane_regions = cnt[RTK_CNT_LANE_HANDED] + cnt[RTK_CNT_LANE_DONE];
     st.n_trim_stored = cnt[RTK_CNT_ROUTES + 0]; st.n_trim_column = cnt[RTK_CNT_ROUTES + 1]; st.n_trim_fallback = cnt[RTK_CNT_ROUTES + 2];
     st.n_consensus_resumed = cnt[RTK_CNT_ROUTES + 3]; st.n_consensus_swept = cnt[RTK_CNT_ROUTES + 4];
+    st.n_fa_linked_run = cnt[RTK_CNT_FA_LINKED + 0]; st.n_fa_linked_skipped = cnt[RTK_CNT_FA_LINKED + 1]; st.n_fa_linked_entries = cnt[RTK_CNT_FA_LINKED + 2];
     st.ms_stitch = R.t_st.elapsed(); st.ms_total = b->t_all.elapsed();
     st.n_windows = b->n_bases;
     st.n_probes_exact = cnt[RTK_CNT_PROBES_EXACT]; st.n_probes_inexact = cnt[RTK_CNT_PROBES_INEXACT]; st.n_hits_inexact = cnt[RTK_CNT_HITS_INEXACT];

@@ -403,9 +403,39 @@ static inline void rtk_site_note(uint32_t m, uint32_t n, int k, bool stored) {
     if ((rtk_sim_site & 31) == 2) { int b = 0; while (b < 7 && (256u << b) <= n) ++b; rtk_sim_site_stat[26][b] += 1; rtk_sim_site_stat[27][b] += n; }
     t[0] += 1; t[1] += cells; t[2] += m; t[3] += n; if (stored) { t[4] += 1; t[5] += cells; } if (k >= 0) t[6] += 1; if (m > 2048) t[7] += 1;
 }
+// Census of repeated alignments (profiles/scripts/sim_pairs.py; off until rtk_sim_pairs(1)): the strings of every alignment of the region in progress, and per site the
+// calls and 32-bit word-columns [site][2 c], [site][2 c + 1] of class c: 0 all; the pair repeats an earlier one of the region 1 exactly, 2 transposed, 3 with a query
+// that is a prefix of the other's on the same target, 4 with a query of the same length at Hamming distance 1 .. 8 on the same target (the first class that holds)
+#include <algorithm>
+#include <string>
+#include <vector>
+struct RtkSimPair { std::string q, t; };
+extern thread_local std::vector<RtkSimPair> rtk_sim_pair_log;
+extern std::atomic<int> rtk_sim_pairs_on;
+extern std::atomic<unsigned long long> rtk_sim_pair_stat[32][10];
+#define RTK_PAIR_REGION() (rtk_sim_pair_log.clear())
+static inline void rtk_pair_note(const char* q, uint32_t m, const char* t, uint32_t n) {
+    if (!rtk_sim_pairs_on.load(std::memory_order_relaxed)) return;
+    RtkSimPair p; p.q.assign(q, m); p.t.assign(t, n);
+    int cls = 5;
+    for (const RtkSimPair& e : rtk_sim_pair_log) {
+        int c = 5;
+        if (e.q == p.q && e.t == p.t) c = 1;
+        else if (e.q == p.t && e.t == p.q) c = 2;
+        else if (e.t == p.t && e.q.size() != p.q.size()) { const size_t l = std::min(e.q.size(), p.q.size()); if (l > 0 && e.q.compare(0, l, p.q, 0, l) == 0) c = 3; }
+        else if (e.t == p.t) { size_t d = 0; for (size_t i = 0; i < p.q.size() && d <= 8; ++i) d += e.q[i] != p.q[i]; if (d <= 8) c = 4; } // (d == 0 is class 1)
+        cls = std::min(cls, c);
+    }
+    std::atomic<unsigned long long>* st = rtk_sim_pair_stat[rtk_sim_site & 31];
+    const unsigned long long cells = static_cast<unsigned long long>((m + 31) / 32) * n;
+    st[0] += 1; st[1] += cells; if (cls < 5) { st[2 * cls] += 1; st[2 * cls + 1] += cells; }
+    rtk_sim_pair_log.push_back(std::move(p));
+}
 #else
 #define RTK_SITE(id) ((void)0)
 #define rtk_site_note(m, n, k, stored) ((void)0)
+#define RTK_PAIR_REGION() ((void)0)
+#define rtk_pair_note(q, m, t, n) ((void)0)
 #endif
 
 RTK_FN_HOT MyersResult rtk_align(const RCtx& c, const char* q_, uint32_t m_, const char* t_, uint32_t n_, int kk_, int mode_, bool iupac_ = true) {
@@ -413,7 +443,7 @@ RTK_FN_HOT MyersResult rtk_align(const RCtx& c, const char* q_, uint32_t m_, con
     const uint32_t m = rtk_u(m_), n = rtk_u(n_); const int kk = rtk_u(kk_), mode = rtk_u(mode_); const bool iupac = rtk_u(iupac_);
     s.cnt[RTK_RC_ALIGN] += 1; s.cnt[RTK_RC_CELLS] += static_cast<unsigned long long>((m + 63) / 64) * n;
     const unsigned long long t0 = rtk_clock();
-    rtk_site_note(m, n, kk, false);
+    rtk_site_note(m, n, kk, false); rtk_pair_note(q, m, t, n);
     const MyersResult r = rtk_myers_distance(s.my, q, static_cast<int>(m), t, static_cast<int>(n), kk, mode, iupac);
     s.cnt[RTK_RC_CYC_MYERS] += rtk_clock() - t0;
     return r;
@@ -425,7 +455,7 @@ RTK_FN_HOT MyersResult rtk_align_path(const RCtx& c_, const char* q_, uint32_t m
     const uint32_t m = rtk_u(m_), n = rtk_u(n_); const int mode = rtk_u(mode_); uint32_t* n_moves = rtk_u(n_moves_);
     s.cnt[RTK_RC_ALIGN] += (m > 0 && n > 0) ? 2 : 1; s.cnt[RTK_RC_CELLS] += static_cast<unsigned long long>((m + 63) / 64) * n;
     const unsigned long long t0 = rtk_clock();
-    rtk_site_note(m, n, -1, true);
+    rtk_site_note(m, n, -1, true); rtk_pair_note(q, m, t, n);
     const MyersResult r = rtk_myers_path(s.my, q, static_cast<int>(m), t, static_cast<int>(n), mode, true, n_moves);
     s.cnt[RTK_RC_CYC_MYERS] += rtk_clock() - t0;
     return r;
@@ -444,7 +474,7 @@ RTK_FN bool rtk_trim_by_column(const RCtx& c_, const char* raw_, uint32_t n_, co
     s.cnt[RTK_RC_CYC_MYERS] += rtk_clock() - t0;
     if (!ok) return false;
     s.cnt[RTK_RC_ALIGN] += 1; s.cnt[RTK_RC_CELLS] += static_cast<unsigned long long>((m + 63) / 64) * n;
-    RTK_SITE(park ? 18 : 19); rtk_site_note(m, n, -1, park);
+    RTK_SITE(park ? 18 : 19); rtk_site_note(m, n, -1, park); rtk_pair_note(corr, m, raw, n);
     s.cnt[park ? RTK_RC_TRIM_STORED : RTK_RC_TRIM_COLUMN] += 1;
     if (!park) return true;
     // the conditions of rtk_myers_path's in-memory route for (corr[0, keep), raw) that the stored sweep of all of corr has not checked already
