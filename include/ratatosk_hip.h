@@ -293,6 +293,19 @@ int rtk_index_colour_begin(int device, int k, const char* seq_pool, const uint64
 int rtk_index_colour_chunk(void* job, const char* chars, uint64_t n_chars, const uint64_t* starts, const uint32_t* ids, uint32_t n_reads);
 int rtk_index_colour_end(void* job, uint64_t** events, uint64_t* n_events, uint64_t** cov);
 
+/* rtk_rescue_*: the rescue of unmapped short reads before the index build (`correct -u`; retrieveMissingReads, src/Graph.cpp:3857-4131, called at
+ * src/Ratatosk.cpp:1040-1056), with exact sets where the reference has Bloom filters ([A11]). One-word k-mers (odd k <= 31).
+ * begin (replaces buildBBF + the long-read graph build, src/Graph.cpp:3880-3884): lr / sr = the canonical k-mers seen at least twice in the long reads / in
+ * the `-s` reads, sorted ascending and distinct, as rtk_index_count_kmers(min_count = 2) returns them (either may be empty). D = lr \ sr is formed on the device
+ * and put into a table in HBM; the inputs are not kept. chunk (replaces the query loop, src/Graph.cpp:3998-4015; any thread, two calls run side by side):
+ * sequences separated by '\n' as for rtk_index_colour_chunk (read r starts at starts[r]; at most 64 MB and 4 M reads per call); keep[r] = 1 when read r has at
+ * least min_positions start positions whose k characters are all A/C/G/T (either case) and spell a k-mer of D (positions are counted, not distinct k-mers:
+ * src/Graph.cpp:4045), else 0. end: the positions that probed D (all-A/C/G/T windows) and those that hit, over all chunks; releases the job (with null
+ * outputs: only that). */
+int rtk_rescue_begin(int device, int k, const uint64_t* lr, uint64_t n_lr, const uint64_t* sr, uint64_t n_sr, uint32_t min_positions, void** job);
+int rtk_rescue_chunk(void* job, const char* chars, uint64_t n_chars, const uint64_t* starts, uint32_t n_reads, unsigned char* keep);
+int rtk_rescue_end(void* job, uint64_t* n_positions_probed, uint64_t* n_hits);
+
 void rtk_free(void* p);
 /* rtk_free of p[0 .. n) (the out_seq / out_qual arrays of rtk_correct_batch in one call; entries are set to NULL). */
 void rtk_free_many(void** p, uint32_t n);
@@ -300,8 +313,8 @@ const char* rtk_last_error(void);
 const char* rtk_version(void);
 /* Interface revision, raised whenever a struct of this header grows or a default changes (5: rtk_opts.struct_size, rtk_stats lane fields, a2_exclusive default 1;
  * 7: rtk_stats route fields n_trim_* / n_consensus_*, the test-only rtk_myers_batch modes 3 and 4, rtk_myers_column_last_routes;
- * 8: rtk_stats fields n_fa_linked_*). */
-#define RTK_API_REVISION 8
+ * 8: rtk_stats fields n_fa_linked_*; 9: rtk_rescue_begin / _chunk / _end). */
+#define RTK_API_REVISION 9
 int rtk_api_revision(void);
 
 #ifdef __cplusplus

@@ -106,6 +106,10 @@ def load_library(path=None):
     L.rtk_coalesce_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.rtk_graph_reserve_batches.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32, C.c_int, C.c_uint64]
     L.rtk_free_many.argtypes = [C.POINTER(C.c_void_p), C.c_uint32]; L.rtk_free_many.restype = None
+    if L.rtk_api_revision() >= 9:  # (an older build given as RTK_LIB_OVERRIDE has no rescue entries: rescue_reads says so)
+        L.rtk_rescue_begin.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_uint64), C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p)]
+        L.rtk_rescue_chunk.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(C.c_ubyte)]
+        L.rtk_rescue_end.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.rtk_free.argtypes = [C.c_void_p]
     _libs[path] = L
     return L
@@ -294,6 +298,58 @@ def myers_batch(queries, targets, ks=None, modes=None, want_path=False, use_iupa
         if want_path:
             c = cig.raw[i * cap_cig:(i + 1) * cap_cig].split(b"\0", 1)[0].decode()
         out.append((dist[i], el, c))
+    return out
+
+
+def _u64_array(a):
+    """(owner, pointer, length) of a sequence of k-mers as uint64_t[]; a numpy array is passed without a copy when it already is one of uint64."""
+    if hasattr(a, "ctypes"):
+        import numpy as np
+        arr = np.ascontiguousarray(a, dtype=np.uint64)
+        return arr, arr.ctypes.data_as(C.POINTER(C.c_uint64)), int(arr.size)
+    arr = (C.c_uint64 * max(1, len(a)))(*[int(x) for x in a])
+    return arr, arr, len(a)
+
+
+def rescue_reads(lr_kmers, sr_kmers, seqs, k=31, min_positions=31, device=0, stats=None, lib_path=None):
+    """The unmapped-read rescue of `correct -u` (retrieveMissingReads, src/Graph.cpp:3857-4131; DESIGN.md section 4 [A11]) over rtk_rescue_begin / _chunk / _end:
+    lr_kmers / sr_kmers = sorted canonical k-mers seen at least twice in the long reads / the mapped short reads; returns [bool] per read of seqs: at least
+    min_positions start positions spell a k-mer of lr_kmers that is not in sr_kmers. stats (a dict) receives n_positions_probed and n_hits."""
+    L = load_library(lib_path)
+    if L.rtk_api_revision() < 9:
+        raise RtkError("%s is of interface revision %d: the rescue entries came with revision 9" % (L._name, L.rtk_api_revision()))
+    keep_lr, p_lr, n_lr = _u64_array(lr_kmers)
+    keep_sr, p_sr, n_sr = _u64_array(sr_kmers)
+    job = C.c_void_p()
+
+    def check(rc):
+        if rc != 0:
+            raise RtkError("rtk error %d: %s" % (rc, L.rtk_last_error().decode()))
+
+    check(L.rtk_rescue_begin(device, k, p_lr, n_lr, p_sr, n_sr, min_positions, C.byref(job)))
+    out = []
+    try:
+        bs = [_b(s) for s in seqs]
+        i = 0
+        while i < len(bs):  # chunks of at most 48 MB of characters and 2 M reads
+            j, size = i, 0
+            while j < len(bs) and (j == i or (size + len(bs[j]) + 1 <= (48 << 20) and j - i < (2 << 20))):
+                size += len(bs[j]) + 1; j += 1
+            starts, at = (C.c_uint64 * (j - i))(), 0
+            for r in range(i, j):
+                starts[r - i] = at; at += len(bs[r]) + 1
+            chars = b"\n".join(bs[i:j]) + b"\n"
+            keep = (C.c_ubyte * (j - i))()
+            check(L.rtk_rescue_chunk(job, chars, len(chars), starts, j - i, keep))
+            out.extend(bool(x) for x in keep)
+            i = j
+    except Exception:
+        L.rtk_rescue_end(job, None, None)
+        raise
+    probed, hits = C.c_uint64(), C.c_uint64()
+    check(L.rtk_rescue_end(job, C.byref(probed), C.byref(hits)))
+    if stats is not None:
+        stats["n_positions_probed"], stats["n_hits"] = probed.value, hits.value
     return out
 
 

@@ -80,6 +80,7 @@ inline int rtk_knob_sim_devices() { return std::max(1, rtk_env_int("RTK_SIM_DEVI
 //   csrc/host (graph file -> flat tables, the Ratatosk driver): RTK_BF1_LOG2BITS, RTK_BF1_OFF, RTK_BF_KEYS_PER_WORD, RTK_HT_DENSE_KMERS, RTK_HX_MAX_GB, RTK_INEXACT_ENUM,
 //     RTK_LOAD_TRACE, RTK_CLI_STATS, RTK_CLI_TRACE, RTK_SERIAL_READER
 //   csrc/tools (rtk_build_index): RTK_FASTA_MEMBER_BYTES, RTK_INDEX_HOST_COLOURS, RTK_INDEX_HOST_UNITIGS, RTK_INDEX_THREADS, RTK_INDEX_TRACE
+//   csrc/tools (rtk_rescue_reads): RTK_INDEX_CHUNK (characters of -u text per batch), RTK_INDEX_THREADS, RTK_INDEX_TRACE
 //   ratatosk_amd/api.py: RTK_LIB_OVERRIDE (another build of the library), RTK_HOST_TABLES
 
 #endif

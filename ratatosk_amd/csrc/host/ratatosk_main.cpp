@@ -16,7 +16,9 @@
 // index): the uncorrected reads are read in lock-step with the pass-1 reads (:774-802), qualities are kept, output goes to OUT.fastq
 // (:622), optionally gzipped (-G; one gzip member per ticket block, compressed by the workers) and trimmed / split at low-quality
 // bases (-t, :508-563). `-f` = fixSNPs() on the reads of the second pass (:828). `correct -s SHORT -l LONG -o OUT` without -g / -d builds the indexes
-// with rtk_build_index --gpu and runs the passes, each step a child process (correct_from_short_reads). Everything else (`index`, `-u`, `-p/-P`, `-a`) is out of scope.
+// with rtk_build_index --gpu and runs the passes, each step a child process (correct_from_short_reads); with `-u UNMAPPED` the run starts with the rescue of the
+// unmapped short reads the long reads call for (rtk_rescue_reads --gpu; retrieveMissingReads, src/Graph.cpp:3857-4131), which join the short reads of both index builds.
+// Everything else (`index`, `-u` next to a pre-built index, `-p/-P`, `-a`) is out of scope.
 #include <getopt.h>
 #include <zlib.h>
 
@@ -46,7 +48,7 @@
 #include "ratatosk_hip.h"
 
 struct Opt {
-    std::vector<std::string> in_long, in_long_raw, in_short; // in_short (-s): the index steps of `correct -s` (below)
+    std::vector<std::string> in_long, in_long_raw, in_short, in_unmapped; // in_short (-s), in_unmapped (-u): the rescue and index steps of `correct -s` (below)
     std::vector<std::string> fwd1, fwd2; // the options given that the first / second correction step of `correct -s` passes on
     bool no_snps = false;
     std::string out, graph, udata;
@@ -62,7 +64,9 @@ static void usage() {
     fprintf(stderr, "Ratatosk (MI355X hot-path build)\n\nUsage: Ratatosk correct -s <short_reads> [-s ...] -l <long_reads> -o <out_prefix> [options]\n"
                     "  both passes in one run: the index of each pass built from the short reads (rtk_build_index --gpu, k1 then k2), pass 1, pass 2;\n"
                     "  writes <out_prefix>.fastq (-G: .fastq.gz). With -1 or -2 (-2: -l <out_prefix>.2.fastq -L <long_reads>) the index of that pass and that pass only.\n"
-                    "  -F, --no-snp-correction  build the indexes without SNP annotations\n\n"
+                    "  -F, --no-snp-correction  build the indexes without SNP annotations\n"
+                    "  -u, --in-unmapped-short  unmapped short reads (may be repeated; or a text file of paths): those with enough k1-mers that the long reads hold and the -s reads\n"
+                    "                        do not are rescued first (rtk_rescue_reads --gpu, <out_prefix>_extra_sr.fasta, removed at the end) and join the short reads of the index builds\n\n"
                     "       Ratatosk correct -1 -g <graph.fasta.gz> -d <unitig_data.rtsk> -l <long_reads> -o <out_prefix> [options]\n"
                     "  -c, --cores           number of host threads (default 1): index parsing, FASTQ formatting\n"
                     "      --gpus            number of GPUs to use (default: all visible)\n"
@@ -112,6 +116,8 @@ static bool gzip_member(const std::string& in, std::string& out) { out.clear(); 
 // this process never opens the GPU. Both passes (neither -1 nor -2): the k1 index of the short reads, pass 1 into OUT.2.fastq, the k2 index of the short
 // reads coloured by OUT.2.fastq, pass 2 into OUT.fastq[.gz]; the temporary index files and OUT.2.fastq are removed afterwards (src/Ratatosk.cpp:1268-1277).
 // -1 / -2: the index of that pass, then that pass. The first step that fails ends the run (non-zero exit, the step named); nothing is tried again.
+// With -u the chain starts with the rescue (src/Ratatosk.cpp:1040-1056: every run without an index, also -1 / -2 alone): rtk_rescue_reads --gpu writes
+// OUT_extra_sr.fasta, which is a further -s of BOTH index steps (both graphs are built from the short reads here) and is removed at the end of the run.
 static int run_step(const char* what, const std::vector<std::string>& args, bool verbose) {
     std::vector<char*> av; for (size_t i = 0; i < args.size(); ++i) av.push_back(const_cast<char*>(args[i].c_str())); av.push_back(nullptr);
     if (verbose) { fprintf(stderr, "Ratatosk::correct: %s:", what); for (size_t i = 0; i < args.size(); ++i) fprintf(stderr, " %s", args[i].c_str()); fprintf(stderr, "\n"); }
@@ -134,11 +140,13 @@ static int correct_from_short_reads(const Opt& opt, const char* argv0) {
     if (opt.k1 < 3 || opt.k1 > 31 || !(opt.k1 & 1) || opt.k2 < 3 || opt.k2 > 63 || !(opt.k2 & 1)) { fprintf(stderr, "Ratatosk::correct: k1 must be odd and <= 31, k2 odd and <= 63\n"); return 1; }
     std::string self = argv0; // this executable and the index tool next to it
     { char exe[4096]; const ssize_t n = readlink("/proc/self/exe", exe, sizeof(exe) - 1); if (n > 0) { exe[n] = 0; self = exe; } }
-    const std::string dir = self.find('/') == std::string::npos ? std::string(".") : self.substr(0, self.rfind('/')), tool = dir + "/rtk_build_index";
+    const std::string dir = self.find('/') == std::string::npos ? std::string(".") : self.substr(0, self.rfind('/')), tool = dir + "/rtk_build_index", rescue_tool = dir + "/rtk_rescue_reads";
     if (opt.cores > 0 && std::find(opt.fwd1.begin(), opt.fwd1.end(), std::string("-c")) != opt.fwd1.end()) setenv("RTK_INDEX_THREADS", std::to_string(opt.cores).c_str(), 1); // (else the tool sizes itself by the machine)
+    std::string extra_sr; // OUT_extra_sr.fasta, when the rescue kept reads
     auto index_args = [&](int k, const std::string& prefix, const std::vector<std::string>& colour) {
         std::vector<std::string> a; a.push_back(tool); a.push_back("--gpu"); a.push_back("-k"); a.push_back(std::to_string(k));
         for (size_t i = 0; i < opt.in_short.size(); ++i) { a.push_back("-s"); a.push_back(opt.in_short[i]); }
+        if (!extra_sr.empty()) { a.push_back("-s"); a.push_back(extra_sr); }
         for (size_t i = 0; i < colour.size(); ++i) { a.push_back("--colour-reads"); a.push_back(colour[i]); }
         if (!opt.no_snps) a.push_back("--snps");
         a.push_back("-o"); a.push_back(prefix); return a;
@@ -151,15 +159,31 @@ static int correct_from_short_reads(const Opt& opt, const char* argv0) {
     const auto t0 = std::chrono::steady_clock::now();
     auto since = [&]() { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); };
     const bool v = opt.verbose;
+    std::vector<std::string> rescued; // removed when the run ends, however it ends
+    auto cleanup_all = [&]() { cleanup(); for (size_t i = 0; i < rescued.size(); ++i) unlink(rescued[i].c_str()); };
+    if (!opt.in_unmapped.empty()) {
+        // the long reads whose k-mers call for more short reads: the uncorrected ones (-2 alone: -L; its -l holds the reads of the first pass)
+        const std::vector<std::string>& lr_in = opt.pass2 ? opt.in_long_raw : opt.in_long;
+        std::vector<std::string> a; a.push_back(rescue_tool); a.push_back("--gpu"); a.push_back("-k"); a.push_back(std::to_string(opt.k1));
+        for (size_t i = 0; i < opt.in_short.size(); ++i) { a.push_back("-s"); a.push_back(opt.in_short[i]); }
+        for (size_t i = 0; i < lr_in.size(); ++i) { a.push_back("-l"); a.push_back(lr_in[i]); }
+        for (size_t i = 0; i < opt.in_unmapped.size(); ++i) { a.push_back("-u"); a.push_back(opt.in_unmapped[i]); }
+        if (v) a.push_back("-v");
+        a.push_back("-o"); a.push_back(opt.out);
+        const std::string fn = opt.out + "_extra_sr.fasta";
+        rescued.push_back(fn);
+        if (run_step("step 0 (rescue of unmapped short reads, rtk_rescue_reads)", a, v)) { cleanup_all(); return 1; }
+        if (access(fn.c_str(), R_OK) == 0) extra_sr = fn; // (no read kept: no file, the run goes on with -s alone, src/Graph.cpp:4124-4128)
+    }
     if (both || opt.pass1) {
         if (v) fprintf(stderr, "Ratatosk::Ratatosk(): Building graph from short reads (1/2).\n");
         tmp_files.push_back(f1.first); tmp_files.push_back(f1.second);
-        if (run_step("step 1 (k1 index, rtk_build_index)", index_args(opt.k1, pre1, std::vector<std::string>()), v)) { cleanup(); return 1; }
+        if (run_step("step 1 (k1 index, rtk_build_index)", index_args(opt.k1, pre1, std::vector<std::string>()), v)) { cleanup_all(); return 1; }
         if (v) fprintf(stderr, "Ratatosk::Ratatosk(): Correcting long reads (1/2). [%.1f s]\n", since());
         std::vector<std::string> a; a.push_back(self); a.push_back("correct"); a.push_back("-1"); a.push_back("-g"); a.push_back(f1.first); a.push_back("-d"); a.push_back(f1.second);
         for (size_t i = 0; i < opt.in_long.size(); ++i) { a.push_back("-l"); a.push_back(opt.in_long[i]); }
         a.push_back("-o"); a.push_back(opt.out); a.insert(a.end(), opt.fwd1.begin(), opt.fwd1.end());
-        if (run_step("step 2 (first correction pass)", a, v)) { cleanup(); return 1; }
+        if (run_step("step 2 (first correction pass)", a, v)) { cleanup_all(); return 1; }
         cleanup(); tmp_files.clear();
     }
     if (both || opt.pass2) {
@@ -167,15 +191,16 @@ static int correct_from_short_reads(const Opt& opt, const char* argv0) {
         if (both) tmp_files.push_back(mid);
         if (v) fprintf(stderr, "Ratatosk::Ratatosk(): Building graph from short reads (2/2). [%.1f s]\n", since());
         tmp_files.push_back(f2.first); tmp_files.push_back(f2.second);
-        if (run_step("step 3 (k2 index, rtk_build_index)", index_args(opt.k2, pre2, p1_reads), v)) { cleanup(); return 1; }
+        if (run_step("step 3 (k2 index, rtk_build_index)", index_args(opt.k2, pre2, p1_reads), v)) { cleanup_all(); return 1; }
         if (v) fprintf(stderr, "Ratatosk::Ratatosk(): Correcting long reads (2/2). [%.1f s]\n", since());
         std::vector<std::string> a; a.push_back(self); a.push_back("correct"); a.push_back("-2"); a.push_back("-g"); a.push_back(f2.first); a.push_back("-d"); a.push_back(f2.second);
         for (size_t i = 0; i < p1_reads.size(); ++i) { a.push_back("-l"); a.push_back(p1_reads[i]); }
         for (size_t i = 0; i < raw.size(); ++i) { a.push_back("-L"); a.push_back(raw[i]); }
         a.push_back("-o"); a.push_back(opt.out); a.insert(a.end(), opt.fwd2.begin(), opt.fwd2.end());
-        if (run_step("step 4 (second correction pass)", a, v)) { cleanup(); return 1; }
+        if (run_step("step 4 (second correction pass)", a, v)) { cleanup_all(); return 1; }
         cleanup();
     }
+    cleanup_all();
     if (v) fprintf(stderr, "Ratatosk::Ratatosk(): Done. [%.1f s]\n", since());
     return 0;
 }
@@ -226,7 +251,8 @@ int main(int argc, char** argv) {
             case 'I': case 'S': case 'M': case 'C': break; // only read by `index` (detectSNPs, .bfi, addCoverage: src/Ratatosk.cpp:1067,1124; src/Graph.cpp:1573,1796,2117)
             case 'O': break; // output is in input order in both passes here (src/Ratatosk.cpp:919 re-orders only when asked in pass 2)
             case 'f': opt.force_snp = true; break; // fixSNPs() before phasing() in the second pass (src/Ratatosk.cpp:279,828); the first pass does not look at it
-            case 'u': case 'a': case 'p': case 'P': fprintf(stderr, "Ratatosk::correct: -%c (unmapped-read rescue / helper long reads / phased input) is not in scope of this build\n", c); return 1;
+            case 'u': opt.in_unmapped.push_back(optarg); break; // (with -g / -d: refused below, once every option is read)
+            case 'a': case 'p': case 'P': fprintf(stderr, "Ratatosk::correct: -%c (helper long reads / phased input) is not in scope of this build\n", c); return 1;
             case 'L': opt.in_long_raw.push_back(optarg); break;
             case 'K': opt.k2 = atoi(optarg); break;
             case 'W': opt.w2 = strtoull(optarg, nullptr, 10); break;
@@ -248,6 +274,11 @@ int main(int argc, char** argv) {
     // `-l a.fq b.fq` corrects a.fq only. Same here, but said aloud.
     for (int i = optind; i < argc - 1; ++i) fprintf(stderr, "Ratatosk::correct: argument '%s' belongs to no option and is ignored (several input files: one -l each, or a text file of paths)\n", argv[1 + i]);
     if (!opt.in_short.empty() && opt.graph.empty() && opt.udata.empty()) return correct_from_short_reads(opt, argv[0]);
+    if (!opt.in_unmapped.empty() && opt.graph.empty() && opt.udata.empty()) { fprintf(stderr, "Ratatosk::correct: -u needs the mapped short reads (-s) it is compared with\n"); return 1; }
+    if (!opt.in_unmapped.empty()) { // the reference ignores -u when it is given an index (src/Ratatosk.cpp:1040: !hasIndex); said aloud here
+        fprintf(stderr, "Ratatosk::correct: -u (unmapped-read rescue) next to a pre-built index (-g, -d) is not in scope of this build: the rescue belongs to the index build (correct -s SHORT -u UNMAPPED -l LONG -o OUT)\n");
+        return 1;
+    }
     for (size_t i = 0; i < opt.in_short.size(); ++i) fprintf(stderr, "Ratatosk::correct: short reads are only needed by `index` (not in scope); ignored\n");
     if (opt.pass1 == opt.pass2) { fprintf(stderr, "Ratatosk::correct: one pass per run with a pre-built index (-g, -d): give -1 or -2\n"); return 1; }
     const bool lrc = opt.pass2;
