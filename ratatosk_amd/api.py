@@ -37,7 +37,8 @@ class RtkStats(C.Structure):
                                          "cyc_colour", "cyc_paths", "cyc_consensus", "cyc_total", "cyc_myers", "cyc_sets", "cyc_tostring", "cyc_pathqual", "n_slots_exact", "n_slots_inexact", "cyc_walk", "n_moves")] + \
                [("ms_lanes", C.c_double), ("n_lane_regions", C.c_uint64), ("n_lane_handed", C.c_uint64), ("ms_phase", C.c_double), ("n_phase_skipped", C.c_uint64)] + \
                [(n, C.c_uint64) for n in ("n_trim_stored", "n_trim_column", "n_trim_fallback", "n_consensus_resumed", "n_consensus_swept",
-                                         "n_fa_linked_run", "n_fa_linked_skipped", "n_fa_linked_entries")]
+                                         "n_fa_linked_run", "n_fa_linked_skipped", "n_fa_linked_entries",
+                                         "n_strand2_run", "n_strand2_skipped", "n_strand2_audit_mismatch")]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}

@@ -1807,6 +1807,91 @@ RTK_FN void rtk_emit_segment(const RCtx& c_, RegionDesc* rd_, const char* sq_, u
     rd->seg_off = off; rd->seq_len = sl; rd->qual_len = qll;
 }
 
+// ------------------------------------------------------------------------------------------------ the second strand of a gap region
+// A gap region that its forward strand does not settle alone (is_corrected, G20) is corrected again on the reverse complement, and the two results are merged
+// by rtk_generate_consensus. When the forward strand corrected every old position, the second strand can change the emitted bytes in two ways only: by coming
+// back is_corrected, or through one of the exits of the consensus that do not take the forward strings. rtk_strand2_skippable decides from the forward
+// result, the read and the graph that neither can happen; the region then emits the forward strings and runs neither the second strand nor the consensus.
+//
+// Lane-local. A corrected string of the second strand with a full bitmap ends in the graph k-mer behind one of the read's anchors (proof: DESIGN.md). Could
+// that be the anchor with mapping `um` (in the FORWARD read's orientation), and the string then pass the end test of rtk_correct_region, which compares it
+// with f = the forward read's first k-mer (A C G T only) reverse-complemented? false: surely not -- the two k-mers differ in a character that no annotation
+// can have rewritten. true: cannot be excluded.
+// Which characters of the k-mer fixAmbiguity can rewrite: those that an annotation of a unitig of the path covers (rtk_amb_collect). These are the unitig's
+// own annotations and, in the k - 1 characters that two consecutive unitigs of a path share, the neighbour's. The second strand's path reaches the k-mer
+// from the side that lies behind the anchor in the forward read, through `beyond` further k-mers of the unitig: a neighbour N on that side shares its first
+// k - 1 characters with the unitig's last, which are the k-mer's characters from beyond + 1 on; and where N holds fewer k-mers than that leaves uncovered, the
+// unitig before N reaches the k-mer too, and every character from there on counts as rewritable.
+RTK_DEV uint64_t rtk_strand2_amb_mask(const GraphView& g, uint32_t u, uint32_t lo, uint32_t n, bool fwd, uint32_t first_bit, uint32_t k) {
+    // bit first_bit + x for every annotation of unitig u at character lo + x (fwd) / lo + n - 1 - x (!fwd), x in [0, n), that falls below bit k
+    const uint64_t* ent = g.amb.get() + (static_cast<uint64_t>(g.n_unitigs) + 1);
+    uint64_t m = 0;
+    for (uint64_t e = g.amb[u]; e < g.amb[u + 1]; ++e) {
+        const uint32_t pos = static_cast<uint32_t>(ent[e] >> 4);
+        if (pos < lo || pos >= lo + n) continue;
+        const uint32_t bit = first_bit + (fwd ? (pos - lo) : (lo + n - 1u - pos));
+        if (bit < k) m |= 1ull << bit;
+    }
+    return m;
+}
+RTK_DEV bool rtk_strand2_end_may_match(const RCtx& c, const UMap& um, const char* f) {
+    const GraphView& g = c.g; const uint32_t k = static_cast<uint32_t>(c.k); // k <= 63: one bit per character of the k-mer, in the forward read's orientation
+    uint64_t soft = 0; // characters that may have been rewritten
+    if (g.n_amb != 0) {
+        soft = rtk_strand2_amb_mask(g, um.unitig, um.dist, k, um.strand != 0, 0, k);
+        const uint32_t beyond = um.strand ? (rtk_nkm(g, um.unitig) - 1u - um.dist) : um.dist;
+        if (beyond < k - 1u) {
+            const uint32_t* adj = g.adj.get() + 8ull * um.unitig + (um.strand ? 0 : 4);
+            for (uint32_t b = 0; b < 4; ++b) {
+                const uint32_t nb = adj[b];
+                if (nb == RTK_NONE32) continue;
+                const uint32_t v = nb >> 1, ul = rtk_ulen(g, v), nkm = ul - k + 1u;
+                const uint32_t shared = (k - 1u) < ul ? (k - 1u) : ul;
+                soft |= rtk_strand2_amb_mask(g, v, (nb & 1u) ? 0u : (ul - shared), shared, (nb & 1u) != 0, beyond + 1u, k);
+                if (beyond + 1u + nkm < k) soft |= ~0ull << (beyond + 1u + nkm);
+            }
+        }
+    }
+    for (uint32_t j = 0; j < k; ++j) {
+        if ((soft >> j) & 1ull) continue;
+        const char uc = rtk_unitig_char(g, um.unitig, um.strand ? (um.dist + j) : (um.dist + k - 1u - j));
+        if ((um.strand ? uc : rtk_comp(uc)) != f[j]) return false;
+    }
+    return true;
+}
+
+// Wave-uniform. fw: the forward result of gap region [pa, pb + k) of read s_fw, made with park = true and not is_corrected; so, i: the read's solid anchors and
+// the index of the one at pa; we, i_weak: the read's weak anchors and the first one at or after pa. (Anchors and indices, not the mappings: a UMap handed on by
+// reference would have to live on the caller's stack.) The conditions R1 .. R5 are those of DESIGN.md §3.2 (f).
+RTK_FN bool rtk_strand2_skippable(const RCtx& c_, const ResCorr& fw_, const char* s_fw_, uint32_t pa_, uint32_t pb_, const Anchors& so_, uint32_t i_, const Anchors& we_, uint32_t i_weak_) {
+    const RCtx& c = *rtk_u(&c_); const ResCorr& fw = *rtk_u(&fw_); RTK_ASSUME_LDS(&fw); const char* s_fw = rtk_u(s_fw_); const uint32_t pa = rtk_u(pa_), pb = rtk_u(pb_);
+    const Anchors& so = *rtk_u(&so_); RTK_ASSUME_LDS(&so); const uint32_t i = rtk_u(i_); const Anchors& we = *rtk_u(&we_); RTK_ASSUME_LDS(&we); const uint32_t i_weak = rtk_u(i_weak_);
+    RegionScratch& s = rtk_hdr(c);
+    const uint32_t k = static_cast<uint32_t>(c.k), ref_len = pb - pa + k;
+    const uint32_t fsl = rtk_u(fw.seq_len), fql = rtk_u(fw.qual_len);
+    // R1: every old position corrected -- the consensus does not swap the strands and its merge is one forward step over the whole raw region
+    if (rtk_bm_card(fw.bm, fw.old_len) != fw.old_len || fw.old_len != ref_len) return false;
+    // R2: the forward trim parked the alignment of exactly this string (what `parked()` of the consensus asks); the merge then copies fw.qual up to fw.seq_len
+    const TrimPark pk = s.loc.park;
+    if (pk.nm == 0 || fsl == 0 || pk.len != fsl || fql > fsl) return false;
+    // R3: the forward string passes the norm test of the consensus (the same doubles)
+    const double max_norm = c.o.weak_region_len_factor;
+    if (max_norm > 0.0 && static_cast<double>(pk.dist) / static_cast<double>(fsl > ref_len ? fsl : ref_len) > max_norm) return false;
+    // R4: the parked moves do not end in an insert (the merge stops at the end of the raw region and would leave trailing inserted characters out)
+    if (rtk_ld(reinterpret_cast<const uint8_t*>(s.rbuf[7].get()) + (pk.nm - 1u)) == 1) return false;
+    // R5: the second strand cannot come back is_corrected. Its fixAmbiguity rewrites annotated positions only when the raw region is plain, and the end test
+    // is a comparison of characters when the read's first k-mer is.
+    if (!rtk_all_acgt(s_fw, k) || !rtk_all_acgt(s_fw + pa, ref_len)) return false;
+    if (rtk_strand2_end_may_match(c, rtk_u(rtk_an_um(so, i)), s_fw) || rtk_strand2_end_may_match(c, rtk_u(rtk_an_um(so, i + 1)), s_fw)) return false;
+    const uint32_t w_hi = rtk_u(rtk_an_first_gt(we, i_weak, we.n, pb)); // the weak anchors of the second strand's region lie in (pa, pb]
+    for (uint32_t x0 = i_weak; x0 < w_hi; x0 += RTK_WAVE) {
+        const uint32_t x = x0 + static_cast<uint32_t>(rtk_lane());
+        const bool may = x < w_hi && rtk_strand2_end_may_match(c, rtk_an_um(we, x), s_fw);
+        if (rtk_ballot(may) != 0ull) return false;
+    }
+    return true;
+}
+
 RTK_FN_DRIVER void rtk_region_program(const RCtx& c_, RegionDesc* rd_) {
     const RCtx& c = *rtk_u(&c_); RegionDesc* rd = rtk_u(rd_);
     RegionScratch& s = rtk_hdr(c);
@@ -1892,8 +1977,20 @@ RTK_FN_DRIVER void rtk_region_program(const RCtx& c_, RegionDesc* rd_) {
                 rtk_app(s, out_s, &osl, s_fw + prev_pos, ks < l_solid ? ks : l_solid); if (ks > l_solid) rtk_app(s, out_s, &osl, seq, ks - l_solid);
                 app_q(prev_pos, kq < l_solid ? kq : l_solid, q_max); if (kq > l_solid) rtk_app(s, out_q, &oql, q, kq - l_solid);
             };
+            // 0: the second strand is skipped where the forward result decides the bytes alone (rtk_strand2_skippable); 1: it always runs; 2: it runs there too, and
+            // the full route's result is emitted and compared with the forward one (rtk_knobs.h: RTK_STRAND2_ALWAYS, RTK_STRAND2_AUDIT)
+            const uint32_t s2_mode = rtk_u(c.o.strand2_mode);
+            const bool skippable = !fw.is_corrected && s2_mode != 1u && rtk_strand2_skippable(c, fw, s_fw, pa, pb, so, i, we, i_weak);
             if (fw.is_corrected) emit_minus_k(fw.seq, fw.seq_len, fw.qual, fw.qual_len);
-            else {
+            else if (skippable && s2_mode == 0u) {
+                s.cnt[RTK_RC_STRAND2_SKIPPED] += 1;
+                s.cnt[RTK_RC_CONS_RESUMED] += 1; // the consensus of this region is decided from the stored sweep of the forward trim alone (R2 .. R4): counted as the call it replaces
+                emit_minus_k(fw.seq, fw.seq_len, fw.qual, fw.qual_len);
+            } else {
+                s.cnt[skippable ? RTK_RC_STRAND2_SKIPPED : RTK_RC_STRAND2_RUN] += 1; // (the audit counts the rule's verdicts and runs both kinds)
+                auto audit = [&](const char* seq, uint32_t sl, const char* q, uint32_t ql) { // what the full route is about to emit against the forward strings
+                    if (skippable && !(sl == fw.seq_len && ql == fw.qual_len && rtk_str_equal(seq, fw.seq, sl) && rtk_str_equal(q, fw.qual, ql))) s.cnt[RTK_RC_STRAND2_AUDIT_MISMATCH] += 1;
+                };
                 const uint32_t i_solid_bw = so.n - i - 2;
                 uint32_t i_weak_bw = we.n - i_weak;
                 i_weak_bw = rtk_an_first_gt(we_r, 0, i_weak_bw, rtk_an_pos(so_r, i_solid_bw));
@@ -1905,6 +2002,7 @@ RTK_FN_DRIVER void rtk_region_program(const RCtx& c_, RegionDesc* rd_) {
                 rtk_rc_reverse_complement(s, bw, s.bm[2], s.rbuf[6]);
                 if (bw.is_corrected) {
                     // l_solid = (|s_bw| - rev_pos(i_solid_bw + 1) - k) - prev_pos == pa - prev_pos
+                    audit(bw.seq, bw.seq_len, bw.qual, bw.qual_len);
                     emit_minus_k(bw.seq, bw.seq_len, bw.qual, bw.qual_len);
                 } else {
                     const uint32_t ref_len = pb - pa + k;
@@ -1920,6 +2018,7 @@ RTK_FN_DRIVER void rtk_region_program(const RCtx& c_, RegionDesc* rd_) {
                         if (lrc) rtk_app(s, s.rbuf[7], &cql, q_fw + pa, ref_len); // :902
                         else { rtk_app_fill(s, s.rbuf[7], &cql, q_max, k); rtk_app_fill(s, s.rbuf[7], &cql, q_min, pb - pa); }
                     }
+                    audit(s.rbuf[6], csl, s.rbuf[7], cql);
                     emit_minus_k(s.rbuf[6], csl, s.rbuf[7], cql);
                 }
             }
