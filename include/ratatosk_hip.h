@@ -117,6 +117,11 @@ typedef struct rtk_stats {
      * RTK_STRAND2_AUDIT=1 runs and emits the full route where the rule says skip and counts the regions whose bytes then differ from the forward result
      * (n_strand2_audit_mismatch: 0 unless the rule is wrong). Appended without a new revision number: see RTK_API_REVISION. */
     uint64_t n_strand2_run, n_strand2_skipped, n_strand2_audit_mismatch;
+    /* The stored sweep of a gap region's forward trim (n_trim_stored) holds the alignment the consensus would ask for. Its path is walked and parked only where
+     * the region goes on to its second strand (n_park_walked); where the second strand is skipped, or the sweep cannot be parked, nobody walks it
+     * (n_park_deferred). n_park_walked + n_park_deferred == n_trim_stored; n_moves counts the moves of the walks that were made. RTK_PARK_EAGER=1 walks every
+     * sweep that can be parked at the trim, as before. Appended without a new revision number, like the fields above. */
+    uint64_t n_park_walked, n_park_deferred;
 } rtk_stats;
 
 /* dbg.read(G.fasta.gz) + readGraphData(G.rtsk) (reference: src/Ratatosk.cpp:1087-1089; src/Graph.cpp:722-784).
@@ -257,11 +262,15 @@ int rtk_myers_batch_waves(uint32_t n, const char* const* query, const uint32_t* 
  *     of end locations, of which end_locs holds the first (slot 0) and the last (slot n_loc - 1) only: the route does not list the others. No path.
  *   RTK_MYERS_MODE_NW_PREFIX: 0 <= k <= qlen. The NW distance and, with want_path, the path of (query[0, k), target), walked from row k of the stored NW sweep of
  *     the WHOLE query; end_locs[0] = tlen - 1.
+ *   RTK_MYERS_MODE_NW_PREFIX_LAST: 0 <= k <= qlen. The NW distance of (query[0, k), target) and in end_locs[0] the LAST move of the path mode 4 walks (0 match,
+ *     1 insert, 2 delete, 3 mismatch), read off the stored sweep without a walk (rtk_myers_last_move: what the deferred park of the forward trim keeps of its
+ *     path); -1 where there is no path (k = 0 or an empty target). No path is returned.
  * A problem the route does not take (a target byte other than A C G T -- the sweep's target: the query in mode 3 --, more than 4096 characters in the swept
  * query, a table or move list too big for the in-memory traceback, an empty string) is answered by the calls the route replaces. How the calling thread's last
  * rtk_myers_batch call split its problems of these modes: rtk_myers_column_last_routes (a route that took nothing would pass on the fallback's results). */
 #define RTK_MYERS_MODE_SHW_BY_COLUMN 3
 #define RTK_MYERS_MODE_NW_PREFIX 4
+#define RTK_MYERS_MODE_NW_PREFIX_LAST 5
 void rtk_myers_column_last_routes(uint64_t* column_route, uint64_t* fallback);
 
 /* rtk_myers_batch with ONE PROBLEM PER LANE: queries of up to 512 characters against targets of up to 2048 over A, C, G, T, N are computed column by column in a
@@ -320,7 +329,7 @@ const char* rtk_last_error(void);
 const char* rtk_version(void);
 /* Interface revision, raised whenever a struct of this header grows or a default changes (5: rtk_opts.struct_size, rtk_stats lane fields, a2_exclusive default 1;
  * 7: rtk_stats route fields n_trim_* / n_consensus_*, the test-only rtk_myers_batch modes 3 and 4, rtk_myers_column_last_routes;
- * 8: rtk_stats fields n_fa_linked_*; 9: rtk_rescue_begin / _chunk / _end; still 9: rtk_stats fields n_strand2_*, appended at the end -- a library of revision 9
+ * 8: rtk_stats fields n_fa_linked_*; 9: rtk_rescue_begin / _chunk / _end; still 9: rtk_stats fields n_strand2_* and n_park_*, the test-only rtk_myers_batch mode 5, appended at the end -- a library of revision 9
  * without them leaves them as the caller set them, and the number stays because tests/test_rescue_reads.py pins it: the next change of this header takes 10). */
 #define RTK_API_REVISION 9
 int rtk_api_revision(void);

@@ -38,7 +38,8 @@ class RtkStats(C.Structure):
                [("ms_lanes", C.c_double), ("n_lane_regions", C.c_uint64), ("n_lane_handed", C.c_uint64), ("ms_phase", C.c_double), ("n_phase_skipped", C.c_uint64)] + \
                [(n, C.c_uint64) for n in ("n_trim_stored", "n_trim_column", "n_trim_fallback", "n_consensus_resumed", "n_consensus_swept",
                                          "n_fa_linked_run", "n_fa_linked_skipped", "n_fa_linked_entries",
-                                         "n_strand2_run", "n_strand2_skipped", "n_strand2_audit_mismatch")]
+                                         "n_strand2_run", "n_strand2_skipped", "n_strand2_audit_mismatch",
+                                         "n_park_walked", "n_park_deferred")]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -354,11 +355,11 @@ def rescue_reads(lr_kmers, sr_kmers, seqs, k=31, min_positions=31, device=0, sta
     return out
 
 
-MODE_SHW_BY_COLUMN, MODE_NW_PREFIX = 3, 4  # test-only modes of myers_batch (include/ratatosk_hip.h)
+MODE_SHW_BY_COLUMN, MODE_NW_PREFIX, MODE_NW_PREFIX_LAST = 3, 4, 5  # test-only modes of myers_batch (include/ratatosk_hip.h)
 
 
 def myers_column_last_routes(lib_path=None):
-    """(problems taken by the column route, problems answered by the calls it replaces) of this thread's last myers_batch call in modes 3 / 4."""
+    """(problems taken by the column route, problems answered by the calls it replaces) of this thread's last myers_batch call in modes 3 / 4 / 5."""
     L = load_library(lib_path)
     a, b = C.c_uint64(), C.c_uint64()
     L.rtk_myers_column_last_routes.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]; L.rtk_myers_column_last_routes.restype = None

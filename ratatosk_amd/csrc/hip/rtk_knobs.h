@@ -57,6 +57,7 @@ inline int rtk_knob_p2_rgrid() { return rtk_env_int("RTK_P2_RGRID", 512); }     
 inline bool rtk_knob_fa_linked_always() { return rtk_env_is1("RTK_FA_LINKED_ALWAYS"); } // '1': fixAmbiguity runs every linked-allele search, also those that cannot append (same results; parity test, A/B traces)
 inline bool rtk_knob_strand2_always() { return rtk_env_is1("RTK_STRAND2_ALWAYS"); } // '1': every gap region that is not corrected by its forward strand alone runs the second strand, as the reference does (same results; parity test, A/B timing)
 inline bool rtk_knob_strand2_audit() { return rtk_env_is1("RTK_STRAND2_AUDIT"); }   // '1': where the rule would skip the second strand the full route runs and is emitted, and every difference to the forward result is counted (rtk_stats::n_strand2_audit_mismatch)
+inline bool rtk_knob_park_eager() { return rtk_env_is1("RTK_PARK_EAGER"); }         // '1': the forward trim of a gap region walks and parks its alignment right away, also where no consensus will read it (same results; parity test, A/B timing)
 inline bool rtk_knob_test_coalesce_fail() { return rtk_env_set("RTK_TEST_COALESCE_FAIL"); } // flag, test hook: a merged batch is reported as failed (its members must come through on their own)
 
 // ---- region stage and rtk_correct_batch: read ONCE per process (the first call fixes the value)

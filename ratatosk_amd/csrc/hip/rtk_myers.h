@@ -1332,6 +1332,24 @@ RTK_FN void rtk_myers_walk(const MyersScratch& sc_, int m_, int n_, int ncols_, 
     { MyersScratch& msc = const_cast<MyersScratch&>(sc); msc.walk_cycles += rtk_clock() - tw0; msc.walk_moves += nt; msc.walk_reloads += n_rel; msc.walk_scalar += n_sc; msc.walk_calls += 1; msc.walk_tail_cycles += rtk_clock() - tw1; }
 }
 
+// The LAST move of the path rtk_myers_walk(sc, m, n, ncols, cur, ...) would append (m, n >= 1): the walk produces its moves backwards, so that is its first
+// step, out of cell (m, n) -- one look at the two table entries around that cell with the walk's own preferences (insert > delete > diagonal; a diagonal
+// is a match, 0, when it keeps the score and a mismatch, 3, when it does not). Nothing is walked and sc.moves is not touched. Wave-uniform: every lane
+// reads the same two entries, of word (m - 1) / 64 whatever the word count of the table.
+RTK_DEV uint8_t rtk_myers_last_move(const MyersScratch& sc_, int m_, int n_, int ncols_, int cur_) {
+    const MyersScratch& sc = *rtk_u(&sc_); RTK_ASSUME_LDS(&sc);
+    const int m = rtk_u(m_), n = rtk_u(n_), ncols = rtk_u(ncols_), cur = rtk_u(cur_);
+    const uint64_t* const tbp = rtk_ld(&sc.tb);
+    const int r = m - 1, c = n - 1, w = r >> 6, b = r & 63;
+    uint64_t a0, a1, a2, a3; rtk_tb_get(tbp + 4ull * RTK_TB(c, w, ncols), a0, a1, a2, a3);
+    if (static_cast<int>((a0 >> b) & 1ull) - static_cast<int>((a1 >> b) & 1ull) == 1) return 1; // vertical delta +1: up
+    const int hd = static_cast<int>((a2 >> b) & 1ull) - static_cast<int>((a3 >> b) & 1ull);
+    if (hd == 1) return 2; // horizontal delta +1: left
+    int diag = m - 1; // column 0: D[m - 1][0]
+    if (c > 0) { uint64_t l0, l1, l2, l3; rtk_tb_get(tbp + 4ull * RTK_TB(c - 1, w, ncols), l0, l1, l2, l3); diag = cur - hd - (static_cast<int>((l0 >> b) & 1ull) - static_cast<int>((l1 >> b) & 1ull)); }
+    return (diag == cur) ? 0 : 3;
+}
+
 RTK_FN void rtk_myers_traceback(const MyersScratch& sc_, MySeq q_, MySeq t_, bool iupac_, uint32_t* n_moves_) {
     const MyersScratch& sc = *rtk_u(&sc_); RTK_ASSUME_LDS(&sc); uint32_t* n_moves = rtk_u(n_moves_); const bool iupac = rtk_u(iupac_);
     MySeq q, t; q.p = rtk_u(q_.p); q.n = rtk_u(q_.n); q.rev = rtk_u(q_.rev); t.p = rtk_u(t_.p); t.n = rtk_u(t_.n); t.rev = rtk_u(t_.rev);
@@ -1572,28 +1590,35 @@ struct MyersSaved { uint32_t valid, gen; int32_t m, n, nw_dist; MyersResult shw;
 RTK_FN bool rtk_myers_nw_and_save(const MyersScratch& sc_, const char* q_, int m_, const char* t_, int n_, bool iupac_, MyersSaved* out_) {
     const MyersScratch& sc = *rtk_u(&sc_); RTK_ASSUME_LDS(&sc); const char* q = rtk_u(q_); const char* t = rtk_u(t_); const int m = rtk_u(m_), n = rtk_u(n_); const bool iupac = rtk_u(iupac_); MyersSaved* out = rtk_u(out_);
     out->valid = 0;
-#ifndef RTK_SIM
     const long long W = (m + 63) >> 6;
     if (!(m > 0 && n > 0 && m <= 4096 && static_cast<uint64_t>(4 * W * n) <= sc.tb_cap_words && static_cast<uint32_t>(m + n) <= sc.mv_cap && static_cast<uint32_t>(n) <= sc.t_cap &&
           static_cast<uint32_t>(m) <= sc.r_cap && static_cast<uint32_t>(W) <= sc.w_cap)) return false;
+    int sbest = 0x7fffffff, sfirst = -1, slast = -1, scnt = 0, sfinal; // the last row of the sweep: its minimum, where it lies, and D[m][n]
+#ifndef RTK_SIM
     MyersScratch& msc = const_cast<MyersScratch&>(sc); const uint32_t gen = rtk_ld(&msc.tb_gen) + 1u; msc.tb_gen = gen;
     const SweepStat st = rtk_myers_fast_any<1, 1>(q, m, t, n, 1, iupac, rtk_ld(&sc.tb));
     rtk_sync();
     if (!st.plain) return false;
+    sbest = st.best; sfirst = st.first; slast = st.last; scnt = st.cnt; sfinal = st.final_score;
+#else
+    // the 1-lane build takes the same route with the generic pass: the same pairs (a target of A/C/G/T only: the device sweep's own test), the same stored table, the
+    // last-row minimum read off colscore -- so that both builds make, and count, the same alignments
+    for (int j = 0; j < n; ++j) { const char ch = t[j]; if (!(ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T')) return false; }
+    MyersScratch& msc = const_cast<MyersScratch&>(sc); const uint32_t gen = rtk_ld(&msc.tb_gen) + 1u; msc.tb_gen = gen;
+    rtk_myers_pass(sc, rtk_seq(q, m), rtk_seq(t, n), 1, iupac, 1, nullptr, nullptr);
+    sfinal = sc.colscore[n - 1];
+    for (int j = 0; j < n; ++j) { const int v = sc.colscore[j]; if (v < sbest) { sbest = v; sfirst = slast = j; scnt = 1; } else if (v == sbest) { slast = j; ++scnt; } }
+#endif
     MyersResult r; // same bookkeeping as rtk_myers_distance (SHW)
-    int best = st.best; const bool pseudo = (m & 63) != 0;
+    int best = sbest; const bool pseudo = (m & 63) != 0;
     if (pseudo && m < best) best = m;
     r.dist = best;
-    if (pseudo && m == best) { r.first = -1; r.last = (st.best == best) ? st.last : -1; r.nloc = 1 + ((st.best == best) ? st.cnt : 0); }
-    else { r.first = st.first; r.last = st.last; r.nloc = st.cnt; }
-    out->m = m; out->n = n; out->nw_dist = st.final_score; out->shw = r; out->gen = gen;
+    if (pseudo && m == best) { r.first = -1; r.last = (sbest == best) ? slast : -1; r.nloc = 1 + ((sbest == best) ? scnt : 0); }
+    else { r.first = sfirst; r.last = slast; r.nloc = scnt; }
+    out->m = m; out->n = n; out->nw_dist = sfinal; out->shw = r; out->gen = gen;
     const long long tn = r.first + 1;
     out->valid = (tn > 0 && (2LL * 8 + 4) * W * tn + 8LL * tn < 1024 * 1024) ? 1u : 0u; // the in-memory traceback branch of obtainAlignment (edlib.cpp:1191-1193)
     return true;
-#else
-    (void)sc; (void)q; (void)t; (void)m; (void)n; (void)iupac;
-    return false;
-#endif
 }
 RTK_FN bool rtk_myers_path_from_saved(const MyersScratch& sc_, const MyersSaved& sv_, uint32_t* n_moves_, MyersResult* r_) {
     const MyersScratch& sc = *rtk_u(&sc_); RTK_ASSUME_LDS(&sc); const MyersSaved& sv = *rtk_u(&sv_); uint32_t* n_moves = rtk_u(n_moves_); MyersResult* r = rtk_u(r_);

@@ -19,6 +19,9 @@
 #include "rtk_sets.h"
 #include "rtk_types.h"
 #include "rtk_wave.h"
+#ifdef RTK_SIM
+#include <assert.h>
+#endif
 
 // ------------------------------------------------------------------------------------------------ data
 struct RegionDesc { // one entry per output segment of a read, in read order
@@ -67,8 +70,10 @@ struct ResCorr { char* seq; char* qual; uint32_t seq_len, qual_len; uint64_t* bm
 // header (LDS in the kernels) instead of the wave's stack, where every wave-uniform word is a 256-byte row per store and per load
 // state of one rtk_correct_region call that its three parts hand on (side lists + colours | path search | assembly + trim)
 struct RegionCall { const char* s_read; const char* q_read; uint64_t complete; UMap um1, um2; uint32_t s_len, p1, p2, first_pos, len_weak_region, lw_lo, lw_hi, n_all, n_partial, n_amb, has_end_pt, found_first, lrc; };
-// the forward trim of a gap region, kept for the consensus (rtk_trim_by_column): nm moves of NW(rbuf[0][0, len), raw region) parked in rbuf[7], distance dist; nm = 0: none
-struct TrimPark { uint32_t nm, len; int32_t dist; };
+// the forward trim of a gap region, kept for the consensus (rtk_trim_by_column): the alignment NW(rbuf[0][0, len), raw region of n characters), distance dist, whose
+// path ends in last_move. pending: the path is still in the stored sweep (table generation gen) and rtk_park_walk makes it when a consensus is going to run; else
+// nm moves are parked in rbuf[7] (nm = 0 and not pending: nothing parked)
+struct TrimPark { uint32_t nm, len; int32_t dist; uint32_t n, last_move, pending, gen; };
 struct DriverLocals { Anchors an[4]; ResCorr rc[2]; SideList side[3]; uint32_t len[6]; int best[2]; MyersSaved saved; RegionCall call; TrimPark park; MyersResult trim; };
 
 struct RegionScratch {
@@ -461,10 +466,34 @@ RTK_FN_HOT MyersResult rtk_align_path(const RCtx& c_, const char* q_, uint32_t m
     return r;
 }
 
+// The walk of a pending park (TrimPark, rtk_trim_by_column below) and its copy to rbuf[7]; no park pending: nothing. Between the trim and this call nothing may write the Myers table: the trim is
+// the last alignment of rtk_correct_region, and rtk_region_program calls this at its decision about the second strand, with rtk_strand2_skippable -- which
+// aligns nothing -- in between. (s.my.moves is written here and copied at once, so what it held does not matter.)
+RTK_FN void rtk_park_walk(const RCtx& c_) {
+    const RCtx& c = *rtk_u(&c_); RegionScratch& s = rtk_hdr(c);
+    TrimPark& pk = s.loc.park;
+    if (!pk.pending) return;
+#ifdef RTK_SIM
+    assert(pk.gen == s.my.tb_gen); // the table still holds the sweep of the trim
+#endif
+    const unsigned long long t1 = rtk_clock();
+    pk.pending = 0;
+    uint32_t& nm = pk.nm; nm = 0;
+    rtk_myers_walk(s.my, static_cast<int>(pk.len), static_cast<int>(pk.n), static_cast<int>(pk.n), pk.dist, &nm);
+    if (nm <= s.str_cap) rtk_wcopy(s.rbuf[7], s.my.moves, nm);
+    else nm = 0;
+    s.cnt[RTK_RC_PARK_WALKED] += 1; s.cnt[RTK_RC_PARK_DEFERRED] -= 1;
+    s.cnt[RTK_RC_CYC_MYERS] += rtk_clock() - t1;
+}
+
 // The trim of rtk_correct_region, edlibAlign(raw, corr, SHW), read off the last column of ONE NW sweep of (corr, raw) (rtk_myers_shw_by_column): a plain
 // NW step instead of the distance call's step with last-row tracking. park: the sweep is stored, and when the consensus's forward alignment -- NW path of the
 // trimmed string corr[0, keep) against this raw region (rtk_generate_consensus) -- would take the in-memory traceback of rtk_myers_path, its moves are walked
-// from row keep right away (D[keep][|raw|] is the minimum the trim found) and parked in rbuf[7], which only the consensus writes, after it has read them.
+// from row keep (D[keep][|raw|] is the minimum the trim found) and parked in rbuf[7], which only the consensus writes, after it has read them. Most gap regions
+// never run a consensus (rtk_strand2_skippable), and the rule that decides so asks three things of the park: that it exists, its distance and its LAST move. So
+// the trim only notes those (rtk_myers_last_move: one look at the table) and leaves the park pending; rtk_region_program has rtk_park_walk make the walk and the
+// copy where the region does go on to its second strand. RTK_PARK_EAGER=1 (tests, A/B runs) walks right here; so does a pair whose
+// moves might not fit the string buffers (the walk then clears the park; the consensus sweeps the pair itself and reports the overflow).
 // false: the route does not apply (no result, no alignment counted) and the caller makes the distance call.
 RTK_FN bool rtk_trim_by_column(const RCtx& c_, const char* raw_, uint32_t n_, const char* corr_, uint32_t m_, bool park_, MyersResult* out_) {
     const RCtx& c = *rtk_u(&c_); RegionScratch& s = rtk_hdr(c); const char* raw = rtk_u(raw_); const char* corr = rtk_u(corr_);
@@ -477,19 +506,19 @@ RTK_FN bool rtk_trim_by_column(const RCtx& c_, const char* raw_, uint32_t n_, co
     RTK_SITE(park ? 18 : 19); rtk_site_note(m, n, -1, park); rtk_pair_note(corr, m, raw, n);
     s.cnt[park ? RTK_RC_TRIM_STORED : RTK_RC_TRIM_COLUMN] += 1;
     if (!park) return true;
+    s.cnt[RTK_RC_PARK_DEFERRED] += 1; // a stored sweep that nothing has walked (yet: rtk_park_walk takes it back)
     // the conditions of rtk_myers_path's in-memory route for (corr[0, keep), raw) that the stored sweep of all of corr has not checked already
     const uint32_t keep = (out->first == -1) ? 0u : static_cast<uint32_t>(out->last + 1);
     const long long W = (keep + 63) >> 6;
     if (keep == 0 || keep > s.my.r_cap || keep + n > s.my.mv_cap || !((2LL * 8 + 4) * W * n + 8LL * n < 1024 * 1024)) return true;
     const unsigned long long t1 = rtk_clock();
-    uint32_t& nm = s.loc.park.nm; nm = 0;
-    rtk_myers_walk(s.my, static_cast<int>(keep), static_cast<int>(n), static_cast<int>(n), out->dist, &nm);
-    if (nm <= s.str_cap) { rtk_wcopy(s.rbuf[7], s.my.moves, nm); s.loc.park.len = keep; s.loc.park.dist = out->dist; }
-    else nm = 0;
+    TrimPark& pk = s.loc.park;
+    pk.nm = 0; pk.len = keep; pk.dist = out->dist; pk.n = n; pk.gen = rtk_ld(&s.my.tb_gen); pk.pending = 1;
+    pk.last_move = rtk_myers_last_move(s.my, static_cast<int>(keep), static_cast<int>(n), static_cast<int>(n), out->dist);
     s.cnt[RTK_RC_CYC_MYERS] += rtk_clock() - t1;
+    if (rtk_u(c.o.park_eager) || keep + n > s.str_cap) rtk_park_walk(c);
     return true;
 }
-
 #include "rtk_ambiguity.h"
 
 // ------------------------------------------------------------------------------------------------ candidate selection (src/Alignment.cpp:3-147, 967-1015)
@@ -1677,7 +1706,7 @@ RTK_FN bool rtk_generate_consensus(const RCtx& c_, const ResCorr* fw_, const Res
     else if (nfw + nbw == 0) return false;
     if (nbw > nfw) { const ResCorr* t = fw; fw = bw; bw = t; }
     // NW path alignments of both corrections against the raw region; the moves are parked in str[3] (fw) and str[4] (bw). The alignment of the
-    // forward strand's string was walked by its trim already (rtk_trim_by_column: s.loc.park, moves in rbuf[7], which is written below only).
+    // forward strand's string was walked from its trim's sweep already (rtk_trim_by_column, rtk_park_walk: s.loc.park, moves in rbuf[7], which is written below only).
     const TrimPark pk = s.loc.park;
     auto parked = [&](const ResCorr* x) { return pk.nm != 0 && x->seq_len == pk.len && (x->seq == s.rbuf[0].get() || rtk_str_equal(x->seq, s.rbuf[0], pk.len)); };
     auto resume = [&](char* dst, uint32_t* nm) { MyersResult r; r.dist = pk.dist; r.first = r.last = static_cast<int32_t>(ref_len) - 1; r.nloc = 1; *nm = pk.nm; rtk_wcopy(dst, s.rbuf[7], pk.nm); return r; };
@@ -1873,12 +1902,13 @@ RTK_FN bool rtk_strand2_skippable(const RCtx& c_, const ResCorr& fw_, const char
     if (rtk_bm_card(fw.bm, fw.old_len) != fw.old_len || fw.old_len != ref_len) return false;
     // R2: the forward trim parked the alignment of exactly this string (what `parked()` of the consensus asks); the merge then copies fw.qual up to fw.seq_len
     const TrimPark pk = s.loc.park;
-    if (pk.nm == 0 || fsl == 0 || pk.len != fsl || fql > fsl) return false;
+    if ((pk.nm == 0 && !pk.pending) || fsl == 0 || pk.len != fsl || fql > fsl) return false; // (a pending park stands for nm != 0: its walk makes at least one move)
     // R3: the forward string passes the norm test of the consensus (the same doubles)
     const double max_norm = c.o.weak_region_len_factor;
     if (max_norm > 0.0 && static_cast<double>(pk.dist) / static_cast<double>(fsl > ref_len ? fsl : ref_len) > max_norm) return false;
-    // R4: the parked moves do not end in an insert (the merge stops at the end of the raw region and would leave trailing inserted characters out)
-    if (rtk_ld(reinterpret_cast<const uint8_t*>(s.rbuf[7].get()) + (pk.nm - 1u)) == 1) return false;
+    // R4: the parked moves do not end in an insert (the merge stops at the end of the raw region and would leave trailing inserted characters out); the last
+    // move is known from the trim, whether the path has been walked or not
+    if (pk.last_move == 1u) return false;
     // R5: the second strand cannot come back is_corrected. Its fixAmbiguity rewrites annotated positions only when the raw region is plain, and the end test
     // is a comparison of characters when the read's first k-mer is.
     if (!rtk_all_acgt(s_fw, k) || !rtk_all_acgt(s_fw + pa, ref_len)) return false;
@@ -1895,7 +1925,7 @@ RTK_FN bool rtk_strand2_skippable(const RCtx& c_, const ResCorr& fw_, const char
 RTK_FN_DRIVER void rtk_region_program(const RCtx& c_, RegionDesc* rd_) {
     const RCtx& c = *rtk_u(&c_); RegionDesc* rd = rtk_u(rd_);
     RegionScratch& s = rtk_hdr(c);
-    s.loc.park.nm = 0; // nothing parked for this region yet
+    s.loc.park.nm = 0; s.loc.park.pending = 0; // nothing parked for this region yet
     const uint32_t r = rtk_u(rd->read), k = static_cast<uint32_t>(c.k);
     const uint64_t base = rtk_u(c.bv.roff[r]);
     const uint32_t L = rtk_u(static_cast<uint32_t>(c.bv.roff[r + 1] - base));
@@ -1988,6 +2018,7 @@ RTK_FN_DRIVER void rtk_region_program(const RCtx& c_, RegionDesc* rd_) {
                 emit_minus_k(fw.seq, fw.seq_len, fw.qual, fw.qual_len);
             } else {
                 s.cnt[skippable ? RTK_RC_STRAND2_SKIPPED : RTK_RC_STRAND2_RUN] += 1; // (the audit counts the rule's verdicts and runs both kinds)
+                rtk_park_walk(c); // the consensus may run now: the forward alignment is walked from the trim's sweep before the second strand overwrites the table
                 auto audit = [&](const char* seq, uint32_t sl, const char* q, uint32_t ql) { // what the full route is about to emit against the forward strings
                     if (skippable && !(sl == fw.seq_len && ql == fw.qual_len && rtk_str_equal(seq, fw.seq, sl) && rtk_str_equal(q, fw.qual, ql))) s.cnt[RTK_RC_STRAND2_AUDIT_MISMATCH] += 1;
                 };

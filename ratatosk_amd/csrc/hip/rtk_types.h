@@ -192,7 +192,9 @@ enum RtkCounterSlot {
     RTK_CNT_FA_LINKED_END = 214,
     RTK_CNT_STRAND2 = 214,          // [3] k_regions, gap regions whose forward strand did not decide alone: second strand run / skipped, audit mismatches (RTK_RC_STRAND2_RUN ..) -> rtk_stats
     RTK_CNT_STRAND2_END = 217,
-    RTK_CNT_USED_END = RTK_CNT_STRAND2_END,
+    RTK_CNT_PARK = 217,             // [2] k_regions, stored sweeps of the forward trims: walked for a consensus / never walked (RTK_RC_PARK_WALKED ..) -> rtk_stats
+    RTK_CNT_PARK_END = 219,
+    RTK_CNT_USED_END = RTK_CNT_PARK_END,
     RTK_CNT_TOTAL = (RTK_CNT_USED_END + 31) / 32 * 32 // words in the block: what is used, rounded up to 256 bytes (the tail is free)
 };
 static_assert(RTK_CNT_TOTAL == 224, "counter map: the size of the block changed (it is part of what the kernels and the host agree on)");
@@ -207,6 +209,7 @@ static_assert(RTK_CNT_LANE_END <= RTK_CNT_ROUTES && RTK_CNT_ROUTES_END <= RTK_CN
 static_assert(RTK_CNT_LANE_END <= RTK_CNT_LANE_PROF && RTK_CNT_LANE_PROF2 - RTK_CNT_LANE_PROF == 24 && RTK_CNT_LANE_PROF_END <= RTK_CNT_PHASE_SKIPPED && RTK_CNT_PHASE_SKIPPED < RTK_CNT_TOTAL, "counter map: the lane ranges overlap");
 static_assert(RTK_CNT_PHASE_SKIPPED < RTK_CNT_FA_LINKED && RTK_CNT_FA_LINKED_END <= RTK_CNT_TOTAL, "counter map: the fixAmbiguity counters overlap the phasing slot or leave the block");
 static_assert(RTK_CNT_FA_LINKED_END <= RTK_CNT_STRAND2 && RTK_CNT_STRAND2_END <= RTK_CNT_TOTAL, "counter map: the second-strand counters overlap the fixAmbiguity counters or leave the block");
+static_assert(RTK_CNT_STRAND2_END <= RTK_CNT_PARK && RTK_CNT_PARK_END <= RTK_CNT_TOTAL, "counter map: the park counters overlap the second-strand counters or leave the block");
 static_assert(rtk_cnt_apart(RTK_CNT_PHASE_TRACE, RTK_CNT_PHASE_TRACE_END, RTK_CNT_FINALIZE_SLOWEST_PHASES, RTK_CNT_FINALIZE_SLOWEST_PHASES_END), "counter map: the two guests of the size-class table overlap");
 static_assert(RTK_CNT_HIST <= RTK_CNT_PHASE_TRACE && RTK_CNT_FINALIZE_SLOWEST_PHASES_END <= RTK_CNT_HIST_END, "counter map: the guests of the size-class table left it (update the comment above)");
 
@@ -222,10 +225,14 @@ enum RtkRegionCnt { RTK_RC_EXPAND = 0, RTK_RC_COLOUR = 1, RTK_RC_PATHBASE = 2, R
     RTK_RC_FA_LINKED_RUN = 21, RTK_RC_FA_LINKED_SKIPPED = 22, RTK_RC_FA_LINKED_ENTRIES = 23,
     // second strand of a gap region (rtk_region_program, rtk_strand2_skippable) -> RTK_CNT_STRAND2 + 0 .. 2: regions that ran it, regions whose forward result
     // decided the bytes alone, and -- RTK_STRAND2_AUDIT=1 -- regions of the second kind whose full route gave other bytes than the forward result
-    RTK_RC_STRAND2_RUN = 24, RTK_RC_STRAND2_SKIPPED = 25, RTK_RC_STRAND2_AUDIT_MISMATCH = 26, RTK_RC_N = 27 };
+    RTK_RC_STRAND2_RUN = 24, RTK_RC_STRAND2_SKIPPED = 25, RTK_RC_STRAND2_AUDIT_MISMATCH = 26,
+    // stored sweeps of the forward trims (rtk_trim_by_column, rtk_park_walk) -> RTK_CNT_PARK + 0 .. 1: those whose path was walked and parked for a consensus, and
+    // those nobody walked (the region skipped its second strand, or the sweep could not be parked); the sum is RTK_RC_TRIM_STORED
+    RTK_RC_PARK_WALKED = 27, RTK_RC_PARK_DEFERRED = 28, RTK_RC_N = 29 };
 static_assert(RTK_CNT_ROUTES_END - RTK_CNT_ROUTES == static_cast<int>(RTK_RC_FA_LINKED_RUN) - static_cast<int>(RTK_RC_TRIM_STORED), "counter map: one slot per route counter");
 static_assert(RTK_CNT_FA_LINKED_END - RTK_CNT_FA_LINKED == static_cast<int>(RTK_RC_STRAND2_RUN) - static_cast<int>(RTK_RC_FA_LINKED_RUN), "counter map: one slot per fixAmbiguity counter");
-static_assert(RTK_CNT_STRAND2_END - RTK_CNT_STRAND2 == static_cast<int>(RTK_RC_N) - static_cast<int>(RTK_RC_STRAND2_RUN), "counter map: one slot per second-strand counter");
+static_assert(RTK_CNT_STRAND2_END - RTK_CNT_STRAND2 == static_cast<int>(RTK_RC_PARK_WALKED) - static_cast<int>(RTK_RC_STRAND2_RUN), "counter map: one slot per second-strand counter");
+static_assert(RTK_CNT_PARK_END - RTK_CNT_PARK == static_cast<int>(RTK_RC_N) - static_cast<int>(RTK_RC_PARK_WALKED), "counter map: one slot per park counter");
 // indices of RegionScratch::fine -> RTK_CNT_FINE + i (their names in the trace: region_trace_report, rtk_pipeline_run.inc)
 enum RtkRegionFine { RTK_FINE_COL_GENERAL = 0 /* [7] the laps of rtk_choose_colors_general: 1 .. 4 are ALSO the laps of rtk_fix_ambiguity (trace only) */, RTK_FINE_COL_UNIONS = 0, RTK_FINE_FA_ALIGN = 1, RTK_FINE_FA_WALK = 2, RTK_FINE_FA_LINKED = 3, RTK_FINE_FA_APPLY = 4, RTK_FINE_COL_S_VECTORS = 5, RTK_FINE_COL_S_SELECT = 6,
     RTK_FINE_SIDE_LISTS = 7, RTK_FINE_TRIM = 8, RTK_FINE_FIX_AMBIGUITY = 9, RTK_FINE_FA_CALLS = 10, RTK_FINE_FA_ALL_CONFIDENT = 11, RTK_FINE_COL_S_CYCLES = 12, RTK_FINE_COL_B_CYCLES = 13,
