@@ -122,6 +122,14 @@ typedef struct rtk_stats {
      * (n_park_deferred). n_park_walked + n_park_deferred == n_trim_stored; n_moves counts the moves of the walks that were made. RTK_PARK_EAGER=1 walks every
      * sweep that can be parked at the trim, as before. Appended without a new revision number, like the fields above. */
     uint64_t n_park_walked, n_park_deferred;
+    /* Revision 10: calls of the region program's colour selection (chooseColors, src/Correction.cpp:215-429; csrc/hip/rtk_region.h, rtk_choose_colors) by the
+     * program that answered: the register program with 8-word bit vectors (n_colours_small: up to 512 ids on up to 24 side unitigs) or with 64-word vectors
+     * (n_colours_wide: up to 1664 ids), the bit-vector program in scratch memory (n_colours_bits) or the general program on sorted arrays (n_colours_general).
+     * The host simulator has neither of the first two. Calls that ended in an overflow are not counted (their region is redone). RTK_COLOURS_ROUTE=bits skips
+     * the register program, RTK_COLOURS_ROUTE=general both bit-vector programs: same selections, same sum. RTK_COLOURS_AUDIT=1 lets the general program repeat
+     * every selection another program answered and counts the calls whose two lists differ (n_colours_audit_mismatch: 0 unless a program is wrong); the
+     * general program's list is the one used, and n_colour_elem counts the ids of both runs. */
+    uint64_t n_colours_small, n_colours_wide, n_colours_bits, n_colours_general, n_colours_audit_mismatch;
 } rtk_stats;
 
 /* dbg.read(G.fasta.gz) + readGraphData(G.rtsk) (reference: src/Ratatosk.cpp:1087-1089; src/Graph.cpp:722-784).
@@ -322,6 +330,35 @@ int rtk_rescue_begin(int device, int k, const uint64_t* lr, uint64_t n_lr, const
 int rtk_rescue_chunk(void* job, const char* chars, uint64_t n_chars, const uint64_t* starts, uint32_t n_reads, unsigned char* keep);
 int rtk_rescue_end(void* job, uint64_t* n_positions_probed, uint64_t* n_hits);
 
+/* Stage entry for tests (revision 10): the wave-cooperative set primitives of the region stage (csrc/hip/rtk_sets.h, rtk_colours.h), one problem per wavefront
+ * in ONE launch, each wave with the LDS buffer to itself as in the region kernel. Problem i: the operation op[i], two arrays of 32-bit words a[i][0 .. na[i]) and
+ * b[i][0 .. nb[i]) and scalar[i]; its output words go to out_pool[out_off[i] .. out_off[i + 1]) (the caller sizes the slices), out_n[i] says how many were
+ * written, result[i] holds the operation's scalar result, status[i] is RTK_SETS_OK or RTK_SETS_NOT_IN_BUILD (the operation has no version in this build: the
+ * host simulator has no radix sorts and no 8-lane vectors). RTK_ERR_ARG when a problem breaks a limit below or its slice is too small.
+ *   UNION, INTER, DIFF: a and b sorted ascending without repeats; out = a | b (slice >= na + nb), a & b, a \ b (slice >= na); result = out_n.
+ *   INTER_COUNT: result = |a & b| counted up to the cap scalar (the count may stop anywhere at or above the cap); no output words.
+ *   SORT_PAIRS: na pairs, a = the 64-bit keys and b = the 64-bit values as (low word, high word) each, nb = na; out = the na keys then the na values, in
+ *     ascending (key, value) order (slice >= 4 na). A pair of two all-ones words cannot be told from the padding.
+ *   RADIX_U32: na <= 1664 keys <= scalar; out = the keys ascending. Keys and counters lie in LDS as the colour selection lays them out: up to 512 keys with the
+ *     second buffer in LDS too, above that -- or whenever nb != 0 -- the wide layout with the second buffer in device memory.
+ *   RADIX_PAIRS_U32: a = na keys <= scalar, b = their payloads (nb = na); out = keys then payloads, stable ascending by key (slice >= 2 na).
+ *   BM_LOWEST: a = a universe of na <= 4096 ids (sorted, no repeats), b = nb ids of it (sorted, no repeats); the bit vector of b over the universe
+ *     (rtk_bm_from_ids), result = its population count, out = the ids of its scalar lowest bits (slice >= min(scalar, nb)).
+ *   BM8_LOWEST: the same with the vector in lanes 0 .. 7 (rtk_bm8_lowest, rtk_bm8_count): na <= 512. */
+#define RTK_SETS_UNION 0
+#define RTK_SETS_INTER 1
+#define RTK_SETS_DIFF 2
+#define RTK_SETS_INTER_COUNT 3
+#define RTK_SETS_SORT_PAIRS 4
+#define RTK_SETS_RADIX_U32 5
+#define RTK_SETS_RADIX_PAIRS_U32 6
+#define RTK_SETS_BM_LOWEST 7
+#define RTK_SETS_BM8_LOWEST 8
+#define RTK_SETS_OK 0
+#define RTK_SETS_NOT_IN_BUILD 1
+int rtk_sets_batch(uint32_t n, const uint32_t* op, const uint32_t* const* a, const uint32_t* na, const uint32_t* const* b, const uint32_t* nb, const uint32_t* scalar,
+                   uint32_t* out_pool, const uint64_t* out_off, uint32_t* out_n, uint32_t* result, uint32_t* status);
+
 void rtk_free(void* p);
 /* rtk_free of p[0 .. n) (the out_seq / out_qual arrays of rtk_correct_batch in one call; entries are set to NULL). */
 void rtk_free_many(void** p, uint32_t n);
@@ -330,8 +367,9 @@ const char* rtk_version(void);
 /* Interface revision, raised whenever a struct of this header grows or a default changes (5: rtk_opts.struct_size, rtk_stats lane fields, a2_exclusive default 1;
  * 7: rtk_stats route fields n_trim_* / n_consensus_*, the test-only rtk_myers_batch modes 3 and 4, rtk_myers_column_last_routes;
  * 8: rtk_stats fields n_fa_linked_*; 9: rtk_rescue_begin / _chunk / _end; still 9: rtk_stats fields n_strand2_* and n_park_*, the test-only rtk_myers_batch mode 5, appended at the end -- a library of revision 9
- * without them leaves them as the caller set them, and the number stays because tests/test_rescue_reads.py pins it: the next change of this header takes 10). */
-#define RTK_API_REVISION 9
+ * without them leaves them as the caller set them;
+ * 10: rtk_sets_batch, rtk_stats fields n_colours_*). */
+#define RTK_API_REVISION 10
 int rtk_api_revision(void);
 
 #ifdef __cplusplus

@@ -39,7 +39,8 @@ class RtkStats(C.Structure):
                [(n, C.c_uint64) for n in ("n_trim_stored", "n_trim_column", "n_trim_fallback", "n_consensus_resumed", "n_consensus_swept",
                                          "n_fa_linked_run", "n_fa_linked_skipped", "n_fa_linked_entries",
                                          "n_strand2_run", "n_strand2_skipped", "n_strand2_audit_mismatch",
-                                         "n_park_walked", "n_park_deferred")]
+                                         "n_park_walked", "n_park_deferred",
+                                         "n_colours_small", "n_colours_wide", "n_colours_bits", "n_colours_general", "n_colours_audit_mismatch")]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -112,6 +113,9 @@ def load_library(path=None):
         L.rtk_rescue_begin.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_uint64), C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p)]
         L.rtk_rescue_chunk.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(C.c_ubyte)]
         L.rtk_rescue_end.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    if L.rtk_api_revision() >= 10:  # (an older build has no rtk_sets_batch: sets_batch says so)
+        L.rtk_sets_batch.argtypes = [C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_uint32), C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_uint32),
+                                     C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.rtk_free.argtypes = [C.c_void_p]
     _libs[path] = L
     return L
@@ -374,6 +378,55 @@ def myers_lanes_last_routes(lib_path=None):
     L.rtk_myers_lanes_last_routes.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]; L.rtk_myers_lanes_last_routes.restype = None
     L.rtk_myers_lanes_last_routes(C.byref(a), C.byref(b))
     return a.value, b.value
+
+
+SETS_UNION, SETS_INTER, SETS_DIFF, SETS_INTER_COUNT, SETS_SORT_PAIRS, SETS_RADIX_U32, SETS_RADIX_PAIRS_U32, SETS_BM_LOWEST, SETS_BM8_LOWEST = range(9)  # operations of sets_batch
+SETS_OK, SETS_NOT_IN_BUILD = 0, 1  # its per-problem statuses
+
+
+def sets_batch(problems, lib_path=None):
+    """The wave set primitives of the region stage on the device, one problem per wavefront in one launch (stage entry rtk_sets_batch, include/ratatosk_hip.h).
+    problems: [(op, a, b, scalar)] with a and b sequences of 32-bit words (SETS_SORT_PAIRS: sequences of 64-bit keys and values). Returns [(words, result, status)]:
+    the output words of the problem (SETS_SORT_PAIRS: (keys, values) as 64-bit integers), the operation's scalar result and SETS_OK or SETS_NOT_IN_BUILD."""
+    import numpy as np
+    L = load_library(lib_path)
+    if L.rtk_api_revision() < 10:
+        raise RtkError("%s is of interface revision %d: rtk_sets_batch came with revision 10" % (L._name, L.rtk_api_revision()))
+    n = len(problems)
+    keep, off = [], [0]
+    ops = (C.c_uint32 * max(1, n))(); na = (C.c_uint32 * max(1, n))(); nb = (C.c_uint32 * max(1, n))(); sc = (C.c_uint32 * max(1, n))()
+    pa = (C.POINTER(C.c_uint32) * max(1, n))(); pb = (C.POINTER(C.c_uint32) * max(1, n))()
+    for i, (op, a, b, scalar) in enumerate(problems):
+        if op == SETS_SORT_PAIRS:  # 64-bit words travel as (low, high) pairs of 32-bit words
+            a = np.ascontiguousarray(a, dtype="<u8"); b = np.ascontiguousarray(b, dtype="<u8")
+            count_a, count_b, a, b = int(a.size), int(b.size), a.view("<u4"), b.view("<u4")
+        else:
+            a = np.ascontiguousarray(a, dtype=np.uint32); b = np.ascontiguousarray(b, dtype=np.uint32)
+            count_a, count_b = int(a.size), int(b.size)
+        keep.append((a, b))
+        ops[i], na[i], nb[i], sc[i] = op, count_a, count_b, scalar
+        pa[i] = a.ctypes.data_as(C.POINTER(C.c_uint32)); pb[i] = b.ctypes.data_as(C.POINTER(C.c_uint32))
+        need = {SETS_UNION: count_a + count_b, SETS_INTER: count_a, SETS_DIFF: count_a, SETS_INTER_COUNT: 0, SETS_SORT_PAIRS: 4 * count_a, SETS_RADIX_U32: count_a,
+                SETS_RADIX_PAIRS_U32: 2 * count_a, SETS_BM_LOWEST: min(scalar, count_b), SETS_BM8_LOWEST: min(scalar, count_b)}.get(op, 0)
+        off.append(off[-1] + need)
+    out = np.zeros(max(1, off[-1]), dtype=np.uint32)
+    offs = (C.c_uint64 * (n + 1))(*off)
+    out_n = (C.c_uint32 * max(1, n))(); res = (C.c_uint32 * max(1, n))(); st = (C.c_uint32 * max(1, n))()
+    rc = L.rtk_sets_batch(n, ops, pa, na, pb, nb, sc, out.ctypes.data_as(C.POINTER(C.c_uint32)), offs, out_n, res, st)
+    if rc != 0:
+        raise RtkError("rtk error %d: %s" % (rc, L.rtk_last_error().decode()))
+    ret = []
+    for i, (op, _, _, _) in enumerate(problems):
+        if out_n[i] > off[i + 1] - off[i]:
+            raise RtkError("rtk_sets_batch: problem %d reports %d output words for a slice of %d" % (i, out_n[i], off[i + 1] - off[i]))
+        w = out[off[i]:off[i] + out_n[i]]
+        if op == SETS_SORT_PAIRS and st[i] == SETS_OK:
+            h = len(w) // 2
+            words = (w[:h].copy().view("<u8").tolist(), w[h:].copy().view("<u8").tolist())
+        else:
+            words = w.tolist()
+        ret.append((words, int(res[i]), int(st[i])))
+    return ret
 
 
 def run_pipelined(batches, opts=None):

@@ -309,6 +309,7 @@ RTK_FN uint32_t rtk_choose_colors_small(const RCtx& c_, const SideList& side_s_,
     { int tot2; uint32_t at = static_cast<uint32_t>(rtk_wave_excl_scan(rtk_popc(all), &tot2)); uint64_t x = all;
       while (x) { const int b = __builtin_ctzll(x); out[at++] = uni[64u * lane + static_cast<uint32_t>(b)]; x &= x - 1ull; } }
     rtk_sync();
+    s.cnt[big ? RTK_RC_COLOURS_WIDE : RTK_RC_COLOURS_SMALL] += 1;
     return n_all;
 }
 #endif

@@ -767,6 +767,134 @@ extern "C" int rtk_myers_batch_lanes(uint32_t n, const char* const* query, const
 
 #include "rtk_pipeline.inc"
 
+// ---- stage entry rtk_sets_batch (tests): the wave set primitives of the region stage (rtk_sets.h, rtk_colours.h), one problem per wave ----
+// Offsets are in 32-bit words of the input / output pools and in 64-bit words of the work pool; the host checks every size, so the kernel writes inside its slices.
+struct SetsProb { uint32_t op, na, nb, scalar; uint64_t a_off, b_off, out_off, work_off; uint32_t out_cap, pad; };
+
+RTK_GLOBAL void k_sets_batch(const SetsProb* probs, uint32_t n, const uint32_t* in_pool, uint32_t* out_pool, uint64_t* work_pool, int grid, uint32_t* out_n, uint32_t* result, uint32_t* status) {
+    const uint32_t lane = static_cast<uint32_t>(rtk_lane());
+    for (uint32_t pi = static_cast<uint32_t>(RTK_BLOCK_ID); pi < n; pi += static_cast<uint32_t>(grid)) {
+        const uint32_t op = rtk_u(probs[pi].op), na = rtk_u(probs[pi].na), nb = rtk_u(probs[pi].nb), sc = rtk_u(probs[pi].scalar), cap = rtk_u(probs[pi].out_cap);
+        const uint32_t* const a = in_pool + rtk_u(probs[pi].a_off); const uint32_t* const b = in_pool + rtk_u(probs[pi].b_off);
+        uint32_t* const out = out_pool + rtk_u(probs[pi].out_off); uint64_t* const work = work_pool + rtk_u(probs[pi].work_off);
+        uint32_t* const work32 = reinterpret_cast<uint32_t*>(work);
+        uint32_t nout = 0, res = 0, st = RTK_SETS_OK;
+        if (op == RTK_SETS_UNION) { nout = res = rtk_u(rtk_set_union(a, na, b, nb, out, work32)); }
+        else if (op == RTK_SETS_INTER) { nout = res = rtk_u(rtk_set_inter(a, na, b, nb, out)); }
+        else if (op == RTK_SETS_DIFF) { nout = res = rtk_u(rtk_set_diff(a, na, b, nb, out)); }
+        else if (op == RTK_SETS_INTER_COUNT) { res = rtk_u(rtk_set_inter_count(a, na, b, nb, sc)); }
+        else if (op == RTK_SETS_SORT_PAIRS) {
+            uint32_t p = 1; while (p < na) p <<= 1;
+            uint64_t* const key = work; uint64_t* const val = work + p; // room for the next power of two, as rtk_sort_pairs asks
+            for (uint32_t i = lane; i < na; i += RTK_WAVE) { key[i] = static_cast<uint64_t>(a[2u * i]) | (static_cast<uint64_t>(a[2u * i + 1u]) << 32); val[i] = static_cast<uint64_t>(b[2u * i]) | (static_cast<uint64_t>(b[2u * i + 1u]) << 32); }
+            rtk_sync();
+            rtk_sort_pairs(key, val, na);
+            rtk_sync();
+            for (uint32_t i = lane; i < na; i += RTK_WAVE) { out[2u * i] = static_cast<uint32_t>(key[i]); out[2u * i + 1u] = static_cast<uint32_t>(key[i] >> 32); out[2u * na + 2u * i] = static_cast<uint32_t>(val[i]); out[2u * na + 2u * i + 1u] = static_cast<uint32_t>(val[i] >> 32); }
+            nout = 4u * na;
+        }
+#ifndef RTK_SIM
+        else if (op == RTK_SETS_RADIX_U32) { // the two layouts of rtk_choose_colors_small
+            uint32_t* const L = rtk_lds_set_buf();
+            const bool wide = na > RTK_CS_MAX_IDS || nb != 0u;
+            for (uint32_t i = lane; i < na; i += RTK_WAVE) L[i] = a[i];
+            RTK_WG_SYNC();
+            if (wide) rtk_radix_sort_u32(L, work32, na, L + RTK_CB_MAX_IDS, sc);
+            else rtk_radix_sort_u32(L, L + 2u * RTK_CS_MAX_IDS, na, L + 2u * RTK_CS_MAX_IDS + RTK_CS_MAX_IDS, sc);
+            RTK_WG_SYNC();
+            for (uint32_t i = lane; i < na; i += RTK_WAVE) out[i] = L[i];
+            nout = na;
+        }
+        else if (op == RTK_SETS_RADIX_PAIRS_U32) {
+            uint32_t* const ka = work32; uint32_t* const pa = ka + na; uint32_t* const kb = pa + na; uint32_t* const pb = kb + na;
+            for (uint32_t i = lane; i < na; i += RTK_WAVE) { ka[i] = a[i]; pa[i] = b[i]; }
+            rtk_sync();
+            rtk_radix_sort_pairs_u32(ka, pa, kb, pb, na, sc);
+            rtk_sync();
+            for (uint32_t i = lane; i < na; i += RTK_WAVE) { out[i] = ka[i]; out[na + i] = pa[i]; }
+            nout = 2u * na;
+        }
+#endif
+        else if (op == RTK_SETS_BM_LOWEST
+#ifndef RTK_SIM
+                 || op == RTK_SETS_BM8_LOWEST
+#endif
+                 ) {
+#ifdef RTK_SIM
+            const uint32_t* const uni = a; uint64_t* const scatter = nullptr;
+            const RtkBM v = rtk_bm_from_ids(uni, na, scatter, b, nb);
+            res = rtk_bm_count(v);
+            const RtkBM low = rtk_bm_lowest(v, sc);
+            for (uint32_t w = 0; w < 64; ++w) { uint64_t x = low.w[w]; while (x) { const int bt = __builtin_ctzll(x); if (nout < cap) out[nout] = uni[64u * w + static_cast<uint32_t>(bt)]; ++nout; x &= x - 1ull; } }
+#else
+            // the universe in LDS when it fits beside the counters and the scatter words, as rtk_choose_colors_bits keeps it; in device memory above that
+            uint32_t* const L = rtk_lds_set_buf(); uint64_t* const scatter = reinterpret_cast<uint64_t*>(L + RTK_CB_MAX_IDS + 256u);
+            const uint32_t* uni = a;
+            if (na <= RTK_CB_MAX_IDS) { for (uint32_t i = lane; i < na; i += RTK_WAVE) L[i] = a[i]; RTK_WG_SYNC(); uni = L; }
+            RtkBM v = rtk_bm_from_ids(uni, na, scatter, b, nb);
+            RtkBM low;
+            if (op == RTK_SETS_BM8_LOWEST) { if (lane >= 8u) v = 0ull; res = rtk_bm8_count(v); low = rtk_bm8_lowest(v, sc); }
+            else { res = rtk_bm_count(v); low = rtk_bm_lowest(v, sc); }
+            int tot; uint32_t at = static_cast<uint32_t>(rtk_wave_excl_scan(rtk_popc(low), &tot)); uint64_t x = low;
+            while (x) { const int bt = __builtin_ctzll(x); if (at < cap) out[at] = uni[64u * lane + static_cast<uint32_t>(bt)]; ++at; x &= x - 1ull; }
+            nout = static_cast<uint32_t>(rtk_u(tot));
+#endif
+        }
+        else st = RTK_SETS_NOT_IN_BUILD;
+        if (lane == 0u) { out_n[pi] = nout; result[pi] = res; status[pi] = st; }
+        rtk_sync(); // (the next problem of this wave reuses the LDS buffer)
+    }
+}
+
+extern "C" int rtk_sets_batch(uint32_t n, const uint32_t* op, const uint32_t* const* a, const uint32_t* na, const uint32_t* const* b, const uint32_t* nb, const uint32_t* scalar,
+                              uint32_t* out_pool, const uint64_t* out_off, uint32_t* out_n, uint32_t* result, uint32_t* status) {
+    if (!op || !a || !na || !b || !nb || !scalar || !out_pool || !out_off || !out_n || !result || !status) return rtk_fail(RTK_ERR_ARG, "rtk_sets_batch: null argument");
+    if (rtk_device_count() <= 0) return rtk_fail(RTK_ERR_NO_DEVICE, "rtk_sets_batch: no HIP device visible (no CPU fallback)");
+    if (n == 0) return RTK_OK;
+    try {
+        std::vector<SetsProb> probs(n);
+        std::vector<uint32_t> in_pool;
+        uint64_t work_top = 0;
+        for (uint32_t i = 0; i < n; ++i) {
+            SetsProb& p = probs[i];
+            if ((na[i] && !a[i]) || (nb[i] && !b[i]) || out_off[i + 1] < out_off[i] || out_off[i + 1] - out_off[i] > 0xFFFFFFFFull) return rtk_fail(RTK_ERR_ARG, "rtk_sets_batch: null array or bad output slice");
+            const uint64_t cap = out_off[i + 1] - out_off[i], A = na[i], B = nb[i];
+            uint64_t need = 0, work = 0, wa = A, wb = B; // output words, 64-bit work words, input words of a and b
+            switch (op[i]) {
+                case RTK_SETS_UNION: need = A + B; work = (B + 1) / 2; break;
+                case RTK_SETS_INTER: case RTK_SETS_DIFF: need = A; break;
+                case RTK_SETS_INTER_COUNT: break;
+                case RTK_SETS_SORT_PAIRS: { if (B != A || A > (1u << 24)) return rtk_fail(RTK_ERR_ARG, "rtk_sets_batch: SORT_PAIRS wants nb == na <= 2^24"); uint64_t pw = 1; while (pw < A) pw <<= 1; need = 4 * A; work = 2 * pw; wa = 2 * A; wb = 2 * B; break; }
+                case RTK_SETS_RADIX_U32: if (A > RTK_CB_MAX_IDS) return rtk_fail(RTK_ERR_ARG, "rtk_sets_batch: RADIX_U32 sorts at most 1664 keys"); need = A; work = (A + 1) / 2; wb = 0; break;
+                case RTK_SETS_RADIX_PAIRS_U32: if (B != A) return rtk_fail(RTK_ERR_ARG, "rtk_sets_batch: RADIX_PAIRS_U32 wants nb == na"); need = 2 * A; work = 2 * A; break;
+                case RTK_SETS_BM_LOWEST: case RTK_SETS_BM8_LOWEST: {
+                    if (A > (op[i] == RTK_SETS_BM8_LOWEST ? 512u : 4096u)) return rtk_fail(RTK_ERR_ARG, "rtk_sets_batch: universe too large for the bit vector");
+                    for (uint64_t x = 1; x < A; ++x) if (a[i][x - 1] >= a[i][x]) return rtk_fail(RTK_ERR_ARG, "rtk_sets_batch: the universe is not sorted and free of repeats");
+                    for (uint64_t x = 0; x < B; ++x) if (!std::binary_search(a[i], a[i] + A, b[i][x]) || (x && b[i][x - 1] >= b[i][x])) return rtk_fail(RTK_ERR_ARG, "rtk_sets_batch: the ids are not a sorted subset of the universe");
+                    need = std::min<uint64_t>(scalar[i], B); break; }
+                default: return rtk_fail(RTK_ERR_ARG, "rtk_sets_batch: unknown operation");
+            }
+            if (cap < need) return rtk_fail(RTK_ERR_ARG, "rtk_sets_batch: output slice too small for problem " + std::to_string(i));
+            p.op = op[i]; p.na = na[i]; p.nb = nb[i]; p.scalar = scalar[i]; p.out_off = out_off[i]; p.out_cap = static_cast<uint32_t>(cap); p.pad = 0;
+            p.a_off = in_pool.size(); in_pool.insert(in_pool.end(), a[i], a[i] + wa);
+            p.b_off = in_pool.size(); in_pool.insert(in_pool.end(), b[i], b[i] + wb);
+            p.work_off = work_top; work_top += work + 1;
+        }
+        const uint64_t out_words = out_off[n];
+        const int grid = static_cast<int>(std::min<uint32_t>(n, static_cast<uint32_t>(default_grid())));
+        struct Held { std::vector<void*> v; void* get(uint64_t bytes) { v.push_back(nullptr); v.back() = rtk_dmalloc(bytes); return v.back(); } void release() { for (void* p : v) if (p) rtk_dfree(p); v.clear(); } ~Held() { release(); } } held; // (freed on every way out)
+        SetsProb* dprobs = static_cast<SetsProb*>(held.get(sizeof(SetsProb) * n));
+        uint32_t* din = static_cast<uint32_t*>(held.get(4ull * in_pool.size() + 8)); uint32_t* dout = static_cast<uint32_t*>(held.get(4ull * out_words + 8));
+        uint64_t* dwork = static_cast<uint64_t*>(held.get(8ull * work_top + 8));
+        uint32_t* dn = static_cast<uint32_t*>(held.get(4ull * n)); uint32_t* dres = static_cast<uint32_t*>(held.get(4ull * n)); uint32_t* dst = static_cast<uint32_t*>(held.get(4ull * n));
+        rtk_h2d(dprobs, probs.data(), sizeof(SetsProb) * n); rtk_h2d(din, in_pool.data(), 4ull * in_pool.size()); rtk_dzero(dout, 4ull * out_words);
+        rtk_launch(k_sets_batch, grid, 0, static_cast<const SetsProb*>(dprobs), n, static_cast<const uint32_t*>(din), dout, dwork, grid, dn, dres, dst);
+        rtk_dsync();
+        rtk_d2h(out_pool, dout, 4ull * out_words); rtk_d2h(out_n, dn, 4ull * n); rtk_d2h(result, dres, 4ull * n); rtk_d2h(status, dst, 4ull * n);
+        return RTK_OK;
+    } catch (const std::exception& e) { return rtk_fail(RTK_ERR_DEVICE, e.what()); }
+}
+
 #ifdef RTK_SIM // the census of repeated alignments (rtk_region.h, rtk_pair_note; profiles/scripts/sim_pairs.py)
 thread_local std::vector<RtkSimPair> rtk_sim_pair_log;
 std::atomic<int> rtk_sim_pairs_on(0);

@@ -57,6 +57,8 @@ inline int rtk_knob_p2_rgrid() { return rtk_env_int("RTK_P2_RGRID", 512); }     
 inline bool rtk_knob_fa_linked_always() { return rtk_env_is1("RTK_FA_LINKED_ALWAYS"); } // '1': fixAmbiguity runs every linked-allele search, also those that cannot append (same results; parity test, A/B traces)
 inline bool rtk_knob_strand2_always() { return rtk_env_is1("RTK_STRAND2_ALWAYS"); } // '1': every gap region that is not corrected by its forward strand alone runs the second strand, as the reference does (same results; parity test, A/B timing)
 inline bool rtk_knob_strand2_audit() { return rtk_env_is1("RTK_STRAND2_AUDIT"); }   // '1': where the rule would skip the second strand the full route runs and is emitted, and every difference to the forward result is counted (rtk_stats::n_strand2_audit_mismatch)
+inline uint32_t rtk_knob_colours_route() { return rtk_env_eq("RTK_COLOURS_ROUTE", "bits") ? 1u : (rtk_env_eq("RTK_COLOURS_ROUTE", "general") ? 2u : 0u); } // "bits": rtk_choose_colors skips its small program; "general": the general program answers every call (same results; tests/test_colour_routes.py)
+inline uint32_t rtk_knob_colours_audit() { return rtk_env_is1("RTK_COLOURS_AUDIT") ? (rtk_env_is1("RTK_TEST_COLOURS_FAULT") ? 3u : 1u) : 0u; } // RTK_COLOURS_AUDIT '1': the general program repeats every selection another program answered, differences are counted (rtk_stats::n_colours_audit_mismatch); with the test hook RTK_TEST_COLOURS_FAULT '1' (3) the first answer loses its largest id before the comparison
 inline bool rtk_knob_park_eager() { return rtk_env_is1("RTK_PARK_EAGER"); }         // '1': the forward trim of a gap region walks and parks its alignment right away, also where no consensus will read it (same results; parity test, A/B timing)
 inline bool rtk_knob_test_coalesce_fail() { return rtk_env_set("RTK_TEST_COALESCE_FAIL"); } // flag, test hook: a merged batch is reported as failed (its members must come through on their own)
 

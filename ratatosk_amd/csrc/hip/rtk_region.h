@@ -1190,16 +1190,41 @@ RTK_DEV uint32_t rtk_rs_union(RegionScratch& s, int a, uint32_t na, const uint32
 RTK_FN uint32_t rtk_choose_colors_general(const RCtx& c_, const SideList& side_s_, const SideList& side_e_, const SideList& side_w_);
 // chooseColors: the two register / bit-vector programs of rtk_colours.h first (nearly every region), the general program below otherwise.
 // Compiled into its caller: the dispatcher itself as a function would save 17 register rows on every region for a path it almost never takes.
+// Every call that ends without an overflow is counted by the program that answered it (RTK_RC_COLOURS_*; the small program counts its own two sizes).
+// OptsView::colours_mode (tests): RTK_CM_ROUTE_BITS skips the small program, RTK_CM_ROUTE_GENERAL both bit-vector programs. RTK_CM_AUDIT: where a bit-vector
+// program answered, its list is kept in the region-level arena (free here: the path search resets it after this call; the general program writes set[1..9],
+// arena level 2, list[3], list[4] and the LDS buffer), the general program selects again into set[0], and a difference in the number of ids or in any id is
+// counted. The region goes on with the general program's list. RTK_CM_FAULT (test hook): the kept list loses its largest id first.
 RTK_DEV uint32_t rtk_choose_colors(const RCtx& c, const SideList& side_s, const SideList& side_e, const SideList& side_w) {
     RegionScratch& s = rtk_hdr(c);
     const unsigned long long tf = rtk_clock();
+    const uint32_t cm = rtk_u(c.o.colours_mode);
+    uint32_t r = RTK_NONE32;
 #ifndef RTK_SIM
-    { const uint32_t r0 = rtk_u(rtk_choose_colors_small(c, side_s, side_e, side_w));
-      if (r0 != RTK_NONE32) { const unsigned long long d_ = rtk_clock() - tf; s.fine[RTK_FINE_COL_UNIONS] += d_; s.fine[RTK_FINE_COL_S_CYCLES] += d_; s.fine[RTK_FINE_COL_S_CALLS] += 1; return rtk_failed(s) ? 0 : r0; } }
+    if ((cm & RTK_CM_ROUTE) == 0u) {
+        r = rtk_u(rtk_choose_colors_small(c, side_s, side_e, side_w));
+        if (r != RTK_NONE32) { const unsigned long long d_ = rtk_clock() - tf; s.fine[RTK_FINE_COL_UNIONS] += d_; s.fine[RTK_FINE_COL_S_CYCLES] += d_; s.fine[RTK_FINE_COL_S_CALLS] += 1; }
+    }
 #endif
-    const uint32_t r = rtk_u(rtk_choose_colors_bits(c, side_s, side_e, side_w));
-    if (r != RTK_NONE32) { const unsigned long long d_ = rtk_clock() - tf; s.fine[RTK_FINE_COL_UNIONS] += d_; s.fine[RTK_FINE_COL_B_CYCLES] += d_; s.fine[RTK_FINE_COL_B_CALLS] += 1; return rtk_failed(s) ? 0 : r; }
-    return rtk_u(rtk_choose_colors_general(c, side_s, side_e, side_w));
+    if (r == RTK_NONE32 && (cm & RTK_CM_ROUTE) != RTK_CM_ROUTE_GENERAL) {
+        r = rtk_u(rtk_choose_colors_bits(c, side_s, side_e, side_w));
+        if (r != RTK_NONE32) { const unsigned long long d_ = rtk_clock() - tf; s.fine[RTK_FINE_COL_UNIONS] += d_; s.fine[RTK_FINE_COL_B_CYCLES] += d_; s.fine[RTK_FINE_COL_B_CALLS] += 1; if (!rtk_failed(s)) s.cnt[RTK_RC_COLOURS_BITS] += 1; }
+    }
+    uint32_t n_first = RTK_NONE32; // audit: ids of the first answer that were kept
+    if (r != RTK_NONE32) {
+        if (rtk_failed(s)) return 0;
+        if ((cm & RTK_CM_AUDIT) == 0u || 4ull * r > s.arena_cap) return r; // (no room to keep the list: not compared)
+        n_first = r - (((cm & RTK_CM_FAULT) != 0u && r != 0u) ? 1u : 0u);
+        rtk_wcopy(s.arena[0].get(), s.set[0].get(), 4ull * n_first);
+    }
+    const uint32_t rg = rtk_u(rtk_choose_colors_general(c, side_s, side_e, side_w));
+    if (rtk_failed(s)) return 0; // (the region is redone: nothing to compare)
+    if (n_first == RTK_NONE32) { s.cnt[RTK_RC_COLOURS_GENERAL] += 1; return rg; }
+    const uint32_t* const first = reinterpret_cast<const uint32_t*>(s.arena[0].get()); const uint32_t* const second = s.set[0].get();
+    bool differs = rg != n_first;
+    for (uint32_t i0 = 0; i0 < rg && !differs; i0 += RTK_WAVE) { const uint32_t i = i0 + static_cast<uint32_t>(rtk_lane()); differs = rtk_ballot(i < rg && first[i] != second[i]) != 0ull; }
+    if (differs) s.cnt[RTK_RC_COLOURS_AUDIT_MISMATCH] += 1;
+    return rg;
 }
 RTK_FN uint32_t rtk_choose_colors_general(const RCtx& c_, const SideList& side_s_, const SideList& side_e_, const SideList& side_w_) {
     const RCtx& c = *rtk_u(&c_); const SideList& side_s = *rtk_u(&side_s_); const SideList& side_e = *rtk_u(&side_e_); const SideList& side_w = *rtk_u(&side_w_); RTK_ASSUME_LDS(&side_s); RTK_ASSUME_LDS(&side_e); RTK_ASSUME_LDS(&side_w);

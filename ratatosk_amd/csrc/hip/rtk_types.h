@@ -194,7 +194,9 @@ enum RtkCounterSlot {
     RTK_CNT_STRAND2_END = 217,
     RTK_CNT_PARK = 217,             // [2] k_regions, stored sweeps of the forward trims: walked for a consensus / never walked (RTK_RC_PARK_WALKED ..) -> rtk_stats
     RTK_CNT_PARK_END = 219,
-    RTK_CNT_USED_END = RTK_CNT_PARK_END,
+    RTK_CNT_COLOURS = 219,          // [5] k_regions, calls of rtk_choose_colors by the program that answered: small, wide, bits, general; audit mismatches (RTK_RC_COLOURS_SMALL ..) -> rtk_stats
+    RTK_CNT_COLOURS_END = 224,
+    RTK_CNT_USED_END = RTK_CNT_COLOURS_END,
     RTK_CNT_TOTAL = (RTK_CNT_USED_END + 31) / 32 * 32 // words in the block: what is used, rounded up to 256 bytes (the tail is free)
 };
 static_assert(RTK_CNT_TOTAL == 224, "counter map: the size of the block changed (it is part of what the kernels and the host agree on)");
@@ -210,6 +212,7 @@ static_assert(RTK_CNT_LANE_END <= RTK_CNT_LANE_PROF && RTK_CNT_LANE_PROF2 - RTK_
 static_assert(RTK_CNT_PHASE_SKIPPED < RTK_CNT_FA_LINKED && RTK_CNT_FA_LINKED_END <= RTK_CNT_TOTAL, "counter map: the fixAmbiguity counters overlap the phasing slot or leave the block");
 static_assert(RTK_CNT_FA_LINKED_END <= RTK_CNT_STRAND2 && RTK_CNT_STRAND2_END <= RTK_CNT_TOTAL, "counter map: the second-strand counters overlap the fixAmbiguity counters or leave the block");
 static_assert(RTK_CNT_STRAND2_END <= RTK_CNT_PARK && RTK_CNT_PARK_END <= RTK_CNT_TOTAL, "counter map: the park counters overlap the second-strand counters or leave the block");
+static_assert(RTK_CNT_PARK_END <= RTK_CNT_COLOURS && RTK_CNT_COLOURS_END <= RTK_CNT_TOTAL, "counter map: the colour-route counters overlap the park counters or leave the block");
 static_assert(rtk_cnt_apart(RTK_CNT_PHASE_TRACE, RTK_CNT_PHASE_TRACE_END, RTK_CNT_FINALIZE_SLOWEST_PHASES, RTK_CNT_FINALIZE_SLOWEST_PHASES_END), "counter map: the two guests of the size-class table overlap");
 static_assert(RTK_CNT_HIST <= RTK_CNT_PHASE_TRACE && RTK_CNT_FINALIZE_SLOWEST_PHASES_END <= RTK_CNT_HIST_END, "counter map: the guests of the size-class table left it (update the comment above)");
 
@@ -228,11 +231,21 @@ enum RtkRegionCnt { RTK_RC_EXPAND = 0, RTK_RC_COLOUR = 1, RTK_RC_PATHBASE = 2, R
     RTK_RC_STRAND2_RUN = 24, RTK_RC_STRAND2_SKIPPED = 25, RTK_RC_STRAND2_AUDIT_MISMATCH = 26,
     // stored sweeps of the forward trims (rtk_trim_by_column, rtk_park_walk) -> RTK_CNT_PARK + 0 .. 1: those whose path was walked and parked for a consensus, and
     // those nobody walked (the region skipped its second strand, or the sweep could not be parked); the sum is RTK_RC_TRIM_STORED
-    RTK_RC_PARK_WALKED = 27, RTK_RC_PARK_DEFERRED = 28, RTK_RC_N = 29 };
+    RTK_RC_PARK_WALKED = 27, RTK_RC_PARK_DEFERRED = 28,
+    // calls of rtk_choose_colors (rtk_region.h) by the program that answered -> RTK_CNT_COLOURS + 0 .. 4: rtk_choose_colors_small with 8-word vectors / with 64-word
+    // vectors ("wide"), rtk_choose_colors_bits, rtk_choose_colors_general; and -- RTK_COLOURS_AUDIT=1 -- calls whose first answer differed from the general program's
+    RTK_RC_COLOURS_SMALL = 29, RTK_RC_COLOURS_WIDE = 30, RTK_RC_COLOURS_BITS = 31, RTK_RC_COLOURS_GENERAL = 32, RTK_RC_COLOURS_AUDIT_MISMATCH = 33, RTK_RC_N = 34 };
 static_assert(RTK_CNT_ROUTES_END - RTK_CNT_ROUTES == static_cast<int>(RTK_RC_FA_LINKED_RUN) - static_cast<int>(RTK_RC_TRIM_STORED), "counter map: one slot per route counter");
 static_assert(RTK_CNT_FA_LINKED_END - RTK_CNT_FA_LINKED == static_cast<int>(RTK_RC_STRAND2_RUN) - static_cast<int>(RTK_RC_FA_LINKED_RUN), "counter map: one slot per fixAmbiguity counter");
 static_assert(RTK_CNT_STRAND2_END - RTK_CNT_STRAND2 == static_cast<int>(RTK_RC_PARK_WALKED) - static_cast<int>(RTK_RC_STRAND2_RUN), "counter map: one slot per second-strand counter");
-static_assert(RTK_CNT_PARK_END - RTK_CNT_PARK == static_cast<int>(RTK_RC_N) - static_cast<int>(RTK_RC_PARK_WALKED), "counter map: one slot per park counter");
+static_assert(RTK_CNT_PARK_END - RTK_CNT_PARK == static_cast<int>(RTK_RC_COLOURS_SMALL) - static_cast<int>(RTK_RC_PARK_WALKED), "counter map: one slot per park counter");
+static_assert(RTK_CNT_COLOURS_END - RTK_CNT_COLOURS == static_cast<int>(RTK_RC_N) - static_cast<int>(RTK_RC_COLOURS_SMALL), "counter map: one slot per colour-route counter");
+// OptsView::colours_mode (rtk_seeds.h; RTK_COLOURS_ROUTE, RTK_COLOURS_AUDIT, RTK_TEST_COLOURS_FAULT of rtk_knobs.h): route in bits 0 .. 1, the audit and its test hook above
+#define RTK_CM_ROUTE 3u
+#define RTK_CM_ROUTE_BITS 1u
+#define RTK_CM_ROUTE_GENERAL 2u
+#define RTK_CM_AUDIT 4u
+#define RTK_CM_FAULT 8u
 // indices of RegionScratch::fine -> RTK_CNT_FINE + i (their names in the trace: region_trace_report, rtk_pipeline_run.inc)
 enum RtkRegionFine { RTK_FINE_COL_GENERAL = 0 /* [7] the laps of rtk_choose_colors_general: 1 .. 4 are ALSO the laps of rtk_fix_ambiguity (trace only) */, RTK_FINE_COL_UNIONS = 0, RTK_FINE_FA_ALIGN = 1, RTK_FINE_FA_WALK = 2, RTK_FINE_FA_LINKED = 3, RTK_FINE_FA_APPLY = 4, RTK_FINE_COL_S_VECTORS = 5, RTK_FINE_COL_S_SELECT = 6,
     RTK_FINE_SIDE_LISTS = 7, RTK_FINE_TRIM = 8, RTK_FINE_FIX_AMBIGUITY = 9, RTK_FINE_FA_CALLS = 10, RTK_FINE_FA_ALL_CONFIDENT = 11, RTK_FINE_COL_S_CYCLES = 12, RTK_FINE_COL_B_CYCLES = 13,

@@ -222,15 +222,15 @@ def test_cli_unmapped_option(data, tmp_path, exe):
     assert "-u, --in-unmapped-short" in subprocess.run([exe, "--help"], capture_output=True, text=True).stderr
 
 
-def test_header_and_libraries_agree_on_revision_9_and_the_rescue_entries():
+def test_header_and_libraries_agree_on_revision_10_and_the_rescue_and_sets_entries():
     txt = open(os.path.join(ROOT, "include", "ratatosk_hip.h")).read()
-    assert re.search(r"#define\s+RTK_API_REVISION\s+9\b", txt)
-    for name in ("rtk_rescue_begin", "rtk_rescue_chunk", "rtk_rescue_end"):
+    assert re.search(r"#define\s+RTK_API_REVISION\s+10\b", txt)
+    for name in ("rtk_rescue_begin", "rtk_rescue_chunk", "rtk_rescue_end", "rtk_sets_batch"):
         assert re.search(r"\bint\s+%s\s*\(" % name, txt), name
     for path in (LIB, SIM_LIB):
         L = ctypes.CDLL(path)
-        assert L.rtk_api_revision() == 9, path
-        for name in ("rtk_rescue_begin", "rtk_rescue_chunk", "rtk_rescue_end"):
+        assert L.rtk_api_revision() == 10, path
+        for name in ("rtk_rescue_begin", "rtk_rescue_chunk", "rtk_rescue_end", "rtk_sets_batch"):
             assert hasattr(L, name), (path, name)
 
 
