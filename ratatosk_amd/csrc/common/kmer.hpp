@@ -87,6 +87,17 @@ template <class KM> inline bool km_encode(const char* s, int k, KM& out) {
     out = x;
     return true;
 }
+// The rolling walk over a sequence: fn(canonical k-mer, start position) for every window of k characters that are all A/C/G/T (either case); any other
+// character starts the window over. The one copy of this loop for the tools (counting, colouring, rescue).
+template <class KM, class Fn> inline void for_each_canonical_kmer(const char* seq, size_t len, int k, KM mask, Fn&& fn) {
+    KM fw = 0; int valid = 0;
+    for (size_t i = 0; i < len; ++i) {
+        const int b = base2bits(seq[i]);
+        if (b < 0) { valid = 0; fw = 0; continue; }
+        fw = ((fw << 2) | static_cast<KM>(b)) & mask;
+        if (++valid >= k) fn(kmer_canonical(fw, k), i + 1 - static_cast<size_t>(k));
+    }
+}
 template <class KM> inline std::string km_decode(KM x, int k) {
     std::string s(k, 'A');
     for (int i = 0; i < k; ++i) s[i] = bits2base(static_cast<int>(static_cast<uint64_t>(x >> (2 * (k - 1 - i))) & 3));

@@ -1,0 +1,198 @@
+// rtk_build_index, pass 2: colours (ids of the read pairs, or of the reads with --colour-reads) and coverage of every unitig. Three read sources
+// number the reads and hand (sequence, id) to one sink, which looks the k-mers up on the host threads or feeds the device job.
+#ifndef RTK_TOOLS_INDEX_COLOUR_HPP
+#define RTK_TOOLS_INDEX_COLOUR_HPP
+
+#include <condition_variable>
+#include <deque>
+#include <memory>
+#include <mutex>
+
+#include "state.hpp"
+
+namespace rtk {
+
+// mates share a name up to a trailing /1 or /2: the length of the name without it
+inline size_t pair_name_len(const char* p, size_t n) { return (n > 2 && p[n - 2] == '/' && (p[n - 1] == '1' || p[n - 1] == '2')) ? n - 2 : n; }
+
+// --gpu: the reads are handed to the device chunk by chunk (csrc/hip/rtk_index.hip rtk_index_colour_*: the k-mer table of the unitigs in HBM, one lane per
+// read position); this tool keeps what is its own -- reading, and the numbering of the reads. Every thread fills a chunk of its own.
+struct Feed {
+    std::string chars; std::vector<uint64_t> starts; std::vector<uint32_t> ids; void* job; HipLib::col_chunk_fn fn; std::atomic<int>* failed;
+    void flush() { if (ids.empty()) return; if (fn(job, chars.data(), chars.size(), starts.data(), ids.data(), static_cast<uint32_t>(ids.size())) != 0) *failed = 1; chars.clear(); starts.clear(); ids.clear(); }
+    void add(const char* seq, size_t len, uint32_t id) {
+        if (len + 1 > (60u << 20)) { *failed = 1; return; } // (a read longer than a chunk)
+        if (chars.size() + len + 1 > (60u << 20) || ids.size() >= (2u << 20) || (chars.size() >= (24u << 20))) flush();
+        starts.push_back(chars.size()); ids.push_back(id); chars.append(seq, len); chars.push_back('\n');
+    }
+};
+
+template <class KM> struct ColourSink {
+    IndexBuild<KM>& s; std::vector<Unitig>& U; const size_t n_u;
+    void* job = nullptr; std::atomic<int> failed; HipLib::col_chunk_fn chunk_fn = nullptr; HipLib::col_end_fn end_fn = nullptr; std::vector<Feed> feeds;
+    std::vector<std::vector<uint64_t> > cov; std::vector<std::vector<std::pair<uint32_t, uint32_t> > > ev; // host: per thread, k-mers per unitig and (unitig, id) events
+
+    explicit ColourSink(IndexBuild<KM>& st) : s(st), U(st.U), n_u(st.U.size()), failed(0), feeds(st.n_thr), cov(st.n_thr), ev(st.n_thr) {
+        HipLib::col_begin_fn begin_fn = nullptr;
+        if (s.o.gpu && s.lib.get(begin_fn, "rtk_index_colour_begin") && s.lib.get(chunk_fn, "rtk_index_colour_chunk") && s.lib.get(end_fn, "rtk_index_colour_end") && !s.knobs.host_colours && n_u > 0) {
+            std::vector<uint64_t> off(n_u + 1, 0); for (size_t u = 0; u < n_u; ++u) off[u + 1] = off[u] + s.U[u].seq.size();
+            std::string pool(off[n_u], 'A');
+            parallel_for(n_u, s.n_thr, [&](size_t b, size_t e, unsigned) { for (size_t u = b; u < e; ++u) memcpy(&pool[off[u]], s.U[u].seq.data(), s.U[u].seq.size()); });
+            if (begin_fn(0, s.k, pool.data(), off.data(), n_u, &job) != 0) { fprintf(stderr, "rtk_build_index: --gpu: colours on the host threads (%s)\n", s.lib.last_error()); job = nullptr; }
+        }
+        for (unsigned t = 0; t < s.n_thr; ++t) { feeds[t].job = job; feeds[t].fn = chunk_fn; feeds[t].failed = &failed; if (!job) cov[t].assign(n_u, 0); }
+    }
+    // one read, from thread t of the source: its k-mers looked up (the table is only read), or the read handed to the device
+    void read(unsigned t, const char* seq, size_t len, uint32_t id) {
+        if (job) { feeds[t].add(seq, len, id); return; }
+        std::vector<uint64_t>& c = cov[t]; std::vector<std::pair<uint32_t, uint32_t> >& e = ev[t];
+        for_each_canonical_kmer<KM>(seq, len, s.k, s.mask, [&](KM km, size_t) {
+            const uint64_t* v = s.km.slot(km, false);
+            if (v) { const uint32_t u = static_cast<uint32_t>((*v >> 32) - 1); ++c[u]; if (e.empty() || e.back().first != u || e.back().second != id) e.push_back(std::make_pair(u, id)); }
+        });
+    }
+    // --gpu: the distinct (unitig, id) events in sorted order and the coverages, back from the device
+    bool finish_device() {
+        if (!job) return true;
+        for (unsigned t = 0; t < s.n_thr; ++t) feeds[t].flush();
+        uint64_t* evs = nullptr; uint64_t* cv = nullptr; uint64_t n_ev = 0;
+        if (end_fn(job, &evs, &n_ev, &cv) != 0 || failed) { fprintf(stderr, "rtk_build_index: --gpu: colouring on the device failed (%s)\n", s.lib.last_error()); return false; }
+        parallel_for(n_u, s.n_thr, [&](size_t b, size_t e, unsigned) {
+            if (b >= e) return;
+            const uint64_t* p = std::lower_bound(evs, evs + n_ev, static_cast<uint64_t>(b) << 32);
+            for (size_t u = b; u < e; ++u) { U[u].cov = cv[u]; const uint64_t* q = p; while (q < evs + n_ev && (*q >> 32) == u) ++q; U[u].colours.resize(static_cast<size_t>(q - p)); for (size_t i = 0; p + i < q; ++i) U[u].colours[i] = static_cast<uint32_t>(p[i] & 0xFFFFFFFFull); p = q; }
+        });
+        s.lib.free(evs); s.lib.free(cv);
+        return true;
+    }
+    // the threads' counts and events into the unitigs; the colours sorted, each id once
+    void finish_host() {
+        if (job) return;
+        for (unsigned t = 0; t < s.n_thr; ++t) {
+            for (size_t u = 0; u < n_u; ++u) U[u].cov += cov[t][u];
+            for (size_t e = 0; e < ev[t].size(); ++e) U[ev[t][e].first].colours.push_back(ev[t][e].second);
+            std::vector<uint64_t>().swap(cov[t]); std::vector<std::pair<uint32_t, uint32_t> >().swap(ev[t]);
+        }
+        parallel_for(U.size(), s.o.fast ? s.n_thr : 1u, [&](size_t b, size_t e, unsigned) { for (size_t i = b; i < e; ++i) { std::sort(U[i].colours.begin(), U[i].colours.end()); U[i].colours.erase(std::unique(U[i].colours.begin(), U[i].colours.end()), U[i].colours.end()); } });
+    }
+};
+
+// Source 1, any input: one reader parses the records and numbers them (a pair keeps one id: the id is the number of name changes before the read;
+// every read its own id with --colour-reads), worker threads take pieces of about 1 MB from a bounded queue.
+template <class KM> static bool colour_from_reader(IndexBuild<KM>& s, ColourSink<KM>& sink, const std::vector<std::string>& col_in, bool by_read) {
+    struct Chunk { std::vector<std::string> seq; std::vector<uint32_t> id; size_t bytes = 0; };
+    std::mutex mq; std::condition_variable cv_put, cv_get; std::deque<std::unique_ptr<Chunk> > q; bool done = false, ok = true;
+    std::vector<std::thread> th;
+    for (unsigned t = 0; t < s.n_thr; ++t) th.emplace_back([&, t]() {
+        while (true) {
+            std::unique_ptr<Chunk> c;
+            { std::unique_lock<std::mutex> lk(mq); cv_get.wait(lk, [&]() { return !q.empty() || done; }); if (q.empty()) return; c = std::move(q.front()); q.pop_front(); }
+            cv_put.notify_one();
+            for (size_t r = 0; r < c->seq.size(); ++r) sink.read(t, c->seq[r].data(), c->seq[r].size(), c->id[r]);
+        }
+    });
+    std::string name, seq, qual, prev_name;
+    uint32_t pair_id = 0; bool first = true;
+    std::unique_ptr<Chunk> cur(new Chunk());
+    auto flush = [&]() { if (cur->seq.empty()) return; { std::unique_lock<std::mutex> lk(mq); cv_put.wait(lk, [&]() { return q.size() < 4u * s.n_thr; }); q.push_back(std::move(cur)); } cv_get.notify_one(); cur.reset(new Chunk()); };
+    for (size_t f = 0; f < col_in.size() && ok; ++f) {
+        FastxReader fr; if (!fr.open(col_in[f], s.o.fast ? static_cast<int>(s.n_thr < 8 ? s.n_thr : 8) : 0)) { fprintf(stderr, "rtk_build_index: cannot open %s\n", col_in[f].c_str()); ok = false; break; }
+        while (fr.next(name, seq, qual)) {
+            for (size_t x = 0; x < seq.size(); ++x) seq[x] = static_cast<char>(seq[x] & 0xDF);
+            name.erase(pair_name_len(name.data(), name.size()));
+            if (first) { first = false; prev_name = name; }
+            else if (by_read || name != prev_name) { ++pair_id; prev_name = name; }
+            cur->bytes += seq.size(); cur->seq.push_back(std::string()); cur->seq.back().swap(seq); cur->id.push_back(pair_id);
+            if (cur->bytes >= (1u << 20)) flush();
+        }
+        if (fr.failed()) { fprintf(stderr, "rtk_build_index: %s ends in a damaged or cut-short gzip stream\n", col_in[f].c_str()); ok = false; }
+    }
+    flush();
+    { std::lock_guard<std::mutex> lk(mq); done = true; }
+    cv_get.notify_all();
+    for (size_t t = 0; t < th.size(); ++t) th[t].join();
+    return ok;
+}
+
+// Source 2, --fast on `sample:` specs: reads sampled from a reference on the fly (common/sample_source.hpp): pair p of a source has the id (pairs of the
+// sources before it) + p (the number of name changes before it: mates share the name "s<p>"); ranges of pairs generated by all threads
+template <class KM> static bool colour_from_samples(IndexBuild<KM>& s, ColourSink<KM>& sink, const std::vector<std::string>& col_in) {
+    uint64_t id_base = 0;
+    for (size_t f = 0; f < col_in.size(); ++f) {
+        std::string err; std::shared_ptr<SampleSource> ss = SampleSource::get(col_in[f], &err);
+        if (!ss) { fprintf(stderr, "rtk_build_index: %s\n", err.c_str()); return false; }
+        if (id_base + ss->n_pairs() > 0xFFFFFFFFull) { fprintf(stderr, "rtk_build_index: more than 2^32 read pairs\n"); return false; }
+        const uint64_t per = 1 << 14, n_ch = (ss->n_pairs() + per - 1) / per; const uint32_t L = ss->read_len();
+        std::atomic<uint64_t> nx(0);
+        std::vector<std::thread> th;
+        for (unsigned t = 0; t < s.n_thr; ++t) th.emplace_back([&, t]() {
+            std::string m(2 * static_cast<size_t>(L), 'A');
+            for (;;) { const uint64_t c = nx.fetch_add(1); if (c >= n_ch) break;
+                const uint64_t p0 = c * per, p1 = std::min<uint64_t>(ss->n_pairs(), p0 + per);
+                for (uint64_t p = p0; p < p1; ++p) { ss->pair(p, &m[0], &m[L]); for (int mate = 0; mate < 2; ++mate) sink.read(t, m.data() + mate * L, L, static_cast<uint32_t>(id_base + p)); }
+            } });
+        for (size_t t = 0; t < th.size(); ++t) th[t].join();
+        id_base += ss->n_pairs();
+    }
+    return true;
+}
+
+// Source 3, --fast on plain files: byte ranges of the files parsed and looked up by all threads. The id of a read is the number of name changes
+// before it (every read with --colour-reads), so a first sweep over the ranges counts the changes inside each and notes its first and last
+// name; the running sums give every range the id of its first read; the second sweep maps the reads.
+template <class KM> static bool colour_from_plain_ranges(IndexBuild<KM>& s, ColourSink<KM>& sink, const std::vector<std::string>& col_in, bool by_read) {
+    struct RangeInfo { uint32_t changes = 0; uint64_t n_reads = 0; std::string first, last; };
+    uint32_t next_id = 0; bool have_prev = false; std::string prev_last;
+    for (size_t f = 0; f < col_in.size(); ++f) {
+        PlainChunks pc; if (!pc.open(col_in[f], 32u << 20)) { fprintf(stderr, "rtk_build_index: cannot open %s\n", col_in[f].c_str()); return false; }
+        const size_t nc = pc.n_chunks();
+        std::vector<RangeInfo> info(nc); std::vector<uint32_t> id0(nc, 0); // id0: id of the first read of every range
+        std::atomic<int> bad(0);
+        // sweep(map the reads, or only count): every range parsed by a thread; the names walked, the changes counted from id0 of the range
+        auto sweep = [&](bool map) {
+            std::atomic<size_t> nx(0); std::vector<std::thread> th;
+            for (unsigned t = 0; t < s.n_thr; ++t) th.emplace_back([&, t]() {
+                for (;;) { const size_t i = nx.fetch_add(1); if (i >= nc) break;
+                    PackedReads r(false); if (!pc.parse_chunk(i, r)) { bad = 1; break; }
+                    RangeInfo& ri = info[i]; uint32_t id = id0[i]; const char* pp = nullptr; size_t pn = 0;
+                    for (size_t x = 0; x < r.size(); ++x) {
+                        const char* p = r.name(x); const size_t n = pair_name_len(p, r.name_len(x));
+                        if (x != 0 && (by_read || n != pn || memcmp(p, pp, n) != 0)) ++id;
+                        pp = p; pn = n;
+                        if (map) sink.read(t, r.seq(x), r.seq_len(x), id);
+                        else if (x == 0) ri.first.assign(p, n);
+                    }
+                    if (!map) { ri.n_reads = r.size(); ri.changes = id - id0[i]; if (r.size()) ri.last.assign(pp, pn); }
+                } });
+            for (size_t t = 0; t < th.size(); ++t) th[t].join();
+        };
+        sweep(false);
+        if (bad) return false;
+        for (size_t i = 0; i < nc; ++i) {
+            if (info[i].n_reads == 0) { id0[i] = next_id; continue; }
+            if (have_prev && (by_read || info[i].first != prev_last)) ++next_id;
+            id0[i] = next_id; next_id += info[i].changes; have_prev = true; prev_last = info[i].last;
+        }
+        sweep(true);
+        if (bad) return false;
+    }
+    return true;
+}
+
+template <class KM> static bool colour_and_cover(IndexBuild<KM>& s) {
+    // second-pass index: the reads that colour the graph are the (pass-1 corrected) long reads, every read its own id
+    // (addCoverage(dbg, opt_pass2, ..., long_read_correct = true), src/Ratatosk.cpp:1218)
+    const bool by_read = !s.o.colour_files.empty();
+    const std::vector<std::string>& col_in = by_read ? s.o.colour_files : s.o.in_files;
+    ColourSink<KM> sink(s);
+    bool all_sampled = s.o.fast && !by_read && !col_in.empty(), all_plain = s.o.fast;
+    for (size_t f = 0; f < col_in.size(); ++f) { all_sampled = all_sampled && SampleSource::is_spec(col_in[f]); all_plain = all_plain && PlainChunks::is_plain(col_in[f]); }
+    const bool ok = all_sampled ? colour_from_samples(s, sink, col_in) : (all_plain ? colour_from_plain_ranges(s, sink, col_in, by_read) : colour_from_reader(s, sink, col_in, by_read));
+    if (!sink.finish_device() || !ok) return false;
+    sink.finish_host();
+    return true;
+}
+
+} // namespace rtk
+
+#endif

@@ -1,0 +1,135 @@
+// rtk_build_index: the options, the knobs and the state that the steps of the build hand to each other (tools/build_index.cpp lists the steps).
+#ifndef RTK_TOOLS_INDEX_STATE_HPP
+#define RTK_TOOLS_INDEX_STATE_HPP
+
+#include <algorithm>
+#include <atomic>
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "../../common/fastx.hpp"
+#include "../../common/hip_lib.hpp"
+#include "../../common/kmer.hpp"
+
+namespace rtk {
+
+struct IndexOptions {
+    std::vector<std::string> in_files;
+    std::string prefix = "out";
+    int k = 31;
+    unsigned min_count = 2;
+    size_t min_cov_vertices = 2;
+    double global_cov_factor = 3.0, min_color_sharing = 0.5;
+    bool detect_cycles = true, detect_snps = false;
+    bool fast = false, gpu = false; // --fast: the same files from thread-parallel counting-table build / compaction / adjacency / cycle search; --gpu: --fast with counting, unitigs and colours on the device (any odd k <= 63)
+    std::string dump_input; // --dump-input FILE: the inputs (sample: sources included) written out as one FASTQ file, nothing else done
+    std::vector<std::string> colour_files; // pass-2 index (`Ratatosk index -2`): colours = ids of these (pass-1 corrected long) reads, one id per read
+    std::string out_file(const char* ext) const { return prefix + ".index.k" + std::to_string(k) + ext; }
+};
+
+// 0, or the exit status (2: the message or the usage text is on stderr)
+inline int parse_options(int argc, char** argv, IndexOptions& o) {
+    for (int i = 1; i < argc; ++i) {
+        const std::string a = argv[i];
+        auto need = [&](const char* n) -> const char* { if (i + 1 >= argc) { fprintf(stderr, "rtk_build_index: missing value for %s\n", n); exit(2); } return argv[++i]; };
+        if (a == "-s") o.in_files.push_back(need("-s"));
+        else if (a == "-o") o.prefix = need("-o");
+        else if (a == "-k") o.k = atoi(need("-k"));
+        else if (a == "--min-count") o.min_count = static_cast<unsigned>(atoi(need("--min-count")));
+        else if (a == "--global-cov-factor") o.global_cov_factor = atof(need("--global-cov-factor"));
+        else if (a == "--no-short-cycles") o.detect_cycles = false;
+        else if (a == "--snps") o.detect_snps = true;
+        else if (a == "--fast") o.fast = true;
+        else if (a == "--gpu") { o.fast = true; o.gpu = true; }
+        else if (a == "--colour-reads") o.colour_files.push_back(need("--colour-reads"));
+        else if (a == "--dump-input") o.dump_input = need("--dump-input");
+        else { fprintf(stderr, "rtk_build_index: unknown option %s\n", a.c_str()); return 2; }
+    }
+    if (o.in_files.empty() || o.k < 3 || o.k > RTK_MAX_K || !(o.k & 1)) { fprintf(stderr, "usage: rtk_build_index -s reads.fq [-s ...] -o PREFIX [-k 31 (odd, <=63)] [--min-count 2] [--global-cov-factor 3.0] [--no-short-cycles] [--snps] [--fast | --gpu (k <= 63: same files, threads / the device for the heavy steps)] [--dump-input FILE] [--colour-reads corrected_long_reads.fq: second-pass index, the graph comes from -s, colours and coverage from these reads]\n"); return 2; }
+    return 0;
+}
+
+// the environment knobs of the tool (listed at the end of hip/rtk_knobs.h), read once
+struct IndexKnobs {
+    bool trace = getenv("RTK_INDEX_TRACE") != nullptr;                 // the laps and the step counts on stderr
+    bool host_unitigs = getenv("RTK_INDEX_HOST_UNITIGS") != nullptr;   // --gpu: the chains on the host threads
+    bool host_colours = getenv("RTK_INDEX_HOST_COLOURS") != nullptr;   // --gpu: the colours on the host threads
+    unsigned threads = 0;                                              // RTK_INDEX_THREADS (0: by the machine)
+    size_t fasta_member_bytes = 32u << 20;                             // RTK_FASTA_MEMBER_BYTES (tests: many small members)
+    IndexKnobs() {
+        if (const char* e = getenv("RTK_INDEX_THREADS")) if (atoi(e) > 0) threads = static_cast<unsigned>(atoi(e));
+        if (const char* e = getenv("RTK_FASTA_MEMBER_BYTES")) fasta_member_bytes = static_cast<size_t>(strtoull(e, nullptr, 10));
+    }
+};
+
+// open-addressing table from canonical k-mers (one- or two-word codes) to a 64-bit value; the all-ones key is no k-mer (odd k <= 63) and marks a free slot
+template <class KM> struct KTable {
+    const KM EMPTY = ~static_cast<KM>(0);
+    std::vector<KM> keys; std::vector<uint64_t> vals;
+    size_t n = 0, mask = 0;
+    explicit KTable(size_t cap_pow2 = 1 << 20) { reset(cap_pow2); }
+    void reset(size_t cap_pow2) { keys.assign(cap_pow2, EMPTY); vals.assign(cap_pow2, 0); mask = cap_pow2 - 1; n = 0; }
+    void grow() {
+        std::vector<KM> ok; std::vector<uint64_t> ov; ok.swap(keys); ov.swap(vals);
+        keys.assign(ok.size() * 2, EMPTY); vals.assign(ok.size() * 2, 0); mask = keys.size() - 1; n = 0;
+        for (size_t i = 0; i < ok.size(); ++i) if (ok[i] != EMPTY) *slot(ok[i], true) = ov[i];
+    }
+    uint64_t* slot(KM key, bool insert) {
+        if (insert && (n + 1) * 10 > keys.size() * 6) grow();
+        size_t i = hash_km(key) & mask;
+        while (true) {
+            if (keys[i] == key) return &vals[i];
+            if (keys[i] == EMPTY) { if (!insert) return nullptr; keys[i] = key; ++n; return &vals[i]; }
+            i = (i + 1) & mask;
+        }
+    }
+};
+
+template <class F> static void parallel_for(size_t n, unsigned n_thr, F f) { // f(begin, end, thread)
+    if (n_thr < 1) n_thr = 1;
+    std::vector<std::thread> th; const size_t per = (n + n_thr - 1) / n_thr;
+    for (unsigned t = 0; t < n_thr; ++t) { const size_t b = std::min(n, per * t), e = std::min(n, per * (t + 1)); if (b < e) th.emplace_back([=]() { f(b, e, t); }); }
+    for (size_t t = 0; t < th.size(); ++t) th[t].join();
+}
+
+struct Unitig { std::string seq; std::vector<uint32_t> colours; uint64_t cov = 0; };
+struct Nb { int64_t u[2][4]; }; // [dir 0 = fw successors, 1 = successors of the reverse strand][base] -> unitig id or -1
+
+inline size_t shared_count(const std::vector<uint32_t>& a, const std::vector<uint32_t>& b) {
+    size_t i = 0, j = 0, c = 0;
+    while (i < a.size() && j < b.size()) { if (a[i] < b[j]) ++i; else if (b[j] < a[i]) ++j; else { ++c; ++i; ++j; } }
+    return c;
+}
+
+template <class KM> struct IndexBuild { // KM: uint64_t for k <= 31, u128 for k in 33..63
+    const IndexOptions& o; const IndexKnobs knobs; HipLib lib; // (lib: loaded with --gpu only)
+    const int k; const KM mask; unsigned n_thr;
+    const std::chrono::steady_clock::time_point t_start = std::chrono::steady_clock::now();
+    std::vector<KM> solid;          // the canonical k-mers seen >= --min-count times, sorted
+    KTable<KM> km;                  // canonical solid k-mer -> 0 (unvisited) or (unitig+1)<<32 | offset<<1 | fw_flag
+    std::vector<Unitig> U;
+    std::vector<KM> headk, tailk;   // per unitig (from the adjacency step on): first and last k-mer,
+    std::vector<Nb> adj; std::vector<uint64_t> kmcov, shared; // neighbours, coverage + branching bit, edge bits (+ 0x100: in a short cycle)
+    std::vector<std::string> cycles;
+    std::vector<std::vector<uint32_t> > ambiguity, global_ids, local_ids;
+    std::thread fasta_thread; std::atomic<int> fasta_rc; // --fast: the unitig FASTA is compressed beside the other steps
+    explicit IndexBuild(const IndexOptions& opt) : o(opt), k(opt.k), mask(km_mask<KM>(opt.k)), km(16), fasta_rc(0) {
+        n_thr = std::thread::hardware_concurrency(); if (n_thr == 0) n_thr = 1; if (n_thr > (o.fast ? 128u : 32u)) n_thr = o.fast ? 128u : 32u; // (--fast: the steps are random accesses into GB-sized tables: latency-bound, SMT threads help)
+        if (knobs.threads) n_thr = knobs.threads;
+    }
+    ~IndexBuild() { if (fasta_thread.joinable()) fasta_thread.join(); } // (whoever leaves early leaves through here: the writer reads U)
+    void lap(const char* what) const { if (knobs.trace) fprintf(stderr, "rtk_build_index: [%8.2f s] %s\n", std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count(), what); }
+    // the oriented neighbours of an oriented k-mer that are in the graph
+    bool in_graph(KM oriented) { return km.slot(kmer_canonical(oriented, k), false) != nullptr; }
+    int succs(KM x, KM out[4]) { int n = 0; for (uint64_t b = 0; b < 4; ++b) { const KM y = ((x << 2) | static_cast<KM>(b)) & mask; if (in_graph(y)) out[n++] = y; } return n; }
+    int preds(KM x, KM out[4]) { int n = 0; for (uint64_t b = 0; b < 4; ++b) { const KM y = (x >> 2) | (static_cast<KM>(b) << (2 * (k - 1))); if (in_graph(y)) out[n++] = y; } return n; }
+};
+
+} // namespace rtk
+
+#endif

@@ -6,7 +6,6 @@
 //   plain    k-mers counted and reads tested on the host threads (no GPU, no library): bisection in the two sorted sets
 //   --gpu    both counts from rtk_index_count_kmers, the filter through rtk_rescue_begin / _chunk / _end of libratatosk_hip.so next to this executable
 // Both write the same bytes. No read kept, or no long-read k-mer seen twice: exit status 0 and no file (src/Graph.cpp:4124-4128).
-#include <dlfcn.h>
 #include <unistd.h>
 
 #include <algorithm>
@@ -24,6 +23,7 @@
 #include <vector>
 
 #include "../common/fastx.hpp"
+#include "../common/hip_lib.hpp"
 #include "../common/kmer.hpp"
 #include "../common/kmer_count.hpp"
 
@@ -38,13 +38,8 @@ static bool in_sorted(const std::vector<uint64_t>& a, uint64_t x) { return std::
 
 // the restated rule on the host: start positions whose k characters are all A/C/G/T and spell a k-mer of lr that is not in sr
 static uint32_t qualifying_positions(const char* s, size_t len, int k, const std::vector<uint64_t>& lr, const std::vector<uint64_t>& sr) {
-    const uint64_t mask = kmer_mask(k); uint64_t fw = 0; int valid = 0; uint32_t n = 0;
-    for (size_t i = 0; i < len; ++i) {
-        const int b = base2bits(s[i]);
-        if (b < 0) { valid = 0; fw = 0; continue; }
-        fw = ((fw << 2) | static_cast<uint64_t>(b)) & mask;
-        if (++valid >= k) { const uint64_t c = kmer_canonical(fw, k); if (in_sorted(lr, c) && !in_sorted(sr, c)) ++n; }
-    }
+    uint32_t n = 0;
+    for_each_canonical_kmer<uint64_t>(s, len, k, kmer_mask(k), [&](uint64_t c, size_t) { if (in_sorted(lr, c) && !in_sorted(sr, c)) ++n; });
     return n;
 }
 
@@ -81,30 +76,24 @@ int main(int argc, char** argv) {
     { const char* e = getenv("RTK_INDEX_CHUNK"); if (e && strtoull(e, nullptr, 10) >= 1024) chunk_chars = std::min<size_t>(strtoull(e, nullptr, 10), 60u << 20); }
     const size_t chunk_reads = 2u << 20;
 
-    typedef int (*count_fn)(int, int, const char* const*, int, uint32_t, int, uint64_t**, uint64_t*);
-    typedef int (*begin_fn)(int, int, const uint64_t*, uint64_t, const uint64_t*, uint64_t, uint32_t, void**);
-    typedef int (*chunk_fn)(void*, const char*, uint64_t, const uint64_t*, uint32_t, unsigned char*);
-    typedef int (*end_fn)(void*, uint64_t*, uint64_t*);
-    typedef const char* (*err_fn)(void); typedef void (*free_fn)(void*);
-    count_fn g_count = nullptr; begin_fn g_begin = nullptr; chunk_fn g_chunk = nullptr; end_fn g_end = nullptr; err_fn g_err = nullptr; free_fn g_free = nullptr;
+    HipLib lib; HipLib::rescue_begin_fn g_begin = nullptr; HipLib::rescue_chunk_fn g_chunk = nullptr; HipLib::rescue_end_fn g_end = nullptr;
     if (gpu) {
-        std::string lib = "libratatosk_hip.so";
-        { char exe[4096]; const ssize_t n = readlink("/proc/self/exe", exe, sizeof(exe) - 1); if (n > 0) { exe[n] = 0; std::string d(exe); d = d.substr(0, d.rfind('/')); lib = d + "/../libratatosk_hip.so"; } }
-        void* h = dlopen(lib.c_str(), RTLD_NOW | RTLD_GLOBAL);
-        if (!h) { fprintf(stderr, "rtk_rescue_reads: --gpu: cannot load %s (%s)\n", lib.c_str(), dlerror()); return 1; }
-        g_count = reinterpret_cast<count_fn>(dlsym(h, "rtk_index_count_kmers")); g_begin = reinterpret_cast<begin_fn>(dlsym(h, "rtk_rescue_begin")); g_chunk = reinterpret_cast<chunk_fn>(dlsym(h, "rtk_rescue_chunk"));
-        g_end = reinterpret_cast<end_fn>(dlsym(h, "rtk_rescue_end")); g_err = reinterpret_cast<err_fn>(dlsym(h, "rtk_last_error")); g_free = reinterpret_cast<free_fn>(dlsym(h, "rtk_free"));
-        if (!g_count || !g_begin || !g_chunk || !g_end || !g_err || !g_free) { fprintf(stderr, "rtk_rescue_reads: --gpu: %s lacks the rescue entry points\n", lib.c_str()); return 1; }
+        if (!lib.open("rtk_rescue_reads")) return 1;
+        if (!lib.count_kmers || !lib.get(g_begin, "rtk_rescue_begin") || !lib.get(g_chunk, "rtk_rescue_chunk") || !lib.get(g_end, "rtk_rescue_end") || !lib.last_error || !lib.free) { fprintf(stderr, "rtk_rescue_reads: --gpu: %s lacks the rescue entry points\n", lib.path.c_str()); return 1; }
     }
 
     // ---- the two k-mer sets: seen at least twice in the -s reads (bf_non_uniq, src/Graph.cpp:3733, 3830), in the long reads (the Bifrost build with its singleton filter, :3884)
     std::vector<uint64_t> sr, lr;
     auto count = [&](const std::vector<std::string>& files, std::vector<uint64_t>& out) -> bool {
-        if (!gpu) { std::string err; if (!count_kmers_host(files, k, 2, n_thr, out, &err)) { fprintf(stderr, "rtk_rescue_reads: %s\n", err.c_str()); return false; } return true; }
+        if (!gpu) {
+            size_t f = 0; const int bad = count_kmers_host<uint64_t>(files, k, 2, n_thr, out, &f);
+            if (bad) fprintf(stderr, bad == 2 ? "rtk_rescue_reads: %s ends in a damaged or cut-short gzip stream\n" : "rtk_rescue_reads: cannot open %s\n", files[f].c_str());
+            return !bad;
+        }
         std::vector<const char*> fp; for (size_t f = 0; f < files.size(); ++f) fp.push_back(files[f].c_str());
         uint64_t* sk = nullptr; uint64_t ns = 0;
-        if (g_count(0, k, fp.data(), static_cast<int>(fp.size()), 2, static_cast<int>(n_thr), &sk, &ns) != 0) { fprintf(stderr, "rtk_rescue_reads: --gpu: %s\n", g_err()); return false; }
-        out.assign(sk, sk + ns); g_free(sk); return true;
+        if (lib.count_kmers(0, k, fp.data(), static_cast<int>(fp.size()), 2, static_cast<int>(n_thr), &sk, &ns) != 0) { fprintf(stderr, "rtk_rescue_reads: --gpu: %s\n", lib.last_error()); return false; }
+        out.assign(sk, sk + ns); lib.free(sk); return true;
     };
     if (verbose) fprintf(stderr, "Ratatosk::retrieveMissingReads(): Creating index of short reads\n");
     if (!count(in_short, sr)) return 1;
@@ -121,7 +110,7 @@ int main(int argc, char** argv) {
     }
     void* job = nullptr;
     if (gpu) {
-        if (g_begin(0, k, lr.data(), lr.size(), sr.data(), sr.size(), MIN_POSITIONS, &job) != 0) { fprintf(stderr, "rtk_rescue_reads: --gpu: %s\n", g_err()); return 1; }
+        if (g_begin(0, k, lr.data(), lr.size(), sr.data(), sr.size(), MIN_POSITIONS, &job) != 0) { fprintf(stderr, "rtk_rescue_reads: --gpu: %s\n", lib.last_error()); return 1; }
         std::vector<uint64_t>().swap(lr); std::vector<uint64_t>().swap(sr); // (the table lives on the device)
     }
     lap("build D");
@@ -180,7 +169,7 @@ int main(int argc, char** argv) {
                 if (b->chars.size() > (60u << 20) || b->n() > (4u << 20) - 1) { fail("a byte range of a -u file holds more than a batch (a read of tens of megabases?)"); return; }
             }
             const size_t n = b->n(); b->keep.assign(n ? n : 1, 0); b->name_off.push_back(b->names.size());
-            if (n && gpu) { if (g_chunk(job, b->chars.data(), b->chars.size(), b->starts.data(), static_cast<uint32_t>(n), b->keep.data()) != 0) { fail(std::string("--gpu: ") + g_err()); return; } }
+            if (n && gpu) { if (g_chunk(job, b->chars.data(), b->chars.size(), b->starts.data(), static_cast<uint32_t>(n), b->keep.data()) != 0) { fail(std::string("--gpu: ") + lib.last_error()); return; } }
             else for (size_t r = 0; r < n; ++r) { const size_t e = (r + 1 < n ? b->starts[r + 1] : b->chars.size()) - 1; // (without the separator)
                 b->keep[r] = qualifying_positions(b->chars.data() + b->starts[r], e - b->starts[r], k, lr, sr) >= MIN_POSITIONS ? 1 : 0; }
             block.clear(); unsigned long long kept = 0;
@@ -210,7 +199,7 @@ int main(int argc, char** argv) {
     if (!first_err.empty()) { fprintf(stderr, "rtk_rescue_reads: %s\n", first_err.c_str()); failed = true; }
     else if (!waiting.empty()) { fprintf(stderr, "rtk_rescue_reads: output incomplete\n"); failed = true; }
     uint64_t n_probed = 0, n_hits = 0;
-    if (job && g_end(job, &n_probed, &n_hits) != 0) { fprintf(stderr, "rtk_rescue_reads: --gpu: %s\n", g_err()); failed = true; }
+    if (job && g_end(job, &n_probed, &n_hits) != 0) { fprintf(stderr, "rtk_rescue_reads: --gpu: %s\n", lib.last_error()); failed = true; }
     if (fclose(fo) != 0) { fprintf(stderr, "rtk_rescue_reads: write error on %s\n", fn_out.c_str()); failed = true; }
     if (failed) { unlink(fn_out.c_str()); return 1; } // a failing step leaves no output file
     lap("filter");
