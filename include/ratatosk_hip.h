@@ -123,13 +123,17 @@ typedef struct rtk_stats {
      * sweep that can be parked at the trim, as before. Appended without a new revision number, like the fields above. */
     uint64_t n_park_walked, n_park_deferred;
     /* Revision 10: calls of the region program's colour selection (chooseColors, src/Correction.cpp:215-429; csrc/hip/rtk_region.h, rtk_choose_colors) by the
-     * program that answered: the register program with 8-word bit vectors (n_colours_small: up to 512 ids on up to 24 side unitigs) or with 64-word vectors
-     * (n_colours_wide: up to 1664 ids), the bit-vector program in scratch memory (n_colours_bits) or the general program on sorted arrays (n_colours_general).
+     * program that answered: the register program (n_colours_small: up to 512 ids on up to 24 side unitigs; n_colours_wide: up to 1664 ids), the bit-vector program in scratch memory (n_colours_bits) or the general program on sorted arrays (n_colours_general).
      * The host simulator has neither of the first two. Calls that ended in an overflow are not counted (their region is redone). RTK_COLOURS_ROUTE=bits skips
      * the register program, RTK_COLOURS_ROUTE=general both bit-vector programs: same selections, same sum. RTK_COLOURS_AUDIT=1 lets the general program repeat
      * every selection another program answered and counts the calls whose two lists differ (n_colours_audit_mismatch: 0 unless a program is wrong); the
      * general program's list is the one used, and n_colour_elem counts the ids of both runs. */
     uint64_t n_colours_small, n_colours_wide, n_colours_bits, n_colours_general, n_colours_audit_mismatch;
+    /* The register program sorts the ids of a call once, sizes its bit vectors by the number of distinct ids and keeps them in LDS behind the universe
+     * (DESIGN.md §3.2 (h)); n_colours_small / n_colours_wide are its calls with at most / more than 512 ids, repeats counted. A call whose universe and vectors
+     * do not fit the LDS buffer is handed on (n_colours_declined_fit) and answered -- and counted -- by one of the other two programs. Appended without a new
+     * revision number, like the fields above. */
+    uint64_t n_colours_declined_fit;
 } rtk_stats;
 
 /* dbg.read(G.fasta.gz) + readGraphData(G.rtsk) (reference: src/Ratatosk.cpp:1087-1089; src/Graph.cpp:722-784).
@@ -344,7 +348,15 @@ int rtk_rescue_end(void* job, uint64_t* n_positions_probed, uint64_t* n_hits);
  *   RADIX_PAIRS_U32: a = na keys <= scalar, b = their payloads (nb = na); out = keys then payloads, stable ascending by key (slice >= 2 na).
  *   BM_LOWEST: a = a universe of na <= 4096 ids (sorted, no repeats), b = nb ids of it (sorted, no repeats); the bit vector of b over the universe
  *     (rtk_bm_from_ids), result = its population count, out = the ids of its scalar lowest bits (slice >= min(scalar, nb)).
- *   BM8_LOWEST: the same with the vector in lanes 0 .. 7 (rtk_bm8_lowest, rtk_bm8_count): na <= 512. */
+ *   BM8_LOWEST: the same with the vector in lanes 0 .. 7 (rtk_bm8_lowest, rtk_bm8_count): na <= 512.
+ *   RADIX_TAGGED: the universe sort of the register program (rtk_radix_sort_tagged in the layout of rtk_colour_universe, rtk_colours.h): a = na <= 1664 ids <= scalar
+ *     <= 0xFFFFFFFE, b = their tags < 48 (nb = na); out = ids then tags, stable ascending by id (slice >= 2 na). The scalar chooses the form as the largest id of a
+ *     call does: below 2^26 the tag rides in the low bits of the id's word, from there on in a byte array beside it. Device only.
+ *   COLOUR_UNIVERSE: universe and bit vectors of the register program (rtk_colour_universe): a = the ids of nb <= 48 lists one after the other (na <= 1664 in
+ *     all, each list sorted without repeats or not: only membership counts), b = the nb list lengths, scalar as for RADIX_TAGGED. out = U, VW, the U distinct
+ *     ids ascending, then nb vectors of VW 64-bit words (low word, high word): bit r of vector t is set when list t holds the id of rank r
+ *     (slice >= 2 + na + 2 nb max(1, ceil(na / 64))); result = U. status RTK_SETS_DECLINED and no output words when universe and vectors do not fit the LDS buffer
+ *     the way the register program lays them out. Device only. */
 #define RTK_SETS_UNION 0
 #define RTK_SETS_INTER 1
 #define RTK_SETS_DIFF 2
@@ -354,8 +366,11 @@ int rtk_rescue_end(void* job, uint64_t* n_positions_probed, uint64_t* n_hits);
 #define RTK_SETS_RADIX_PAIRS_U32 6
 #define RTK_SETS_BM_LOWEST 7
 #define RTK_SETS_BM8_LOWEST 8
+#define RTK_SETS_RADIX_TAGGED 9
+#define RTK_SETS_COLOUR_UNIVERSE 10
 #define RTK_SETS_OK 0
 #define RTK_SETS_NOT_IN_BUILD 1
+#define RTK_SETS_DECLINED 2
 int rtk_sets_batch(uint32_t n, const uint32_t* op, const uint32_t* const* a, const uint32_t* na, const uint32_t* const* b, const uint32_t* nb, const uint32_t* scalar,
                    uint32_t* out_pool, const uint64_t* out_off, uint32_t* out_n, uint32_t* result, uint32_t* status);
 

@@ -40,7 +40,7 @@ class RtkStats(C.Structure):
                                          "n_fa_linked_run", "n_fa_linked_skipped", "n_fa_linked_entries",
                                          "n_strand2_run", "n_strand2_skipped", "n_strand2_audit_mismatch",
                                          "n_park_walked", "n_park_deferred",
-                                         "n_colours_small", "n_colours_wide", "n_colours_bits", "n_colours_general", "n_colours_audit_mismatch")]
+                                         "n_colours_small", "n_colours_wide", "n_colours_bits", "n_colours_general", "n_colours_audit_mismatch", "n_colours_declined_fit")]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -380,8 +380,8 @@ def myers_lanes_last_routes(lib_path=None):
     return a.value, b.value
 
 
-SETS_UNION, SETS_INTER, SETS_DIFF, SETS_INTER_COUNT, SETS_SORT_PAIRS, SETS_RADIX_U32, SETS_RADIX_PAIRS_U32, SETS_BM_LOWEST, SETS_BM8_LOWEST = range(9)  # operations of sets_batch
-SETS_OK, SETS_NOT_IN_BUILD = 0, 1  # its per-problem statuses
+SETS_UNION, SETS_INTER, SETS_DIFF, SETS_INTER_COUNT, SETS_SORT_PAIRS, SETS_RADIX_U32, SETS_RADIX_PAIRS_U32, SETS_BM_LOWEST, SETS_BM8_LOWEST, SETS_RADIX_TAGGED, SETS_COLOUR_UNIVERSE = range(11)  # operations of sets_batch
+SETS_OK, SETS_NOT_IN_BUILD, SETS_DECLINED = 0, 1, 2  # its per-problem statuses
 
 
 def sets_batch(problems, lib_path=None):
@@ -407,7 +407,8 @@ def sets_batch(problems, lib_path=None):
         ops[i], na[i], nb[i], sc[i] = op, count_a, count_b, scalar
         pa[i] = a.ctypes.data_as(C.POINTER(C.c_uint32)); pb[i] = b.ctypes.data_as(C.POINTER(C.c_uint32))
         need = {SETS_UNION: count_a + count_b, SETS_INTER: count_a, SETS_DIFF: count_a, SETS_INTER_COUNT: 0, SETS_SORT_PAIRS: 4 * count_a, SETS_RADIX_U32: count_a,
-                SETS_RADIX_PAIRS_U32: 2 * count_a, SETS_BM_LOWEST: min(scalar, count_b), SETS_BM8_LOWEST: min(scalar, count_b)}.get(op, 0)
+                SETS_RADIX_PAIRS_U32: 2 * count_a, SETS_BM_LOWEST: min(scalar, count_b), SETS_BM8_LOWEST: min(scalar, count_b),
+                SETS_RADIX_TAGGED: 2 * count_a, SETS_COLOUR_UNIVERSE: 2 + count_a + 2 * count_b * max(1, (count_a + 63) // 64)}.get(op, 0)
         off.append(off[-1] + need)
     out = np.zeros(max(1, off[-1]), dtype=np.uint32)
     offs = (C.c_uint64 * (n + 1))(*off)

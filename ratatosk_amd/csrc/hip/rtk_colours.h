@@ -1,6 +1,7 @@
 // chooseColors (reference: src/Correction.cpp:215-429) on bit vectors, for the regions that make up nearly all of a batch: the colour
 // sets of the anchors around one weak region hold a few hundred distinct pair ids together (measured on configs[1]: < 512 in 90 % of
-// the calls). Those ids are sorted once into a small universe kept in LDS; every set of the algorithm -- the six anchor classes, their
+// the calls; on the 1 Mb set of the bench's generator arguments a median of 235, at most 526, out of a median of 405 ids with repeats).
+// Those ids are sorted once into a small universe kept in LDS; every set of the algorithm -- the six anchor classes, their
 // unions / intersections / differences, curr_pid, all_pids -- is then ONE 64-bit word per lane (4096 bits), the whole class loop runs
 // in registers (OR / AND / ANDN, popcount + wave sum, "the quota lowest ids" = a prefix count), and all_pids is expanded back into a
 // sorted id list at the end. Same selections as the general sorted-array version in rtk_region.h, which stays the fallback for
@@ -61,6 +62,62 @@ RTK_DEV void rtk_radix_sort_u32(uint32_t* a, uint32_t* b, uint32_t n, uint32_t* 
         uint32_t* t_ = src; src = dst; dst = t_;
     }
 }
+
+// The universe sort of the register program: n (32-bit key, tag) entries sorted by key, stable, by one wave. Two forms of the tag. ta == nullptr: the tag rides in
+// the low `lo` bits of the word and the key sits above them (key < 2^(32 - lo)); the digits start at bit `lo`. Otherwise lo = 0, the word is the key and the tags
+// are a byte array moved with the words (ta <-> tb as a <-> b). Differences from rtk_radix_sort_u32: as many passes as the largest key has bytes, odd or even --
+// the result is where the last pass left it and the routine returns that buffer (a or b; the tags are in ta or tb accordingly); the histograms are plain LDS adds,
+// one per key (a histogram needs no order: the match network is kept for the scatter alone), and where `bins` has 256 counters per pass they are all taken in
+// one read of the keys. `a` is in LDS; b, ta, tb in LDS or device memory.
+RTK_DEV uint32_t* rtk_radix_sort_tagged(uint32_t* a, uint32_t* b, uint8_t* ta, uint8_t* tb, uint32_t n, uint32_t* bins, uint32_t bins_words, uint32_t lo, uint32_t max_key) {
+    const uint32_t lane = static_cast<uint32_t>(rtk_lane());
+    const uint64_t lt = (1ull << lane) - 1ull;
+    uint32_t passes = 0; { uint32_t m = max_key; while (m) { ++passes; m >>= 8; } if (passes == 0) passes = 1; }
+    const bool fused = passes * 256u <= bins_words;
+    if (fused) {
+        for (uint32_t i = lane; i < passes * 256u; i += RTK_WAVE) bins[i] = 0u;
+        RTK_WG_SYNC();
+        for (uint32_t i = lane; i < n; i += RTK_WAVE) { const uint32_t key = a[i] >> lo; for (uint32_t ps = 0; ps < passes; ++ps) atomicAdd(&bins[256u * ps + ((key >> (8u * ps)) & 0xFFu)], 1u); }
+        RTK_WG_SYNC();
+    }
+    uint32_t* src = a; uint32_t* dst = b; uint8_t* ts = ta; uint8_t* td = tb;
+    for (uint32_t ps = 0; ps < passes; ++ps) {
+        const uint32_t sh = lo + 8u * ps;
+        uint32_t* const pb = fused ? bins + 256u * ps : bins;
+        if (!fused) {
+            for (uint32_t i = lane; i < 256u; i += RTK_WAVE) pb[i] = 0u;
+            RTK_WG_SYNC();
+            for (uint32_t i = lane; i < n; i += RTK_WAVE) atomicAdd(&pb[(src[i] >> sh) & 0xFFu], 1u);
+            RTK_WG_SYNC();
+        }
+        { // exclusive prefix over the 256 bins: four bins per lane
+            uint32_t v[4]; uint32_t sum = 0;
+            for (int x = 0; x < 4; ++x) { v[x] = pb[4u * lane + static_cast<uint32_t>(x)]; sum += v[x]; }
+            int tot; uint32_t base = static_cast<uint32_t>(rtk_wave_excl_scan(static_cast<int>(sum), &tot));
+            RTK_WG_SYNC();
+            for (int x = 0; x < 4; ++x) { pb[4u * lane + static_cast<uint32_t>(x)] = base; base += v[x]; }
+        }
+        RTK_WG_SYNC();
+        // stable scatter, chunk by chunk
+        for (uint32_t c0 = 0; c0 < n; c0 += RTK_WAVE) {
+            const uint32_t i = c0 + lane; const bool ok = i < n;
+            const uint32_t key = ok ? src[i] : 0u;
+            const uint32_t tag = (ok && ts) ? ts[i] : 0u;
+            const uint32_t d = ok ? ((key >> sh) & 0xFFu) : 0x100u;
+            uint64_t eq = rtk_ballot(ok);
+            for (int bt = 0; bt < 8; ++bt) { const uint64_t bb = rtk_ballot((d >> bt) & 1u); eq &= ((d >> bt) & 1u) ? bb : ~bb; }
+            const uint32_t before = static_cast<uint32_t>(rtk_popc(eq & lt));
+            uint32_t base = 0;
+            if (ok) base = pb[d];
+            RTK_WG_SYNC();
+            if (ok && before == 0u) pb[d] = base + static_cast<uint32_t>(rtk_popc(eq));
+            if (ok) { dst[base + before] = key; if (ts) td[base + before] = static_cast<uint8_t>(tag); }
+            RTK_WG_SYNC();
+        }
+        { uint32_t* t_ = src; src = dst; dst = t_; uint8_t* u_ = ts; ts = td; td = u_; }
+    }
+    return src;
+}
 #endif
 
 #ifdef RTK_SIM
@@ -111,15 +168,85 @@ RTK_DEV RtkBM rtk_bm_from_ids(const uint32_t* uni, uint32_t U, uint64_t* scatter
 
 
 #ifndef RTK_SIM
-// The same selection for the common small case -- at most 512 ids (with repeats) on at most 24 side unitigs -- with every chain of
-// dependent memory round trips taken out: slot s lives in lane s (unitig, offsets and sizes of its colour lists, cardinality, flags:
-// three round trips for all slots together instead of five per slot and pass), the candidate anchors are ranked in registers, the
-// ids go from the colour pool straight into LDS (one flat pass over all lists), and the per-slot bit vectors (8 words at this size)
-// stay in LDS. Returns RTK_NONE32 when the case is not small (caller goes on to rtk_choose_colors_bits).
+// The same selection for the common case -- at most 1664 ids (with repeats) on at most 24 side unitigs -- with every chain of dependent memory round trips
+// taken out: slot s lives in lane s (unitig, offsets and sizes of its colour lists, cardinality, flags: three round trips for all slots together instead of
+// five per slot and pass), the candidate anchors are ranked in registers, the ids go from the colour pool straight into LDS (one flat pass over all lists),
+// each with the number of the list it came from (its tag: 2 x slot + global), and the per-list bit vectors stay in LDS behind the universe. Returns
+// RTK_NONE32 when the case does not fit (caller goes on to rtk_choose_colors_bits).
 #ifndef RTK_CS_MAX_IDS
 #define RTK_CS_MAX_IDS 512u // (developer builds with a smaller LDS buffer lower it: profiles/scripts/build_wpe_variant.sh)
 #endif
-static_assert(2u * RTK_CS_MAX_IDS + 768u <= RTK_LDS_SET_CAP && RTK_CS_MAX_IDS <= 512u, "small path of the colour selection: universe + unsorted ids + 24 x 2 x 8 vector words in the LDS buffer");
+#define RTK_CS_TAG_BITS 6u                                  // a tag is below 2 x RTK_CB_MAX_SLOTS = 48
+#define RTK_CS_PACKED_LIMIT (1u << (32u - RTK_CS_TAG_BITS)) // ids below it carry their tag in the low bits of their word; larger ones have it in a byte array
+static_assert(2u * RTK_CB_MAX_SLOTS <= (1u << RTK_CS_TAG_BITS), "colour selection: a tag fits its bits");
+static_assert(2u * RTK_CS_MAX_IDS + 768u + RTK_CS_MAX_IDS / 2u <= RTK_LDS_SET_CAP && RTK_CS_MAX_IDS <= 512u && RTK_CS_MAX_IDS % 4u == 0u, "colour selection, at most RTK_CS_MAX_IDS ids: two key buffers, 24 x 2 x 8 vector words (before them: three sets of sort counters) and two tag arrays in the LDS buffer");
+
+// Universe and bit vectors of one call. In: T <= RTK_CB_MAX_IDS entries in L (the wave's LDS buffer), each an id and a tag < n_vec <= 48; mx = the largest id.
+// packed (mx < RTK_CS_PACKED_LIMIT): L[i] = (id << RTK_CS_TAG_BITS) | tag. Otherwise L[i] = id and the tag is byte i of rtk_cu_tags(). Out: the U distinct ids
+// in rising order in L[0, U), and n_vec bit vectors of VW = ceil(U / 64) 64-bit words each at `vec` (in L, behind the universe): bit r of vector t is set when
+// list t holds the id of rank r. The entries are sorted by id (rtk_radix_sort_tagged); a first pass over the sorted entries counts U, which fixes the layout;
+// a second one writes the universe and ORs every entry's bit into the vector of its tag -- an entry's rank is the number of run heads up to it, so nothing is
+// searched. Returns false when universe and vectors do not fit the buffer (nothing of the caller's is changed then).
+// T <= RTK_CS_MAX_IDS: keys in L[0, 512) and L[512, 1024), counters, then vectors, in L[1024, 1792), tag arrays in L[1792, 2048).
+// Above: keys in L[0, 1664) and in gbuf (device memory, T words), counters in L[1664, 1920), tag arrays in gtags (device memory, 2 x 1664 bytes); the sorted
+// entries are read from gbuf (copied there when the sort ended in L), so that the vectors can take the place of the keys.
+RTK_DEV uint8_t* rtk_cu_tags(uint32_t* L, uint32_t T, uint8_t* gtags) { return T > RTK_CS_MAX_IDS ? gtags : reinterpret_cast<uint8_t*>(L + 2u * RTK_CS_MAX_IDS + 768u); }
+// the sort of that layout: returns the sorted entries (in L, or in the second key buffer after an odd number of passes) and, in *tsrt, their tags when they travel apart
+RTK_DEV uint32_t* rtk_cu_sort(uint32_t* L, uint32_t T, uint32_t mx, uint32_t* gbuf, uint8_t* gtags, const uint8_t** tsrt) {
+    const bool big = T > RTK_CS_MAX_IDS, packed = mx < RTK_CS_PACKED_LIMIT;
+    uint8_t* const ta = packed ? nullptr : rtk_cu_tags(L, T, gtags); uint8_t* const tb = packed ? nullptr : ta + (big ? RTK_CB_MAX_IDS : RTK_CS_MAX_IDS);
+    uint32_t* const srt = rtk_radix_sort_tagged(L, big ? gbuf : L + RTK_CS_MAX_IDS, ta, tb, T, big ? L + RTK_CB_MAX_IDS : L + 2u * RTK_CS_MAX_IDS, big ? 256u : 768u, packed ? RTK_CS_TAG_BITS : 0u, mx);
+    *tsrt = srt == L ? ta : tb;
+    return srt;
+}
+RTK_DEV bool rtk_colour_universe(uint32_t* L, uint32_t T, uint32_t n_vec, uint32_t mx, uint32_t* gbuf, uint8_t* gtags, uint32_t* U_out, uint32_t* VW_out, uint64_t** vec_out) {
+    const uint32_t lane = static_cast<uint32_t>(rtk_lane());
+    const uint64_t le = (2ull << lane) - 1ull; // this lane and the ones below
+    const bool big = T > RTK_CS_MAX_IDS, packed = mx < RTK_CS_PACKED_LIMIT;
+    const uint8_t* tsrt;
+    const uint32_t* srt = rtk_cu_sort(L, T, mx, gbuf, gtags, &tsrt);
+    if (big && srt == L) { for (uint32_t i = lane; i < T; i += RTK_WAVE) gbuf[i] = L[i]; RTK_WG_SYNC(); srt = gbuf; }
+    // run heads of one chunk of 64 sorted entries (four chunks are loaded at a time: their round trips overlap when the entries are in device memory)
+    uint32_t carry = 0; // id of the entry before the chunk
+    auto heads = [&](uint32_t idx, uint32_t w, uint32_t* id) -> uint64_t {
+        *id = packed ? (w >> RTK_CS_TAG_BITS) : w;
+        const uint32_t prev = rtk_shfl_up1(*id, carry);
+        carry = rtk_shfl(*id, 63);
+        return rtk_ballot(idx < T && (idx == 0u || *id != prev));
+    };
+    uint32_t U = 0;
+    for (uint32_t i0 = 0; i0 < T; i0 += 4u * RTK_WAVE) {
+        uint32_t w[4];
+        for (uint32_t k = 0; k < 4u; ++k) { const uint32_t idx = i0 + k * RTK_WAVE + lane; w[k] = idx < T ? srt[idx] : 0u; }
+        for (uint32_t k = 0; k < 4u; ++k) { uint32_t id; U += static_cast<uint32_t>(rtk_popc(heads(i0 + k * RTK_WAVE + lane, w[k], &id))); }
+    }
+    const uint32_t VW = U ? (U + 63u) / 64u : 1u;
+    *U_out = U; *VW_out = VW;
+    const uint32_t at = big ? ((U + 1u) & ~1u) : 2u * RTK_CS_MAX_IDS;
+    if (at + 2u * n_vec * VW > (big ? RTK_LDS_SET_CAP : 2u * RTK_CS_MAX_IDS + 768u)) return false;
+    uint64_t* const vec = reinterpret_cast<uint64_t*>(L + at);
+    for (uint32_t i = lane; i < n_vec * VW; i += RTK_WAVE) vec[i] = 0ull;
+    RTK_WG_SYNC();
+    uint32_t R = 0; carry = 0;
+    for (uint32_t i0 = 0; i0 < T; i0 += 4u * RTK_WAVE) {
+        uint32_t w[4], tg[4];
+        for (uint32_t k = 0; k < 4u; ++k) { const uint32_t idx = i0 + k * RTK_WAVE + lane; w[k] = idx < T ? srt[idx] : 0u; tg[k] = packed ? (w[k] & ((1u << RTK_CS_TAG_BITS) - 1u)) : (idx < T ? tsrt[idx] : 0u); }
+        RTK_WG_SYNC(); // (T <= RTK_CS_MAX_IDS and an even number of passes: the universe is written over entries read above, at or below their own place)
+        for (uint32_t k = 0; k < 4u; ++k) {
+            const uint32_t idx = i0 + k * RTK_WAVE + lane; uint32_t id;
+            const uint64_t bal = heads(idx, w[k], &id);
+            if (idx < T) {
+                const uint32_t rank = R + static_cast<uint32_t>(rtk_popc(bal & le)) - 1u;
+                if ((bal >> lane) & 1ull) L[rank] = id;
+                atomicOr(reinterpret_cast<unsigned long long*>(vec) + tg[k] * VW + (rank >> 6), 1ull << (rank & 63u));
+            }
+            R += static_cast<uint32_t>(rtk_popc(bal));
+        }
+    }
+    RTK_WG_SYNC();
+    *vec_out = vec;
+    return true;
+}
 // the 512-bit vectors of the small case live in lanes 0..7 (the other lanes hold zero): sums and prefix sums over eight lanes by DPP
 // moves inside one row (quad permutes, half-row mirror, row shifts) instead of six cross-lane permutes through LDS
 RTK_DEV int rtk_sum8(int v) { // every lane of 0..7 gets the sum over lanes 0..7 (callers read lane 0)
@@ -163,9 +290,9 @@ RTK_FN uint32_t rtk_choose_colors_small(const RCtx& c_, const SideList& side_s_,
     }
     int total = 0; const uint32_t st = static_cast<uint32_t>(rtk_wave_excl_scan(static_cast<int>(m_nl + m_ng), &total)); // first id of the slot in the flat order
     const uint32_t T = static_cast<uint32_t>(rtk_u(total));
-    // two sizes: <= 512 ids -> 8-word bit vectors, the unsorted ids and the vectors in LDS; <= 1664 ids -> 64-word vectors in scratch memory
+    // (above RTK_CS_MAX_IDS ids the sort's second buffer is set[1], and set[2] holds the tags of ids too large to carry them)
     const bool big = T > RTK_CS_MAX_IDS;
-    if (T > RTK_CB_MAX_IDS || (big && (s.set_cap < RTK_CB_MAX_IDS || s.set_cap < 2u * 2u * 64u * RTK_CB_MAX_SLOTS))) return RTK_NONE32;
+    if (T > RTK_CB_MAX_IDS || (big && s.set_cap < RTK_CB_MAX_IDS)) return RTK_NONE32;
     RTK_CS_LAP(1)
     // ---- B. candidate anchors: cardinality >= min_cov_vertices, first occurrence of their unitig, ordered by (cardinality, unitig) [D1] ----
     const uint32_t min_cov_v = c.o.min_cov_vertices;
@@ -183,69 +310,42 @@ RTK_FN uint32_t rtk_choose_colors_small(const RCtx& c_, const SideList& side_s_,
     const uint32_t k_slot = src; const uint32_t k_card = rtk_shfl(m_card, static_cast<int>(src));
     uint32_t k_quota = k_card < cov ? k_card : cov;
     RTK_CS_LAP(2)
-    // ---- C. universe: every id of every side unitig, straight into LDS, sorted, duplicates dropped ----
+    // ---- C. every id of every side unitig, with its tag, straight into LDS ----
     uint32_t* const L = rtk_lds_set_buf();
-    uint32_t* const uni = L; uint32_t* const raw = L + RTK_CS_MAX_IDS;
-    // small: [0, 512) universe, [512, 1024) unsorted ids, [1024, 1792) 24 x 2 x 8 vector words (before that: second sort buffer + counters)
-    // big:   [0, 1664) universe, [1664, 1920) sort counters; second sort buffer = set[1], 64-word vectors = set[2] (scratch memory)
-    uint64_t* const cbm = big ? reinterpret_cast<uint64_t*>(s.set[2].get()) : reinterpret_cast<uint64_t*>(L + 2u * RTK_CS_MAX_IDS);
-    const uint32_t VW = big ? 64u : 8u; // words per bit vector
-    uint32_t P = 64; while (P < T) P <<= 1;
-    for (uint32_t t0 = 0; t0 < P; t0 += RTK_WAVE) {
-        const uint32_t t = t0 + lane;
-        uint32_t i = 0;
-        for (uint32_t j = 1; j < n_slots; ++j) { const uint32_t sj = rtk_shfl(st, static_cast<int>(j)); if (sj <= t) i = j; } // the last slot that starts at or before t (empty slots share their start with the next one)
-        const uint32_t s_i = rtk_shfl(st, static_cast<int>(i)), nl_i = rtk_shfl(m_nl, static_cast<int>(i));
-        const uint64_t lo_i = rtk_shfl(m_lo, static_cast<int>(i)), go_i = rtk_shfl(m_go, static_cast<int>(i));
-        uint32_t x = 0xFFFFFFFFu;
-        if (t < T) { const uint32_t off = t - s_i; x = col[off < nl_i ? lo_i + off : go_i + (off - nl_i)]; if (!big) raw[t] = x; }
-        if (t < T || !big) uni[t] = x;
-    }
-    RTK_WG_SYNC();
-    s.cnt[RTK_RC_COLOUR] += T;
-    RTK_CS_LAP(3)
-    { // sorted by id (radix, 8 bits per pass; the second buffer and the counters sit in the part of the LDS buffer the slot bit vectors take later)
-        uint32_t mx = 0; for (uint32_t i2 = lane; i2 < T; i2 += RTK_WAVE) mx = uni[i2] > mx ? uni[i2] : mx;
-        for (int o = 32; o > 0; o >>= 1) { const uint32_t v2 = static_cast<uint32_t>(__shfl_xor(static_cast<int>(mx), o, 64)); mx = v2 > mx ? v2 : mx; }
-        if (big) rtk_radix_sort_u32(uni, s.set[1], T, L + RTK_CB_MAX_IDS, rtk_u(mx));
-        else rtk_radix_sort_u32(uni, L + 2u * RTK_CS_MAX_IDS, T, L + 2u * RTK_CS_MAX_IDS + RTK_CS_MAX_IDS, rtk_u(mx));
-    }
-    uint32_t U = 0;
-    for (uint32_t i0 = 0; i0 < T; i0 += RTK_WAVE) {
-        const uint32_t i = i0 + lane;
-        uint32_t x = 0; bool keep = false;
-        if (i < T) { x = uni[i]; keep = (i == 0) || (uni[i - 1] != x); }
-        RTK_WG_SYNC();
-        const uint64_t bal = rtk_ballot(keep);
-        if (keep) uni[U + static_cast<uint32_t>(rtk_popc(bal & ((1ull << lane) - 1ull)))] = x;
-        U += static_cast<uint32_t>(rtk_popc(bal));
-        RTK_WG_SYNC();
-    }
-    RTK_CS_LAP(4)
-    // ---- D. bit vectors of every slot (local part, global part), 8 words each, in LDS: one flat pass over the gathered ids, every id
-    // ranked in the universe by a binary search in LDS and its bit set in the vector of the list it came from ----
-    for (uint32_t i = lane; i < n_slots * 2u * VW; i += RTK_WAVE) cbm[i] = 0ull;
-    RTK_WG_SYNC();
-    for (uint32_t t0 = 0; t0 < T; t0 += RTK_WAVE) {
-        const uint32_t t = t0 + lane;
-        uint32_t i = 0;
-        for (uint32_t j = 1; j < n_slots; ++j) { const uint32_t sj = rtk_shfl(st, static_cast<int>(j)); if (sj <= t) i = j; }
-        const uint32_t s_i = rtk_shfl(st, static_cast<int>(i)), nl_i = rtk_shfl(m_nl, static_cast<int>(i));
-        const uint64_t lo_i2 = rtk_shfl(m_lo, static_cast<int>(i)), go_i2 = rtk_shfl(m_go, static_cast<int>(i));
-        if (t < T) {
-            const uint32_t off2 = t - s_i;
-            const uint32_t id = big ? col[off2 < nl_i ? lo_i2 + off2 : go_i2 + (off2 - nl_i)] : raw[t];
-            uint32_t lo = 0, hi = U; while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (uni[mid] < id) lo = mid + 1; else hi = mid; }
-            const uint32_t seg = 2u * i + ((t - s_i) >= nl_i ? 1u : 0u);
-            atomicOr(reinterpret_cast<unsigned long long*>(cbm) + seg * VW + (lo >> 6), 1ull << (lo & 63u));
+    uint32_t* const uni = L;
+    uint8_t* const gtags = reinterpret_cast<uint8_t*>(s.set[2].get());
+    uint32_t mx = 0;
+    for (bool packed = true;; packed = false) { // (a second time, tags apart, when an id turns out too large to carry its tag)
+        uint8_t* const tags = rtk_cu_tags(L, T, gtags);
+        for (uint32_t t0 = 0; t0 < T; t0 += RTK_WAVE) {
+            const uint32_t t = t0 + lane;
+            uint32_t i = 0;
+            for (uint32_t j = 1; j < n_slots; ++j) { const uint32_t sj = rtk_shfl(st, static_cast<int>(j)); if (sj <= t) i = j; } // the last slot that starts at or before t (empty slots share their start with the next one)
+            const uint32_t s_i = rtk_shfl(st, static_cast<int>(i)), nl_i = rtk_shfl(m_nl, static_cast<int>(i));
+            const uint64_t lo_i = rtk_shfl(m_lo, static_cast<int>(i)), go_i = rtk_shfl(m_go, static_cast<int>(i));
+            if (t < T) {
+                const uint32_t off = t - s_i; const uint32_t tag = 2u * i + (off >= nl_i ? 1u : 0u);
+                const uint32_t x = col[off < nl_i ? lo_i + off : go_i + (off - nl_i)];
+                mx = x > mx ? x : mx;
+                if (packed) L[t] = (x << RTK_CS_TAG_BITS) | tag; else { L[t] = x; tags[t] = static_cast<uint8_t>(tag); }
+            }
         }
+        for (int o = 32; o > 0; o >>= 1) { const uint32_t v2 = static_cast<uint32_t>(__shfl_xor(static_cast<int>(mx), o, 64)); mx = v2 > mx ? v2 : mx; }
+        mx = rtk_u(mx);
+        if (!packed || mx < RTK_CS_PACKED_LIMIT) break;
     }
     RTK_WG_SYNC();
-    RTK_CS_LAP(5)
-    // (big: the vectors were written by L2 atomics, so they are read past the L1, whose copy of these lines may be older)
-    auto ld = [&](uint32_t idx) -> RtkBM { if (lane >= VW) return 0ull; return big ? static_cast<RtkBM>(__hip_atomic_load(reinterpret_cast<const unsigned long long*>(cbm) + idx * VW + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) : cbm[idx * VW + lane]; };
-    auto cnt_ = [&](RtkBM a) -> uint32_t { return big ? rtk_bm_count(a) : rtk_bm8_count(a); };
-    auto low_ = [&](RtkBM a, uint32_t q) -> RtkBM { return big ? rtk_bm_lowest(a, q) : rtk_bm8_lowest(a, q); };
+    RTK_CS_LAP(3)
+    // ---- D. universe (sorted, duplicates dropped) and the bit vectors of every slot (local part, global part), both in LDS ----
+    uint32_t U = 0, VW = 1; uint64_t* cbm = nullptr;
+    if (!rtk_colour_universe(L, T, 2u * n_slots, mx, s.set[1], gtags, &U, &VW, &cbm)) { s.cnt[RTK_RC_COLOURS_DECLINED_FIT] += 1; return RTK_NONE32; }
+    s.cnt[RTK_RC_COLOUR] += T;
+    RTK_CS_LAP(4)
+    // (up to 8 words a vector lives in lanes 0..7 and the 8-lane forms count it)
+    const bool w8 = VW <= 8u;
+    auto ld = [&](uint32_t idx) -> RtkBM { return lane < VW ? cbm[idx * VW + lane] : 0ull; };
+    auto cnt_ = [&](RtkBM a) -> uint32_t { return w8 ? rtk_bm8_count(a) : rtk_bm_count(a); };
+    auto low_ = [&](RtkBM a, uint32_t q) -> RtkBM { return w8 ? rtk_bm8_lowest(a, q) : rtk_bm_lowest(a, q); };
     // ---- E. the six anchor classes: side (middle, right, left) x branching / non-branching; G2: the global set alone when there is one ----
     RtkBM a[6];
     for (int sh = 0; sh < 6; ++sh) {
@@ -301,7 +401,7 @@ RTK_FN uint32_t rtk_choose_colors_small(const RCtx& c_, const SideList& side_s_,
             nb_unselected += quota > 0 ? 1u : 0u;
         }
     }
-    RTK_CS_LAP(6)
+    RTK_CS_LAP(5)
     // ---- all_pids back to a sorted id list in set[0] ----
     const uint32_t n_all = rtk_bm_count(all);
     if (n_all > s.set_cap) { rtk_fail_ovf(s, 9); return 0; }

@@ -814,6 +814,34 @@ RTK_GLOBAL void k_sets_batch(const SetsProb* probs, uint32_t n, const uint32_t* 
             for (uint32_t i = lane; i < na; i += RTK_WAVE) { out[i] = ka[i]; out[na + i] = pa[i]; }
             nout = 2u * na;
         }
+        else if (op == RTK_SETS_RADIX_TAGGED || op == RTK_SETS_COLOUR_UNIVERSE) { // the entries as rtk_choose_colors_small lays them out: a = ids; b = their tags / the lengths of the lists they came from
+            uint32_t* const L = rtk_lds_set_buf(); uint8_t* const gtags = reinterpret_cast<uint8_t*>(work32 + RTK_CB_MAX_IDS);
+            const bool packed = sc < RTK_CS_PACKED_LIMIT; uint8_t* const tags = rtk_cu_tags(L, na, gtags);
+            for (uint32_t i = lane; i < na; i += RTK_WAVE) {
+                uint32_t tag = 0;
+                if (op == RTK_SETS_RADIX_TAGGED) tag = b[i];
+                else { uint32_t end = 0; for (uint32_t j = 0; j < nb; ++j) { end += b[j]; if (i >= end) tag = j + 1u; } } // the list that holds entry i (an empty list holds none)
+                if (packed) L[i] = (a[i] << RTK_CS_TAG_BITS) | tag; else { L[i] = a[i]; tags[i] = static_cast<uint8_t>(tag); }
+            }
+            rtk_sync();
+            if (op == RTK_SETS_RADIX_TAGGED) {
+                const uint8_t* tsrt; const uint32_t* const srt = rtk_cu_sort(L, na, sc, work32, gtags, &tsrt);
+                rtk_sync();
+                for (uint32_t i = lane; i < na; i += RTK_WAVE) { out[i] = packed ? (srt[i] >> RTK_CS_TAG_BITS) : srt[i]; out[na + i] = packed ? (srt[i] & ((1u << RTK_CS_TAG_BITS) - 1u)) : tsrt[i]; }
+                nout = 2u * na;
+            } else {
+                uint32_t U = 0, VW = 1; uint64_t* vec = nullptr;
+                const bool fits = rtk_colour_universe(L, na, nb, sc, work32, gtags, &U, &VW, &vec);
+                res = U;
+                if (!fits) st = RTK_SETS_DECLINED;
+                else { // U, the words of a vector, the universe, the nb vectors (low word, high word)
+                    if (lane == 0u) { out[0] = U; out[1] = VW; }
+                    for (uint32_t i = lane; i < U; i += RTK_WAVE) out[2u + i] = L[i];
+                    for (uint32_t i = lane; i < nb * VW; i += RTK_WAVE) { out[2u + U + 2u * i] = static_cast<uint32_t>(vec[i]); out[2u + U + 2u * i + 1u] = static_cast<uint32_t>(vec[i] >> 32); }
+                    nout = 2u + U + 2u * nb * VW;
+                }
+            }
+        }
 #endif
         else if (op == RTK_SETS_BM_LOWEST
 #ifndef RTK_SIM
@@ -867,6 +895,19 @@ extern "C" int rtk_sets_batch(uint32_t n, const uint32_t* op, const uint32_t* co
                 case RTK_SETS_SORT_PAIRS: { if (B != A || A > (1u << 24)) return rtk_fail(RTK_ERR_ARG, "rtk_sets_batch: SORT_PAIRS wants nb == na <= 2^24"); uint64_t pw = 1; while (pw < A) pw <<= 1; need = 4 * A; work = 2 * pw; wa = 2 * A; wb = 2 * B; break; }
                 case RTK_SETS_RADIX_U32: if (A > RTK_CB_MAX_IDS) return rtk_fail(RTK_ERR_ARG, "rtk_sets_batch: RADIX_U32 sorts at most 1664 keys"); need = A; work = (A + 1) / 2; wb = 0; break;
                 case RTK_SETS_RADIX_PAIRS_U32: if (B != A) return rtk_fail(RTK_ERR_ARG, "rtk_sets_batch: RADIX_PAIRS_U32 wants nb == na"); need = 2 * A; work = 2 * A; break;
+                case RTK_SETS_RADIX_TAGGED: case RTK_SETS_COLOUR_UNIVERSE: {
+                    if (A > RTK_CB_MAX_IDS || scalar[i] == 0xFFFFFFFFu) return rtk_fail(RTK_ERR_ARG, "rtk_sets_batch: at most 1664 ids, none above the scalar <= 0xFFFFFFFE");
+                    for (uint64_t x = 0; x < A; ++x) if (a[i][x] > scalar[i]) return rtk_fail(RTK_ERR_ARG, "rtk_sets_batch: an id above the scalar");
+                    if (op[i] == RTK_SETS_RADIX_TAGGED) {
+                        if (B != A) return rtk_fail(RTK_ERR_ARG, "rtk_sets_batch: RADIX_TAGGED wants nb == na");
+                        for (uint64_t x = 0; x < B; ++x) if (b[i][x] >= 2u * RTK_CB_MAX_SLOTS) return rtk_fail(RTK_ERR_ARG, "rtk_sets_batch: a tag above 47");
+                        need = 2 * A;
+                    } else {
+                        uint64_t sum = 0; for (uint64_t x = 0; x < B; ++x) sum += b[i][x];
+                        if (B == 0 || B > 2u * RTK_CB_MAX_SLOTS || sum != A) return rtk_fail(RTK_ERR_ARG, "rtk_sets_batch: COLOUR_UNIVERSE wants 1 .. 48 list lengths that add up to na");
+                        need = 2 + A + 2 * B * std::max<uint64_t>(1, (A + 63) / 64);
+                    }
+                    work = (RTK_CB_MAX_IDS + RTK_CB_MAX_IDS / 2u) / 2u; break; } // second key buffer + two tag arrays
                 case RTK_SETS_BM_LOWEST: case RTK_SETS_BM8_LOWEST: {
                     if (A > (op[i] == RTK_SETS_BM8_LOWEST ? 512u : 4096u)) return rtk_fail(RTK_ERR_ARG, "rtk_sets_batch: universe too large for the bit vector");
                     for (uint64_t x = 1; x < A; ++x) if (a[i][x - 1] >= a[i][x]) return rtk_fail(RTK_ERR_ARG, "rtk_sets_batch: the universe is not sorted and free of repeats");

@@ -789,8 +789,8 @@ static void region_trace_report(const unsigned long long* cnt) {
             cnt[RTK_CNT_FA_LINKED + 2], double(cnt[RTK_CNT_FINE + RTK_FINE_FA_LINKED]));
     fprintf(stderr, "[rtk trace] second strand of gap regions: run %llu, skipped %llu (the forward result decides), audit mismatches %llu\n", cnt[RTK_CNT_STRAND2 + 0], cnt[RTK_CNT_STRAND2 + 1], cnt[RTK_CNT_STRAND2 + 2]);
     fprintf(stderr, "[rtk trace] stored sweeps of the forward trims: walked for a consensus %llu, never walked %llu\n", cnt[RTK_CNT_PARK + 0], cnt[RTK_CNT_PARK + 1]);
-    fprintf(stderr, "[rtk trace] colour selections answered by: small %llu, wide %llu, bits %llu, general %llu; audit mismatches %llu\n", cnt[RTK_CNT_COLOURS + 0], cnt[RTK_CNT_COLOURS + 1], cnt[RTK_CNT_COLOURS + 2],
-            cnt[RTK_CNT_COLOURS + 3], cnt[RTK_CNT_COLOURS + 4]);
+    fprintf(stderr, "[rtk trace] colour selections answered by: small %llu, wide %llu, bits %llu, general %llu; audit mismatches %llu; handed on by the register program for room %llu\n", cnt[RTK_CNT_COLOURS + 0], cnt[RTK_CNT_COLOURS + 1], cnt[RTK_CNT_COLOURS + 2],
+            cnt[RTK_CNT_COLOURS + 3], cnt[RTK_CNT_COLOURS + 4], cnt[RTK_CNT_COLOURS + 5]);
     fprintf(stderr, "[rtk trace] walks %llu moves %llu reloads %llu scalar steps %llu cycles %.3g tail cycles %.3g\n", cnt[RTK_CNT_WALK_CALLS], cnt[RTK_CNT_WALK_MOVES],
             cnt[RTK_CNT_WALK_RELOADS], cnt[RTK_CNT_WALK_SCALAR], double(cnt[RTK_CNT_WALK_CYCLES]), double(cnt[RTK_CNT_WALK_TAIL]));
 }
@@ -812,7 +812,7 @@ static void region_stats(RegionRun& R, const unsigned long long* cnt) {
     st.n_strand2_run = cnt[RTK_CNT_STRAND2 + 0]; st.n_strand2_skipped = cnt[RTK_CNT_STRAND2 + 1]; st.n_strand2_audit_mismatch = cnt[RTK_CNT_STRAND2 + 2];
     st.n_park_walked = cnt[RTK_CNT_PARK + 0]; st.n_park_deferred = cnt[RTK_CNT_PARK + 1];
     st.n_colours_small = cnt[RTK_CNT_COLOURS + 0]; st.n_colours_wide = cnt[RTK_CNT_COLOURS + 1]; st.n_colours_bits = cnt[RTK_CNT_COLOURS + 2]; st.n_colours_general = cnt[RTK_CNT_COLOURS + 3];
-    st.n_colours_audit_mismatch = cnt[RTK_CNT_COLOURS + 4];
+    st.n_colours_audit_mismatch = cnt[RTK_CNT_COLOURS + 4]; st.n_colours_declined_fit = cnt[RTK_CNT_COLOURS + 5];
     st.ms_stitch = R.t_st.elapsed(); st.ms_total = b->t_all.elapsed();
     st.n_windows = b->n_bases;
     st.n_probes_exact = cnt[RTK_CNT_PROBES_EXACT]; st.n_probes_inexact = cnt[RTK_CNT_PROBES_INEXACT]; st.n_hits_inexact = cnt[RTK_CNT_HITS_INEXACT];

@@ -1190,7 +1190,8 @@ RTK_DEV uint32_t rtk_rs_union(RegionScratch& s, int a, uint32_t na, const uint32
 RTK_FN uint32_t rtk_choose_colors_general(const RCtx& c_, const SideList& side_s_, const SideList& side_e_, const SideList& side_w_);
 // chooseColors: the two register / bit-vector programs of rtk_colours.h first (nearly every region), the general program below otherwise.
 // Compiled into its caller: the dispatcher itself as a function would save 17 register rows on every region for a path it almost never takes.
-// Every call that ends without an overflow is counted by the program that answered it (RTK_RC_COLOURS_*; the small program counts its own two sizes).
+// Every call that ends without an overflow is counted by the program that answered it (RTK_RC_COLOURS_*; the small program counts its own two sizes, and the
+// calls it hands on because universe and bit vectors do not fit its LDS buffer: RTK_RC_COLOURS_DECLINED_FIT).
 // OptsView::colours_mode (tests): RTK_CM_ROUTE_BITS skips the small program, RTK_CM_ROUTE_GENERAL both bit-vector programs. RTK_CM_AUDIT: where a bit-vector
 // program answered, its list is kept in the region-level arena (free here: the path search resets it after this call; the general program writes set[1..9],
 // arena level 2, list[3], list[4] and the LDS buffer), the general program selects again into set[0], and a difference in the number of ids or in any id is

@@ -194,12 +194,12 @@ enum RtkCounterSlot {
     RTK_CNT_STRAND2_END = 217,
     RTK_CNT_PARK = 217,             // [2] k_regions, stored sweeps of the forward trims: walked for a consensus / never walked (RTK_RC_PARK_WALKED ..) -> rtk_stats
     RTK_CNT_PARK_END = 219,
-    RTK_CNT_COLOURS = 219,          // [5] k_regions, calls of rtk_choose_colors by the program that answered: small, wide, bits, general; audit mismatches (RTK_RC_COLOURS_SMALL ..) -> rtk_stats
-    RTK_CNT_COLOURS_END = 224,
+    RTK_CNT_COLOURS = 219,          // [6] k_regions, calls of rtk_choose_colors by the program that answered: small, wide, bits, general; audit mismatches; calls the register program declined for room (RTK_RC_COLOURS_SMALL ..) -> rtk_stats
+    RTK_CNT_COLOURS_END = 225,
     RTK_CNT_USED_END = RTK_CNT_COLOURS_END,
     RTK_CNT_TOTAL = (RTK_CNT_USED_END + 31) / 32 * 32 // words in the block: what is used, rounded up to 256 bytes (the tail is free)
 };
-static_assert(RTK_CNT_TOTAL == 224, "counter map: the size of the block changed (it is part of what the kernels and the host agree on)");
+static_assert(RTK_CNT_TOTAL == 256, "counter map: the size of the block changed (it is part of what the kernels and the host agree on)");
 // Two trace-only users sit INSIDE the size-class table today: RTK_CNT_PHASE_TRACE (written by the phasing step, which runs before the seed stage clears the block
 // -- so it is read back right there) and RTK_CNT_FINALIZE_SLOWEST_PHASES (written by k_finalize, read back by the seed stage; k_regions then adds its table on top).
 // Both only garble developer trace lines of the size-class table; renumbering them is a follow-up, because it changes device code. What reaches rtk_stats must
@@ -232,9 +232,10 @@ enum RtkRegionCnt { RTK_RC_EXPAND = 0, RTK_RC_COLOUR = 1, RTK_RC_PATHBASE = 2, R
     // stored sweeps of the forward trims (rtk_trim_by_column, rtk_park_walk) -> RTK_CNT_PARK + 0 .. 1: those whose path was walked and parked for a consensus, and
     // those nobody walked (the region skipped its second strand, or the sweep could not be parked); the sum is RTK_RC_TRIM_STORED
     RTK_RC_PARK_WALKED = 27, RTK_RC_PARK_DEFERRED = 28,
-    // calls of rtk_choose_colors (rtk_region.h) by the program that answered -> RTK_CNT_COLOURS + 0 .. 4: rtk_choose_colors_small with 8-word vectors / with 64-word
-    // vectors ("wide"), rtk_choose_colors_bits, rtk_choose_colors_general; and -- RTK_COLOURS_AUDIT=1 -- calls whose first answer differed from the general program's
-    RTK_RC_COLOURS_SMALL = 29, RTK_RC_COLOURS_WIDE = 30, RTK_RC_COLOURS_BITS = 31, RTK_RC_COLOURS_GENERAL = 32, RTK_RC_COLOURS_AUDIT_MISMATCH = 33, RTK_RC_N = 34 };
+    // calls of rtk_choose_colors (rtk_region.h) by the program that answered -> RTK_CNT_COLOURS + 0 .. 5: rtk_choose_colors_small with at most RTK_CS_MAX_IDS ids
+    // (repeats counted) / with more ("wide"), rtk_choose_colors_bits, rtk_choose_colors_general; -- RTK_COLOURS_AUDIT=1 -- calls whose first answer differed from the
+    // general program's; and calls rtk_choose_colors_small handed on because universe and bit vectors did not fit its LDS buffer (they are answered, and counted, further on)
+    RTK_RC_COLOURS_SMALL = 29, RTK_RC_COLOURS_WIDE = 30, RTK_RC_COLOURS_BITS = 31, RTK_RC_COLOURS_GENERAL = 32, RTK_RC_COLOURS_AUDIT_MISMATCH = 33, RTK_RC_COLOURS_DECLINED_FIT = 34, RTK_RC_N = 35 };
 static_assert(RTK_CNT_ROUTES_END - RTK_CNT_ROUTES == static_cast<int>(RTK_RC_FA_LINKED_RUN) - static_cast<int>(RTK_RC_TRIM_STORED), "counter map: one slot per route counter");
 static_assert(RTK_CNT_FA_LINKED_END - RTK_CNT_FA_LINKED == static_cast<int>(RTK_RC_STRAND2_RUN) - static_cast<int>(RTK_RC_FA_LINKED_RUN), "counter map: one slot per fixAmbiguity counter");
 static_assert(RTK_CNT_STRAND2_END - RTK_CNT_STRAND2 == static_cast<int>(RTK_RC_PARK_WALKED) - static_cast<int>(RTK_RC_STRAND2_RUN), "counter map: one slot per second-strand counter");
