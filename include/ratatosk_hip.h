@@ -320,6 +320,24 @@ int rtk_index_unitigs(int device, int k, const uint64_t* solid, uint64_t n_solid
 int rtk_index_colour_begin(int device, int k, const char* seq_pool, const uint64_t* seq_off, uint64_t n_unitigs, void** job);
 int rtk_index_colour_chunk(void* job, const char* chars, uint64_t n_chars, const uint64_t* starts, const uint32_t* ids, uint32_t n_reads);
 int rtk_index_colour_end(void* job, uint64_t** events, uint64_t* n_events, uint64_t** cov);
+/* Colours subsampled by coverage on the device (rtk_build_index --gpu --subsample-colours; the reference: addCoverage, src/Graph.cpp:2312-2870; the rule and its three
+ * deviations: DESIGN.md section 4 [A12], csrc/tools/index/subsample.hpp). The caller works out what needs coverage and structure, the device does everything that
+ * touches an event or an id, so that only the kept events are copied to the host.
+ * rtk_index_colour_cov: finishes the pending chunks and the last sort-and-unique and hands out the k-mer coverage of every unitig (rtk_free); the job stays alive.
+ * rtk_index_colour_end_subsampled: bin_of_unitig[u] = the coverage bin of unitig u, 0 .. n_bins - 1 (n_bins <= 64), or 255 for none; forced_candidate[u] = 1 when the
+ * unitig is non-branching; bin_is_sampled[j] = 1 when the ids of bin j are drawn. An id belongs to the smallest bin among the unitigs it colours; it is kept when that
+ * bin is not sampled, or when u(id) <= rate with u(id) = (h(id) >> 11) * 2^-53, h(id) = the splitmix64 finalizer of id + seed * 0x9E3779B97F4A7C15. Beside that the mcv
+ * (<= 64) ids of smallest (h(id), id) of every forced candidate are kept, all of them when it has no more. The kept ids, ascending, are renumbered from 0.
+ * *events: the kept events unitig << 32 | new id, ascending and distinct (renumbering is monotone), *n_events of them (rtk_free); *n_events_before = the events before
+ * the thinning, *n_ids_before / *n_ids_after = the distinct ids before and after. The job is gone afterwards, also on error. rtk_index_colour_end stays as it is.
+ * rtk_index_subsample_events: stage entry for tests -- the same device function on the caller's events (host arrays; ascending, distinct, unitigs < n_unitigs);
+ * events_out has room for n_events words. RTK_ERR_NO_DEVICE without a GPU, like every compute entry. */
+int rtk_index_colour_cov(void* job, uint64_t** cov);
+int rtk_index_colour_end_subsampled(void* job, const uint8_t* bin_of_unitig, const uint8_t* forced_candidate, const uint8_t* bin_is_sampled, uint32_t n_bins, uint32_t mcv,
+                                    double rate, uint64_t seed, uint64_t** events, uint64_t* n_events, uint64_t* n_events_before, uint64_t* n_ids_before, uint64_t* n_ids_after);
+int rtk_index_subsample_events(int device, const uint64_t* events, uint64_t n_events, uint32_t n_unitigs, const uint8_t* bin_of_unitig, const uint8_t* forced_candidate,
+                               const uint8_t* bin_is_sampled, uint32_t n_bins, uint32_t mcv, double rate, uint64_t seed, uint64_t* events_out, uint64_t* n_out,
+                               uint64_t* n_ids_before, uint64_t* n_ids_after);
 
 /* rtk_rescue_*: the rescue of unmapped short reads before the index build (`correct -u`; retrieveMissingReads, src/Graph.cpp:3857-4131, called at
  * src/Ratatosk.cpp:1040-1056), with exact sets where the reference has Bloom filters ([A11]). One-word k-mers (odd k <= 31).
@@ -383,7 +401,8 @@ const char* rtk_version(void);
  * 7: rtk_stats route fields n_trim_* / n_consensus_*, the test-only rtk_myers_batch modes 3 and 4, rtk_myers_column_last_routes;
  * 8: rtk_stats fields n_fa_linked_*; 9: rtk_rescue_begin / _chunk / _end; still 9: rtk_stats fields n_strand2_* and n_park_*, the test-only rtk_myers_batch mode 5, appended at the end -- a library of revision 9
  * without them leaves them as the caller set them;
- * 10: rtk_sets_batch, rtk_stats fields n_colours_*). */
+ * 10: rtk_sets_batch, rtk_stats fields n_colours_*; still 10: rtk_index_colour_cov, rtk_index_colour_end_subsampled, rtk_index_subsample_events, appended -- a library
+ * of revision 10 without them lacks the symbols, and callers look them up by name). */
 #define RTK_API_REVISION 10
 int rtk_api_revision(void);
 

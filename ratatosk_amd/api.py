@@ -116,6 +116,12 @@ def load_library(path=None):
     if L.rtk_api_revision() >= 10:  # (an older build has no rtk_sets_batch: sets_batch says so)
         L.rtk_sets_batch.argtypes = [C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_uint32), C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_uint32),
                                      C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    if hasattr(L, "rtk_index_subsample_events"):  # (still revision 10: appended; a library without them: index_subsample_events says so)
+        L.rtk_index_colour_cov.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_uint64))]
+        L.rtk_index_colour_end_subsampled.argtypes = [C.c_void_p, C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte), C.c_uint32, C.c_uint32, C.c_double, C.c_uint64,
+                                                      C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.rtk_index_subsample_events.argtypes = [C.c_int, C.POINTER(C.c_uint64), C.c_uint64, C.c_uint32, C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte), C.c_uint32, C.c_uint32,
+                                                 C.c_double, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.rtk_free.argtypes = [C.c_void_p]
     _libs[path] = L
     return L
@@ -428,6 +434,29 @@ def sets_batch(problems, lib_path=None):
             words = w.tolist()
         ret.append((words, int(res[i]), int(st[i])))
     return ret
+
+
+def index_subsample_events(events, n_unitigs, bin_of_unitig, forced_candidate, bin_is_sampled, mcv, rate, seed=1, device=0, lib_path=None):
+    """The colour subsampling of the index build on the device (stage entry rtk_index_subsample_events, include/ratatosk_hip.h: the device function behind
+    rtk_index_colour_end_subsampled; the rule: DESIGN.md section 4 [A12]). events: words unitig << 32 | id, ascending and distinct; bin_of_unitig[u] in 0 .. len(bin_is_sampled) - 1
+    or 255; forced_candidate[u] and bin_is_sampled[j] 0 or 1. Returns (kept events with their ids renumbered, as a numpy array of uint64; distinct ids before; after)."""
+    import numpy as np
+    L = load_library(lib_path)
+    missing = [s for s in ("rtk_index_colour_cov", "rtk_index_colour_end_subsampled", "rtk_index_subsample_events") if not hasattr(L, s)]
+    if missing:
+        raise RtkError("%s lacks %s (colour subsampling: appended at interface revision 10)" % (L._name, ", ".join(missing)))
+    ev = np.ascontiguousarray(events, dtype=np.uint64)
+    bins = np.ascontiguousarray(bin_of_unitig, dtype=np.uint8); forced = np.ascontiguousarray(forced_candidate, dtype=np.uint8); sampled = np.ascontiguousarray(bin_is_sampled, dtype=np.uint8)
+    if bins.size != n_unitigs or forced.size != n_unitigs:
+        raise RtkError("index_subsample_events: bin_of_unitig and forced_candidate hold one entry per unitig")
+    out = np.zeros(max(1, ev.size), dtype=np.uint64)
+    n_out, before, after = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    u8, u64 = C.POINTER(C.c_ubyte), C.POINTER(C.c_uint64)
+    rc = L.rtk_index_subsample_events(device, ev.ctypes.data_as(u64), ev.size, n_unitigs, bins.ctypes.data_as(u8), forced.ctypes.data_as(u8), sampled.ctypes.data_as(u8), sampled.size, mcv,
+                                      float(rate), seed, out.ctypes.data_as(u64), C.byref(n_out), C.byref(before), C.byref(after))
+    if rc != 0:
+        raise RtkError("rtk error %d: %s" % (rc, L.rtk_last_error().decode()))
+    return out[:n_out.value].copy(), before.value, after.value
 
 
 def run_pipelined(batches, opts=None):

@@ -5,7 +5,8 @@
 //                           the window packed 2 bits per base without branches), the k-mers of the pass are radix-sorted (rocPRIM) and the first
 //                           element of every run of >= min_count equal keys is kept. HBM-bound: 1 byte read + 8 (16) bytes written per base, then the sort.
 //   rtk_index_unitigs       the chains of the compacted graph walked, numbered and spelt (k_ut_*)
-//   rtk_index_colour_*      every read k-mer mapped onto its unitig: colour events and coverage (k_col_map)
+//   rtk_index_colour_*      every read k-mer mapped onto its unitig: colour events and coverage (k_col_map); with rtk_index_colour_end_subsampled the events
+//                           thinned out by coverage and their ids renumbered before they leave the device (k_sub_*)
 // Every step serves one-word k-mers (k <= 31, key type uint64_t) and two-word k-mers (33 <= k <= 63, key type unsigned __int128: the 2k-bit code,
 // first base in the most significant bits; in memory the low word first). Own translation unit: rocPRIM's templates.
 #include <string.h>
@@ -344,6 +345,7 @@ struct ColourJob {
     int device = 0, k = 31; uint32_t n_unitigs = 0; GraphView g; // g: the k-mer table and the packed unitigs (the only fields k_col_map reads)
     DevBuf useq, uoff, ht, cov, events, alt, top, tmp;
     uint64_t slots = 0, cap = 0, n_events = 0; // n_events: sorted, distinct events at the front of `events`
+    uint64_t n_ids = 0;                        // largest id fed + 1: the size of the id tables of the subsampling
     DevBuf d_chars[2], d_starts[2], d_ids[2]; PinBuf h_chars[2], h_starts[2], h_ids[2]; uint64_t chunk_cap = 0, reads_cap = 0;
     hipStream_t st[2] = {nullptr, nullptr}; int slot = 0;
     std::mutex m; uint64_t bases = 0, chunks = 0, compactions = 0; double t_table = 0.0;
@@ -665,6 +667,7 @@ extern "C" int rtk_index_colour_chunk(void* job, const char* chars, uint64_t n_c
             unsigned long long n = 0; rtk_check(hipMemcpy(&n, J->top.p, 8, hipMemcpyDeviceToHost), "hipMemcpy");
             if (n > J->cap / 2) J->compact();
         }
+        { uint32_t mx = 0; for (uint32_t r = 0; r < n_reads; ++r) mx = ids[r] > mx ? ids[r] : mx; J->n_ids = std::max<uint64_t>(J->n_ids, static_cast<uint64_t>(mx) + 1); }
         const int sl = J->slot; J->slot ^= 1;
         rtk_check(hipStreamSynchronize(J->st[sl]), "hipStreamSynchronize");
         memcpy(J->h_chars[sl].p, chars, n_chars); memcpy(J->h_starts[sl].p, starts, 8ull * n_reads); memcpy(J->h_ids[sl].p, ids, 4ull * n_reads);
@@ -699,5 +702,217 @@ extern "C" int rtk_index_colour_end(void* job, uint64_t** events, uint64_t* n_ev
         if (rtk_knob_index_trace()) fprintf(stderr, "rtk_index_colour: %llu characters in %llu chunks -> %llu distinct (unitig, read) events (sorted and thinned out %llu times); table %.2f s, all %.2f s\n", static_cast<unsigned long long>(J->bases),
                                                static_cast<unsigned long long>(J->chunks), static_cast<unsigned long long>(J->n_events), static_cast<unsigned long long>(J->compactions), J->t_table, std::chrono::duration<double>(std::chrono::steady_clock::now() - J->t0).count());
     } catch (const std::exception& e) { return rtk_fail(RTK_ERR_DEVICE, std::string("rtk_index_colour_end: ") + e.what()); }
+    return RTK_OK;
+}
+
+
+// ------------------------------------------------------------------------------------------------ colours subsampled by coverage (k_sub_*)
+// The rule is that of the index tool's host step (csrc/tools/index/subsample.hpp; the reference: addCoverage, src/Graph.cpp:2312-2870; DESIGN.md section 4 [A12]),
+// and the two give the same words. The host works out what needs coverage and structure: the bin of every unitig (0 .. n_bins - 1, 255: none), which unitigs force
+// ids (the non-branching ones), which bins are sampled and the rate. Everything that touches an event or an id happens here, on the sorted distinct events
+// unitig << 32 | id in HBM:
+//   k_sub_first_bin  one lane per event: the smallest bin among the unitigs an id colours, one byte per id (255: the id colours nothing, 254: only unitigs of no bin)
+//   k_sub_forced     the events of a unitig are one segment; its first lane finds the end by bisection. Up to mcv events: all forced. Up to 64: the lane selects the
+//                    mcv smallest (h(id), id) itself. Longer: the wave selects them together, mcv laps of a strided sweep and a minimum across the lanes.
+//   k_sub_keep       one wave per word of the keep bitmap: an id is kept when its bin is not sampled, or u(id) <= rate; OR-ed onto the forced bits
+//   ranks            exclusive scan of the population counts of the bitmap words (rocPRIM); the new id of a kept id = prefix of its word + the kept bits below it
+//   compaction       rocprim::select over the events with the id replaced by its rank; renumbering is monotone, so the output is ascending and distinct
+// h(id) = splitmix64 finalizer of id + seed * 0x9E3779B97F4A7C15; u(id) = (h >> 11) * 2^-53: an integer below 2^53 converted and scaled by a power of two, both exact,
+// so host and device agree bit for bit. Bounds: events < the caller's count, ids < n_ids (tables of n_ids bytes / bits), unitigs < n_unitigs; an event that breaks
+// one is skipped and reported.
+namespace {
+#define RTK_SUB_MAX_MCV 64u
+__device__ __forceinline__ uint64_t sub_hash(uint64_t id, uint64_t seed) {
+    uint64_t z = id + seed * 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull; z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+__device__ __forceinline__ bool sub_key_less(uint64_t h1, uint64_t id1, uint64_t h2, uint64_t id2) { return h1 < h2 || (h1 == h2 && id1 < id2); }
+
+__global__ void k_sub_first_bin(const uint64_t* __restrict__ ev, uint64_t n, const uint8_t* __restrict__ bin_of_unitig, uint32_t n_unitigs, uint32_t n_bins, uint64_t n_ids,
+                                uint32_t* __restrict__ first_bin, uint32_t* __restrict__ bad) {
+    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
+    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const uint64_t e = ev[i], u = e >> 32, id = e & 0xFFFFFFFFull;
+        if (u >= n_unitigs || id >= n_ids) { atomicOr(bad, 1u); continue; }
+        uint32_t v = bin_of_unitig[u];
+        if (v == 255u) v = 254u; else if (v >= n_bins) { atomicOr(bad, 2u); continue; }
+        uint32_t* w = first_bin + (id >> 2); const uint32_t sh = static_cast<uint32_t>(id & 3u) * 8u; // (the table is a whole number of words)
+        uint32_t old = *w;
+        while (((old >> sh) & 255u) > v) { const uint32_t seen = atomicCAS(w, old, (old & ~(255u << sh)) | (v << sh)); if (seen == old) break; old = seen; }
+    }
+}
+
+__global__ void k_sub_forced(const uint64_t* __restrict__ ev, uint64_t n, const uint8_t* __restrict__ forced_candidate, uint32_t n_unitigs, uint32_t mcv, uint64_t seed, uint64_t n_ids,
+                             unsigned long long* __restrict__ keep) {
+    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
+    const int lane = threadIdx.x & 63;
+    auto force = [&](uint64_t id) { if (id < n_ids) atomicOr(keep + (id >> 6), 1ull << (id & 63ull)); };
+    for (uint64_t i0 = static_cast<uint64_t>(blockIdx.x) * blockDim.x; i0 < n; i0 += stride) { // (whole waves take part in every round)
+        const uint64_t i = i0 + threadIdx.x;
+        bool head = false; uint64_t len = 0;
+        if (i < n) { const uint64_t u = ev[i] >> 32; head = (i == 0 || (ev[i - 1] >> 32) != u) && u < n_unitigs && forced_candidate[u] != 0;
+            if (head) { // the end of the segment: the first event of a later unitig
+                const uint64_t key = (u + 1) << 32; uint64_t lo = i + 1, hi = n;
+                while (lo < hi) { const uint64_t mid = lo + (hi - lo) / 2; if (ev[mid] < key) lo = mid + 1; else hi = mid; }
+                len = lo - i;
+            } }
+        if (head && len <= mcv) for (uint64_t j = 0; j < len; ++j) force(ev[i + j] & 0xFFFFFFFFull);
+        else if (head && len <= 64) { // the lane alone: mcv laps, each takes the smallest key above the one before
+            uint64_t ph = 0, pid = 0;
+            for (uint32_t r = 0; r < mcv; ++r) {
+                uint64_t bh = ~0ull, bid = 1ull << 32;
+                for (uint64_t j = 0; j < len; ++j) { const uint64_t id = ev[i + j] & 0xFFFFFFFFull, h = sub_hash(id, seed); if ((r == 0 || sub_key_less(ph, pid, h, id)) && sub_key_less(h, id, bh, bid)) { bh = h; bid = id; } }
+                force(bid); ph = bh; pid = bid;
+            }
+        }
+        uint64_t wide = __ballot(head && len > 64 && len > mcv ? 1 : 0);
+        while (wide) { // the wave together, one long segment after the other
+            const int src = __ffsll(static_cast<unsigned long long>(wide)) - 1; wide &= wide - 1;
+            const uint64_t s0 = __shfl(static_cast<unsigned long long>(i), src, 64), sl = __shfl(static_cast<unsigned long long>(len), src, 64);
+            uint64_t ph = 0, pid = 0;
+            for (uint32_t r = 0; r < mcv; ++r) {
+                uint64_t bh = ~0ull, bid = 1ull << 32;
+                for (uint64_t j = static_cast<uint64_t>(lane); j < sl; j += 64) { const uint64_t id = ev[s0 + j] & 0xFFFFFFFFull, h = sub_hash(id, seed); if ((r == 0 || sub_key_less(ph, pid, h, id)) && sub_key_less(h, id, bh, bid)) { bh = h; bid = id; } }
+                for (int d = 32; d >= 1; d >>= 1) { const uint64_t oh = __shfl_xor(static_cast<unsigned long long>(bh), d, 64), oid = __shfl_xor(static_cast<unsigned long long>(bid), d, 64); if (sub_key_less(oh, oid, bh, bid)) { bh = oh; bid = oid; } }
+                if (lane == 0) force(bid);
+                ph = bh; pid = bid;
+            }
+        }
+    }
+}
+
+__global__ void k_sub_keep(const uint8_t* __restrict__ first_bin, uint64_t n_ids, uint64_t n_words, const uint8_t* __restrict__ bin_is_sampled, uint32_t n_bins, double rate, uint64_t seed,
+                           unsigned long long* __restrict__ keep, unsigned long long* __restrict__ n_present) {
+    const uint64_t wave = (static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x) >> 6, n_waves = (static_cast<uint64_t>(gridDim.x) * blockDim.x) >> 6;
+    const int lane = threadIdx.x & 63;
+    unsigned long long present = 0;
+    for (uint64_t w = wave; w < n_words; w += n_waves) {
+        const uint64_t id = 64 * w + static_cast<uint64_t>(lane);
+        const uint32_t fb = id < n_ids ? first_bin[id] : 255u;
+        bool kept = fb < n_bins;
+        if (kept && bin_is_sampled[fb]) kept = static_cast<double>(sub_hash(id, seed) >> 11) * (1.0 / 9007199254740992.0) <= rate;
+        const uint64_t bits = __ballot(kept ? 1 : 0), there = __ballot(fb != 255u ? 1 : 0);
+        if (lane == 0) { if (bits) atomicOr(keep + w, static_cast<unsigned long long>(bits)); present += static_cast<unsigned long long>(__popcll(there)); }
+    }
+    if (lane == 0 && present) atomicAdd(n_present, present);
+}
+
+struct SubPopc { const unsigned long long* keep; uint64_t n_words; __device__ uint64_t operator()(uint64_t w) const { return w < n_words ? static_cast<uint64_t>(__popcll(keep[w])) : 0ull; } };
+struct SubKept { const uint64_t* ev; const unsigned long long* keep; uint64_t n_ids; __device__ bool operator()(uint64_t i) const { const uint64_t id = ev[i] & 0xFFFFFFFFull; return id < n_ids && ((keep[id >> 6] >> (id & 63ull)) & 1ull) != 0; } };
+struct SubRenumber { const uint64_t* ev; const unsigned long long* keep; const uint64_t* prefix; uint64_t n_ids;
+    __device__ uint64_t operator()(uint64_t i) const { const uint64_t e = ev[i], id = e & 0xFFFFFFFFull; if (id >= n_ids) return e;
+        return (e & 0xFFFFFFFF00000000ull) | (prefix[id >> 6] + static_cast<uint64_t>(__popcll(keep[id >> 6] & ((1ull << (id & 63ull)) - 1ull)))); } };
+
+// d_ev: n sorted distinct events in device memory; d_out: room for n events there. The per-unitig and per-bin arrays are the caller's host arrays. Throws.
+void subsample_events_device(const uint64_t* d_ev, uint64_t n, uint64_t* d_out, uint32_t n_unitigs, uint64_t n_ids, const uint8_t* bin_of_unitig, const uint8_t* forced_candidate, const uint8_t* bin_is_sampled,
+                             uint32_t n_bins, uint32_t mcv, double rate, uint64_t seed, uint64_t* n_out, uint64_t* ids_before, uint64_t* ids_after) {
+    *n_out = 0; *ids_before = 0; *ids_after = 0;
+    if (n == 0 || n_ids == 0) return;
+    auto grid = [](uint64_t items) { const uint64_t b = (items + 255) / 256; return dim3(static_cast<unsigned>(b < 1 ? 1 : (b > 65536 ? 65536 : b))); };
+    const uint64_t n_words = (n_ids + 63) / 64, fb_bytes = (n_ids + 3) / 4 * 4;
+    DevBuf d_bin, d_forced, d_sampled, d_fb, d_keep, d_prefix, d_cnt, d_tmp;
+    d_bin.alloc(n_unitigs); d_forced.alloc(n_unitigs); d_sampled.alloc(n_bins); d_fb.alloc(fb_bytes); d_keep.alloc(8 * n_words); d_prefix.alloc(8 * (n_words + 1)); d_cnt.alloc(24);
+    rtk_check(hipMemcpy(d_bin.p, bin_of_unitig, n_unitigs, hipMemcpyHostToDevice), "hipMemcpy"); rtk_check(hipMemcpy(d_forced.p, forced_candidate, n_unitigs, hipMemcpyHostToDevice), "hipMemcpy");
+    rtk_check(hipMemcpy(d_sampled.p, bin_is_sampled, n_bins, hipMemcpyHostToDevice), "hipMemcpy");
+    rtk_check(hipMemset(d_fb.p, 0xFF, fb_bytes), "hipMemset"); rtk_check(hipMemset(d_keep.p, 0, 8 * n_words), "hipMemset"); rtk_check(hipMemset(d_cnt.p, 0, 24), "hipMemset");
+    unsigned long long* keep = static_cast<unsigned long long*>(d_keep.p); unsigned long long* cnt = static_cast<unsigned long long*>(d_cnt.p); // cnt: ids present, events kept, flags of broken bounds
+    hipLaunchKernelGGL(k_sub_first_bin, grid(n), dim3(256), 0, 0, d_ev, n, static_cast<const uint8_t*>(d_bin.p), n_unitigs, n_bins, n_ids, static_cast<uint32_t*>(d_fb.p), reinterpret_cast<uint32_t*>(cnt + 2));
+    rtk_check(hipGetLastError(), "kernel launch (k_sub_first_bin)");
+    if (mcv) { hipLaunchKernelGGL(k_sub_forced, grid(n), dim3(256), 0, 0, d_ev, n, static_cast<const uint8_t*>(d_forced.p), n_unitigs, mcv, seed, n_ids, keep); rtk_check(hipGetLastError(), "kernel launch (k_sub_forced)"); }
+    hipLaunchKernelGGL(k_sub_keep, grid(64 * n_words), dim3(256), 0, 0, static_cast<const uint8_t*>(d_fb.p), n_ids, n_words, static_cast<const uint8_t*>(d_sampled.p), n_bins, rate, seed, keep, cnt);
+    rtk_check(hipGetLastError(), "kernel launch (k_sub_keep)");
+    auto idx = rocprim::make_counting_iterator<uint64_t>(0);
+    SubPopc pc; pc.keep = keep; pc.n_words = n_words;
+    auto counts = rocprim::make_transform_iterator(idx, pc);
+    size_t sb = 0; rtk_check(rocprim::exclusive_scan(nullptr, sb, counts, static_cast<uint64_t*>(d_prefix.p), 0ull, static_cast<size_t>(n_words + 1), rocprim::plus<uint64_t>()), "rocprim::exclusive_scan");
+    d_tmp.alloc(sb);
+    rtk_check(rocprim::exclusive_scan(d_tmp.p, sb, counts, static_cast<uint64_t*>(d_prefix.p), 0ull, static_cast<size_t>(n_words + 1), rocprim::plus<uint64_t>()), "rocprim::exclusive_scan");
+    SubKept kp; kp.ev = d_ev; kp.keep = keep; kp.n_ids = n_ids;
+    SubRenumber rn; rn.ev = d_ev; rn.keep = keep; rn.prefix = static_cast<const uint64_t*>(d_prefix.p); rn.n_ids = n_ids;
+    auto flags = rocprim::make_transform_iterator(idx, kp); auto vals = rocprim::make_transform_iterator(idx, rn);
+    size_t lb = 0; rtk_check(rocprim::select(nullptr, lb, vals, flags, d_out, cnt + 1, static_cast<size_t>(n)), "rocprim::select");
+    d_tmp.alloc(lb);
+    rtk_check(rocprim::select(d_tmp.p, lb, vals, flags, d_out, cnt + 1, static_cast<size_t>(n)), "rocprim::select");
+    rtk_check(hipDeviceSynchronize(), "colours subsampled");
+    unsigned long long h_cnt[3] = {0, 0, 0}; rtk_check(hipMemcpy(h_cnt, cnt, 24, hipMemcpyDeviceToHost), "hipMemcpy");
+    if (h_cnt[2]) throw std::runtime_error("an event names a unitig, an id or a bin outside the tables");
+    if (h_cnt[1] > n) throw std::runtime_error("more events kept than there were");
+    uint64_t total = 0; rtk_check(hipMemcpy(&total, static_cast<uint64_t*>(d_prefix.p) + n_words, 8, hipMemcpyDeviceToHost), "hipMemcpy");
+    *n_out = h_cnt[1]; *ids_before = h_cnt[0]; *ids_after = total;
+}
+const char* subsample_args_bad(const uint8_t* bin_of_unitig, const uint8_t* forced_candidate, const uint8_t* bin_is_sampled, uint32_t n_bins, uint32_t mcv, double rate) {
+    if (!bin_of_unitig || !forced_candidate || !bin_is_sampled) return "null argument";
+    if (n_bins < 1 || n_bins > 64) return "1 to 64 bins";
+    if (mcv > RTK_SUB_MAX_MCV) return "at most 64 forced ids per unitig";
+    if (!(rate >= 0.0)) return "the rate is not a number >= 0";
+    return nullptr;
+}
+} // namespace
+
+// The coverage of every unitig once all chunks are mapped (and the events sorted, the distinct ones kept); the job stays alive for rtk_index_colour_end or
+// rtk_index_colour_end_subsampled: the caller needs the coverage to work out the bins before the events can be thinned.
+extern "C" int rtk_index_colour_cov(void* job, uint64_t** cov) {
+    ColourJob* J = static_cast<ColourJob*>(job);
+    if (!J || !cov) return rtk_fail(RTK_ERR_ARG, "rtk_index_colour_cov: null argument");
+    *cov = nullptr;
+    try {
+        std::lock_guard<std::mutex> lk(J->m);
+        rtk_check(hipSetDevice(J->device), "hipSetDevice");
+        J->compact();
+        uint64_t* cv = static_cast<uint64_t*>(malloc(8ull * J->n_unitigs));
+        if (!cv) return rtk_fail(RTK_ERR_IO, "rtk_index_colour_cov: out of host memory");
+        rtk_check(hipMemcpy(cv, J->cov.p, 8ull * J->n_unitigs, hipMemcpyDeviceToHost), "hipMemcpy");
+        *cov = cv;
+    } catch (const std::exception& e) { return rtk_fail(RTK_ERR_DEVICE, std::string("rtk_index_colour_cov: ") + e.what()); }
+    return RTK_OK;
+}
+
+// rtk_index_colour_end with the events thinned out by coverage and renumbered on the device (the rule above); only the kept events are copied to the host.
+extern "C" int rtk_index_colour_end_subsampled(void* job, const uint8_t* bin_of_unitig, const uint8_t* forced_candidate, const uint8_t* bin_is_sampled, uint32_t n_bins, uint32_t mcv, double rate, uint64_t seed,
+                                               uint64_t** events, uint64_t* n_events, uint64_t* n_events_before, uint64_t* n_ids_before, uint64_t* n_ids_after) {
+    std::unique_ptr<ColourJob> J(static_cast<ColourJob*>(job));
+    if (!J) return rtk_fail(RTK_ERR_ARG, "rtk_index_colour_end_subsampled: null job");
+    if (!events || !n_events || !n_events_before || !n_ids_before || !n_ids_after) return rtk_fail(RTK_ERR_ARG, "rtk_index_colour_end_subsampled: null argument");
+    *events = nullptr; *n_events = 0;
+    if (const char* bad = subsample_args_bad(bin_of_unitig, forced_candidate, bin_is_sampled, n_bins, mcv, rate)) return rtk_fail(RTK_ERR_ARG, std::string("rtk_index_colour_end_subsampled: ") + bad);
+    try {
+        rtk_check(hipSetDevice(J->device), "hipSetDevice");
+        J->compact();
+        const auto t_sub = std::chrono::steady_clock::now();
+        uint64_t n_out = 0;
+        subsample_events_device(static_cast<const uint64_t*>(J->events.p), J->n_events, static_cast<uint64_t*>(J->alt.p), J->n_unitigs, J->n_ids, bin_of_unitig, forced_candidate, bin_is_sampled, n_bins, mcv, rate, seed, &n_out, n_ids_before, n_ids_after);
+        uint64_t* ev = static_cast<uint64_t*>(malloc(8 * (n_out ? n_out : 1)));
+        if (!ev) return rtk_fail(RTK_ERR_IO, "rtk_index_colour_end_subsampled: out of host memory");
+        if (n_out) { const hipError_t rc = hipMemcpy(ev, J->alt.p, 8 * n_out, hipMemcpyDeviceToHost); if (rc != hipSuccess) { free(ev); rtk_check(rc, "hipMemcpy"); } }
+        *events = ev; *n_events = n_out; *n_events_before = J->n_events;
+        if (rtk_knob_index_trace()) fprintf(stderr, "rtk_index_colour: %llu characters in %llu chunks -> %llu distinct (unitig, read) events (sorted and thinned out %llu times), %llu left after subsampling (%.3f s); table %.2f s, all %.2f s\n", static_cast<unsigned long long>(J->bases),
+                                               static_cast<unsigned long long>(J->chunks), static_cast<unsigned long long>(J->n_events), static_cast<unsigned long long>(J->compactions), static_cast<unsigned long long>(n_out),
+                                               std::chrono::duration<double>(std::chrono::steady_clock::now() - t_sub).count(), J->t_table, std::chrono::duration<double>(std::chrono::steady_clock::now() - J->t0).count());
+    } catch (const std::exception& e) { return rtk_fail(RTK_ERR_DEVICE, std::string("rtk_index_colour_end_subsampled: ") + e.what()); }
+    return RTK_OK;
+}
+
+// Stage entry for tests: the device function behind rtk_index_colour_end_subsampled on events of the caller (host arrays; ascending, distinct, unitigs < n_unitigs);
+// events_out has room for n_events words.
+extern "C" int rtk_index_subsample_events(int device, const uint64_t* events, uint64_t n_events, uint32_t n_unitigs, const uint8_t* bin_of_unitig, const uint8_t* forced_candidate, const uint8_t* bin_is_sampled,
+                                          uint32_t n_bins, uint32_t mcv, double rate, uint64_t seed, uint64_t* events_out, uint64_t* n_out, uint64_t* n_ids_before, uint64_t* n_ids_after) {
+    if ((!events && n_events) || (!events_out && n_events) || !n_out || !n_ids_before || !n_ids_after || n_unitigs == 0) return rtk_fail(RTK_ERR_ARG, "rtk_index_subsample_events: null argument");
+    if (const char* bad = subsample_args_bad(bin_of_unitig, forced_candidate, bin_is_sampled, n_bins, mcv, rate)) return rtk_fail(RTK_ERR_ARG, std::string("rtk_index_subsample_events: ") + bad);
+    if (rtk_device_count() <= device || device < 0) return rtk_fail(RTK_ERR_NO_DEVICE, "rtk_index_subsample_events: no such HIP device (no CPU fallback)");
+    uint64_t n_ids = 0;
+    for (uint64_t i = 0; i < n_events; ++i) {
+        if (i && events[i] <= events[i - 1]) return rtk_fail(RTK_ERR_ARG, "rtk_index_subsample_events: the events are not ascending and distinct");
+        if ((events[i] >> 32) >= n_unitigs) return rtk_fail(RTK_ERR_ARG, "rtk_index_subsample_events: an event names a unitig >= n_unitigs");
+        n_ids = std::max<uint64_t>(n_ids, (events[i] & 0xFFFFFFFFull) + 1);
+    }
+    for (uint32_t u = 0; u < n_unitigs; ++u) if (bin_of_unitig[u] != 255 && bin_of_unitig[u] >= n_bins) return rtk_fail(RTK_ERR_ARG, "rtk_index_subsample_events: a unitig names a bin >= n_bins");
+    try {
+        rtk_check(hipSetDevice(device), "hipSetDevice");
+        DevBuf d_ev, d_out; d_ev.alloc(8 * n_events); d_out.alloc(8 * n_events);
+        if (n_events) rtk_check(hipMemcpy(d_ev.p, events, 8 * n_events, hipMemcpyHostToDevice), "hipMemcpy");
+        subsample_events_device(static_cast<const uint64_t*>(d_ev.p), n_events, static_cast<uint64_t*>(d_out.p), n_unitigs, n_ids, bin_of_unitig, forced_candidate, bin_is_sampled, n_bins, mcv, rate, seed, n_out, n_ids_before, n_ids_after);
+        if (*n_out) rtk_check(hipMemcpy(events_out, d_out.p, 8 * *n_out, hipMemcpyDeviceToHost), "hipMemcpy");
+    } catch (const std::exception& e) { return rtk_fail(RTK_ERR_DEVICE, std::string("rtk_index_subsample_events: ") + e.what()); }
     return RTK_OK;
 }

@@ -11,8 +11,8 @@
 
 namespace rtk {
 
-// ---- adjacency, branching, edge bits ----
-template <class KM> static void adjacency(IndexBuild<KM>& s) {
+// ---- adjacency and branching (structure: the sequences and the k-mer table alone), then the edge bits (the colours) ----
+template <class KM> static void adjacency_structure(IndexBuild<KM>& s) {
     const int k = s.k; const size_t n = s.U.size(); const std::vector<Unitig>& U = s.U;
     s.adj.resize(n); s.headk.resize(n); s.tailk.resize(n); s.kmcov.assign(n, 0); s.shared.assign(n, 0); s.cycles.assign(n, std::string()); s.ambiguity.assign(n, std::vector<uint32_t>()); // (what the later steps fill per unitig)
     parallel_for(n, s.o.fast ? s.n_thr : 1u, [&](size_t b0, size_t e0, unsigned) { for (size_t u = b0; u < e0; ++u) { // (unitigs are independent: the table is only read)
@@ -26,14 +26,21 @@ template <class KM> static void adjacency(IndexBuild<KM>& s) {
             const KM y = ((ends[d] << 2) | static_cast<KM>(b)) & s.mask;
             const uint64_t* v = s.km.slot(kmer_canonical(y, k), false);
             if (!v) continue;
-            const size_t w = (*v >> 32) - 1;
-            s.adj[u].u[d][b] = static_cast<int64_t>(w);
+            s.adj[u].u[d][b] = static_cast<int64_t>((*v >> 32) - 1);
             ++deg[d];
-            if (shared_count(U[u].colours, U[w].colours) >= s.o.min_cov_vertices) s.shared[u] |= (d == 0) ? ((1ULL << b) << 4) : (1ULL << b); // idx(A,C,G,T)=1,2,4,8 (src/Common.hpp:260,358)
         }
         const uint64_t cov = std::min<uint64_t>(U[u].cov, 0x7fffffffULL);
         s.kmcov[u] = (cov << 31) | ((deg[0] > 1 || deg[1] > 1) ? (1ULL << 63) : 0ULL);
     } });
+}
+template <class KM> static void edge_bits(IndexBuild<KM>& s) {
+    const size_t n = s.U.size(); const std::vector<Unitig>& U = s.U;
+    parallel_for(n, s.o.fast ? s.n_thr : 1u, [&](size_t b0, size_t e0, unsigned) { for (size_t u = b0; u < e0; ++u)
+        for (int d = 0; d < 2; ++d) for (uint64_t b = 0; b < 4; ++b) {
+            const int64_t w = s.adj[u].u[d][b];
+            if (w >= 0 && shared_count(U[u].colours, U[static_cast<size_t>(w)].colours) >= s.o.min_cov_vertices) s.shared[u] |= (d == 0) ? ((1ULL << b) << 4) : (1ULL << b); // idx(A,C,G,T)=1,2,4,8 (src/Common.hpp:260,358)
+        }
+    });
 }
 
 // ---- short cycles (restatement of detectShortCycles, src/Graph.cpp:4660-4735): for every unitig U in forward direction, breadth

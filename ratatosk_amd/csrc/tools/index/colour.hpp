@@ -30,18 +30,23 @@ struct Feed {
 template <class KM> struct ColourSink {
     IndexBuild<KM>& s; std::vector<Unitig>& U; const size_t n_u;
     void* job = nullptr; std::atomic<int> failed; HipLib::col_chunk_fn chunk_fn = nullptr; HipLib::col_end_fn end_fn = nullptr; std::vector<Feed> feeds;
+    HipLib::col_cov_fn cov_fn = nullptr; HipLib::col_end_sub_fn end_sub_fn = nullptr; bool open_job = false; // --subsample-colours: the job stays open (open_job) between the coverage and the thinned events
     std::vector<std::vector<uint64_t> > cov; std::vector<std::vector<std::pair<uint32_t, uint32_t> > > ev; // host: per thread, k-mers per unitig and (unitig, id) events
 
     explicit ColourSink(IndexBuild<KM>& st) : s(st), U(st.U), n_u(st.U.size()), failed(0), feeds(st.n_thr), cov(st.n_thr), ev(st.n_thr) {
         HipLib::col_begin_fn begin_fn = nullptr;
         if (s.o.gpu && s.lib.get(begin_fn, "rtk_index_colour_begin") && s.lib.get(chunk_fn, "rtk_index_colour_chunk") && s.lib.get(end_fn, "rtk_index_colour_end") && !s.knobs.host_colours && n_u > 0) {
+            if (s.o.subsample && !(s.lib.get(cov_fn, "rtk_index_colour_cov") && s.lib.get(end_sub_fn, "rtk_index_colour_end_subsampled"))) { // (the events are then fetched the old way, rtk_index_colour_end)
+                cov_fn = nullptr; end_sub_fn = nullptr; fprintf(stderr, "rtk_build_index: --gpu: %s lacks rtk_index_colour_cov / rtk_index_colour_end_subsampled: colours subsampled on the host threads\n", s.lib.path.c_str()); }
             std::vector<uint64_t> off(n_u + 1, 0); for (size_t u = 0; u < n_u; ++u) off[u + 1] = off[u] + s.U[u].seq.size();
             std::string pool(off[n_u], 'A');
             parallel_for(n_u, s.n_thr, [&](size_t b, size_t e, unsigned) { for (size_t u = b; u < e; ++u) memcpy(&pool[off[u]], s.U[u].seq.data(), s.U[u].seq.size()); });
             if (begin_fn(0, s.k, pool.data(), off.data(), n_u, &job) != 0) { fprintf(stderr, "rtk_build_index: --gpu: colours on the host threads (%s)\n", s.lib.last_error()); job = nullptr; }
+            open_job = job != nullptr;
         }
         for (unsigned t = 0; t < s.n_thr; ++t) { feeds[t].job = job; feeds[t].fn = chunk_fn; feeds[t].failed = &failed; if (!job) cov[t].assign(n_u, 0); }
     }
+    ~ColourSink() { if (open_job) end_fn(job, nullptr, nullptr, nullptr); } // (left early: the job released)
     // one read, from thread t of the source: its k-mers looked up (the table is only read), or the read handed to the device
     void read(unsigned t, const char* seq, size_t len, uint32_t id) {
         if (job) { feeds[t].add(seq, len, id); return; }
@@ -51,18 +56,44 @@ template <class KM> struct ColourSink {
             if (v) { const uint32_t u = static_cast<uint32_t>((*v >> 32) - 1); ++c[u]; if (e.empty() || e.back().first != u || e.back().second != id) e.push_back(std::make_pair(u, id)); }
         });
     }
+    // sorted events unitig << 32 | id into the colours of the unitigs
+    void take_events(const uint64_t* evs, uint64_t n_ev) {
+        parallel_for(n_u, s.n_thr, [&](size_t b, size_t e, unsigned) {
+            if (b >= e) return;
+            const uint64_t* p = std::lower_bound(evs, evs + n_ev, static_cast<uint64_t>(b) << 32);
+            for (size_t u = b; u < e; ++u) { const uint64_t* q = p; while (q < evs + n_ev && (*q >> 32) == u) ++q; U[u].colours.resize(static_cast<size_t>(q - p)); for (size_t i = 0; p + i < q; ++i) U[u].colours[i] = static_cast<uint32_t>(p[i] & 0xFFFFFFFFull); p = q; }
+        });
+    }
+    void take_cov(const uint64_t* cv) { parallel_for(n_u, s.n_thr, [&](size_t b, size_t e, unsigned) { for (size_t u = b; u < e; ++u) U[u].cov = cv[u]; }); }
     // --gpu: the distinct (unitig, id) events in sorted order and the coverages, back from the device
     bool finish_device() {
         if (!job) return true;
         for (unsigned t = 0; t < s.n_thr; ++t) feeds[t].flush();
         uint64_t* evs = nullptr; uint64_t* cv = nullptr; uint64_t n_ev = 0;
+        open_job = false;
         if (end_fn(job, &evs, &n_ev, &cv) != 0 || failed) { fprintf(stderr, "rtk_build_index: --gpu: colouring on the device failed (%s)\n", s.lib.last_error()); return false; }
-        parallel_for(n_u, s.n_thr, [&](size_t b, size_t e, unsigned) {
-            if (b >= e) return;
-            const uint64_t* p = std::lower_bound(evs, evs + n_ev, static_cast<uint64_t>(b) << 32);
-            for (size_t u = b; u < e; ++u) { U[u].cov = cv[u]; const uint64_t* q = p; while (q < evs + n_ev && (*q >> 32) == u) ++q; U[u].colours.resize(static_cast<size_t>(q - p)); for (size_t i = 0; p + i < q; ++i) U[u].colours[i] = static_cast<uint32_t>(p[i] & 0xFFFFFFFFull); p = q; }
-        });
+        take_cov(cv); take_events(evs, n_ev);
         s.lib.free(evs); s.lib.free(cv);
+        return true;
+    }
+    // --gpu --subsample-colours, first half: the reads are all fed, the coverages come back; the events stay on the device
+    bool cov_device() {
+        if (!job) return true;
+        for (unsigned t = 0; t < s.n_thr; ++t) feeds[t].flush();
+        uint64_t* cv = nullptr;
+        if (cov_fn(job, &cv) != 0 || failed) { fprintf(stderr, "rtk_build_index: --gpu: colouring on the device failed (%s)\n", s.lib.last_error()); return false; }
+        take_cov(cv); s.lib.free(cv);
+        return true;
+    }
+    // second half: the events thinned and renumbered on the device (tools/index/subsample.hpp has the rule), only the kept ones copied back
+    bool finish_device_subsampled(const uint8_t* bin_of_unitig, const uint8_t* forced_candidate, const uint8_t* bin_is_sampled, uint32_t n_bins, double rate, uint64_t seed,
+                                  uint64_t* ev_before, uint64_t* ev_after, uint64_t* ids_before, uint64_t* ids_after) {
+        uint64_t* evs = nullptr; uint64_t n_ev = 0;
+        open_job = false;
+        if (end_sub_fn(job, bin_of_unitig, forced_candidate, bin_is_sampled, n_bins, static_cast<uint32_t>(s.o.min_cov_vertices), rate, seed, &evs, &n_ev, ev_before, ids_before, ids_after) != 0) {
+            fprintf(stderr, "rtk_build_index: --gpu: subsampling on the device failed (%s)\n", s.lib.last_error()); return false; }
+        *ev_after = n_ev;
+        take_events(evs, n_ev); s.lib.free(evs);
         return true;
     }
     // the threads' counts and events into the unitigs; the colours sorted, each id once
@@ -184,10 +215,15 @@ template <class KM> static bool colour_and_cover(IndexBuild<KM>& s) {
     // (addCoverage(dbg, opt_pass2, ..., long_read_correct = true), src/Ratatosk.cpp:1218)
     const bool by_read = !s.o.colour_files.empty();
     const std::vector<std::string>& col_in = by_read ? s.o.colour_files : s.o.in_files;
-    ColourSink<KM> sink(s);
+    std::shared_ptr<ColourSink<KM> > sink_p = std::make_shared<ColourSink<KM> >(s); ColourSink<KM>& sink = *sink_p;
     bool all_sampled = s.o.fast && !by_read && !col_in.empty(), all_plain = s.o.fast;
     for (size_t f = 0; f < col_in.size(); ++f) { all_sampled = all_sampled && SampleSource::is_spec(col_in[f]); all_plain = all_plain && PlainChunks::is_plain(col_in[f]); }
     const bool ok = all_sampled ? colour_from_samples(s, sink, col_in) : (all_plain ? colour_from_plain_ranges(s, sink, col_in, by_read) : colour_from_reader(s, sink, col_in, by_read));
+    if (s.o.subsample && sink.job && sink.end_sub_fn) { // the events wait on the device for the subsampling step
+        if (!sink.cov_device() || !ok) return false;
+        s.colour_sink = sink_p;
+        return true;
+    }
     if (!sink.finish_device() || !ok) return false;
     sink.finish_host();
     return true;
