@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Developer census on the CPU simulator: which alignments of a region repeat an earlier one of the same region (rtk_pair_note, csrc/hip/rtk_region.h). Per call
+"""Developer census on the CPU simulator: which alignments of a region repeat an earlier one of the same region (rtk_pair_note, csrc/hip/rtk_sim_census.h). Per call
 site: calls and 32-bit word-columns, and of them those whose (query, target) pair was swept before exactly, transposed, with a query that is a prefix of the
 other's on the same target, or with a query of the same length at Hamming distance 1..8 on the same target (the first class that holds). The strings are the
 swept ones: a trim by column counts as (corrected, raw). Usage: sim_pairs.py PREFIX [max_reads]"""

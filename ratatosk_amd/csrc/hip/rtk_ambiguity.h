@@ -1,18 +1,18 @@
 // SNP annotations on the chosen paths of a region: getAmbiguityVector (src/GraphTraversal.cpp:966-1036) and fixAmbiguity
 // (src/Alignment.cpp:527-844), for an undetermined haplotype (no phasing input: the isValidHap tests of :741,:801 are
-// short-circuited). Included by rtk_region.h; everything here is wave-uniform bookkeeping over a handful of annotated positions,
+// short-circuited). Included by rtk_region.h (and rtk_fixsnps.h); the lists are named in rtk_region_types.h. Everything here is wave-uniform bookkeeping over a handful of annotated positions,
 // except the walk over the alignment moves, which is done 64 moves at a time.
 //
 // Small sets are kept as arrays of `position << 8 | character` in the region scratch lists:
-//   list[RTK_L_AMB]      v_ambiguity of the region (path-string coordinates of s_corrected)
-//   list[RTK_L_AMB + 1]  m_ambiguity_safe   (while collecting: the running vector of one path)
-//   list[RTK_L_AMB + 2]  m_ambiguity_all    (while collecting: merge buffer)
-//   list[RTK_L_AMB + 3]  annotations of one unitig mapping
-//   list[RTK_L_AMB + 4]  s_ambiguity (alleles of linked SNPs)
+//   list[RTK_L_AMB]         v_ambiguity of the region (path-string coordinates of s_corrected)
+//   list[RTK_L_AMB_SAFE]    m_ambiguity_safe   (while collecting: the running vector of one path)
+//   list[RTK_L_AMB_ALL]     m_ambiguity_all    (while collecting: merge buffer)
+//   list[RTK_L_AMB_UNITIG]  annotations of one unitig mapping
+//   list[RTK_L_AMB_LINKED]  s_ambiguity (alleles of linked SNPs)
 #ifndef RTK_AMBIGUITY_H
 #define RTK_AMBIGUITY_H
 
-#define RTK_L_AMB 6
+#include "rtk_region_align.h"
 
 RTK_DEV uint64_t rtk_amb_mk(uint64_t pos, char ch) { return (pos << 8) | static_cast<uint64_t>(static_cast<unsigned char>(ch)); }
 RTK_DEV uint32_t rtk_amb_pos(uint64_t e) { return static_cast<uint32_t>(e >> 8); }
@@ -52,7 +52,7 @@ RTK_DEV uint32_t rtk_amb_of_um(const RCtx& c, const UMap& um, uint64_t* out, uin
         const uint64_t e = ent[um.strand ? (a0 + j) : (a1 - 1 - j)];
         const uint32_t pos = static_cast<uint32_t>(e >> 4); const char ch = rtk_iupac_chr(static_cast<uint32_t>(e & 15ull));
         if (pos < um.dist || pos >= end) continue;
-        if (n >= cap) { rtk_fail_ovf(*c.sc, 11); return 0; }
+        if (n >= cap) { rtk_fail_ovf(*c.sc, RTK_OVF_AMB); return 0; }
         out[n++] = um.strand ? rtk_amb_mk(pos - um.dist, ch) : rtk_amb_mk(sz - (pos - um.dist) - 1, rtk_iupac_comp(ch));
     }
     return n;
@@ -75,7 +75,7 @@ RTK_FN uint32_t rtk_amb_collect(const RCtx& c_, uint64_t h_, uint32_t offset_, u
         }
         if (!any) return n_amb;
     }
-    uint64_t* va = s.list[RTK_L_AMB + 1]; uint64_t* vt = s.list[RTK_L_AMB + 2]; uint64_t* vu = s.list[RTK_L_AMB + 3];
+    uint64_t* va = s.list[RTK_L_AMB_SAFE]; uint64_t* vt = s.list[RTK_L_AMB_ALL]; uint64_t* vu = s.list[RTK_L_AMB_UNITIG];
     uint32_t nva = 0, prev_l = 0, pos_prev_l = 0;
     for (uint32_t x = 0; x < n; ++x) {
         const UMap um = rtk_u(ums[x]);
@@ -89,7 +89,7 @@ RTK_FN uint32_t rtk_amb_collect(const RCtx& c_, uint64_t h_, uint32_t offset_, u
             else if (pp > cur_pos) vt[nvt++] = rtk_amb_mk(cur_pos, rtk_amb_chr(vu[ic++]));
             else { vt[nvt++] = rtk_amb_mk(pp, rtk_iupac_chr(rtk_iupac_idx(rtk_amb_chr(va[ip])) | rtk_iupac_idx(rtk_amb_chr(vu[ic])))); ++ip; ++ic; }
         }
-        if (nvt + (nva - ip) + (nvu - ic) > cap || pos_prev_l + nvt + (nva - ip) + (nvu - ic) > cap) { rtk_fail_ovf(s, 11); return n_amb; }
+        if (nvt + (nva - ip) + (nvu - ic) > cap || pos_prev_l + nvt + (nva - ip) + (nvu - ic) > cap) { rtk_fail_ovf(s, RTK_OVF_AMB); return n_amb; }
         for (; ip != nva; ++ip) vt[nvt++] = va[ip];
         for (; ic != nvu; ++ic) vt[nvt++] = rtk_amb_mk(rtk_amb_pos(vu[ic]) + prev_l, rtk_amb_chr(vu[ic]));
         prev_l += um.len;
@@ -98,7 +98,7 @@ RTK_FN uint32_t rtk_amb_collect(const RCtx& c_, uint64_t h_, uint32_t offset_, u
     }
     uint64_t* v = s.list[RTK_L_AMB];
     uint32_t na = n_amb;
-    if (na + nva > cap) { rtk_fail_ovf(s, 11); return n_amb; }
+    if (na + nva > cap) { rtk_fail_ovf(s, RTK_OVF_AMB); return n_amb; }
     for (uint32_t i = 0; i < nva; ++i) v[na++] = rtk_amb_mk(static_cast<uint64_t>(offset) + rtk_amb_pos(va[i]), rtk_amb_chr(va[i]));
     return na;
 }
@@ -153,13 +153,13 @@ RTK_FN void rtk_fix_ambiguity(const RCtx& c_, char* query_, uint32_t query_len_,
     RegionScratch& s = rtk_hdr(c);
     const GraphView& g = c.g;
     const uint32_t k = static_cast<uint32_t>(c.k), cap = s.list_cap;
-    if (quality_len < query_len || query_len > s.str_cap) { rtk_fail_ovf(s, 11); return; }
+    if (quality_len < query_len || query_len > s.str_cap) { rtk_fail_ovf(s, RTK_OVF_AMB); return; }
     const char q_max_corr = rtk_get_qual(1.0, static_cast<uint64_t>(c.o.out_qual), static_cast<uint64_t>(c.o.max_qual));
     const char q_min_corr = rtk_get_qual(0.0, static_cast<uint64_t>(c.o.out_qual), static_cast<uint64_t>(c.o.max_qual));
     const char q_min_conf_corr = rtk_get_qual(c.o.min_confidence_snp_corr, 0, static_cast<uint64_t>(c.o.max_qual));
     const char c_no = 'X';
     const uint64_t* v = s.list[RTK_L_AMB];
-    uint64_t* ms = s.list[RTK_L_AMB + 1]; uint64_t* ma = s.list[RTK_L_AMB + 2]; uint64_t* vu = s.list[RTK_L_AMB + 3]; uint64_t* sa = s.list[RTK_L_AMB + 4];
+    uint64_t* ms = s.list[RTK_L_AMB_SAFE]; uint64_t* ma = s.list[RTK_L_AMB_ALL]; uint64_t* vu = s.list[RTK_L_AMB_UNITIG]; uint64_t* sa = s.list[RTK_L_AMB_LINKED];
     uint32_t nms = 0, nma = 0, nsa = 0;
     for (uint32_t i = 0; i < n_amb; ++i) {
         const uint32_t p = rtk_amb_pos(v[i]);
@@ -174,7 +174,7 @@ RTK_FN void rtk_fix_ambiguity(const RCtx& c_, char* query_, uint32_t query_len_,
         for (uint32_t i = static_cast<uint32_t>(rtk_lane()); i < ref_len; i += RTK_WAVE) odd |= !rtk_is_dna(ref[i]);
         if (rtk_ballot(odd) == 0) { s.fine[RTK_FINE_FA_ALL_CONFIDENT] += 1; return; }
     }
-    char* qt = s.str[0]; // query_tmp
+    char* qt = s.str[RTK_STR_AMB_QUERY]; // query_tmp
     rtk_wcopy(qt, query, query_len);
     rtk_sync();
     for (uint32_t i = 0; i < n_amb; ++i) {
@@ -187,7 +187,7 @@ RTK_FN void rtk_fix_ambiguity(const RCtx& c_, char* query_, uint32_t query_len_,
     uint32_t nm = 0;
     unsigned long long tfa_ = rtk_clock();
 #define RTK_FA_LAP(i) { const unsigned long long tn_ = rtk_clock(); s.fine[i] += tn_ - tfa_; tfa_ = tn_; }
-    RTK_SITE(17); rtk_align_path(c, qt, query_len, ref, ref_len, RTK_MODE_SHW, &nm); nm = rtk_u(nm);
+    RTK_SITE(RTK_SITE_FIX_AMBIGUITY); rtk_align_path(c, qt, query_len, ref, ref_len, RTK_MODE_SHW, &nm); nm = rtk_u(nm);
     if (rtk_failed(s)) return;
     RTK_FA_LAP(RTK_FINE_FA_ALIGN)
     { // walk of the alignment (:612-706); only moves touching a non-ACGT character on either side do anything
@@ -214,7 +214,7 @@ RTK_FN void rtk_fix_ambiguity(const RCtx& c_, char* query_, uint32_t query_len_,
                         else if (quality[q_pos] >= q_min_corr) { if (rtk_iupac_overlap(qc, tc)) { const int x = rtk_amb_find(ms, nms, q_pos); if (x >= 0) ms[x] = rtk_amb_mk(q_pos, tc); } }
                         const int y = rtk_amb_find(ma, nma, q_pos); if (y >= 0) ma[y] = rtk_amb_mk(q_pos, tc);
                     } else if (quality[q_pos] < q_min_conf_corr || !rtk_iupac_overlap(qc, tc)) { // the read carries a code here
-                        if (nms >= cap || nma >= cap) { rtk_fail_ovf(s, 11); return; }
+                        if (nms >= cap || nma >= cap) { rtk_fail_ovf(s, RTK_OVF_AMB); return; }
                         if (rtk_amb_find(ms, nms, q_pos) < 0) ms[nms++] = rtk_amb_mk(q_pos, c_no);
                         if (rtk_amb_find(ma, nma, q_pos) < 0) ma[nma++] = rtk_amb_mk(q_pos, tc);
                     }
@@ -232,7 +232,7 @@ RTK_FN void rtk_fix_ambiguity(const RCtx& c_, char* query_, uint32_t query_len_,
     // A/C/G/T (:755-759 -- the two `continue`s in front of `uc` below); positions are unique in `ms`, so x != e, and `ms` is not written in this loop. An entry
     // that is searched for is decided, so it is none of the undecided ones: with n_open == 0 no search of this call can append, whatever the graph holds, and
     // `sa`, all that the loop hands on, stays empty. The reference runs those searches too, without effect. ('X', c_no, counts as undecided: rtk_is_dna('X')
-    // is false.) A skipped search cannot raise overflow code 11 (rtk_amb_of_um, the capacity of `sa`) either: such a region used to be redone with bigger
+    // is false.) A skipped search cannot raise RTK_OVF_AMB (rtk_amb_of_um, the capacity of `sa`) either: such a region used to be redone with bigger
     // work areas and then gave the same bytes; now it is done at once. RTK_FA_LINKED_ALWAYS=1 (rtk_knobs.h) runs every search.
     uint32_t n_open = 0;
     for (uint32_t e = 0; e < nms; ++e) n_open += rtk_is_dna(rtk_amb_chr(ms[e])) ? 0u : 1u;
@@ -246,7 +246,7 @@ RTK_FN void rtk_fix_ambiguity(const RCtx& c_, char* query_, uint32_t query_len_,
         const uint32_t pos_buff = (p < k - 1) ? 0 : (p - k + 1);
         const uint32_t len_buff = ((p + k < query_len) ? (p + k) : query_len) - pos_buff;
         const uint32_t pos_snp_buff = p - pos_buff;
-        char* q_sub = s.str[1];
+        char* q_sub = s.str[RTK_STR_AMB_SUB];
         rtk_wcopy(q_sub, query + pos_buff, len_buff);
         rtk_sync();
         q_sub[pos_snp_buff] = pc;
@@ -300,7 +300,7 @@ RTK_FN void rtk_fix_ambiguity(const RCtx& c_, char* query_, uint32_t query_len_,
                 const uint64_t ent = rtk_amb_mk(static_cast<uint64_t>(pos), uc);
                 bool dup = false;
                 for (uint32_t z = 0; z < nsa && !dup; ++z) dup = sa[z] == ent;
-                if (!dup) { if (nsa >= cap) { rtk_fail_ovf(s, 11); return; } sa[nsa++] = ent; }
+                if (!dup) { if (nsa >= cap) { rtk_fail_ovf(s, RTK_OVF_AMB); return; } sa[nsa++] = ent; }
             }
             skip_until = w + (um.len - 1); skip_one = um.len >= 2; // it_km += um.len - 1, then ++it_km
         }

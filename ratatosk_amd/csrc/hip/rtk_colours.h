@@ -1,17 +1,43 @@
-// chooseColors (reference: src/Correction.cpp:215-429) on bit vectors, for the regions that make up nearly all of a batch: the colour
+// chooseColors (reference: src/Correction.cpp:215-429), all of it: the side lists, the two bit-vector programs for the regions that make up
+// nearly all of a batch, the general sorted-array program for the rest, and the dispatcher rtk_choose_colors (at the end of the file).
+//
+// The bit-vector programs, for the regions that make up nearly all of a batch: the colour
 // sets of the anchors around one weak region hold a few hundred distinct pair ids together (measured on configs[1]: < 512 in 90 % of
 // the calls; on the 1 Mb set of the bench's generator arguments a median of 235, at most 526, out of a median of 405 ids with repeats).
 // Those ids are sorted once into a small universe kept in LDS; every set of the algorithm -- the six anchor classes, their
 // unions / intersections / differences, curr_pid, all_pids -- is then ONE 64-bit word per lane (4096 bits), the whole class loop runs
 // in registers (OR / AND / ANDN, popcount + wave sum, "the quota lowest ids" = a prefix count), and all_pids is expanded back into a
-// sorted id list at the end. Same selections as the general sorted-array version in rtk_region.h, which stays the fallback for
+// sorted id list at the end. Same selections as the general sorted-array version further down, which stays the fallback for
 // larger universes (returns RTK_NONE32 then). Bit order = id order, so "lowest ids first" is "lowest bits first".
 #ifndef RTK_COLOURS_H
 #define RTK_COLOURS_H
 
+#include "rtk_region_paths.h"
+#include "rtk_sets.h"
+#include "rtk_sim_census.h"
+
 #define RTK_CB_MAX_IDS (RTK_LDS_SET_CAP - 384u)   // ids gathered from all anchors (with repeats); universe (u32), 256 radix counters and 64 scatter words share the 8 KB LDS buffer
 #define RTK_CB_MAX_SLOTS 24u   // side-list entries whose bit vectors are kept
 
+// ------------------------------------------------------------------------------------------------ side lists
+// anchors of the three sides are given as small (unitig, non-branching) lists, first insertion wins (unordered_map::insert).
+RTK_DEV bool rtk_side_insert(SideList& l, uint32_t u, bool nonbranching) { // returns true when unseen
+    const uint32_t n = rtk_u(l.n); const uint32_t* lu = rtk_u(l.u);
+    for (uint32_t i0 = 0; i0 < n; i0 += RTK_WAVE) { // 64 entries per step
+        const uint32_t i = i0 + static_cast<uint32_t>(rtk_lane());
+        if (rtk_ballot(i < n && lu[i] == u)) return false;
+    }
+    if (n < rtk_u(l.cap)) { l.u[n] = u; l.nb[n] = nonbranching ? 1 : 0; l.n = n + 1; rtk_sync(); }
+    return true;
+}
+
+// set-buffer helpers on RegionScratch: buffers are addressed by index; sizes kept by the caller
+RTK_DEV uint32_t rtk_rs_union(RegionScratch& s, int a, uint32_t na, const uint32_t* b, uint32_t nb, int out) {
+    if (na + nb > s.set_cap) { rtk_fail_ovf(s, RTK_OVF_SET); return 0; }
+    return rtk_set_union(s.set[a], na, b, nb, s.set[out], s.set[RTK_SET_UNION_TMP]);
+}
+
+// ------------------------------------------------------------------------------------------------ the bit-vector programs
 #ifndef RTK_SIM
 // Least-significant-digit radix sort of n 32-bit keys by one wave, 8 bits per pass: the bitonic network it replaces costs 45-66 stages of
 // LDS compare-exchanges (1 400 LDS operations per lane for 512 keys), this costs two passes over the keys per digit. `a` holds the keys
@@ -277,8 +303,8 @@ RTK_FN uint32_t rtk_choose_colors_small(const RCtx& c_, const SideList& side_s_,
     const uint32_t* const pw = rtk_u(side_w.u); const uint32_t* const pe = rtk_u(side_e.u); const uint32_t* const ps = rtk_u(side_s.u);
     const uint8_t* const qw = rtk_u(side_w.nb); const uint8_t* const qe = rtk_u(side_e.nb); const uint8_t* const qs = rtk_u(side_s.nb);
     const uint32_t* const col = g.col; const uint64_t* const loff = g.loff; const uint64_t* const goff = g.goff; const int32_t* const gid = g.gid; const uint32_t* const cardp = g.card;
-    unsigned long long tl_ = rtk_clock();
-#define RTK_CS_LAP(i) { (void)tl_; }
+    (void)rtk_clock(); // (what is left of a retired lap profile: one read of the cycle counter. Without it the compiler emits other code for this function,
+                       // so it stays until a change that touches this kernel anyway)
     // ---- A. one lane per slot ----
     uint32_t m_u = 0, m_nl = 0, m_ng = 0, m_card = 0, m_nb = 0; uint64_t m_lo = 0, m_go = 0; int32_t m_gi = -1;
     if (lane < n_slots) {
@@ -290,10 +316,9 @@ RTK_FN uint32_t rtk_choose_colors_small(const RCtx& c_, const SideList& side_s_,
     }
     int total = 0; const uint32_t st = static_cast<uint32_t>(rtk_wave_excl_scan(static_cast<int>(m_nl + m_ng), &total)); // first id of the slot in the flat order
     const uint32_t T = static_cast<uint32_t>(rtk_u(total));
-    // (above RTK_CS_MAX_IDS ids the sort's second buffer is set[1], and set[2] holds the tags of ids too large to carry them)
+    // (above RTK_CS_MAX_IDS ids the sort's second buffer is set[RTK_SET_CS_SORT], and set[RTK_SET_CS_TAGS] holds the tags of ids too large to carry them)
     const bool big = T > RTK_CS_MAX_IDS;
     if (T > RTK_CB_MAX_IDS || (big && s.set_cap < RTK_CB_MAX_IDS)) return RTK_NONE32;
-    RTK_CS_LAP(1)
     // ---- B. candidate anchors: cardinality >= min_cov_vertices, first occurrence of their unitig, ordered by (cardinality, unitig) [D1] ----
     const uint32_t min_cov_v = c.o.min_cov_vertices;
     bool dup = false;
@@ -309,11 +334,10 @@ RTK_FN uint32_t rtk_choose_colors_small(const RCtx& c_, const SideList& side_s_,
     const uint32_t cov = 30;
     const uint32_t k_slot = src; const uint32_t k_card = rtk_shfl(m_card, static_cast<int>(src));
     uint32_t k_quota = k_card < cov ? k_card : cov;
-    RTK_CS_LAP(2)
     // ---- C. every id of every side unitig, with its tag, straight into LDS ----
     uint32_t* const L = rtk_lds_set_buf();
     uint32_t* const uni = L;
-    uint8_t* const gtags = reinterpret_cast<uint8_t*>(s.set[2].get());
+    uint8_t* const gtags = reinterpret_cast<uint8_t*>(s.set[RTK_SET_CS_TAGS].get());
     uint32_t mx = 0;
     for (bool packed = true;; packed = false) { // (a second time, tags apart, when an id turns out too large to carry its tag)
         uint8_t* const tags = rtk_cu_tags(L, T, gtags);
@@ -335,12 +359,10 @@ RTK_FN uint32_t rtk_choose_colors_small(const RCtx& c_, const SideList& side_s_,
         if (!packed || mx < RTK_CS_PACKED_LIMIT) break;
     }
     RTK_WG_SYNC();
-    RTK_CS_LAP(3)
     // ---- D. universe (sorted, duplicates dropped) and the bit vectors of every slot (local part, global part), both in LDS ----
     uint32_t U = 0, VW = 1; uint64_t* cbm = nullptr;
-    if (!rtk_colour_universe(L, T, 2u * n_slots, mx, s.set[1], gtags, &U, &VW, &cbm)) { s.cnt[RTK_RC_COLOURS_DECLINED_FIT] += 1; return RTK_NONE32; }
+    if (!rtk_colour_universe(L, T, 2u * n_slots, mx, s.set[RTK_SET_CS_SORT], gtags, &U, &VW, &cbm)) { s.cnt[RTK_RC_COLOURS_DECLINED_FIT] += 1; return RTK_NONE32; }
     s.cnt[RTK_RC_COLOUR] += T;
-    RTK_CS_LAP(4)
     // (up to 8 words a vector lives in lanes 0..7 and the 8-lane forms count it)
     const bool w8 = VW <= 8u;
     auto ld = [&](uint32_t idx) -> RtkBM { return lane < VW ? cbm[idx * VW + lane] : 0ull; };
@@ -401,11 +423,10 @@ RTK_FN uint32_t rtk_choose_colors_small(const RCtx& c_, const SideList& side_s_,
             nb_unselected += quota > 0 ? 1u : 0u;
         }
     }
-    RTK_CS_LAP(5)
-    // ---- all_pids back to a sorted id list in set[0] ----
+    // ---- all_pids back to a sorted id list in set[RTK_SET_ALL_PIDS] ----
     const uint32_t n_all = rtk_bm_count(all);
-    if (n_all > s.set_cap) { rtk_fail_ovf(s, 9); return 0; }
-    uint32_t* out = s.set[0];
+    if (n_all > s.set_cap) { rtk_fail_ovf(s, RTK_OVF_SET); return 0; }
+    uint32_t* out = s.set[RTK_SET_ALL_PIDS];
     { int tot2; uint32_t at = static_cast<uint32_t>(rtk_wave_excl_scan(rtk_popc(all), &tot2)); uint64_t x = all;
       while (x) { const int b = __builtin_ctzll(x); out[at++] = uni[64u * lane + static_cast<uint32_t>(b)]; x &= x - 1ull; } }
     rtk_sync();
@@ -414,7 +435,7 @@ RTK_FN uint32_t rtk_choose_colors_small(const RCtx& c_, const SideList& side_s_,
 }
 #endif
 
-// Returns |all_pids| (ids in s.set[0]), or RTK_NONE32 when the anchors' sets do not fit the small universe (caller falls back).
+// Returns |all_pids| (ids in s.set[RTK_SET_ALL_PIDS]), or RTK_NONE32 when the anchors' sets do not fit the small universe (caller falls back).
 RTK_FN uint32_t rtk_choose_colors_bits(const RCtx& c_, const SideList& side_s_, const SideList& side_e_, const SideList& side_w_) {
     const RCtx& c = *rtk_u(&c_); const SideList& side_s = *rtk_u(&side_s_); const SideList& side_e = *rtk_u(&side_e_); const SideList& side_w = *rtk_u(&side_w_); RTK_ASSUME_LDS(&side_s); RTK_ASSUME_LDS(&side_e); RTK_ASSUME_LDS(&side_w);
     RegionScratch& s = rtk_hdr(c);
@@ -431,7 +452,7 @@ RTK_FN uint32_t rtk_choose_colors_bits(const RCtx& c_, const SideList& side_s_, 
     }
     // candidate anchors: cardinality >= min_cov_vertices, ordered by (cardinality, unitig id) [D1]; the value carried through the sort is
     // the anchor's slot (its position in the concatenated side lists: middle, right, left)
-    uint64_t* keys = s.list[4]; uint64_t* vals = s.list[3]; uint64_t* slot_of = s.list[5];
+    uint64_t* keys = s.list[RTK_L_COL_KEYS]; uint64_t* vals = s.list[RTK_L_COL_VALS]; uint64_t* slot_of = s.list[RTK_L_COL_SLOT_OF];
     uint32_t nsp = 0;
     { uint32_t slot = 0;
       for (int sd = 0; sd < 3; ++sd) for (uint32_t i = 0; i < sides[sd]->n; ++i, ++slot) {
@@ -446,7 +467,7 @@ RTK_FN uint32_t rtk_choose_colors_bits(const RCtx& c_, const SideList& side_s_, 
     for (uint32_t j = static_cast<uint32_t>(rtk_lane()); j < nsp; j += RTK_WAVE) { slot_of[j] = vals[j]; const uint32_t cd = static_cast<uint32_t>(keys[j] >> 32); vals[j] = cd < cov ? cd : cov; } // remaining quota (p_spid.second)
     rtk_sync();
     // ---- universe: every id of every side unitig, sorted, duplicates dropped ----
-    uint32_t* gathered = s.set[1];
+    uint32_t* gathered = s.set[RTK_SET_CB_IDS];
     { uint32_t at = 0;
       for (int sd = 0; sd < 3; ++sd) for (uint32_t i = 0; i < sides[sd]->n; ++i) {
         const uint32_t u = sides[sd]->u[i]; const int32_t gi = g.gid[u];
@@ -460,7 +481,7 @@ RTK_FN uint32_t rtk_choose_colors_bits(const RCtx& c_, const SideList& side_s_, 
     s.cnt[RTK_RC_COLOUR] += T;
     uint32_t U = 0;
 #ifdef RTK_SIM
-    uint32_t* const uni = s.set[1] + RTK_CB_MAX_IDS; uint64_t* const scatter = nullptr;
+    uint32_t* const uni = s.set[RTK_SET_CB_IDS] + RTK_CB_MAX_IDS; uint64_t* const scatter = nullptr;
     { for (uint32_t i = 0; i < T; ++i) uni[i] = gathered[i];
       std::sort(uni, uni + T);
       for (uint32_t i = 0; i < T; ++i) if (i == 0 || uni[i] != uni[i - 1]) uni[U++] = uni[i]; }
@@ -484,7 +505,7 @@ RTK_FN uint32_t rtk_choose_colors_bits(const RCtx& c_, const SideList& side_s_, 
       } }
 #endif
     // ---- bit vectors of every side unitig: global part, local part (kept in scratch: 2 x 512 B per slot) ----
-    uint64_t* const store = reinterpret_cast<uint64_t*>(s.set[2].get());
+    uint64_t* const store = reinterpret_cast<uint64_t*>(s.set[RTK_SET_CB_STORE].get());
     { uint32_t slot = 0;
       for (int sd = 0; sd < 3; ++sd) for (uint32_t i = 0; i < sides[sd]->n; ++i, ++slot) {
         const uint32_t u = sides[sd]->u[i]; const int32_t gi = g.gid[u];
@@ -550,10 +571,10 @@ RTK_FN uint32_t rtk_choose_colors_bits(const RCtx& c_, const SideList& side_s_, 
         }
         rtk_sync();
     }
-    // ---- all_pids back to a sorted id list in set[0] ----
+    // ---- all_pids back to a sorted id list in set[RTK_SET_ALL_PIDS] ----
     const uint32_t n_all = rtk_bm_count(all);
-    if (n_all > s.set_cap) { rtk_fail_ovf(s, 9); return 0; }
-    uint32_t* out = s.set[0];
+    if (n_all > s.set_cap) { rtk_fail_ovf(s, RTK_OVF_SET); return 0; }
+    uint32_t* out = s.set[RTK_SET_ALL_PIDS];
 #ifdef RTK_SIM
     { uint32_t at = 0; for (uint32_t w = 0; w < 64; ++w) { uint64_t x = all.w[w]; while (x) { const int b = __builtin_ctzll(x); out[at++] = uni[64u * w + static_cast<uint32_t>(b)]; x &= x - 1ull; } } }
 #else
@@ -562,6 +583,197 @@ RTK_FN uint32_t rtk_choose_colors_bits(const RCtx& c_, const SideList& side_s_, 
 #endif
     rtk_sync();
     return n_all;
+}
+
+// ------------------------------------------------------------------------------------------------ dispatcher and general program
+// Computes all_pids into set[RTK_SET_ALL_PIDS]; returns its size. Every other member of `set` is its temporary (RtkSet).
+RTK_FN uint32_t rtk_choose_colors_general(const RCtx& c_, const SideList& side_s_, const SideList& side_e_, const SideList& side_w_);
+// chooseColors: the two register / bit-vector programs of rtk_colours.h first (nearly every region), the general program below otherwise.
+// Compiled into its caller: the dispatcher itself as a function would save 17 register rows on every region for a path it almost never takes.
+// Every call that ends without an overflow is counted by the program that answered it (RTK_RC_COLOURS_*; the small program counts its own two sizes, and the
+// calls it hands on because universe and bit vectors do not fit its LDS buffer: RTK_RC_COLOURS_DECLINED_FIT).
+// OptsView::colours_mode (tests): RTK_CM_ROUTE_BITS skips the small program, RTK_CM_ROUTE_GENERAL both bit-vector programs. RTK_CM_AUDIT: where a bit-vector
+// program answered, its list is kept in the region-level arena (free here: the path search resets it after this call; the general program writes every other member of `set`,
+// arena level RTK_ARENA_COL_SETS, list[RTK_L_COL_VALS], list[RTK_L_COL_KEYS] and the LDS buffer), the general program selects again into set[RTK_SET_ALL_PIDS], and a difference in the number of ids or in any id is
+// counted. The region goes on with the general program's list. RTK_CM_FAULT (test hook): the kept list loses its largest id first.
+RTK_DEV uint32_t rtk_choose_colors(const RCtx& c, const SideList& side_s, const SideList& side_e, const SideList& side_w) {
+    RegionScratch& s = rtk_hdr(c);
+    const unsigned long long tf = rtk_clock();
+    const uint32_t cm = rtk_u(c.o.colours_mode);
+    uint32_t r = RTK_NONE32;
+#ifndef RTK_SIM
+    if ((cm & RTK_CM_ROUTE) == 0u) {
+        r = rtk_u(rtk_choose_colors_small(c, side_s, side_e, side_w));
+        if (r != RTK_NONE32) { const unsigned long long d_ = rtk_clock() - tf; s.fine[RTK_FINE_COL_UNIONS] += d_; s.fine[RTK_FINE_COL_S_CYCLES] += d_; s.fine[RTK_FINE_COL_S_CALLS] += 1; }
+    }
+#endif
+    if (r == RTK_NONE32 && (cm & RTK_CM_ROUTE) != RTK_CM_ROUTE_GENERAL) {
+        r = rtk_u(rtk_choose_colors_bits(c, side_s, side_e, side_w));
+        if (r != RTK_NONE32) { const unsigned long long d_ = rtk_clock() - tf; s.fine[RTK_FINE_COL_UNIONS] += d_; s.fine[RTK_FINE_COL_B_CYCLES] += d_; s.fine[RTK_FINE_COL_B_CALLS] += 1; if (!rtk_failed(s)) s.cnt[RTK_RC_COLOURS_BITS] += 1; }
+    }
+    uint32_t n_first = RTK_NONE32; // audit: ids of the first answer that were kept
+    if (r != RTK_NONE32) {
+        if (rtk_failed(s)) return 0;
+        if ((cm & RTK_CM_AUDIT) == 0u || 4ull * r > s.arena_cap) return r; // (no room to keep the list: not compared)
+        n_first = r - (((cm & RTK_CM_FAULT) != 0u && r != 0u) ? 1u : 0u);
+        rtk_wcopy(s.arena[RTK_ARENA_COL_AUDIT].get(), s.set[RTK_SET_ALL_PIDS].get(), 4ull * n_first);
+    }
+    const uint32_t rg = rtk_u(rtk_choose_colors_general(c, side_s, side_e, side_w));
+    if (rtk_failed(s)) return 0; // (the region is redone: nothing to compare)
+    if (n_first == RTK_NONE32) { s.cnt[RTK_RC_COLOURS_GENERAL] += 1; return rg; }
+    const uint32_t* const first = reinterpret_cast<const uint32_t*>(s.arena[RTK_ARENA_COL_AUDIT].get()); const uint32_t* const second = s.set[RTK_SET_ALL_PIDS].get();
+    bool differs = rg != n_first;
+    for (uint32_t i0 = 0; i0 < rg && !differs; i0 += RTK_WAVE) { const uint32_t i = i0 + static_cast<uint32_t>(rtk_lane()); differs = rtk_ballot(i < rg && first[i] != second[i]) != 0ull; }
+    if (differs) s.cnt[RTK_RC_COLOURS_AUDIT_MISMATCH] += 1;
+    return rg;
+}
+RTK_FN uint32_t rtk_choose_colors_general(const RCtx& c_, const SideList& side_s_, const SideList& side_e_, const SideList& side_w_) {
+    const RCtx& c = *rtk_u(&c_); const SideList& side_s = *rtk_u(&side_s_); const SideList& side_e = *rtk_u(&side_e_); const SideList& side_w = *rtk_u(&side_w_); RTK_ASSUME_LDS(&side_s); RTK_ASSUME_LDS(&side_e); RTK_ASSUME_LDS(&side_w);
+    RegionScratch& s = rtk_hdr(c);
+    const GraphView& g = c.g;
+    unsigned long long tf = rtk_clock();
+    // a_pid[shift], shift = side index (0 middle, 1 right, 2 left) + 3 * nonbranching: built one after the other into the arena (level RTK_ARENA_COL_SETS, the DFS level, is free here)
+    s.top[RTK_ARENA_COL_SETS] = 0;
+    tf = rtk_clock();
+#define RTK_FINE_LAP(i) { const unsigned long long tn_ = rtk_clock(); s.fine[i] += tn_ - tf; tf = tn_; }
+    const SideList* sides[3] = {&side_w, &side_e, &side_s};
+    const uint32_t* a_ptr[6]; uint32_t a_n[6];
+    for (int sh = 0; sh < 6 && !rtk_failed(s); ++sh) {
+        const SideList& sl = *sides[sh % 3]; const uint8_t want_nb = sh >= 3 ? 1 : 0;
+        int cur = RTK_SET_UNION_A; uint32_t n = 0, n_src = 0; const uint32_t* one = nullptr;
+        for (uint32_t i = 0; i < sl.n && !rtk_failed(s); ++i) {
+            if (sl.nb[i] != want_nb) continue;
+            const uint32_t u = sl.u[i];
+            const int32_t gi = g.gid[u]; // G2: only the global set when there is one
+            const uint32_t* src = gi >= 0 ? g.col + g.goff[gi] : g.col + g.loff[u];
+            const uint32_t ns = gi >= 0 ? static_cast<uint32_t>(g.goff[gi + 1] - g.goff[gi]) : static_cast<uint32_t>(g.loff[u + 1] - g.loff[u]);
+            s.cnt[RTK_RC_COLOUR] += ns;
+            if (ns == 0) continue;
+            // a class fed by ONE anchor set (the usual case: a region is flanked by a unitig or two) is that set: used where it lies in
+            // the graph's colour pool, neither merged nor copied
+            if (n_src == 0) { one = src; n = ns; n_src = 1; continue; }
+            if (n_src == 1) { if (n > s.set_cap) { rtk_fail_ovf(s, RTK_OVF_SET); break; } rtk_wcopy(s.set[cur], one, 4ull * n); rtk_sync(); }
+            n = rtk_rs_union(s, cur, n, src, ns, cur ^ 3); cur ^= 3; ++n_src; // ping-pong between set[RTK_SET_UNION_A] and set[RTK_SET_UNION_B]
+#ifdef RTK_SIM
+            rtk_sim_site_stat[29][4] += 1;
+#endif
+        }
+        a_n[sh] = n;
+        if (n_src <= 1) a_ptr[sh] = n_src ? one : reinterpret_cast<const uint32_t*>(s.arena[RTK_ARENA_COL_SETS].get());
+        else {
+            const uint64_t off = rtk_arena_alloc(s, RTK_ARENA_COL_SETS, 4ull * n + 4);
+            if (!rtk_failed(s)) rtk_wcopy(s.arena[RTK_ARENA_COL_SETS] + off, s.set[cur], 4ull * n);
+            a_ptr[sh] = reinterpret_cast<const uint32_t*>(s.arena[RTK_ARENA_COL_SETS] + off);
+        }
+    }
+    if (rtk_failed(s)) return 0;
+#ifdef RTK_SIM
+    { std::atomic<unsigned long long>* t = rtk_sim_site_stat[29]; t[0] += 1; t[1] += side_s.n; t[2] += side_e.n; t[3] += side_w.n; for (int i = 0; i < 6; ++i) rtk_sim_site_stat[30][i] += a_n[i];
+      unsigned long long tot = 0; for (int i = 0; i < 6; ++i) tot += a_n[i]; int b = 0; while (b < 7 && (256ull << b) <= tot) ++b; rtk_sim_site_stat[31][b] += 1; }
+#endif
+    RTK_FINE_LAP(RTK_FINE_COL_GENERAL + 0)
+    auto A = [&](int i) -> const uint32_t* { return a_ptr[i]; };
+    // candidate anchors: cardinality >= min_cov_vertices, ordered by (cardinality, unitig id) [D1]
+    uint64_t* keys = s.list[RTK_L_COL_KEYS]; uint64_t* vals = s.list[RTK_L_COL_VALS];
+    uint32_t nsp = 0;
+    for (int sd = 0; sd < 3; ++sd) for (uint32_t i = 0; i < sides[sd]->n; ++i) {
+        const uint32_t u = sides[sd]->u[i];
+        if (g.card[u] < c.o.min_cov_vertices) continue;
+        bool dup = false; for (uint32_t j0 = 0; j0 < nsp && !dup; j0 += RTK_WAVE) { const uint32_t j = j0 + static_cast<uint32_t>(rtk_lane()); dup = rtk_ballot(j < nsp && rtk_d1_unitig(keys[j], c.o.d1_desc) == u) != 0ull; }
+        if (dup) continue;
+        if (2 * (nsp + 1) > s.list_cap) { rtk_fail_ovf(s, RTK_OVF_LIST); return 0; }
+        keys[nsp] = rtk_d1_key(g.card[u], u, c.o.d1_desc); vals[nsp] = 0; ++nsp; rtk_sync();
+    }
+    rtk_sort_pairs(keys, vals, nsp);
+    RTK_FINE_LAP(RTK_FINE_COL_GENERAL + 1)
+    const uint32_t cov = 30;
+    for (uint32_t j = 0; j < nsp; ++j) { const uint32_t cd = static_cast<uint32_t>(keys[j] >> 32); vals[j] = cd < cov ? cd : cov; } // remaining quota (p_spid.second)
+    // Set expressions of src/Correction.cpp:233-275,300-352 on immutable operands: a result is either one of its operands (union with
+    // / difference by the empty set -- the usual case: most regions have no weak anchor, so the whole "middle" side is empty) or a
+    // fresh slice of the DFS-level arena; nothing is copied to be kept, and a class only computes what it reads.
+    struct SetRef { const uint32_t* p; uint32_t n; };
+    const SetRef EMPTY = { reinterpret_cast<const uint32_t*>(s.arena[RTK_ARENA_COL_SETS].get()), 0u };
+    auto alloc = [&](uint32_t n) -> uint32_t* { const uint64_t off = rtk_arena_alloc(s, RTK_ARENA_COL_SETS, 4ull * n + 4); return rtk_failed(s) ? nullptr : reinterpret_cast<uint32_t*>(s.arena[RTK_ARENA_COL_SETS] + off); };
+    auto Un = [&](SetRef a, SetRef b) -> SetRef {
+        if (!a.n) return b; if (!b.n) return a;
+        if (a.n + b.n > s.set_cap) { rtk_fail_ovf(s, RTK_OVF_SET); return EMPTY; } // set[RTK_SET_UNION_TMP] holds b \ a
+        uint32_t* o = alloc(a.n + b.n); if (!o) return EMPTY;
+        SetRef r; r.p = o; r.n = rtk_set_union(a.p, a.n, b.p, b.n, o, s.set[RTK_SET_UNION_TMP]); return r; };
+    auto In = [&](SetRef a, SetRef b) -> SetRef {
+        if (!a.n || !b.n) return EMPTY;
+        if (a.n > b.n) { const SetRef t = a; a = b; b = t; } // walk the smaller set, search the larger one
+        uint32_t* o = alloc(a.n); if (!o) return EMPTY;
+        SetRef r; r.p = o; r.n = rtk_set_inter(a.p, a.n, b.p, b.n, o); return r; };
+    auto Di = [&](SetRef a, SetRef b) -> SetRef {
+        if (!a.n) return EMPTY; if (!b.n) return a;
+        uint32_t* o = alloc(a.n); if (!o) return EMPTY;
+        SetRef r; r.p = o; r.n = rtk_set_diff(a.p, a.n, b.p, b.n, o); return r; };
+    SetRef a[6]; for (int i = 0; i < 6; ++i) { a[i].p = a_ptr[i]; a[i].n = a_n[i]; }
+    const SetRef pos0 = Un(a[0], a[3]), pos1 = Un(a[1], a[4]), pos2 = Un(a[2], a[5]);
+    const SetRef a01 = In(pos0, pos1), a12 = In(pos1, pos2), a02 = In(pos0, pos2);
+    const SetRef nobranch_all = Un(Un(a[3], a[4]), a[5]);
+    if (rtk_failed(s)) return 0;
+    RTK_FINE_LAP(RTK_FINE_COL_GENERAL + 2)
+    uint32_t n_all = 0; int allb = RTK_SET_ALL_PIDS; // all_pids lives in set[RTK_SET_ALL_PIDS] (while it is being built: in set[allb])
+    uint32_t nb_unselected = nsp;
+    SetRef nobranch = nobranch_all, branching = EMPTY, i3 = EMPTY, i2 = EMPTY, prev2 = EMPTY; // prev2: a_pid2 of the previous class
+    bool have_i3 = false, have_i2 = false;
+    for (int i = 5; i >= 0 && !rtk_failed(s); --i) {
+        if (nb_unselected == 0) break;
+        if ((i == 5 || i == 2) && !have_i3) { i3 = In(a01, a12); have_i3 = true; }
+        if ((i == 4 || i == 1) && !have_i2) { i2 = Un(Un(a01, a12), a02); have_i2 = true; }
+        SetRef a2 = EMPTY; // a_pid2[i]
+        if (i == 5) a2 = In(nobranch, i3);
+        else if (i == 4) { nobranch = Di(nobranch, prev2); a2 = In(nobranch, i2); }
+        else if (i == 3) { nobranch = Di(nobranch, prev2); a2 = nobranch; }
+        else if (i == 2) { branching = Di(Un(Un(a[0], a[1]), a[2]), nobranch_all); a2 = In(branching, i3); }
+        else if (i == 1) { branching = Di(branching, prev2); a2 = In(branching, i2); }
+        else { branching = Di(branching, prev2); a2 = branching; }
+        const uint32_t n2 = a2.n;
+        if (rtk_failed(s)) break;
+        prev2 = a2; // a_pid2[i] is needed by the next class
+        RTK_FINE_LAP(RTK_FINE_COL_GENERAL + 3)
+        if (n2 != 0) {
+            nb_unselected = 0;
+            const uint32_t* cur_p = a2.p; uint32_t ncur = n2; int curb = RTK_SET_CUR_B; // curr_pid: a_pid2[i] itself until the first selection, then set[RTK_SET_CUR_A] / set[RTK_SET_CUR_B] (ping-pong)
+            for (uint32_t j = 0; j < nsp && !rtk_failed(s); ++j) {
+                const uint32_t u = rtk_d1_unitig(keys[j], c.o.d1_desc);
+                int quota = static_cast<int>(vals[j]);
+                bool touch = false;
+                if (quota > 0) { touch = (i == 0 || rtk_shared_with_set(g, u, cur_p, ncur, 1) >= 1); RTK_FINE_LAP(RTK_FINE_COL_GENERAL + 4) }
+#ifdef RTK_SIM
+                rtk_sim_site_stat[29][5] += 1; if (touch) rtk_sim_site_stat[29][6] += 1;
+#endif
+                if (touch) {
+                    const uint32_t min_cov = g.card[u] < cov ? g.card[u] : cov;
+                    const uint32_t sh = rtk_shared_with_set(g, u, s.set[allb], n_all, min_cov);
+                    RTK_FINE_LAP(RTK_FINE_COL_GENERAL + 5)
+                    quota = static_cast<int>(min_cov - (sh < min_cov ? sh : min_cov));
+                    if (quota > 0) {
+                        const uint32_t all_card = n_all;
+                        // pid = (global & curr) | (local & curr), truncated to its `quota` lowest ids
+                        const uint32_t npid = rtk_first_shared(g, u, cur_p, ncur, static_cast<uint32_t>(quota), s.set[RTK_SET_PICKED]);
+                        if (n_all + npid > s.set_cap) { rtk_fail_ovf(s, RTK_OVF_SET); break; }
+                        const uint32_t nn = rtk_set_union(s.set[allb], n_all, s.set[RTK_SET_PICKED], npid, s.set[allb ^ 3], s.set[RTK_SET_UNION_TMP]);
+                        allb ^= 3; n_all = nn; // all_pids alternates between set[RTK_SET_ALL_PIDS] and set[RTK_SET_ALL_PIDS_ALT]; it is moved to the former once, at the end
+                        const int nb2 = curb == RTK_SET_CUR_B ? RTK_SET_CUR_A : RTK_SET_CUR_B;
+                        if (ncur > s.set_cap) { rtk_fail_ovf(s, RTK_OVF_SET); break; }
+                        ncur = rtk_set_diff(cur_p, ncur, s.set[RTK_SET_PICKED], npid, s.set[nb2]); curb = nb2; cur_p = s.set[nb2];
+#ifdef RTK_SIM
+                        rtk_sim_site_stat[29][7] += 1; rtk_sim_site_stat[30][6] += ncur; rtk_sim_site_stat[30][7] += n_all;
+#endif
+                        const int gained = static_cast<int>(n_all - all_card);
+                        quota -= gained < quota ? gained : quota;
+                        RTK_FINE_LAP(RTK_FINE_COL_GENERAL + 6)
+                    }
+                }
+                vals[j] = static_cast<uint64_t>(quota);
+                nb_unselected += quota > 0 ? 1u : 0u;
+            }
+        }
+    }
+    if (allb != RTK_SET_ALL_PIDS && !rtk_failed(s)) rtk_wcopy(s.set[RTK_SET_ALL_PIDS], s.set[RTK_SET_ALL_PIDS_ALT], 4ull * n_all);
+    return rtk_failed(s) ? 0 : n_all;
 }
 
 #endif

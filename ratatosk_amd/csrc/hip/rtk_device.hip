@@ -939,7 +939,7 @@ extern "C" int rtk_sets_batch(uint32_t n, const uint32_t* op, const uint32_t* co
     } catch (const std::exception& e) { return rtk_fail(RTK_ERR_DEVICE, e.what()); }
 }
 
-#ifdef RTK_SIM // the census of repeated alignments (rtk_region.h, rtk_pair_note; profiles/scripts/sim_pairs.py)
+#ifdef RTK_SIM // the census of repeated alignments (rtk_sim_census.h, rtk_pair_note; profiles/scripts/sim_pairs.py)
 thread_local std::vector<RtkSimPair> rtk_sim_pair_log;
 std::atomic<int> rtk_sim_pairs_on(0);
 std::atomic<unsigned long long> rtk_sim_pair_stat[32][10];

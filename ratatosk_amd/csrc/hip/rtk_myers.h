@@ -73,14 +73,6 @@ RTK_DEV bool rtk_need_none(const uint64_t* bm, int lo, int hi) {
 // An entry is 32 bytes: the low 32-bit halves of {Pv, Mv, Ph, Mh}, then their high halves, so that each of the two lanes that share a
 // 64-bit word in the 32-bit sweep writes its four words with ONE 16-byte store.
 struct RtkTbHalf { uint32_t pv, mv, ph, mh; };
-#if defined(RTK_EXPERIMENT_NO_TB) && !defined(RTK_SIM) // timing experiment only (results are wrong): the sweeps do not write the table at all
-#define RTK_TB_ST(p, hv) ((void)(p), (void)(hv))
-#elif defined(RTK_TB_NT) && !defined(RTK_SIM) // A/B build: the table is written once and read along one path: streaming stores, so that it does not push the waves' stacks out of the L2
-typedef uint32_t rtk_v4u __attribute__((ext_vector_type(4)));
-#define RTK_TB_ST(p, hv) __builtin_nontemporal_store(rtk_v4u{(hv).pv, (hv).mv, (hv).ph, (hv).mh}, reinterpret_cast<rtk_v4u*>(p))
-#else
-#define RTK_TB_ST(p, hv) (*(p) = (hv))
-#endif
 RTK_DEV void rtk_tb_put(uint64_t* e, uint64_t Pv, uint64_t Mv, uint64_t Ph, uint64_t Mh) {
     RtkTbHalf lo, hi;
     lo.pv = static_cast<uint32_t>(Pv); lo.mv = static_cast<uint32_t>(Mv); lo.ph = static_cast<uint32_t>(Ph); lo.mh = static_cast<uint32_t>(Mh);
@@ -445,12 +437,12 @@ __device__ __forceinline__ SweepStat rtk_myers_fast32(const char* __restrict__ q
         const int col = s - lane;                                                                                                            \
         if (MASKED) {                                                                                                                        \
             const bool active = has_word && col >= 0 && col < n;                                                                             \
-            if (STORE) { if (active) { RtkTbHalf hv; hv.pv = nPv; hv.mv = nMv; hv.ph = Ph; hv.mh = Mh; RTK_TB_ST(&tbh[2ull * static_cast<uint64_t>(col)], hv); } } \
+            if (STORE) { if (active) { RtkTbHalf hv; hv.pv = nPv; hv.mv = nMv; hv.ph = Ph; hv.mh = Mh; tbh[2ull * static_cast<uint64_t>(col)] = hv; } } \
             Pv = active ? nPv : Pv; Mv = active ? nMv : Mv;                                                                                  \
             hout_prev = active ? hout : hout_prev;                                                                                           \
             score += active ? hout : 0;                                                                                                      \
         } else {                                                                                                                             \
-            if (STORE) { if (has_word) { RtkTbHalf hv; hv.pv = nPv; hv.mv = nMv; hv.ph = Ph; hv.mh = Mh; RTK_TB_ST(&tbh[2ull * static_cast<uint64_t>(col)], hv); } } \
+            if (STORE) { if (has_word) { RtkTbHalf hv; hv.pv = nPv; hv.mv = nMv; hv.ph = Ph; hv.mh = Mh; tbh[2ull * static_cast<uint64_t>(col)] = hv; } } \
             Pv = nPv; Mv = nMv; hout_prev = hout; score += hout;                                                                             \
         }                                                                                                                                    \
         m1_prev = m1; m2_prev = m2;                                                                                                          \

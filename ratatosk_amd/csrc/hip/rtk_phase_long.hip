@@ -43,7 +43,7 @@ __global__ void __launch_bounds__(1024) k_phase_long(const LaunchCtx* L, GraphVi
     for (uint32_t ri = blockIdx.x; ri < n_list; ri += gridDim.x) {
         const uint32_t r = list[ri];
         if (only_flagged && bv.status[r] == 0) continue;
-        *sc->overflow = 0; sc->top[0] = 0;
+        *sc->overflow = 0; sc->top[RTK_ARENA_REGION] = 0;
         rtk_phase_read(c, pv, r);
         if (rtk_lane() == 0) bv.status[r] = *sc->overflow;
     }

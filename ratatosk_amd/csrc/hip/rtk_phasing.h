@@ -52,9 +52,9 @@ RTK_FN void rtk_phase_read(const RCtx& c_, const PhaseView& pv_, uint32_t r_) {
     const char* raw = pv.raw + rbase;
     const char q_min = rtk_get_qual(0.0, 0, static_cast<uint64_t>(c.o.max_qual)), q_max = rtk_get_qual(1.0, 0, static_cast<uint64_t>(c.o.max_qual));
     const uint32_t nwin = L >= k ? L - k + 1 : 0;
-    if (L + M + 64 > s.str_cap || (L + k + 63) / 64 + 2 > s.bm_words || (L + M + 63) / 64 + 2 > s.bm_words) { rtk_fail_ovf(s, 7); return; }
+    if (L + M + 64 > s.str_cap || (L + k + 63) / 64 + 2 > s.bm_words || (L + M + 63) / 64 + 2 > s.bm_words) { rtk_fail_ovf(s, RTK_OVF_STRING); return; }
     // ---- 1. the read mapped stretch by stretch (:889-917): findUnitig = an exact hit extended while the next windows continue on the unitig [A7]
-    uint64_t* run_pos = s.list[0]; uint64_t* run_ul = s.list[1]; // position; unitig << 32 | length in k-mers
+    uint64_t* run_pos = s.list[RTK_L_PHASE_RUN_POS]; uint64_t* run_ul = s.list[RTK_L_PHASE_RUN_UNITIG]; // position; unitig << 32 | length in k-mers
     uint32_t n_runs = 0, max_nb_pids = 0;
     auto continues = [&](uint32_t p) -> bool { // window p continues the stretch of window p - 1
         if (p == 0 || p >= nwin) return false;
@@ -81,7 +81,7 @@ RTK_FN void rtk_phase_read(const RCtx& c_, const PhaseView& pv_, uint32_t r_) {
             const uint32_t u = rtk_unpack_hit(rtk_ld(hits + ps)).unitig;
             const uint32_t card = rtk_ld(rtk_u(g.card) + u);
             if (!rtk_is_branching(g, u) && card <= 1000u) {
-                if (n_runs >= s.list_cap) { rtk_fail_ovf(s, 8); break; }
+                if (n_runs >= s.list_cap) { rtk_fail_ovf(s, RTK_OVF_LIST); break; }
                 run_pos[n_runs] = ps; run_ul[n_runs] = (static_cast<uint64_t>(u) << 32) | len; ++n_runs;
                 max_nb_pids = card > max_nb_pids ? card : max_nb_pids;
             }
@@ -90,7 +90,7 @@ RTK_FN void rtk_phase_read(const RCtx& c_, const PhaseView& pv_, uint32_t r_) {
     rtk_sync();
     if (rtk_failed(s)) return;
     // ---- 2. one TinyBloomFilter per stretch (:921-936) ----
-    uint64_t* rm = s.bm[0]; // pos2rm, one bit per position of the corrected read
+    uint64_t* rm = s.bm[RTK_BM_PHASE_RM]; // pos2rm, one bit per position of the corrected read
     bool any_rm = false;    // (wave-uniform) some stretch was not supported: only then does the walk of the alignment change anything
     const uint32_t rm_words = (L + k + 63) / 64 + 1;
     for (uint32_t w = static_cast<uint32_t>(rtk_lane()); w < rm_words; w += RTK_WAVE) rm[w] = 0;
@@ -99,9 +99,9 @@ RTK_FN void rtk_phase_read(const RCtx& c_, const PhaseView& pv_, uint32_t r_) {
         uint64_t bits = 64; while (bits < 14ull * max_nb_pids) bits <<= 1; // max(rndup(bits_per_elem * nb_elem), 64)
         const uint32_t words = static_cast<uint32_t>(bits / 64);
         const uint64_t mask = bits - 1, nb_h = pv.tbf_nb_h;
-        if (static_cast<uint64_t>(n_runs) * words * 8ull > s.arena_cap) { rtk_fail_ovf(s, 3); return; }
-        uint64_t* tbf = reinterpret_cast<uint64_t*>(s.arena[0].get());
-        uint64_t* nbits = s.list[2]; uint64_t* state = s.list[3]; // set bits of every filter; bit 0 valid, bit 1 invalid
+        if (static_cast<uint64_t>(n_runs) * words * 8ull > s.arena_cap) { rtk_fail_ovf(s, RTK_OVF_ARENA); return; }
+        uint64_t* tbf = reinterpret_cast<uint64_t*>(s.arena[RTK_ARENA_PHASE_FILTERS].get());
+        uint64_t* nbits = s.list[RTK_L_PHASE_NBITS]; uint64_t* state = s.list[RTK_L_PHASE_STATE]; // set bits of every filter; bit 0 valid, bit 1 invalid
         for (uint64_t x = static_cast<uint64_t>(rtk_lane()); x < static_cast<uint64_t>(n_runs) * words; x += RTK_WAVE) tbf[x] = 0;
         rtk_sync();
         for (uint32_t i = 0; i < n_runs; ++i) {
@@ -178,8 +178,8 @@ RTK_FN void rtk_phase_read(const RCtx& c_, const PhaseView& pv_, uint32_t r_) {
     s.my.need_bm = nullptr; rtk_sync();
     nm = rtk_u(nm);
     if (rtk_failed(s)) return;
-    char* out_s = s.rbuf[0]; char* out_q = s.rbuf[1];
-    uint64_t* newb = s.bm[1]; // one bit per OUTPUT position: the base came from the raw read and differs from the corrected one
+    char* out_s = s.rbuf[RTK_RB_PHASE_SEQ]; char* out_q = s.rbuf[RTK_RB_PHASE_QUAL];
+    uint64_t* newb = s.bm[RTK_BM_PHASE_NEW]; // one bit per OUTPUT position: the base came from the raw read and differs from the corrected one
     const uint32_t out_words_cap = (L + M + 63) / 64 + 1;
     for (uint32_t w = static_cast<uint32_t>(rtk_lane()); w < out_words_cap; w += RTK_WAVE) newb[w] = 0;
     rtk_sync();
@@ -212,7 +212,7 @@ RTK_FN void rtk_phase_read(const RCtx& c_, const PhaseView& pv_, uint32_t r_) {
     // ---- 5. bases that came back and sit on graph k-mers get the maximum quality again (:1071-1089) ----
     if (olen >= k) {
         const uint32_t ow = (olen + 63) / 64;
-        uint64_t* cov = s.bm[2]; // position is within k - 1 of a new base: the only characters of s_new that are not 'N'
+        uint64_t* cov = s.bm[RTK_BM_PHASE_COV]; // position is within k - 1 of a new base: the only characters of s_new that are not 'N'
         for (uint32_t w = static_cast<uint32_t>(rtk_lane()); w < ow + 1; w += RTK_WAVE) cov[w] = 0;
         rtk_sync();
         for (uint32_t p0 = 0; p0 < olen; p0 += RTK_WAVE) {

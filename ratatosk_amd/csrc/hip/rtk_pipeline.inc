@@ -2,6 +2,7 @@
 // (included by rtk_device.hip)
 #include "rtk_seeds.h"
 #include "rtk_region.h"
+#include "rtk_region_enum.h"
 #include "rtk_region_lane.h"
 #ifdef RTK_SIM
 thread_local RlEnv rl_env; thread_local uint32_t rl_lst[RL_S_N * RL_STRIDE]; thread_local uint64_t rl_peq_all[RL_NSYM * RL_MAXW * RL_STRIDE];
@@ -13,7 +14,7 @@ thread_local RlEnv rl_env; thread_local uint32_t rl_lst[RL_S_N * RL_STRIDE]; thr
 #endif
 
 // ------------------------------------------------------------------------------------------------ kernels
-// the views of the next launches of a batch, written once where every wave reads them (rtk_region.h: LaunchCtx)
+// the views of the next launches of a batch, written once where every wave reads them (rtk_region_types.h: LaunchCtx)
 RTK_GLOBAL void k_set_ctx(LaunchCtx* out, GraphView g, OptsView o, BatchView bv, RegionBatch rb) {
     if (RTK_BLOCK_ID == 0 && rtk_lane() == 0) { out->g = g; out->o = o; out->bv = bv; out->rb = rb; }
 }
@@ -406,7 +407,7 @@ RTK_GLOBAL void k_phase(const LaunchCtx* L, GraphView g, OptsView o, BatchView b
     for (uint32_t ri = static_cast<uint32_t>(RTK_BLOCK_ID); ri < n_list; ri += static_cast<uint32_t>(grid)) { // list: the reads of this kernel, longest first
         const uint32_t r = list[ri];
         if (only_flagged && bv.status[r] == 0) continue;
-        *sc->overflow = 0; sc->top[0] = 0;
+        *sc->overflow = 0; sc->top[RTK_ARENA_REGION] = 0;
         rtk_phase_read(c, pv, r);
         if (rtk_lane() == 0) bv.status[r] = *sc->overflow;
     }

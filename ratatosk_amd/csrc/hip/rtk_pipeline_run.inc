@@ -301,11 +301,11 @@ RTK_GLOBAL void k_regions(const LaunchCtx* L, GraphView g, OptsView o, BatchView
         RegionDesc* rd = rb.regions + ri;
         if (only_flagged && rd->status == 0) continue;
         if (trace_class >= 0) { // developer runs (RTK_TRACE_CLASS): only the regions of one size class, so that the cycle shares are that class's (output is not valid)
-            int hb = 7;
-            if (rd->kind == RTK_RG_GAP) { const uint32_t* sp = bv.s_pos + bv.roff[rd->read]; const uint32_t gl = sp[rd->i_solid + 1] - sp[rd->i_solid]; hb = gl < 40 ? 0 : gl < 64 ? 1 : gl < 128 ? 2 : gl < 256 ? 3 : gl < 512 ? 4 : gl < 1024 ? 5 : 6; }
+            int hb = RTK_GAP_CLASS_HEAD_TAIL;
+            if (rd->kind == RTK_RG_GAP) { const uint32_t* sp = bv.s_pos + bv.roff[rd->read]; const uint32_t gl = sp[rd->i_solid + 1] - sp[rd->i_solid]; hb = rtk_gap_class(gl); }
             if (hb != trace_class) continue;
         }
-        *sc->overflow = 0; sc->top[0] = 0; sc->top[1] = 0; sc->top[2] = 0; sc->memo_n = 0;
+        *sc->overflow = 0; sc->top[RTK_ARENA_REGION] = 0; sc->top[RTK_ARENA_BFS] = 0; sc->top[RTK_ARENA_DFS] = 0; sc->memo_n = 0;
         RTK_PAIR_REGION();
 #ifdef RTK_PROF
         { // in-situ latency probes (developer build): a chain of 4 dependent loads from random slots of the k-mer table (cold: HBM), one of 4 dependent
@@ -318,23 +318,23 @@ RTK_GLOBAL void k_regions(const LaunchCtx* L, GraphView g, OptsView o, BatchView
             uint64_t y = x & 7ull;
             for (int q = 0; q < 4; ++q) { y = (rtk_u(g.uoff[y & 63ull]) + y) & 63ull; }
             unsigned long long t2_ = rtk_clock();
-            volatile uint64_t* slab = reinterpret_cast<volatile uint64_t*>(sc->str[4].get());
+            volatile uint64_t* slab = reinterpret_cast<volatile uint64_t*>(sc->str[RTK_STR_PROBE].get());
             slab[rtk_lane()] = y + x; const uint64_t z = slab[(rtk_lane() + 1) & 63];
             unsigned long long t3_ = rtk_clock() + (z & 1ull);
-            sc->prof[40] += t1_ - t0_; sc->prof[41] += t2_ - t1_; sc->prof[42] += t3_ - t2_; sc->prof[43] += 1; sc->prof_t = rtk_clock();
+            sc->prof[RTK_LAP_PROBE_COLD] += t1_ - t0_; sc->prof[RTK_LAP_PROBE_WARM] += t2_ - t1_; sc->prof[RTK_LAP_PROBE_SLAB] += t3_ - t2_; sc->prof[RTK_LAP_PROBE_SAMPLES] += 1; sc->prof_t = rtk_clock();
         }
 #endif
         const unsigned long long t0 = rtk_clock();
-        const unsigned long long exp0 = RTK_HIST_GET(*sc, 31);
+        const unsigned long long exp0 = RTK_HIST_GET(*sc, RTK_H_DFS_RUNNING);
         rtk_region_program(c, rd);
         { const unsigned long long dt = rtk_clock() - t0; sc->cnt[RTK_RC_CYC_TOTAL] += dt;
 #if !defined(RTK_SIM)
           if (trace_class < -1) { ++n_mine; if (dt > dt_max) { dt_max = dt; idx_of_max = idx; } }
 #endif
-          int hb = 7; // head / tail
-          if (rd->kind == RTK_RG_GAP) { const uint32_t* sp = bv.s_pos + bv.roff[rd->read]; const uint32_t gl = sp[rd->i_solid + 1] - sp[rd->i_solid]; hb = gl < 40 ? 0 : gl < 64 ? 1 : gl < 128 ? 2 : gl < 256 ? 3 : gl < 512 ? 4 : gl < 1024 ? 5 : 6; }
+          int hb = RTK_GAP_CLASS_HEAD_TAIL;
+          if (rd->kind == RTK_RG_GAP) { const uint32_t* sp = bv.s_pos + bv.roff[rd->read]; const uint32_t gl = sp[rd->i_solid + 1] - sp[rd->i_solid]; hb = rtk_gap_class(gl); }
           else if (rd->kind != RTK_RG_HEAD && rd->kind != RTK_RG_TAIL) hb = -1;
-          if (hb >= 0) { RTK_HIST_ADD(*sc, hb, dt); RTK_HIST_ADD(*sc, 8 + hb, 1); RTK_HIST_ADD(*sc, 24 + hb, RTK_HIST_GET(*sc, 31) - exp0); } }
+          if (hb >= 0) { RTK_HIST_ADD(*sc, RTK_H_CYCLES + hb, dt); RTK_HIST_ADD(*sc, RTK_H_REGIONS + hb, 1); RTK_HIST_ADD(*sc, RTK_H_DFS + hb, RTK_HIST_GET(*sc, RTK_H_DFS_RUNNING) - exp0); } } // (hb == RTK_GAP_CLASS_HEAD_TAIL: the last slot is RTK_H_DFS_RUNNING itself, see RtkHist)
         rd->status = *sc->overflow;
         if (*sc->overflow && rtk_lane() == 0) {
             rtk_atomic_add(rb.n_overflow, 1ull);
@@ -363,9 +363,9 @@ RTK_GLOBAL void k_regions(const LaunchCtx* L, GraphView g, OptsView o, BatchView
         for (int i = RTK_RC_STRAND2_RUN; i < RTK_RC_PARK_WALKED; ++i) rtk_atomic_add(bv.counters + RTK_CNT_STRAND2 + (i - RTK_RC_STRAND2_RUN), sc->cnt[i]);
         for (int i = RTK_RC_PARK_WALKED; i < RTK_RC_COLOURS_SMALL; ++i) rtk_atomic_add(bv.counters + RTK_CNT_PARK + (i - RTK_RC_PARK_WALKED), sc->cnt[i]);
         for (int i = RTK_RC_COLOURS_SMALL; i < RTK_RC_N; ++i) rtk_atomic_add(bv.counters + RTK_CNT_COLOURS + (i - RTK_RC_COLOURS_SMALL), sc->cnt[i]);
-        for (int i = 0; i < 32; ++i) rtk_atomic_add(bv.counters + RTK_CNT_HIST + i, static_cast<unsigned long long>(RTK_HIST_GET(*sc, i)));
+        for (int i = 0; i < RTK_H_N; ++i) rtk_atomic_add(bv.counters + RTK_CNT_HIST + i, static_cast<unsigned long long>(RTK_HIST_GET(*sc, i)));
 #ifdef RTK_PROF
-        for (int i = 0; i < 48; ++i) rtk_atomic_add(bv.counters + RTK_CNT_PROF + i, static_cast<unsigned long long>(sc->prof[i]));
+        for (int i = 0; i < RTK_LAP_N; ++i) rtk_atomic_add(bv.counters + RTK_CNT_PROF + i, static_cast<unsigned long long>(sc->prof[i]));
 #endif
     }
 }
@@ -623,7 +623,8 @@ static int region_grid(const RegionGridIn& in) {
     return rgrid;
 }
 
-// which capacity the flagged regions ran out of (status codes of rtk_fail_ovf), and the wave figures of a traced launch
+// which capacity the flagged regions ran out of (status codes of rtk_fail_ovf, by number: RtkOvf in rtk_region_types.h -- 1, 2 alignment, 3 arena, 4 .. 6 working path,
+// 7 string, 8 list, 9 set, 10 bitmap, 11 SNP annotations / consensus stall, 12 segment pool, 14 fixRepeats), and the wave figures of a traced launch
 static void region_attempt_trace(RegionRun& R, int attempt, int rgrid, uint64_t stride) {
     const BatchView& bv = R.b->bv; const rtk_stream_t sm = R.sm;
     std::vector<RegionDesc> rds(R.n_regions); rtk_d2h_s(rds.data(), R.b->rb.regions, sizeof(RegionDesc) * R.n_regions, sm);
@@ -714,7 +715,7 @@ static void region_trace_report(const unsigned long long* cnt) {
     auto share = [&](int slot) { return double(cnt[slot]) / total; };
 #ifdef RTK_PROF
     {
-        static const char* const pn[RTK_CNT_PROF_END - RTK_CNT_PROF] = {
+        static const char* const pn[RTK_LAP_N] = { // by slot number: RtkLap
             "driver: dispatch + anchors", "driver: same-unitig shortcut", "region: prologue", "region: side lists", "region: chooseColors",
             "semiweak: glue", "paths: prologue", "explore: prefix", "dfs: pop + adj", "dfs: nkm + colour_ok", "dfs T: load/extend",
             "dfs T: to_string", "dfs T: NW sweep", "dfs T: commit", "dfs NT: load/extend", "dfs NT: commit/rest", "dfs post: nt scoring",
@@ -723,10 +724,10 @@ static void region_trace_report(const unsigned long long* cnt) {
             "driver: between fw/bw", "consensus: rc + card", "consensus: fw NW path", "consensus: bw path / checks", "consensus: merge",
             "consensus: final", "driver: emit prep", "dequeue", "emit", 0, 0, 0, 0, "probe: 4 dependent cold loads", "probe: 4 dependent warm loads",
             "probe: slab store + load", 0};
-        const unsigned long long* pr = cnt + RTK_CNT_PROF; const int n = RTK_CNT_PROF_END - RTK_CNT_PROF;
-        if (pr[43]) fprintf(stderr, "[rtk trace] in-situ probes: cold load %.0f cycles, warm load %.0f cycles, slab store + load %.0f cycles "
+        const unsigned long long* pr = cnt + RTK_CNT_PROF; const int n = RTK_LAP_N;
+        if (pr[RTK_LAP_PROBE_SAMPLES]) fprintf(stderr, "[rtk trace] in-situ probes: cold load %.0f cycles, warm load %.0f cycles, slab store + load %.0f cycles "
                                     "(per round trip, %llu samples)\n",
-                            double(pr[40]) / 4.0 / double(pr[43]), double(pr[41]) / 4.0 / double(pr[43]), double(pr[42]) / double(pr[43]), pr[43]);
+                            double(pr[RTK_LAP_PROBE_COLD]) / 4.0 / double(pr[RTK_LAP_PROBE_SAMPLES]), double(pr[RTK_LAP_PROBE_WARM]) / 4.0 / double(pr[RTK_LAP_PROBE_SAMPLES]), double(pr[RTK_LAP_PROBE_SLAB]) / double(pr[RTK_LAP_PROBE_SAMPLES]), pr[RTK_LAP_PROBE_SAMPLES]);
         unsigned long long tot = 0; for (int i = 0; i < n; ++i) tot += pr[i];
         fprintf(stderr, "[rtk trace] k_regions lap profile (%.3g cycles):", double(tot));
         for (int i = 0; i < n; ++i) if (pr[i] && pn[i]) fprintf(stderr, " [%d %s %.4f]", i, pn[i], double(pr[i]) / double(tot ? tot : 1));
@@ -734,13 +735,13 @@ static void region_trace_report(const unsigned long long* cnt) {
     }
 #endif
     {
-        static const char* const hn[8] = {"gap<40", "gap<64", "gap<128", "gap<256", "gap<512", "gap<1024", "gap>=1024", "head/tail"};
-        const unsigned long long* h = cnt + RTK_CNT_HIST; // RegionScratch::hist: [b] cycles, [8 + b] regions, [16 + b] second strand too, [24 + b] DFS calls
+        static const char* const hn[RTK_GAP_CLASSES] = {"gap<40", "gap<64", "gap<128", "gap<256", "gap<512", "gap<1024", "gap>=1024", "head/tail"};
+        const unsigned long long* h = cnt + RTK_CNT_HIST; // RegionScratch::hist (RtkHist)
         fprintf(stderr, "[rtk trace] k_regions by size class (share of region time, regions, avg kcycles, second-strand share, DFS calls per region):");
-        for (int i = 0; i < 8; ++i) {
-            const unsigned long long cyc = h[i], n = h[8 + i];
-            if (n) fprintf(stderr, " [%s %.3f n=%llu %.0fk bw=%.2f dfs=%.1f]", hn[i], double(cyc) / total, n, 1e-3 * double(cyc) / double(n), double(h[16 + i]) / double(n),
-                           double(h[24 + i]) / double(n));
+        for (int i = 0; i < RTK_GAP_CLASSES; ++i) {
+            const unsigned long long cyc = h[RTK_H_CYCLES + i], n = h[RTK_H_REGIONS + i];
+            if (n) fprintf(stderr, " [%s %.3f n=%llu %.0fk bw=%.2f dfs=%.1f]", hn[i], double(cyc) / total, n, 1e-3 * double(cyc) / double(n), double(h[RTK_H_STRAND2 + i]) / double(n),
+                           double(h[RTK_H_DFS + i]) / double(n));
         }
         fprintf(stderr, "\n");
     }

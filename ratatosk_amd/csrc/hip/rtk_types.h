@@ -216,7 +216,7 @@ static_assert(RTK_CNT_PARK_END <= RTK_CNT_COLOURS && RTK_CNT_COLOURS_END <= RTK_
 static_assert(rtk_cnt_apart(RTK_CNT_PHASE_TRACE, RTK_CNT_PHASE_TRACE_END, RTK_CNT_FINALIZE_SLOWEST_PHASES, RTK_CNT_FINALIZE_SLOWEST_PHASES_END), "counter map: the two guests of the size-class table overlap");
 static_assert(RTK_CNT_HIST <= RTK_CNT_PHASE_TRACE && RTK_CNT_FINALIZE_SLOWEST_PHASES_END <= RTK_CNT_HIST_END, "counter map: the guests of the size-class table left it (update the comment above)");
 
-// indices of RegionScratch::cnt (rtk_region.h): a wave's own accumulators, added to the block when its kernel ends
+// indices of RegionScratch::cnt (rtk_region_types.h): a wave's own accumulators, added to the block when its kernel ends
 enum RtkRegionCnt { RTK_RC_EXPAND = 0, RTK_RC_COLOUR = 1, RTK_RC_PATHBASE = 2, RTK_RC_ALIGN = 3, RTK_RC_CELLS = 4, // -> RTK_CNT_EXPAND .. RTK_CNT_CELLS
     RTK_RC_CYC_COLOUR = 5, RTK_RC_CYC_PATHS = 6, RTK_RC_CYC_CONSENSUS = 7, RTK_RC_CYC_TOTAL = 8, RTK_RC_CYC_MYERS = 9, RTK_RC_CYC_SETS = 10, // [5, 11) -> RTK_CNT_CYC + 0 .. 5
     RTK_RC_CYC_PATHREC = 11 /* -> RTK_CNT_CYC_SETS as well */, RTK_RC_CYC_TOSTRING = 12, RTK_RC_CYC_PATHQUAL = 13, RTK_RC_CYC_DFS = 14, RTK_RC_CYC_COLOUR_OK = 15,
@@ -232,7 +232,7 @@ enum RtkRegionCnt { RTK_RC_EXPAND = 0, RTK_RC_COLOUR = 1, RTK_RC_PATHBASE = 2, R
     // stored sweeps of the forward trims (rtk_trim_by_column, rtk_park_walk) -> RTK_CNT_PARK + 0 .. 1: those whose path was walked and parked for a consensus, and
     // those nobody walked (the region skipped its second strand, or the sweep could not be parked); the sum is RTK_RC_TRIM_STORED
     RTK_RC_PARK_WALKED = 27, RTK_RC_PARK_DEFERRED = 28,
-    // calls of rtk_choose_colors (rtk_region.h) by the program that answered -> RTK_CNT_COLOURS + 0 .. 5: rtk_choose_colors_small with at most RTK_CS_MAX_IDS ids
+    // calls of rtk_choose_colors (rtk_colours.h) by the program that answered -> RTK_CNT_COLOURS + 0 .. 5: rtk_choose_colors_small with at most RTK_CS_MAX_IDS ids
     // (repeats counted) / with more ("wide"), rtk_choose_colors_bits, rtk_choose_colors_general; -- RTK_COLOURS_AUDIT=1 -- calls whose first answer differed from the
     // general program's; and calls rtk_choose_colors_small handed on because universe and bit vectors did not fit its LDS buffer (they are answered, and counted, further on)
     RTK_RC_COLOURS_SMALL = 29, RTK_RC_COLOURS_WIDE = 30, RTK_RC_COLOURS_BITS = 31, RTK_RC_COLOURS_GENERAL = 32, RTK_RC_COLOURS_AUDIT_MISMATCH = 33, RTK_RC_COLOURS_DECLINED_FIT = 34, RTK_RC_N = 35 };

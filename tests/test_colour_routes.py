@@ -1,6 +1,6 @@
 """The routes of the colour selection (chooseColors, src/Correction.cpp:215-429): counted, forced and audited.
 
-rtk_choose_colors (csrc/hip/rtk_region.h) asks up to three programs for the sorted id list a region's graph walk may follow: the register program of
+rtk_choose_colors (csrc/hip/rtk_colours.h) asks up to three programs for the sorted id list a region's graph walk may follow: the register program of
 rtk_colours.h (device only; 8-word bit vectors up to 512 ids, "small", and 64-word vectors up to 1664 ids, "wide"), rtk_choose_colors_bits (bit vectors in
 scratch memory; its device branch sorts in LDS and scatters with atomicOr, its simulator branch calls std::sort) and the general program on sorted arrays, which
 is the definition. Corrected bytes equal to the oracle's do not show a list that is off by one id at a quota edge, and the default order leaves the device

@@ -1,7 +1,7 @@
 """Canonical rule [D1] as a switch. `chooseColors` (src/Correction.cpp:215-429) visits the anchors' colour sets in ascending order of cardinality, but
 the list it sorts comes out of an `unordered_map` keyed by POINTERS (src/Correction.cpp:286) and `std::sort` is not stable (:293): the order of sets of
 equal cardinality depends on heap addresses in the reference. This build orders such ties by unitig id; both directions are kept alive, in the oracle
-(oracle_correct.cpp, RTK_D1_ORDER) and on the device (rtk_colours.h / rtk_region.h, rtk_opts::d1_desc):
+(oracle_correct.cpp, RTK_D1_ORDER) and on the device (rtk_colours.h, rtk_opts::d1_desc):
   asc   ties by ascending unitig id   (RTK_D1_ORDER unset or =asc)
   desc  ties by descending unitig id  (RTK_D1_ORDER=desc)
 Device == oracle under each; the number of reads the rule decides is printed (profiles/r04_d1_count.json holds it for configs[1] and the diploid set)."""

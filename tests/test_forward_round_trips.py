@@ -1,4 +1,4 @@
-"""The forward strand of a gap region does not walk an alignment that nobody reads (csrc/hip/rtk_region.h, rtk_trim_by_column and rtk_park_walk).
+"""The forward strand of a gap region does not walk an alignment that nobody reads (csrc/hip/rtk_region_align.h, rtk_trim_by_column and rtk_park_walk).
 
 The forward trim of a gap region stores its NW sweep, which also holds the alignment the consensus would ask for. Since most gap regions skip their second strand
 and with it the consensus (§3.2 (f)), the trim keeps only what the rule of the skip reads -- that the alignment exists, its distance, its last move -- and the

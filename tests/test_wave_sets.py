@@ -1,6 +1,6 @@
 """The wave set primitives of the region stage, run on their own and compared with plain Python (stage entry rtk_sets_batch, api.sets_batch).
 
-The colour selection of the region program (csrc/hip/rtk_region.h, rtk_colours.h) is built on a handful of wave-cooperative primitives, each written once for
+The colour selection of the region program (csrc/hip/rtk_colours.h) is built on a handful of wave-cooperative primitives, each written once for
 the 1-lane simulator and once for the device: rtk_set_filter / rtk_set_union / rtk_set_inter_count and rtk_sort_pairs (rtk_sets.h), the two radix sorts, and the
 bit vectors rtk_bm_from_ids / rtk_bm_lowest / rtk_bm_count with their 8-lane forms (rtk_colours.h). The device versions switch between code paths by size: the
 searched set is staged in LDS when nb <= 2048 and na >= 16, the bitonic network runs in LDS up to 512 pairs and blocked above, the radix sorts make one pass per
