@@ -338,6 +338,20 @@ int rtk_index_colour_end_subsampled(void* job, const uint8_t* bin_of_unitig, con
 int rtk_index_subsample_events(int device, const uint64_t* events, uint64_t n_events, uint32_t n_unitigs, const uint8_t* bin_of_unitig, const uint8_t* forced_candidate,
                                const uint8_t* bin_is_sampled, uint32_t n_bins, uint32_t mcv, double rate, uint64_t seed, uint64_t* events_out, uint64_t* n_out,
                                uint64_t* n_ids_before, uint64_t* n_ids_after);
+/* Ids of read pairs on the same unitigs merged on the device (rtk_build_index --gpu --merge-duplicates; the reference: "Detecting and removing duplicated reads",
+ * src/Graph.cpp:1630-1705 and 2089-2134; the rule and its deviations: DESIGN.md section 4 [A13], csrc/tools/index/merge.hpp). With U(i) the unitigs of id i, g(u) the
+ * splitmix64 finalizer of u + 1, S(i) the sum of g over U(i) modulo 2^64 and low(i) = min U(i): ids with equal (S, low) are one class, its leader is its smallest id,
+ * the leaders in ascending order are numbered from 0 and every id takes its leader's number. Tables are sized by the ids that have events, never by the largest id.
+ * rtk_index_colour_merge: finishes the pending chunks and the last sort-and-unique of an open job, merges its events in place (they stay ascending and distinct) and sets
+ * the job's events and ids; the job stays alive, so rtk_index_colour_end, rtk_index_colour_cov and rtk_index_colour_end_subsampled go on from the merged events. Outputs:
+ * the events and the distinct ids before and after. rtk_index_colour_merge_classes: what that call found about the classes: how many hold more than one id, and the
+ * number of ids of the largest.
+ * rtk_index_merge_events: stage entry for tests -- the same device function on the caller's events (host arrays; ascending, distinct, unitigs < n_unitigs); events_out
+ * has room for n_events words. RTK_ERR_NO_DEVICE without a GPU, like every compute entry. */
+int rtk_index_colour_merge(void* job, uint64_t* n_events_before, uint64_t* n_events_after, uint64_t* n_ids_before, uint64_t* n_ids_after);
+int rtk_index_colour_merge_classes(void* job, uint64_t* classes_above_one, uint64_t* largest);
+int rtk_index_merge_events(int device, const uint64_t* events, uint64_t n_events, uint32_t n_unitigs, uint64_t* events_out, uint64_t* n_out, uint64_t* n_ids_before,
+                           uint64_t* n_ids_after);
 
 /* rtk_rescue_*: the rescue of unmapped short reads before the index build (`correct -u`; retrieveMissingReads, src/Graph.cpp:3857-4131, called at
  * src/Ratatosk.cpp:1040-1056), with exact sets where the reference has Bloom filters ([A11]). One-word k-mers (odd k <= 31).
@@ -401,8 +415,8 @@ const char* rtk_version(void);
  * 7: rtk_stats route fields n_trim_* / n_consensus_*, the test-only rtk_myers_batch modes 3 and 4, rtk_myers_column_last_routes;
  * 8: rtk_stats fields n_fa_linked_*; 9: rtk_rescue_begin / _chunk / _end; still 9: rtk_stats fields n_strand2_* and n_park_*, the test-only rtk_myers_batch mode 5, appended at the end -- a library of revision 9
  * without them leaves them as the caller set them;
- * 10: rtk_sets_batch, rtk_stats fields n_colours_*; still 10: rtk_index_colour_cov, rtk_index_colour_end_subsampled, rtk_index_subsample_events, appended -- a library
- * of revision 10 without them lacks the symbols, and callers look them up by name). */
+ * 10: rtk_sets_batch, rtk_stats fields n_colours_*; still 10: rtk_index_colour_cov, rtk_index_colour_end_subsampled, rtk_index_subsample_events, then rtk_index_colour_merge,
+ * rtk_index_colour_merge_classes, rtk_index_merge_events, appended -- a library of revision 10 without them lacks the symbols, and callers look them up by name). */
 #define RTK_API_REVISION 10
 int rtk_api_revision(void);
 

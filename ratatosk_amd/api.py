@@ -122,6 +122,10 @@ def load_library(path=None):
                                                       C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.rtk_index_subsample_events.argtypes = [C.c_int, C.POINTER(C.c_uint64), C.c_uint64, C.c_uint32, C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte), C.c_uint32, C.c_uint32,
                                                  C.c_double, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    if hasattr(L, "rtk_index_merge_events"):  # (still revision 10: appended; a library without them: index_merge_events says so)
+        L.rtk_index_colour_merge.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.rtk_index_colour_merge_classes.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.rtk_index_merge_events.argtypes = [C.c_int, C.POINTER(C.c_uint64), C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.rtk_free.argtypes = [C.c_void_p]
     _libs[path] = L
     return L
@@ -454,6 +458,25 @@ def index_subsample_events(events, n_unitigs, bin_of_unitig, forced_candidate, b
     u8, u64 = C.POINTER(C.c_ubyte), C.POINTER(C.c_uint64)
     rc = L.rtk_index_subsample_events(device, ev.ctypes.data_as(u64), ev.size, n_unitigs, bins.ctypes.data_as(u8), forced.ctypes.data_as(u8), sampled.ctypes.data_as(u8), sampled.size, mcv,
                                       float(rate), seed, out.ctypes.data_as(u64), C.byref(n_out), C.byref(before), C.byref(after))
+    if rc != 0:
+        raise RtkError("rtk error %d: %s" % (rc, L.rtk_last_error().decode()))
+    return out[:n_out.value].copy(), before.value, after.value
+
+
+def index_merge_events(events, n_unitigs, device=0, lib_path=None):
+    """The merging of the ids of read pairs that lie on the same unitigs, on the device (stage entry rtk_index_merge_events, include/ratatosk_hip.h: the device
+    function behind rtk_index_colour_merge; the rule: DESIGN.md section 4 [A13]). events: words unitig << 32 | id, ascending and distinct, unitigs < n_unitigs.
+    Returns (merged events with their new ids, ascending and distinct, as a numpy array of uint64; distinct ids before; after)."""
+    import numpy as np
+    L = load_library(lib_path)
+    missing = [s for s in ("rtk_index_colour_merge", "rtk_index_colour_merge_classes", "rtk_index_merge_events") if not hasattr(L, s)]
+    if missing:
+        raise RtkError("%s lacks %s (merged ids: appended at interface revision 10)" % (L._name, ", ".join(missing)))
+    ev = np.ascontiguousarray(events, dtype=np.uint64)
+    out = np.zeros(max(1, ev.size), dtype=np.uint64)
+    n_out, before, after = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    u64 = C.POINTER(C.c_uint64)
+    rc = L.rtk_index_merge_events(device, ev.ctypes.data_as(u64), ev.size, n_unitigs, out.ctypes.data_as(u64), C.byref(n_out), C.byref(before), C.byref(after))
     if rc != 0:
         raise RtkError("rtk error %d: %s" % (rc, L.rtk_last_error().decode()))
     return out[:n_out.value].copy(), before.value, after.value

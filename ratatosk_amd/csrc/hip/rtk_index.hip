@@ -6,7 +6,8 @@
 //                           element of every run of >= min_count equal keys is kept. HBM-bound: 1 byte read + 8 (16) bytes written per base, then the sort.
 //   rtk_index_unitigs       the chains of the compacted graph walked, numbered and spelt (k_ut_*)
 //   rtk_index_colour_*      every read k-mer mapped onto its unitig: colour events and coverage (k_col_map); with rtk_index_colour_end_subsampled the events
-//                           thinned out by coverage and their ids renumbered before they leave the device (k_sub_*)
+//                           thinned out by coverage and their ids renumbered before they leave the device (k_sub_*); with rtk_index_colour_merge the ids of read
+//                           pairs on the same unitigs merged in place before that (k_merge_*)
 // Every step serves one-word k-mers (k <= 31, key type uint64_t) and two-word k-mers (33 <= k <= 63, key type unsigned __int128: the 2k-bit code,
 // first base in the most significant bits; in memory the low word first). Own translation unit: rocPRIM's templates.
 #include <string.h>
@@ -341,11 +342,26 @@ __global__ void k_col_map(const char* __restrict__ chars, uint64_t n, int k, con
     }
 }
 
+// n words at `cur` sorted, the distinct ones kept: they end up at `cur` or at `other` (room for n words each; the place is returned), *n_out of them
+uint64_t* sort_unique_events(uint64_t* cur, uint64_t* other, uint64_t n, DevBuf& tmp, uint64_t* n_out) {
+    rocprim::double_buffer<uint64_t> db(cur, other);
+    size_t tb = 0; rtk_check(rocprim::radix_sort_keys(nullptr, tb, db, static_cast<size_t>(n), 0, 64), "rocprim::radix_sort_keys");
+    tmp.alloc(tb); rtk_check(rocprim::radix_sort_keys(tmp.p, tb, db, static_cast<size_t>(n), 0, 64), "rocprim::radix_sort_keys");
+    uint64_t* sorted = db.current(); uint64_t* out = db.alternate();
+    DevBuf d_n; d_n.alloc(8);
+    size_t ub = 0; rtk_check(rocprim::unique(nullptr, ub, sorted, out, static_cast<unsigned long long*>(d_n.p), static_cast<size_t>(n)), "rocprim::unique");
+    tmp.alloc(ub); rtk_check(rocprim::unique(tmp.p, ub, sorted, out, static_cast<unsigned long long*>(d_n.p), static_cast<size_t>(n)), "rocprim::unique");
+    rtk_check(hipDeviceSynchronize(), "events sorted");
+    unsigned long long nu = 0; rtk_check(hipMemcpy(&nu, d_n.p, 8, hipMemcpyDeviceToHost), "hipMemcpy");
+    *n_out = nu; return out;
+}
+
 struct ColourJob {
     int device = 0, k = 31; uint32_t n_unitigs = 0; GraphView g; // g: the k-mer table and the packed unitigs (the only fields k_col_map reads)
     DevBuf useq, uoff, ht, cov, events, alt, top, tmp;
     uint64_t slots = 0, cap = 0, n_events = 0; // n_events: sorted, distinct events at the front of `events`
-    uint64_t n_ids = 0;                        // largest id fed + 1: the size of the id tables of the subsampling
+    uint64_t n_ids = 0;                        // largest id fed + 1 (after rtk_index_colour_merge: the number of merged ids): the size of the id tables of the subsampling
+    uint64_t merge_classes_above_one = 0, merge_largest = 0; // what the last rtk_index_colour_merge found
     DevBuf d_chars[2], d_starts[2], d_ids[2]; PinBuf h_chars[2], h_starts[2], h_ids[2]; uint64_t chunk_cap = 0, reads_cap = 0;
     hipStream_t st[2] = {nullptr, nullptr}; int slot = 0;
     std::mutex m; uint64_t bases = 0, chunks = 0, compactions = 0; double t_table = 0.0;
@@ -358,16 +374,8 @@ struct ColourJob {
         if (n > cap) throw std::runtime_error("more (unitig, read) events than the device buffer holds between two compactions (RTK_INDEX_EVENTS: number of events to make room for)");
         if (n == n_events) return;
         ++compactions;
-        rocprim::double_buffer<uint64_t> db(static_cast<uint64_t*>(events.p), static_cast<uint64_t*>(alt.p));
-        size_t tb = 0; rtk_check(rocprim::radix_sort_keys(nullptr, tb, db, static_cast<size_t>(n), 0, 64), "rocprim::radix_sort_keys");
-        tmp.alloc(tb); rtk_check(rocprim::radix_sort_keys(tmp.p, tb, db, static_cast<size_t>(n), 0, 64), "rocprim::radix_sort_keys");
-        uint64_t* sorted = db.current(); uint64_t* other = db.alternate();
-        DevBuf d_n; d_n.alloc(8);
-        size_t ub = 0; rtk_check(rocprim::unique(nullptr, ub, sorted, other, static_cast<unsigned long long*>(d_n.p), static_cast<size_t>(n)), "rocprim::unique");
-        tmp.alloc(ub); rtk_check(rocprim::unique(tmp.p, ub, sorted, other, static_cast<unsigned long long*>(d_n.p), static_cast<size_t>(n)), "rocprim::unique");
-        rtk_check(hipDeviceSynchronize(), "events sorted");
-        unsigned long long nu = 0; rtk_check(hipMemcpy(&nu, d_n.p, 8, hipMemcpyDeviceToHost), "hipMemcpy");
-        if (other != static_cast<uint64_t*>(events.p)) rtk_check(hipMemcpy(events.p, other, 8 * nu, hipMemcpyDeviceToDevice), "hipMemcpy");
+        uint64_t nu = 0; const uint64_t* res = sort_unique_events(static_cast<uint64_t*>(events.p), static_cast<uint64_t*>(alt.p), n, tmp, &nu);
+        if (res != static_cast<uint64_t*>(events.p)) rtk_check(hipMemcpy(events.p, res, 8 * nu, hipMemcpyDeviceToDevice), "hipMemcpy");
         n_events = nu; rtk_check(hipMemcpy(top.p, &nu, 8, hipMemcpyHostToDevice), "hipMemcpy");
     }
 };
@@ -914,5 +922,203 @@ extern "C" int rtk_index_subsample_events(int device, const uint64_t* events, ui
         subsample_events_device(static_cast<const uint64_t*>(d_ev.p), n_events, static_cast<uint64_t*>(d_out.p), n_unitigs, n_ids, bin_of_unitig, forced_candidate, bin_is_sampled, n_bins, mcv, rate, seed, n_out, n_ids_before, n_ids_after);
         if (*n_out) rtk_check(hipMemcpy(events_out, d_out.p, 8 * *n_out, hipMemcpyDeviceToHost), "hipMemcpy");
     } catch (const std::exception& e) { return rtk_fail(RTK_ERR_DEVICE, std::string("rtk_index_subsample_events: ") + e.what()); }
+    return RTK_OK;
+}
+
+
+// ------------------------------------------------------------------------------------------------ ids of pairs on the same unitigs merged (k_merge_*)
+// The rule is that of the index tool's host step (csrc/tools/index/merge.hpp; the reference: "Detecting and removing duplicated reads", src/Graph.cpp:1630-1705 and
+// 2089-2134; DESIGN.md section 4 [A13]), and the two give the same words: ids whose unitig sets have the same sum S of g(u) = splitmix64 finalizer of u + 1 (modulo
+// 2^64) and the same smallest unitig `low` are one class and take the number of the class's smallest id, the leaders numbered from 0 in ascending order.
+// On the n sorted distinct events unitig << 32 | id, in the job's two event buffers and in tables of R entries, R = the ids that have events (never the largest id):
+//   re-key + sort       the events as id << 32 | unitig, sorted (rocPRIM): an id is one run with its unitigs ascending; the other buffer takes the number of every
+//                       event's run, counted from 1 (inclusive scan of the run heads), so R is its last word
+//   k_merge_signature   one lane per event: the lanes of a run inside a wave are a segment (ballot of the segment heads), summed by a segmented shuffle sum; one
+//                       64-bit add per run and wave into the high word of the run's key, the run's first event writes the low word low << 32 | id
+//   sort                the R keys S << 64 | low << 32 | id with the run numbers as values (rocPRIM, 128-bit keys): a class is a stretch, its smallest id first
+//   k_merge_leaders     one lane per sorted run: a class starts where (S, low) differs from the entry before; the leader comes from the head lane of the wave, and a
+//                       wave whose first entry is no head finds the start of that class by bisection over the entries before it. Writes the leader's run for
+//                       every run and the leader flags; the last entry of a class counts the classes above one id and the largest
+//   ranks               exclusive scan of the leader flags in run (= id) order (rocPRIM)
+//   k_merge_relabel     the id-major events rewritten in place to unitig << 32 | new id; the job's sort-and-unique brings them back to ascending and distinct
+// No scratch, no LDS. Bounds: events < n, runs < R, unitigs < n_unitigs; an event that breaks one is skipped and reported.
+namespace {
+struct MergeRekey { __device__ uint64_t operator()(uint64_t e) const { return (e << 32) | (e >> 32); } };
+struct MergeRunHead { const uint64_t* ev; __device__ uint64_t operator()(uint64_t i) const { return i == 0 || (ev[i] >> 32) != (ev[i - 1] >> 32) ? 1ull : 0ull; } };
+struct MergeLeaderFlag { const uint32_t* flag; uint64_t R; __device__ uint32_t operator()(uint64_t r) const { return r < R ? flag[r] : 0u; } };
+
+__global__ void k_merge_signature(const uint64_t* __restrict__ ev, const uint64_t* __restrict__ run_of, uint64_t n, uint64_t R, uint32_t n_unitigs, unsigned long long* __restrict__ keys, uint32_t* __restrict__ bad) {
+    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
+    const int lane = threadIdx.x & 63;
+    for (uint64_t i0 = static_cast<uint64_t>(blockIdx.x) * blockDim.x; i0 < n; i0 += stride) { // (whole waves take part in every round)
+        const uint64_t i = i0 + threadIdx.x;
+        uint64_t run = ~0ull, g = 0, e = 0; // (a lane past the end, or with a broken event: a segment of its own that adds nothing)
+        if (i < n) {
+            e = ev[i]; run = run_of[i] - 1;
+            if (run >= R || (e & 0xFFFFFFFFull) >= n_unitigs) { atomicOr(bad, 1u); run = ~0ull; }
+            else g = sub_hash((e & 0xFFFFFFFFull) + 1, 0);
+        }
+        const uint64_t before = __shfl_up(static_cast<unsigned long long>(run), 1, 64);
+        const bool head = lane == 0 || before != run;
+        const uint64_t heads = __ballot(head ? 1 : 0);
+        const uint64_t above = lane == 63 ? 0ull : (heads >> (lane + 1)) << (lane + 1); // the next segment head of the wave, if any
+        const int end = above ? __ffsll(static_cast<unsigned long long>(above)) - 1 : 64;
+        uint64_t sum = g; // after the laps: the sum over the lanes from this one to the end of its segment
+        for (int d = 1; d < 64; d <<= 1) { const uint64_t t = __shfl_down(static_cast<unsigned long long>(sum), d, 64); if (lane + d < end) sum += t; }
+        if (head && run != ~0ull) {
+            atomicAdd(keys + 2 * run + 1, static_cast<unsigned long long>(sum));
+            if (i == 0 || run_of[i - 1] != run_of[i]) keys[2 * run] = ((e & 0xFFFFFFFFull) << 32) | (e >> 32); // the run's first event: its smallest unitig, and the id
+        }
+    }
+}
+
+// (S, low) of entry a below that of entry b
+__device__ __forceinline__ bool merge_class_less(uint64_t a_hi, uint64_t a_lo, uint64_t b_hi, uint64_t b_lo) { return a_hi < b_hi || (a_hi == b_hi && (a_lo >> 32) < (b_lo >> 32)); }
+
+__global__ void k_merge_leaders(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ order, uint64_t R, uint32_t* __restrict__ leader_of, uint32_t* __restrict__ is_leader,
+                                unsigned long long* __restrict__ counts, uint32_t* __restrict__ bad) {
+    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
+    const int lane = threadIdx.x & 63;
+    for (uint64_t j0 = static_cast<uint64_t>(blockIdx.x) * blockDim.x; j0 < R; j0 += stride) { // (whole waves take part in every round)
+        const uint64_t w0 = j0 + (threadIdx.x & ~63u), j = w0 + static_cast<uint64_t>(lane); // w0: the wave's first entry
+        const bool there = j < R;
+        uint64_t hi = 0, lo = 0; uint32_t ord = 0; bool head = false, last = false;
+        if (there) {
+            lo = keys[2 * j]; hi = keys[2 * j + 1]; ord = order[j];
+            head = j == 0 || keys[2 * j - 1] != hi || (keys[2 * j - 2] >> 32) != (lo >> 32);
+            last = j + 1 == R || keys[2 * j + 3] != hi || (keys[2 * j + 2] >> 32) != (lo >> 32);
+        }
+        // the class of the wave's first entry starts before the wave: the first entry that is not below it, found by bisection by lane 0
+        uint64_t start0 = w0; uint32_t ord0 = 0;
+        if (lane == 0 && there && !head) {
+            uint64_t a = 0, b = w0;
+            while (a < b) { const uint64_t mid = a + (b - a) / 2; if (merge_class_less(keys[2 * mid + 1], keys[2 * mid], hi, lo)) a = mid + 1; else b = mid; }
+            start0 = a; ord0 = order[a];
+        }
+        start0 = __shfl(static_cast<unsigned long long>(start0), 0, 64); ord0 = __shfl(ord0, 0, 64);
+        const uint64_t heads = __ballot(head ? 1 : 0), below = heads & (lane == 63 ? ~0ull : ((2ull << lane) - 1ull)); // the heads at or below this lane
+        const int src = below ? 63 - __clzll(static_cast<unsigned long long>(below)) : 0;
+        const uint32_t ord_head = __shfl(ord, src, 64);
+        const uint64_t start = below ? w0 + static_cast<uint64_t>(src) : start0;
+        const uint32_t leader = below ? ord_head : ord0;
+        const bool ok = there && ord < R && leader < R;
+        if (there && !ok) atomicOr(bad, 2u);
+        if (ok) { leader_of[ord] = leader; is_leader[ord] = head ? 1u : 0u; }
+        // the last entry of a class knows its size: the wave's count of classes above one id and its largest, one atomic each
+        unsigned long long size = ok && last ? j - start + 1 : 0ull;
+        const uint64_t above_one = __ballot(size > 1 ? 1 : 0);
+        for (int d = 32; d >= 1; d >>= 1) { const unsigned long long o = __shfl_xor(size, d, 64); size = o > size ? o : size; }
+        if (lane == 0) { if (above_one) atomicAdd(counts, static_cast<unsigned long long>(__popcll(above_one))); if (size) atomicMax(counts + 1, size); }
+    }
+}
+
+__global__ void k_merge_relabel(uint64_t* __restrict__ ev, const uint64_t* __restrict__ run_of, uint64_t n, uint64_t R, const uint32_t* __restrict__ leader_of, const uint32_t* __restrict__ rank) {
+    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
+    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const uint64_t e = ev[i], run = run_of[i] - 1;
+        if (run >= R) continue; // (reported by k_merge_signature)
+        const uint32_t ld = leader_of[run];
+        ev[i] = (e << 32) | static_cast<uint64_t>(ld < R ? rank[ld] : 0u);
+    }
+}
+
+struct MergeResult { uint64_t n_out = 0, ids_before = 0, ids_after = 0, classes_above_one = 0, largest = 0; };
+// a: n sorted distinct events in device memory, b: room for n words there. The merged events, ascending and distinct, end up in a or in b: the place is returned. Throws.
+uint64_t* merge_events_device(uint64_t* a, uint64_t* b, uint64_t n, uint32_t n_unitigs, DevBuf& tmp, MergeResult* res) {
+    *res = MergeResult();
+    if (n == 0) return a;
+    auto grid = [](uint64_t items) { const uint64_t blocks = (items + 255) / 256; return dim3(static_cast<unsigned>(blocks < 1 ? 1 : (blocks > 65536 ? 65536 : blocks))); };
+    rtk_check(rocprim::transform(a, a, static_cast<size_t>(n), MergeRekey()), "rocprim::transform");
+    rocprim::double_buffer<uint64_t> db(a, b);
+    size_t tb = 0; rtk_check(rocprim::radix_sort_keys(nullptr, tb, db, static_cast<size_t>(n), 0, 64), "rocprim::radix_sort_keys");
+    tmp.alloc(tb); rtk_check(rocprim::radix_sort_keys(tmp.p, tb, db, static_cast<size_t>(n), 0, 64), "rocprim::radix_sort_keys");
+    uint64_t* ev = db.current(); uint64_t* run_of = db.alternate();
+    auto idx = rocprim::make_counting_iterator<uint64_t>(0);
+    MergeRunHead rh; rh.ev = ev;
+    auto run_heads = rocprim::make_transform_iterator(idx, rh);
+    size_t sb = 0; rtk_check(rocprim::inclusive_scan(nullptr, sb, run_heads, run_of, static_cast<size_t>(n), rocprim::plus<uint64_t>()), "rocprim::inclusive_scan");
+    tmp.alloc(sb); rtk_check(rocprim::inclusive_scan(tmp.p, sb, run_heads, run_of, static_cast<size_t>(n), rocprim::plus<uint64_t>()), "rocprim::inclusive_scan");
+    rtk_check(hipDeviceSynchronize(), "runs of the ids");
+    uint64_t R = 0; rtk_check(hipMemcpy(&R, run_of + (n - 1), 8, hipMemcpyDeviceToHost), "hipMemcpy");
+    if (R == 0 || R > n || R > (1ull << 32)) throw std::runtime_error("the runs of the ids do not add up");
+    DevBuf d_keys, d_keys2, d_order, d_leader, d_flag, d_rank, d_cnt;
+    d_keys.alloc(16 * R); d_keys2.alloc(16 * R); d_order.alloc(4 * R); d_leader.alloc(4 * R); d_flag.alloc(4 * R); d_rank.alloc(4 * (R + 1)); d_cnt.alloc(24);
+    rtk_check(hipMemset(d_keys.p, 0, 16 * R), "hipMemset"); rtk_check(hipMemset(d_cnt.p, 0, 24), "hipMemset");
+    unsigned long long* cnt = static_cast<unsigned long long*>(d_cnt.p); uint32_t* bad = reinterpret_cast<uint32_t*>(cnt + 2); // cnt: classes above one id, the largest class, flags of broken bounds
+    hipLaunchKernelGGL(k_merge_signature, grid(n), dim3(256), 0, 0, static_cast<const uint64_t*>(ev), static_cast<const uint64_t*>(run_of), n, R, n_unitigs, static_cast<unsigned long long*>(d_keys.p), bad);
+    rtk_check(hipGetLastError(), "kernel launch (k_merge_signature)");
+    auto iota = rocprim::make_transform_iterator(idx, Iota32());
+    size_t kb = 0; rtk_check(rocprim::radix_sort_pairs(nullptr, kb, static_cast<km2_t*>(d_keys.p), static_cast<km2_t*>(d_keys2.p), iota, static_cast<uint32_t*>(d_order.p), static_cast<size_t>(R), 0, 128), "rocprim::radix_sort_pairs");
+    tmp.alloc(kb); rtk_check(rocprim::radix_sort_pairs(tmp.p, kb, static_cast<km2_t*>(d_keys.p), static_cast<km2_t*>(d_keys2.p), iota, static_cast<uint32_t*>(d_order.p), static_cast<size_t>(R), 0, 128), "rocprim::radix_sort_pairs");
+    hipLaunchKernelGGL(k_merge_leaders, grid(R), dim3(256), 0, 0, static_cast<const uint64_t*>(d_keys2.p), static_cast<const uint32_t*>(d_order.p), R, static_cast<uint32_t*>(d_leader.p), static_cast<uint32_t*>(d_flag.p), cnt, bad);
+    rtk_check(hipGetLastError(), "kernel launch (k_merge_leaders)");
+    MergeLeaderFlag lf; lf.flag = static_cast<const uint32_t*>(d_flag.p); lf.R = R;
+    auto flags = rocprim::make_transform_iterator(idx, lf);
+    size_t rb = 0; rtk_check(rocprim::exclusive_scan(nullptr, rb, flags, static_cast<uint32_t*>(d_rank.p), 0u, static_cast<size_t>(R + 1), rocprim::plus<uint32_t>()), "rocprim::exclusive_scan");
+    tmp.alloc(rb); rtk_check(rocprim::exclusive_scan(tmp.p, rb, flags, static_cast<uint32_t*>(d_rank.p), 0u, static_cast<size_t>(R + 1), rocprim::plus<uint32_t>()), "rocprim::exclusive_scan");
+    hipLaunchKernelGGL(k_merge_relabel, grid(n), dim3(256), 0, 0, ev, static_cast<const uint64_t*>(run_of), n, R, static_cast<const uint32_t*>(d_leader.p), static_cast<const uint32_t*>(d_rank.p));
+    rtk_check(hipGetLastError(), "kernel launch (k_merge_relabel)");
+    rtk_check(hipDeviceSynchronize(), "ids merged");
+    unsigned long long h_cnt[3] = {0, 0, 0}; rtk_check(hipMemcpy(h_cnt, cnt, 24, hipMemcpyDeviceToHost), "hipMemcpy");
+    if (h_cnt[2]) throw std::runtime_error("an event names a unitig or a run outside the tables");
+    uint32_t n_leaders = 0; rtk_check(hipMemcpy(&n_leaders, static_cast<uint32_t*>(d_rank.p) + R, 4, hipMemcpyDeviceToHost), "hipMemcpy");
+    uint64_t n_out = 0; uint64_t* out = sort_unique_events(ev, run_of, n, tmp, &n_out);
+    res->n_out = n_out; res->ids_before = R; res->ids_after = n_leaders; res->classes_above_one = h_cnt[0]; res->largest = h_cnt[1];
+    return out;
+}
+} // namespace
+
+// The ids of an open colouring job merged in place (the rule above): finishes the pending chunks and the last sort-and-unique, merges, and sets the job's events
+// and ids, so that rtk_index_colour_end, rtk_index_colour_cov and rtk_index_colour_end_subsampled go on from the merged events. The job stays alive, also on error.
+extern "C" int rtk_index_colour_merge(void* job, uint64_t* n_events_before, uint64_t* n_events_after, uint64_t* n_ids_before, uint64_t* n_ids_after) {
+    ColourJob* J = static_cast<ColourJob*>(job);
+    if (!J || !n_events_before || !n_events_after || !n_ids_before || !n_ids_after) return rtk_fail(RTK_ERR_ARG, "rtk_index_colour_merge: null argument");
+    try {
+        std::lock_guard<std::mutex> lk(J->m);
+        rtk_check(hipSetDevice(J->device), "hipSetDevice");
+        J->compact();
+        const auto t_merge = std::chrono::steady_clock::now();
+        MergeResult r; const uint64_t before = J->n_events;
+        const uint64_t* out = merge_events_device(static_cast<uint64_t*>(J->events.p), static_cast<uint64_t*>(J->alt.p), J->n_events, J->n_unitigs, J->tmp, &r);
+        if (before) {
+            if (out != static_cast<uint64_t*>(J->events.p)) rtk_check(hipMemcpy(J->events.p, out, 8 * r.n_out, hipMemcpyDeviceToDevice), "hipMemcpy");
+            J->n_events = r.n_out; J->n_ids = r.ids_after; rtk_check(hipMemcpy(J->top.p, &r.n_out, 8, hipMemcpyHostToDevice), "hipMemcpy");
+        }
+        J->merge_classes_above_one = r.classes_above_one; J->merge_largest = r.largest;
+        *n_events_before = before; *n_events_after = J->n_events; *n_ids_before = r.ids_before; *n_ids_after = r.ids_after;
+        if (rtk_knob_index_trace()) fprintf(stderr, "rtk_index_colour: ids merged on the device: %llu -> %llu ids, %llu -> %llu events (%.3f s)\n", static_cast<unsigned long long>(r.ids_before), static_cast<unsigned long long>(r.ids_after),
+                                               static_cast<unsigned long long>(before), static_cast<unsigned long long>(J->n_events), std::chrono::duration<double>(std::chrono::steady_clock::now() - t_merge).count());
+    } catch (const std::exception& e) { return rtk_fail(RTK_ERR_DEVICE, std::string("rtk_index_colour_merge: ") + e.what()); }
+    return RTK_OK;
+}
+
+// what the job's last rtk_index_colour_merge found about its classes: how many hold more than one id, and the ids of the largest (0 and 0 before any merge)
+extern "C" int rtk_index_colour_merge_classes(void* job, uint64_t* classes_above_one, uint64_t* largest) {
+    ColourJob* J = static_cast<ColourJob*>(job);
+    if (!J || !classes_above_one || !largest) return rtk_fail(RTK_ERR_ARG, "rtk_index_colour_merge_classes: null argument");
+    std::lock_guard<std::mutex> lk(J->m);
+    *classes_above_one = J->merge_classes_above_one; *largest = J->merge_largest;
+    return RTK_OK;
+}
+
+// Stage entry for tests: the device function behind rtk_index_colour_merge on events of the caller (host arrays; ascending, distinct, unitigs < n_unitigs);
+// events_out has room for n_events words.
+extern "C" int rtk_index_merge_events(int device, const uint64_t* events, uint64_t n_events, uint32_t n_unitigs, uint64_t* events_out, uint64_t* n_out, uint64_t* n_ids_before, uint64_t* n_ids_after) {
+    if ((!events && n_events) || (!events_out && n_events) || !n_out || !n_ids_before || !n_ids_after || n_unitigs == 0) return rtk_fail(RTK_ERR_ARG, "rtk_index_merge_events: null argument");
+    if (rtk_device_count() <= device || device < 0) return rtk_fail(RTK_ERR_NO_DEVICE, "rtk_index_merge_events: no such HIP device (no CPU fallback)");
+    for (uint64_t i = 0; i < n_events; ++i) {
+        if (i && events[i] <= events[i - 1]) return rtk_fail(RTK_ERR_ARG, "rtk_index_merge_events: the events are not ascending and distinct");
+        if ((events[i] >> 32) >= n_unitigs) return rtk_fail(RTK_ERR_ARG, "rtk_index_merge_events: an event names a unitig >= n_unitigs");
+    }
+    *n_out = 0; *n_ids_before = 0; *n_ids_after = 0;
+    try {
+        rtk_check(hipSetDevice(device), "hipSetDevice");
+        DevBuf d_a, d_b, d_tmp; d_a.alloc(8 * n_events); d_b.alloc(8 * n_events);
+        if (n_events) rtk_check(hipMemcpy(d_a.p, events, 8 * n_events, hipMemcpyHostToDevice), "hipMemcpy");
+        MergeResult r; const uint64_t* out = merge_events_device(static_cast<uint64_t*>(d_a.p), static_cast<uint64_t*>(d_b.p), n_events, n_unitigs, d_tmp, &r);
+        if (r.n_out > n_events) return rtk_fail(RTK_ERR_DEVICE, "rtk_index_merge_events: more events after the merge than before");
+        if (r.n_out) rtk_check(hipMemcpy(events_out, out, 8 * r.n_out, hipMemcpyDeviceToHost), "hipMemcpy");
+        *n_out = r.n_out; *n_ids_before = r.ids_before; *n_ids_after = r.ids_after;
+    } catch (const std::exception& e) { return rtk_fail(RTK_ERR_DEVICE, std::string("rtk_index_merge_events: ") + e.what()); }
     return RTK_OK;
 }

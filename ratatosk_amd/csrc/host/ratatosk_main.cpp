@@ -57,6 +57,7 @@ struct Opt {
     bool force_snp = false;
     double min_conf_snp = 0.9;
     size_t insert_sz = 500, w1 = 1000, w2 = 5000, batch_bases = 0; // 0: not given (64 Mi for the first pass, 32 Mi for the second)
+    bool merge_duplicates = false; // --merge-duplicates: handed to both index steps of `correct -s` (the second colours by long reads and leaves them alone)
     bool subsample = false; std::string subsample_seed; // --subsample-colours [--subsample-seed N]: handed to both index steps of `correct -s`
     bool pass1 = false, pass2 = false, verbose = false, correct = false, strip = false, gzip = false, parse_only = false;
 };
@@ -69,6 +70,8 @@ static void usage() {
                     "      --subsample-colours  the read ids that colour the graphs subsampled by coverage, as the reference's index step does by default (\"Subsampling: Auto\":\n"
                     "                        about 5 reads per haplotype kept on every vertex once the estimated haplotype coverage is 10 or more); handed to both index steps\n"
                     "      --subsample-seed N  seed of the hash that stands in for the reference's random draws (default 1; only with --subsample-colours)\n"
+                    "      --merge-duplicates  short-read pairs that lie on the same unitigs share one colour id, as the reference's index step merges duplicated reads;\n"
+                    "                        handed to both index steps (the second colours by long reads, one id each, and says so)\n"
                     "  -u, --in-unmapped-short  unmapped short reads (may be repeated; or a text file of paths): those with enough k1-mers that the long reads hold and the -s reads\n"
                     "                        do not are rescued first (rtk_rescue_reads --gpu, <out_prefix>_extra_sr.fasta, removed at the end) and join the short reads of the index builds\n\n"
                     "       Ratatosk correct -1 -g <graph.fasta.gz> -d <unitig_data.rtsk> -l <long_reads> -o <out_prefix> [options]\n"
@@ -153,6 +156,7 @@ static int correct_from_short_reads(const Opt& opt, const char* argv0) {
         if (!extra_sr.empty()) { a.push_back("-s"); a.push_back(extra_sr); }
         for (size_t i = 0; i < colour.size(); ++i) { a.push_back("--colour-reads"); a.push_back(colour[i]); }
         if (!opt.no_snps) a.push_back("--snps");
+        if (opt.merge_duplicates) a.push_back("--merge-duplicates");
         if (opt.subsample) { a.push_back("--subsample-colours"); if (!opt.subsample_seed.empty()) { a.push_back("--subsample-seed"); a.push_back(opt.subsample_seed); } }
         a.push_back("-o"); a.push_back(prefix); return a;
     };
@@ -227,7 +231,7 @@ int main(int argc, char** argv) {
         {"correction-rounds", required_argument, 0, 'r'}, {"no-snp-correction", no_argument, 0, 'F'}, {"force-io-order", no_argument, 0, 'O'}, {"no-graph-index", no_argument, 0, 'I'},
         {"in-unmapped-short", required_argument, 0, 'u'}, {"in-accurate-long", required_argument, 0, 'a'}, {"in-short-phase", required_argument, 0, 'p'}, {"in-long-phase", required_argument, 0, 'P'}, {"force-correct-snp", no_argument, 0, 'f'},
         {"sampling", required_argument, 0, 'S'}, {"min-conf-color2", required_argument, 0, 'M'}, {"min-len-color2", required_argument, 0, 'C'},
-        {"batch-bases", required_argument, 0, 'B'}, {"strip-annotations", no_argument, 0, 1001}, {"gpus", required_argument, 0, 1002}, {"workers-per-gpu", required_argument, 0, 1003}, {"parse-only", no_argument, 0, 1004}, {"allow-tinybitmap", no_argument, 0, 1005}, {"subsample-colours", no_argument, 0, 1006}, {"subsample-seed", required_argument, 0, 1007}, {"verbose", no_argument, 0, 'v'}, {0, 0, 0, 0}};
+        {"batch-bases", required_argument, 0, 'B'}, {"strip-annotations", no_argument, 0, 1001}, {"gpus", required_argument, 0, 1002}, {"workers-per-gpu", required_argument, 0, 1003}, {"parse-only", no_argument, 0, 1004}, {"allow-tinybitmap", no_argument, 0, 1005}, {"subsample-colours", no_argument, 0, 1006}, {"subsample-seed", required_argument, 0, 1007}, {"merge-duplicates", no_argument, 0, 1008}, {"verbose", no_argument, 0, 'v'}, {0, 0, 0, 0}};
     int c, idx = 0;
     while ((c = getopt_long(argc - 1, argv + 1, "s:l:o:c:g:d:i:k:w:Q:m:B:L:K:W:t:r:u:a:p:P:S:M:C:GFOIf12v", lo, &idx)) != -1) {
         { // what `correct -s` hands on to its correction steps: the option as given (long options by their long name)
@@ -274,6 +278,7 @@ int main(int argc, char** argv) {
             case 1006: opt.subsample = true; break; // (with -g / -d: refused below)
             case 1007: { opt.subsample_seed = optarg; char* end = nullptr; (void)strtoull(optarg, &end, 10); // (on its own it switches nothing on: refused below, as rtk_build_index does)
                 if (*optarg < '0' || *optarg > '9' || *end) { fprintf(stderr, "Ratatosk::correct: --subsample-seed takes an unsigned number, not '%s'\n", optarg); return 1; } break; }
+            case 1008: opt.merge_duplicates = true; break; // (with -g / -d: refused below)
             case 's': opt.in_short.push_back(optarg); break; // (with -g / -d: ignored, said below)
             default: usage(); return 0; // the reference returns 0 on option errors too (src/Ratatosk.cpp:1018)
         }
@@ -290,6 +295,10 @@ int main(int argc, char** argv) {
     }
     if (opt.subsample || !opt.subsample_seed.empty()) { // the colours of a pre-built index are what they are
         fprintf(stderr, "Ratatosk::correct: --subsample-colours belongs to the index build (correct -s SHORT --subsample-colours -l LONG -o OUT, or rtk_build_index --subsample-colours): not accepted next to a pre-built index (-g, -d)\n");
+        return 1;
+    }
+    if (opt.merge_duplicates) { // likewise
+        fprintf(stderr, "Ratatosk::correct: --merge-duplicates belongs to the index build (correct -s SHORT --merge-duplicates -l LONG -o OUT, or rtk_build_index --merge-duplicates): not accepted next to a pre-built index (-g, -d)\n");
         return 1;
     }
     for (size_t i = 0; i < opt.in_short.size(); ++i) fprintf(stderr, "Ratatosk::correct: short reads are only needed by `index` (not in scope); ignored\n");

@@ -11,6 +11,7 @@
 //   * kmCov          = number of read k-mers mapped on the unitig (unphased coverage, bits 31..61)
 //   * branching bit  = >1 predecessors or >1 successors            (reference: src/Graph.cpp:1997)
 //   * edge bits      = neighbour shares >= min_cov_vertices colours (reference: src/Graph.cpp:1999-2017)
+//   * merged ids     (--merge-duplicates only) = read pairs on the same unitigs share one colour id, as src/Graph.cpp:1630-1705, 2089-2134 do (index/merge.hpp)
 //   * subsampling    (--subsample-colours only) = the colours thinned by coverage as src/Graph.cpp:2312-2870 does (index/subsample.hpp)
 //   * global/local   = simplified form of the colour compaction of src/Graph.cpp:2874-2985
 //   * short cycles   = restatement of detectShortCycles (src/Graph.cpp:4660-4735), so that fixRepeats has inputs
@@ -26,6 +27,7 @@
 #include "../common/rtsk_io.hpp"
 #include "index/annotate.hpp"
 #include "index/colour.hpp"
+#include "index/merge.hpp"
 #include "index/subsample.hpp"
 #include "index/unitigs.hpp"
 
@@ -131,6 +133,7 @@ template <class KM> static int run(const IndexOptions& o) {
     start_fasta_writer(s);
     if (!colour_and_cover(s)) return 1;
     s.lap("colours and coverage done");
+    if (o.merge) { if (!merge_duplicates(s)) return 1; s.lap("duplicates merged"); }
     adjacency_structure(s);
     if (o.subsample) { if (!subsample_colours(s)) return 1; s.lap("colours subsampled"); }
     edge_bits(s);

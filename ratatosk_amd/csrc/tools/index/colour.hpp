@@ -31,12 +31,17 @@ template <class KM> struct ColourSink {
     IndexBuild<KM>& s; std::vector<Unitig>& U; const size_t n_u;
     void* job = nullptr; std::atomic<int> failed; HipLib::col_chunk_fn chunk_fn = nullptr; HipLib::col_end_fn end_fn = nullptr; std::vector<Feed> feeds;
     HipLib::col_cov_fn cov_fn = nullptr; HipLib::col_end_sub_fn end_sub_fn = nullptr; bool open_job = false; // --subsample-colours: the job stays open (open_job) between the coverage and the thinned events
+    HipLib::col_merge_fn merge_fn = nullptr; HipLib::col_merge_classes_fn merge_classes_fn = nullptr; // --merge-duplicates (pairs only): the events merged in place in the open job
     std::vector<std::vector<uint64_t> > cov; std::vector<std::vector<std::pair<uint32_t, uint32_t> > > ev; // host: per thread, k-mers per unitig and (unitig, id) events
 
     explicit ColourSink(IndexBuild<KM>& st) : s(st), U(st.U), n_u(st.U.size()), failed(0), feeds(st.n_thr), cov(st.n_thr), ev(st.n_thr) {
         HipLib::col_begin_fn begin_fn = nullptr;
         if (s.o.gpu && s.lib.get(begin_fn, "rtk_index_colour_begin") && s.lib.get(chunk_fn, "rtk_index_colour_chunk") && s.lib.get(end_fn, "rtk_index_colour_end") && !s.knobs.host_colours && n_u > 0) {
-            if (s.o.subsample && !(s.lib.get(cov_fn, "rtk_index_colour_cov") && s.lib.get(end_sub_fn, "rtk_index_colour_end_subsampled"))) { // (the events are then fetched the old way, rtk_index_colour_end)
+            if (s.o.merge && s.o.colour_files.empty() && !(s.lib.get(merge_fn, "rtk_index_colour_merge") && s.lib.get(merge_classes_fn, "rtk_index_colour_merge_classes"))) { // (the events are then fetched at once and every later step runs on the host threads)
+                merge_fn = nullptr; merge_classes_fn = nullptr; fprintf(stderr, "rtk_build_index: --gpu: %s lacks rtk_index_colour_merge / rtk_index_colour_merge_classes: ids merged on the host threads\n", s.lib.path.c_str()); }
+            const bool host_merge = s.o.merge && s.o.colour_files.empty() && !merge_fn;
+            if (s.o.subsample && host_merge) { cov_fn = nullptr; end_sub_fn = nullptr; }
+            else if (s.o.subsample && !(s.lib.get(cov_fn, "rtk_index_colour_cov") && s.lib.get(end_sub_fn, "rtk_index_colour_end_subsampled"))) { // (the events are then fetched the old way, rtk_index_colour_end)
                 cov_fn = nullptr; end_sub_fn = nullptr; fprintf(stderr, "rtk_build_index: --gpu: %s lacks rtk_index_colour_cov / rtk_index_colour_end_subsampled: colours subsampled on the host threads\n", s.lib.path.c_str()); }
             std::vector<uint64_t> off(n_u + 1, 0); for (size_t u = 0; u < n_u; ++u) off[u + 1] = off[u] + s.U[u].seq.size();
             std::string pool(off[n_u], 'A');
@@ -83,6 +88,13 @@ template <class KM> struct ColourSink {
         uint64_t* cv = nullptr;
         if (cov_fn(job, &cv) != 0 || failed) { fprintf(stderr, "rtk_build_index: --gpu: colouring on the device failed (%s)\n", s.lib.last_error()); return false; }
         take_cov(cv); s.lib.free(cv);
+        return true;
+    }
+    // --gpu --merge-duplicates: the reads are all fed; the events merged in place on the device (tools/index/merge.hpp has the rule), the job stays open
+    bool merge_device(uint64_t* ev_before, uint64_t* ev_after, uint64_t* ids_before, uint64_t* ids_after, uint64_t* classes_above_one, uint64_t* largest) {
+        for (unsigned t = 0; t < s.n_thr; ++t) feeds[t].flush();
+        if (failed || merge_fn(job, ev_before, ev_after, ids_before, ids_after) != 0 || merge_classes_fn(job, classes_above_one, largest) != 0) {
+            fprintf(stderr, "rtk_build_index: --gpu: merging the ids on the device failed (%s)\n", s.lib.last_error()); return false; }
         return true;
     }
     // second half: the events thinned and renumbered on the device (tools/index/subsample.hpp has the rule), only the kept ones copied back
@@ -219,8 +231,9 @@ template <class KM> static bool colour_and_cover(IndexBuild<KM>& s) {
     bool all_sampled = s.o.fast && !by_read && !col_in.empty(), all_plain = s.o.fast;
     for (size_t f = 0; f < col_in.size(); ++f) { all_sampled = all_sampled && SampleSource::is_spec(col_in[f]); all_plain = all_plain && PlainChunks::is_plain(col_in[f]); }
     const bool ok = all_sampled ? colour_from_samples(s, sink, col_in) : (all_plain ? colour_from_plain_ranges(s, sink, col_in, by_read) : colour_from_reader(s, sink, col_in, by_read));
-    if (s.o.subsample && sink.job && sink.end_sub_fn) { // the events wait on the device for the subsampling step
-        if (!sink.cov_device() || !ok) return false;
+    const bool sub_there = s.o.subsample && sink.job && sink.end_sub_fn, merge_there = sink.job && sink.merge_fn;
+    if (sub_there || merge_there) { // the events wait on the device for the merging or the subsampling step
+        if ((sub_there && !sink.cov_device()) || !ok) return false;
         s.colour_sink = sink_p;
         return true;
     }

@@ -30,6 +30,7 @@ struct IndexOptions {
     bool fast = false, gpu = false; // --fast: the same files from thread-parallel counting-table build / compaction / adjacency / cycle search; --gpu: --fast with counting, unitigs and colours on the device (any odd k <= 63)
     std::string dump_input; // --dump-input FILE: the inputs (sample: sources included) written out as one FASTQ file, nothing else done
     bool subsample = false; uint64_t subsample_seed = 1; // --subsample-colours [--subsample-seed N]: the colours thinned out by coverage (tools/index/subsample.hpp)
+    bool merge = false; // --merge-duplicates: read pairs on the same unitigs share one colour id (tools/index/merge.hpp)
     std::vector<std::string> colour_files; // pass-2 index (`Ratatosk index -2`): colours = ids of these (pass-1 corrected long) reads, one id per read
     std::string out_file(const char* ext) const { return prefix + ".index.k" + std::to_string(k) + ext; }
 };
@@ -51,13 +52,14 @@ inline int parse_options(int argc, char** argv, IndexOptions& o) {
         else if (a == "--gpu") { o.fast = true; o.gpu = true; }
         else if (a == "--colour-reads") o.colour_files.push_back(need("--colour-reads"));
         else if (a == "--subsample-colours") o.subsample = true;
+        else if (a == "--merge-duplicates") o.merge = true;
         else if (a == "--subsample-seed") { const char* v = need("--subsample-seed"); char* end = nullptr; o.subsample_seed = strtoull(v, &end, 10); seed_given = true;
             if (*v < '0' || *v > '9' || *end) { fprintf(stderr, "rtk_build_index: --subsample-seed takes an unsigned number, not '%s'\n", v); return 2; } }
         else if (a == "--dump-input") o.dump_input = need("--dump-input");
         else { fprintf(stderr, "rtk_build_index: unknown option %s\n", a.c_str()); return 2; }
     }
     if (seed_given && !o.subsample) { fprintf(stderr, "rtk_build_index: --subsample-seed without --subsample-colours\n"); return 2; }
-    if (o.in_files.empty() || o.k < 3 || o.k > RTK_MAX_K || !(o.k & 1)) { fprintf(stderr, "usage: rtk_build_index -s reads.fq [-s ...] -o PREFIX [-k 31 (odd, <=63)] [--min-count 2] [--global-cov-factor 3.0] [--no-short-cycles] [--snps] [--fast | --gpu (k <= 63: same files, threads / the device for the heavy steps)] [--dump-input FILE] [--subsample-colours [--subsample-seed 1 (only with --subsample-colours)]: colours subsampled by coverage as the reference's index step does by default] [--colour-reads corrected_long_reads.fq: second-pass index, the graph comes from -s, colours and coverage from these reads]\n"); return 2; }
+    if (o.in_files.empty() || o.k < 3 || o.k > RTK_MAX_K || !(o.k & 1)) { fprintf(stderr, "usage: rtk_build_index -s reads.fq [-s ...] -o PREFIX [-k 31 (odd, <=63)] [--min-count 2] [--global-cov-factor 3.0] [--no-short-cycles] [--snps] [--fast | --gpu (k <= 63: same files, threads / the device for the heavy steps)] [--dump-input FILE] [--subsample-colours [--subsample-seed 1 (only with --subsample-colours)]: colours subsampled by coverage as the reference's index step does by default] [--merge-duplicates: read pairs that lie on the same unitigs share one colour id, as the reference's index step merges duplicated reads (no effect with --colour-reads)] [--colour-reads corrected_long_reads.fq: second-pass index, the graph comes from -s, colours and coverage from these reads]\n"); return 2; }
     return 0;
 }
 
@@ -124,7 +126,7 @@ template <class KM> struct IndexBuild { // KM: uint64_t for k <= 31, u128 for k 
     std::vector<Nb> adj; std::vector<uint64_t> kmcov, shared; // neighbours, coverage + branching bit, edge bits (+ 0x100: in a short cycle)
     std::vector<std::string> cycles;
     std::vector<std::vector<uint32_t> > ambiguity, global_ids, local_ids;
-    std::shared_ptr<void> colour_sink; // --gpu --subsample-colours: the ColourSink whose job still holds the events on the device
+    std::shared_ptr<void> colour_sink; // --gpu --subsample-colours / --merge-duplicates: the ColourSink whose job still holds the events on the device
     std::thread fasta_thread; std::atomic<int> fasta_rc; // --fast: the unitig FASTA is compressed beside the other steps
     explicit IndexBuild(const IndexOptions& opt) : o(opt), k(opt.k), mask(km_mask<KM>(opt.k)), km(16), fasta_rc(0) {
         n_thr = std::thread::hardware_concurrency(); if (n_thr == 0) n_thr = 1; if (n_thr > (o.fast ? 128u : 32u)) n_thr = o.fast ? 128u : 32u; // (--fast: the steps are random accesses into GB-sized tables: latency-bound, SMT threads help)
