@@ -320,6 +320,16 @@ int rtk_index_unitigs(int device, int k, const uint64_t* solid, uint64_t n_solid
 int rtk_index_colour_begin(int device, int k, const char* seq_pool, const uint64_t* seq_off, uint64_t n_unitigs, void** job);
 int rtk_index_colour_chunk(void* job, const char* chars, uint64_t n_chars, const uint64_t* starts, const uint32_t* ids, uint32_t n_reads);
 int rtk_index_colour_end(void* job, uint64_t** events, uint64_t* n_events, uint64_t** cov);
+/* rtk_index_colour_chunk with the base-confidence rule of a second-pass index (addCoverage with long_read_correct, src/Graph.cpp:1573, 1806-1814, 1872-1880; DESIGN.md
+ * section 4 [A14]): quals runs parallel to chars (quals[i] is the quality byte of chars[i]; the bytes at the '\n' separators are ignored), and a base whose quality byte
+ * is below q_min (unsigned comparison; q_min = getQual(min_confidence_2nd_pass, 1, max_qual), src/Common.hpp:410-418) is no base: every k-mer window that holds it gives
+ * no event and no coverage, as an 'N' in the sequence does. The characters are rewritten on the device (k_col_mask, on the chunk's stream ahead of the look-up); the
+ * caller's buffers are only read. quals == NULL or q_min == 0: exactly rtk_index_colour_chunk. Chunks with and without qualities may follow each other in one job; a job
+ * that never sees qualities allocates and launches what it did before this entry existed. The read-length rule of the same block (a read shorter than
+ * min_len_2nd_pass colours nothing, src/Graph.cpp:1796, 1870) is the caller's: such reads are not fed, and keep their id. Appended without a new revision number: see
+ * RTK_API_REVISION. */
+int rtk_index_colour_chunk_q(void* job, const char* chars, const unsigned char* quals, unsigned char q_min, uint64_t n_chars, const uint64_t* starts, const uint32_t* ids,
+                             uint32_t n_reads);
 /* Colours subsampled by coverage on the device (rtk_build_index --gpu --subsample-colours; the reference: addCoverage, src/Graph.cpp:2312-2870; the rule and its three
  * deviations: DESIGN.md section 4 [A12], csrc/tools/index/subsample.hpp). The caller works out what needs coverage and structure, the device does everything that
  * touches an event or an id, so that only the kept events are copied to the host.
@@ -416,7 +426,7 @@ const char* rtk_version(void);
  * 8: rtk_stats fields n_fa_linked_*; 9: rtk_rescue_begin / _chunk / _end; still 9: rtk_stats fields n_strand2_* and n_park_*, the test-only rtk_myers_batch mode 5, appended at the end -- a library of revision 9
  * without them leaves them as the caller set them;
  * 10: rtk_sets_batch, rtk_stats fields n_colours_*; still 10: rtk_index_colour_cov, rtk_index_colour_end_subsampled, rtk_index_subsample_events, then rtk_index_colour_merge,
- * rtk_index_colour_merge_classes, rtk_index_merge_events, appended -- a library of revision 10 without them lacks the symbols, and callers look them up by name). */
+ * rtk_index_colour_merge_classes, rtk_index_merge_events, then rtk_index_colour_chunk_q, appended -- a library of revision 10 without them lacks the symbols, and callers look them up by name). */
 #define RTK_API_REVISION 10
 int rtk_api_revision(void);
 

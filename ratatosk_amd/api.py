@@ -126,6 +126,8 @@ def load_library(path=None):
         L.rtk_index_colour_merge.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.rtk_index_colour_merge_classes.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.rtk_index_merge_events.argtypes = [C.c_int, C.POINTER(C.c_uint64), C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    if hasattr(L, "rtk_index_colour_chunk_q"):  # (still revision 10: appended; a library without it: index_colour_reads says so)
+        L.rtk_index_colour_chunk_q.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_ubyte, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.c_uint32]
     L.rtk_free.argtypes = [C.c_void_p]
     _libs[path] = L
     return L
@@ -480,6 +482,73 @@ def index_merge_events(events, n_unitigs, device=0, lib_path=None):
     if rc != 0:
         raise RtkError("rtk error %d: %s" % (rc, L.rtk_last_error().decode()))
     return out[:n_out.value].copy(), before.value, after.value
+
+
+def index_colour_reads(unitigs, k, reads, ids=None, quals=None, q_min=0, device=0, lib_path=None, chunks=None):
+    """Colour events and k-mer coverage of `unitigs` under `reads`, on the device: one job over rtk_index_colour_begin, one rtk_index_colour_chunk or
+    rtk_index_colour_chunk_q per chunk, rtk_index_colour_end (include/ratatosk_hip.h; the base-confidence rule: DESIGN.md section 4 [A14]). reads[r] colours with
+    ids[r] (default: r). quals: None, or one entry per read -- its quality string, or None. A chunk whose reads all have a quality string goes through
+    rtk_index_colour_chunk_q with q_min (a base whose quality byte is below q_min is no base), one whose reads have none through rtk_index_colour_chunk; a chunk
+    that mixes the two is refused. chunks: the read indices at which a new chunk begins (default: one chunk). A library without rtk_index_colour_chunk_q raises an
+    RtkError that names it as soon as a chunk needs it. Returns (events unitig << 32 | id, ascending and distinct; k-mers mapped per unitig) as numpy uint64 arrays."""
+    import numpy as np
+    L = load_library(lib_path)
+    u64p, u32p = C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)
+    L.rtk_index_colour_begin.argtypes = [C.c_int, C.c_int, C.c_char_p, u64p, C.c_uint64, C.POINTER(C.c_void_p)]
+    L.rtk_index_colour_chunk.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, u64p, u32p, C.c_uint32]
+    L.rtk_index_colour_end.argtypes = [C.c_void_p, C.POINTER(u64p), u64p, C.POINTER(u64p)]
+
+    def as_bytes(x):
+        return x if isinstance(x, bytes) else x.encode()
+
+    reads = [as_bytes(r) for r in reads]
+    ids = list(range(len(reads))) if ids is None else list(ids)
+    quals = [None] * len(reads) if quals is None else [None if q is None else as_bytes(q) for q in quals]
+    if len(ids) != len(reads) or len(quals) != len(reads):
+        raise ValueError("index_colour_reads: ids and quals need one entry per read")
+    for r, q in zip(reads, quals):
+        if q is not None and len(q) != len(r):
+            raise ValueError("index_colour_reads: a quality string is as long as its read")
+    cuts = [0] + sorted(chunks or []) + [len(reads)]
+    parts = [(a, b) for a, b in zip(cuts[:-1], cuts[1:]) if a < b]
+    for a, b in parts:
+        n_q = sum(q is not None for q in quals[a:b])
+        if n_q not in (0, b - a):
+            raise ValueError("index_colour_reads: reads %d .. %d: a chunk holds reads with qualities or reads without, not both" % (a, b))
+        if n_q and not hasattr(L, "rtk_index_colour_chunk_q"):
+            raise RtkError("%s lacks rtk_index_colour_chunk_q (colouring by base confidence: appended at interface revision 10)" % L._name)
+
+    def ok(rc):
+        if rc != 0:
+            raise RtkError("rtk error %d: %s" % (rc, L.rtk_last_error().decode()))
+
+    seqs = [as_bytes(u) for u in unitigs]
+    off = np.zeros(len(seqs) + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(u) for u in seqs], dtype=np.uint64)
+    job = C.c_void_p()
+    ok(L.rtk_index_colour_begin(device, k, b"".join(seqs), off.ctypes.data_as(u64p), len(seqs), C.byref(job)))
+    try:
+        for a, b in parts:
+            chars = b"".join(r + b"\n" for r in reads[a:b])
+            starts = np.zeros(b - a, dtype=np.uint64)
+            starts[1:] = np.cumsum([len(r) + 1 for r in reads[a:b - 1]], dtype=np.uint64)
+            cid = np.ascontiguousarray(ids[a:b], dtype=np.uint32)
+            if quals[a] is None:
+                ok(L.rtk_index_colour_chunk(job, chars, len(chars), starts.ctypes.data_as(u64p), cid.ctypes.data_as(u32p), b - a))
+            else:
+                qs = b"".join(q + b"\0" for q in quals[a:b])  # (the byte beside a separator is not looked at)
+                ok(L.rtk_index_colour_chunk_q(job, chars, qs, q_min, len(chars), starts.ctypes.data_as(u64p), cid.ctypes.data_as(u32p), b - a))
+    except BaseException:
+        L.rtk_index_colour_end(job, None, None, None)
+        raise
+    ev_p, cov_p, n_ev = u64p(), u64p(), C.c_uint64(0)
+    ok(L.rtk_index_colour_end(job, C.byref(ev_p), C.byref(n_ev), C.byref(cov_p)))
+    try:
+        events = np.ctypeslib.as_array(ev_p, shape=(max(1, n_ev.value),))[:n_ev.value].copy()
+        cov = np.ctypeslib.as_array(cov_p, shape=(len(seqs),)).copy()
+    finally:
+        L.rtk_free(ev_p); L.rtk_free(cov_p)
+    return events, cov
 
 
 def run_pipelined(batches, opts=None):

@@ -20,6 +20,7 @@ struct HipLib {
     typedef int (*unitigs_fn)(int, int, const uint64_t*, uint64_t, char**, uint64_t**, uint64_t**, uint64_t*, uint64_t**, uint64_t*);        // rtk_index_unitigs
     typedef int (*col_begin_fn)(int, int, const char*, const uint64_t*, uint64_t, void**);                                                   // rtk_index_colour_begin
     typedef int (*col_chunk_fn)(void*, const char*, uint64_t, const uint64_t*, const uint32_t*, uint32_t);                                   // rtk_index_colour_chunk
+    typedef int (*col_chunk_q_fn)(void*, const char*, const unsigned char*, unsigned char, uint64_t, const uint64_t*, const uint32_t*, uint32_t);     // rtk_index_colour_chunk_q
     typedef int (*col_end_fn)(void*, uint64_t**, uint64_t*, uint64_t**);                                                                     // rtk_index_colour_end
     typedef int (*col_cov_fn)(void*, uint64_t**);                                                                                            // rtk_index_colour_cov
     typedef int (*col_end_sub_fn)(void*, const uint8_t*, const uint8_t*, const uint8_t*, uint32_t, uint32_t, double, uint64_t, uint64_t**, uint64_t*, uint64_t*, uint64_t*, uint64_t*); // rtk_index_colour_end_subsampled

@@ -252,6 +252,7 @@ extern "C" int rtk_n_devices(void) { return rtk_device_count(); }
 extern "C" int rtk_index_count_kmers(int, int, const char* const*, int, uint32_t, int, uint64_t**, uint64_t*) { return rtk_fail(RTK_ERR_UNSUPPORTED, "rtk_index_count_kmers: not part of the simulator build"); }
 extern "C" int rtk_index_colour_begin(int, int, const char*, const uint64_t*, uint64_t, void**) { return rtk_fail(RTK_ERR_UNSUPPORTED, "rtk_index_colour_begin: not part of the simulator build"); }
 extern "C" int rtk_index_colour_chunk(void*, const char*, uint64_t, const uint64_t*, const uint32_t*, uint32_t) { return rtk_fail(RTK_ERR_UNSUPPORTED, "rtk_index_colour_chunk: not part of the simulator build"); }
+extern "C" int rtk_index_colour_chunk_q(void*, const char*, const unsigned char*, unsigned char, uint64_t, const uint64_t*, const uint32_t*, uint32_t) { return rtk_fail(RTK_ERR_UNSUPPORTED, "rtk_index_colour_chunk_q: not part of the simulator build"); }
 extern "C" int rtk_index_colour_end(void*, uint64_t**, uint64_t*, uint64_t**) { return rtk_fail(RTK_ERR_UNSUPPORTED, "rtk_index_colour_end: not part of the simulator build"); }
 extern "C" int rtk_index_colour_cov(void*, uint64_t**) { return rtk_fail(RTK_ERR_UNSUPPORTED, "rtk_index_colour_cov: not part of the simulator build"); }
 extern "C" int rtk_index_colour_end_subsampled(void*, const uint8_t*, const uint8_t*, const uint8_t*, uint32_t, uint32_t, double, uint64_t, uint64_t**, uint64_t*, uint64_t*, uint64_t*, uint64_t*) { return rtk_fail(RTK_ERR_UNSUPPORTED, "rtk_index_colour_end_subsampled: not part of the simulator build"); }

@@ -7,7 +7,8 @@
 //   rtk_index_unitigs       the chains of the compacted graph walked, numbered and spelt (k_ut_*)
 //   rtk_index_colour_*      every read k-mer mapped onto its unitig: colour events and coverage (k_col_map); with rtk_index_colour_end_subsampled the events
 //                           thinned out by coverage and their ids renumbered before they leave the device (k_sub_*); with rtk_index_colour_merge the ids of read
-//                           pairs on the same unitigs merged in place before that (k_merge_*)
+//                           pairs on the same unitigs merged in place before that (k_merge_*); with rtk_index_colour_chunk_q the bases of a chunk whose quality
+//                           is below a threshold turned into N ahead of the mapping (k_col_mask)
 // Every step serves one-word k-mers (k <= 31, key type uint64_t) and two-word k-mers (33 <= k <= 63, key type unsigned __int128: the 2k-bit code,
 // first base in the most significant bits; in memory the low word first). Own translation unit: rocPRIM's templates.
 #include <string.h>
@@ -342,6 +343,26 @@ __global__ void k_col_map(const char* __restrict__ chars, uint64_t n, int k, con
     }
 }
 
+// The base-confidence rule of a second-pass index (DESIGN.md section 4 [A14]; the reference: addCoverage, src/Graph.cpp:1806-1814 and 1872-1880): a base whose quality
+// byte is below q_min becomes 'N' before the k-mers are looked up, so that k_col_map, which is not changed, gives no event and no coverage for a window over it. In
+// place on the chunk's characters, on the chunk's stream, before k_col_map; the separators keep their byte whatever lies beside them in `quals`. Both buffers come from
+// hipMalloc (16-byte aligned) and hold n bytes: a body of 16 bytes per lane and round, then the n & 15 bytes of the tail one per lane. Bytes compare unsigned.
+__device__ __forceinline__ uint32_t col_mask_word(uint32_t c, uint32_t q, uint32_t q_min) {
+    uint32_t r = c;
+    for (int b = 0; b < 32; b += 8) if (((c >> b) & 255u) != static_cast<uint32_t>('\n') && ((q >> b) & 255u) < q_min) r = (r & ~(255u << b)) | (static_cast<uint32_t>('N') << b);
+    return r;
+}
+__global__ void k_col_mask(char* __restrict__ chars, const unsigned char* __restrict__ quals, uint64_t n, uint32_t q_min) {
+    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x, t = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x, n16 = n >> 4;
+    uint4* __restrict__ c4 = reinterpret_cast<uint4*>(chars); const uint4* __restrict__ q4 = reinterpret_cast<const uint4*>(quals);
+    for (uint64_t v = t; v < n16; v += stride) {
+        uint4 c = c4[v]; const uint4 q = q4[v];
+        c.x = col_mask_word(c.x, q.x, q_min); c.y = col_mask_word(c.y, q.y, q_min); c.z = col_mask_word(c.z, q.z, q_min); c.w = col_mask_word(c.w, q.w, q_min);
+        c4[v] = c;
+    }
+    for (uint64_t i = (n16 << 4) + t; i < n; i += stride) if (chars[i] != '\n' && quals[i] < q_min) chars[i] = 'N';
+}
+
 // n words at `cur` sorted, the distinct ones kept: they end up at `cur` or at `other` (room for n words each; the place is returned), *n_out of them
 uint64_t* sort_unique_events(uint64_t* cur, uint64_t* other, uint64_t n, DevBuf& tmp, uint64_t* n_out) {
     rocprim::double_buffer<uint64_t> db(cur, other);
@@ -363,6 +384,7 @@ struct ColourJob {
     uint64_t n_ids = 0;                        // largest id fed + 1 (after rtk_index_colour_merge: the number of merged ids): the size of the id tables of the subsampling
     uint64_t merge_classes_above_one = 0, merge_largest = 0; // what the last rtk_index_colour_merge found
     DevBuf d_chars[2], d_starts[2], d_ids[2]; PinBuf h_chars[2], h_starts[2], h_ids[2]; uint64_t chunk_cap = 0, reads_cap = 0;
+    DevBuf d_quals[2]; PinBuf h_quals[2]; bool has_quals = false; // one chunk of quality bytes per slot, there from the job's first chunk with qualities on (rtk_index_colour_chunk_q)
     hipStream_t st[2] = {nullptr, nullptr}; int slot = 0;
     std::mutex m; uint64_t bases = 0, chunks = 0, compactions = 0; double t_table = 0.0;
     std::chrono::steady_clock::time_point t0;
@@ -661,11 +683,12 @@ extern "C" int rtk_index_colour_begin(int device, int k, const char* seq_pool, c
     return RTK_OK;
 }
 
-extern "C" int rtk_index_colour_chunk(void* job, const char* chars, uint64_t n_chars, const uint64_t* starts, const uint32_t* ids, uint32_t n_reads) {
+// one chunk of either entry; quals == nullptr: no quality bytes, nothing of the masking step runs
+static int colour_chunk(const char* entry, void* job, const char* chars, const unsigned char* quals, unsigned char q_min, uint64_t n_chars, const uint64_t* starts, const uint32_t* ids, uint32_t n_reads) {
     ColourJob* J = static_cast<ColourJob*>(job);
-    if (!J || !chars || !starts || !ids) return rtk_fail(RTK_ERR_ARG, "rtk_index_colour_chunk: null argument");
+    if (!J || !chars || !starts || !ids) return rtk_fail(RTK_ERR_ARG, std::string(entry) + ": null argument");
     if (n_reads == 0 || n_chars == 0) return RTK_OK;
-    if (n_chars > J->chunk_cap || n_reads > J->reads_cap) return rtk_fail(RTK_ERR_ARG, "rtk_index_colour_chunk: chunk larger than 64 MB of characters / 4 M reads");
+    if (n_chars > J->chunk_cap || n_reads > J->reads_cap) return rtk_fail(RTK_ERR_ARG, std::string(entry) + ": chunk larger than 64 MB of characters / 4 M reads");
     try {
         std::lock_guard<std::mutex> lk(J->m);
         rtk_check(hipSetDevice(J->device), "hipSetDevice");
@@ -682,6 +705,13 @@ extern "C" int rtk_index_colour_chunk(void* job, const char* chars, uint64_t n_c
         rtk_check(hipMemcpyAsync(J->d_chars[sl].p, J->h_chars[sl].p, n_chars, hipMemcpyHostToDevice, J->st[sl]), "hipMemcpyAsync");
         rtk_check(hipMemcpyAsync(J->d_starts[sl].p, J->h_starts[sl].p, 8ull * n_reads, hipMemcpyHostToDevice, J->st[sl]), "hipMemcpyAsync");
         rtk_check(hipMemcpyAsync(J->d_ids[sl].p, J->h_ids[sl].p, 4ull * n_reads, hipMemcpyHostToDevice, J->st[sl]), "hipMemcpyAsync");
+        if (quals) { // (the slot's stream is idle since the synchronisation above: its pinned quality bytes are free to be written)
+            if (!J->has_quals) { for (int i = 0; i < 2; ++i) { J->d_quals[i].alloc(J->chunk_cap); J->h_quals[i].alloc(J->chunk_cap); } J->has_quals = true; }
+            memcpy(J->h_quals[sl].p, quals, n_chars);
+            rtk_check(hipMemcpyAsync(J->d_quals[sl].p, J->h_quals[sl].p, n_chars, hipMemcpyHostToDevice, J->st[sl]), "hipMemcpyAsync");
+            hipLaunchKernelGGL(k_col_mask, dim3(256), dim3(256), 0, J->st[sl], static_cast<char*>(J->d_chars[sl].p), static_cast<const unsigned char*>(J->d_quals[sl].p), n_chars, static_cast<uint32_t>(q_min));
+            rtk_check(hipGetLastError(), "kernel launch (k_col_mask)");
+        }
         if (J->k <= 31)
             hipLaunchKernelGGL(k_col_map<uint64_t>, dim3(4096), dim3(256), 0, J->st[sl], static_cast<const char*>(J->d_chars[sl].p), n_chars, J->k, static_cast<const uint64_t*>(J->d_starts[sl].p), static_cast<const uint32_t*>(J->d_ids[sl].p), n_reads,
                                J->g, static_cast<unsigned long long*>(J->cov.p), static_cast<uint64_t*>(J->events.p), static_cast<unsigned long long*>(J->top.p), J->cap);
@@ -690,8 +720,17 @@ extern "C" int rtk_index_colour_chunk(void* job, const char* chars, uint64_t n_c
                                J->g, static_cast<unsigned long long*>(J->cov.p), static_cast<uint64_t*>(J->events.p), static_cast<unsigned long long*>(J->top.p), J->cap);
         rtk_check(hipGetLastError(), "kernel launch (k_col_map)");
         J->bases += n_chars; ++J->chunks;
-    } catch (const std::exception& e) { return rtk_fail(RTK_ERR_DEVICE, std::string("rtk_index_colour_chunk: ") + e.what()); }
+    } catch (const std::exception& e) { return rtk_fail(RTK_ERR_DEVICE, std::string(entry) + ": " + e.what()); }
     return RTK_OK;
+}
+
+extern "C" int rtk_index_colour_chunk(void* job, const char* chars, uint64_t n_chars, const uint64_t* starts, const uint32_t* ids, uint32_t n_reads) {
+    return colour_chunk("rtk_index_colour_chunk", job, chars, nullptr, 0, n_chars, starts, ids, n_reads);
+}
+// The same with the quality bytes of the reads beside their characters (a second-pass index coloured by base confidence: DESIGN.md section 4 [A14]). No qualities or
+// q_min == 0 (no byte is below it): rtk_index_colour_chunk.
+extern "C" int rtk_index_colour_chunk_q(void* job, const char* chars, const unsigned char* quals, unsigned char q_min, uint64_t n_chars, const uint64_t* starts, const uint32_t* ids, uint32_t n_reads) {
+    return colour_chunk("rtk_index_colour_chunk_q", job, chars, q_min ? quals : nullptr, q_min, n_chars, starts, ids, n_reads);
 }
 
 extern "C" int rtk_index_colour_end(void* job, uint64_t** events, uint64_t* n_events, uint64_t** cov) {

@@ -59,6 +59,8 @@ struct Opt {
     size_t insert_sz = 500, w1 = 1000, w2 = 5000, batch_bases = 0; // 0: not given (64 Mi for the first pass, 32 Mi for the second)
     bool merge_duplicates = false; // --merge-duplicates: handed to both index steps of `correct -s` (the second colours by long reads and leaves them alone)
     bool subsample = false; std::string subsample_seed; // --subsample-colours [--subsample-seed N]: handed to both index steps of `correct -s`
+    // -M / -C / -Q as given: `correct -s` hands them to the index step of the second pass (rtk_build_index --colour-min-conf / --colour-min-len / --colour-max-qual)
+    std::string min_conf_colour2, min_len_colour2, max_qual_given;
     bool pass1 = false, pass2 = false, verbose = false, correct = false, strip = false, gzip = false, parse_only = false;
 };
 
@@ -72,6 +74,10 @@ static void usage() {
                     "      --subsample-seed N  seed of the hash that stands in for the reference's random draws (default 1; only with --subsample-colours)\n"
                     "      --merge-duplicates  short-read pairs that lie on the same unitigs share one colour id, as the reference's index step merges duplicated reads;\n"
                     "                        handed to both index steps (the second colours by long reads, one id each, and says so)\n"
+                    "  -M, --min-conf-color2  a base of a first-pass read whose quality is below that of this confidence (0 .. 1; 0: the '!' bases) does not colour the graph of the\n"
+                    "                        second pass; -C, --min-len-color2: a first-pass read of fewer bases colours nothing. Handed to the k2 index step, with -Q if given\n"
+                    "                        (rtk_build_index --colour-min-conf / --colour-min-len / --colour-max-qual). The reference applies -M 0 -C 3000 by default; here neither\n"
+                    "                        applies unless given. Next to a pre-built index (-g, -d) they are ignored\n"
                     "  -u, --in-unmapped-short  unmapped short reads (may be repeated; or a text file of paths): those with enough k1-mers that the long reads hold and the -s reads\n"
                     "                        do not are rescued first (rtk_rescue_reads --gpu, <out_prefix>_extra_sr.fasta, removed at the end) and join the short reads of the index builds\n\n"
                     "       Ratatosk correct -1 -g <graph.fasta.gz> -d <unitig_data.rtsk> -l <long_reads> -o <out_prefix> [options]\n"
@@ -145,6 +151,15 @@ static int correct_from_short_reads(const Opt& opt, const char* argv0) {
     if (opt.in_long.empty() || opt.out.empty()) { fprintf(stderr, "Ratatosk::correct: -s, -l and -o are required\n"); return 1; }
     if (opt.pass2 && opt.in_long_raw.empty()) { fprintf(stderr, "Ratatosk::correct: -2 needs the uncorrected long reads (-L) next to the pass-1 reads (-l)\n"); return 1; }
     if (opt.k1 < 3 || opt.k1 > 31 || !(opt.k1 & 1) || opt.k2 < 3 || opt.k2 > 63 || !(opt.k2 & 1)) { fprintf(stderr, "Ratatosk::correct: k1 must be odd and <= 31, k2 odd and <= 63\n"); return 1; }
+    if (!opt.min_conf_colour2.empty()) { // src/Ratatosk.cpp:378-388
+        char* end = nullptr; const double m = strtod(opt.min_conf_colour2.c_str(), &end);
+        if (end == opt.min_conf_colour2.c_str() || *end || !(m >= 0.0)) { fprintf(stderr, "Ratatosk::Ratatosk(): Minimum confidence threshold of a 1st pass corrected base to be used for coloring in 2nd pass must be greater or equal to 0.0.\n"); return 1; }
+        if (m > 1.0) { fprintf(stderr, "Ratatosk::Ratatosk(): Minimum confidence threshold of a 1st pass corrected base to be used for coloring in 2nd pass must be lower or equal to 1.0.\n"); return 1; }
+    }
+    if (!opt.min_len_colour2.empty()) { // src/Ratatosk.cpp:390-394
+        char* end = nullptr; const long long n = strtoll(opt.min_len_colour2.c_str(), &end, 10);
+        if (end == opt.min_len_colour2.c_str() || *end || n < 0) { fprintf(stderr, "Ratatosk::Ratatosk(): Minimum length of a 1st-pass-corrected read to be used for coloring in 2nd pass cannot be less than 0.\n"); return 1; }
+    }
     std::string self = argv0; // this executable and the index tool next to it
     { char exe[4096]; const ssize_t n = readlink("/proc/self/exe", exe, sizeof(exe) - 1); if (n > 0) { exe[n] = 0; self = exe; } }
     const std::string dir = self.find('/') == std::string::npos ? std::string(".") : self.substr(0, self.rfind('/')), tool = dir + "/rtk_build_index", rescue_tool = dir + "/rtk_rescue_reads";
@@ -155,6 +170,11 @@ static int correct_from_short_reads(const Opt& opt, const char* argv0) {
         for (size_t i = 0; i < opt.in_short.size(); ++i) { a.push_back("-s"); a.push_back(opt.in_short[i]); }
         if (!extra_sr.empty()) { a.push_back("-s"); a.push_back(extra_sr); }
         for (size_t i = 0; i < colour.size(); ++i) { a.push_back("--colour-reads"); a.push_back(colour[i]); }
+        if (!colour.empty() && (!opt.min_conf_colour2.empty() || !opt.min_len_colour2.empty())) { // the second-pass index alone (DESIGN.md section 4 [A14]); neither given: the command line of before
+            if (!opt.min_conf_colour2.empty()) { a.push_back("--colour-min-conf"); a.push_back(opt.min_conf_colour2); }
+            if (!opt.min_len_colour2.empty()) { a.push_back("--colour-min-len"); a.push_back(opt.min_len_colour2); }
+            if (!opt.max_qual_given.empty()) { a.push_back("--colour-max-qual"); a.push_back(opt.max_qual_given); }
+        }
         if (!opt.no_snps) a.push_back("--snps");
         if (opt.merge_duplicates) a.push_back("--merge-duplicates");
         if (opt.subsample) { a.push_back("--subsample-colours"); if (!opt.subsample_seed.empty()) { a.push_back("--subsample-seed"); a.push_back(opt.subsample_seed); } }
@@ -252,12 +272,14 @@ int main(int argc, char** argv) {
             case 'i': opt.insert_sz = strtoull(optarg, nullptr, 10); break;
             case 'k': opt.k1 = atoi(optarg); break;
             case 'w': opt.w1 = strtoull(optarg, nullptr, 10); break;
-            case 'Q': opt.max_qual = atoi(optarg); break;
+            case 'Q': opt.max_qual = atoi(optarg); opt.max_qual_given = optarg; break;
             case 'm': opt.min_conf_snp = atof(optarg); break;
             case 'B': opt.batch_bases = strtoull(optarg, nullptr, 10); break;
             case 'r': opt.rounds = atoi(optarg); break;
             case 'F': opt.no_snps = true; break; // only read by the index step (detectSNPs, src/Ratatosk.cpp:1067,1124): `correct -s` builds its indexes without --snps
-            case 'I': case 'S': case 'M': case 'C': break; // only read by `index` (detectSNPs, .bfi, addCoverage: src/Ratatosk.cpp:1067,1124; src/Graph.cpp:1573,1796,2117)
+            case 'I': case 'S': break; // only read by `index` (detectSNPs, .bfi, addCoverage: src/Ratatosk.cpp:1067,1124; src/Graph.cpp:2117)
+            case 'M': opt.min_conf_colour2 = optarg; break; // addCoverage of the second-pass index (src/Graph.cpp:1573, 1796): `correct -s` hands them to its k2 index step;
+            case 'C': opt.min_len_colour2 = optarg; break;  // next to a pre-built index (-g, -d) nothing reads them
             case 'O': break; // output is in input order in both passes here (src/Ratatosk.cpp:919 re-orders only when asked in pass 2)
             case 'f': opt.force_snp = true; break; // fixSNPs() before phasing() in the second pass (src/Ratatosk.cpp:279,828); the first pass does not look at it
             case 'u': opt.in_unmapped.push_back(optarg); break; // (with -g / -d: refused below, once every option is read)

@@ -8,6 +8,7 @@
 #include <memory>
 #include <mutex>
 
+#include "colour_filter.hpp"
 #include "state.hpp"
 
 namespace rtk {
@@ -17,13 +18,26 @@ inline size_t pair_name_len(const char* p, size_t n) { return (n > 2 && p[n - 2]
 
 // --gpu: the reads are handed to the device chunk by chunk (csrc/hip/rtk_index.hip rtk_index_colour_*: the k-mer table of the unitigs in HBM, one lane per
 // read position); this tool keeps what is its own -- reading, and the numbering of the reads. Every thread fills a chunk of its own.
+// With a confidence threshold (q_min != 0; tools/index/colour_filter.hpp) the quality bytes travel beside the characters and the device masks (fn_q); a library without
+// that entry gets characters masked here.
 struct Feed {
-    std::string chars; std::vector<uint64_t> starts; std::vector<uint32_t> ids; void* job; HipLib::col_chunk_fn fn; std::atomic<int>* failed;
-    void flush() { if (ids.empty()) return; if (fn(job, chars.data(), chars.size(), starts.data(), ids.data(), static_cast<uint32_t>(ids.size())) != 0) *failed = 1; chars.clear(); starts.clear(); ids.clear(); }
-    void add(const char* seq, size_t len, uint32_t id) {
+    std::string chars, quals; std::vector<uint64_t> starts; std::vector<uint32_t> ids; void* job; HipLib::col_chunk_fn fn; std::atomic<int>* failed;
+    HipLib::col_chunk_q_fn fn_q = nullptr; unsigned char q_min = 0;
+    void flush() {
+        if (ids.empty()) return;
+        const int rc = q_min && fn_q ? fn_q(job, chars.data(), reinterpret_cast<const unsigned char*>(quals.data()), q_min, chars.size(), starts.data(), ids.data(), static_cast<uint32_t>(ids.size()))
+                                     : fn(job, chars.data(), chars.size(), starts.data(), ids.data(), static_cast<uint32_t>(ids.size()));
+        if (rc != 0) *failed = 1;
+        chars.clear(); quals.clear(); starts.clear(); ids.clear();
+    }
+    void add(const char* seq, const char* qual, size_t len, uint32_t id) {
         if (len + 1 > (60u << 20)) { *failed = 1; return; } // (a read longer than a chunk)
         if (chars.size() + len + 1 > (60u << 20) || ids.size() >= (2u << 20) || (chars.size() >= (24u << 20))) flush();
-        starts.push_back(chars.size()); ids.push_back(id); chars.append(seq, len); chars.push_back('\n');
+        starts.push_back(chars.size()); ids.push_back(id);
+        if (q_min && !fn_q) { const size_t at = chars.size(); chars.resize(at + len); colour_mask_bases(seq, qual, len, q_min, &chars[at]); }
+        else chars.append(seq, len);
+        chars.push_back('\n');
+        if (q_min && fn_q) { quals.append(qual, len); quals.push_back('\n'); } // (the byte beside a separator is not looked at)
     }
 };
 
@@ -33,8 +47,12 @@ template <class KM> struct ColourSink {
     HipLib::col_cov_fn cov_fn = nullptr; HipLib::col_end_sub_fn end_sub_fn = nullptr; bool open_job = false; // --subsample-colours: the job stays open (open_job) between the coverage and the thinned events
     HipLib::col_merge_fn merge_fn = nullptr; HipLib::col_merge_classes_fn merge_classes_fn = nullptr; // --merge-duplicates (pairs only): the events merged in place in the open job
     std::vector<std::vector<uint64_t> > cov; std::vector<std::vector<std::pair<uint32_t, uint32_t> > > ev; // host: per thread, k-mers per unitig and (unitig, id) events
+    // --colour-reads with --colour-min-conf / --colour-min-len (tools/index/colour_filter.hpp): q_min = 0 and min_len = 0 when not given
+    const unsigned char q_min; const uint64_t min_len; HipLib::col_chunk_q_fn chunk_q_fn = nullptr;
+    struct PerThread { std::string masked; uint64_t too_short = 0; char pad[64]; }; std::vector<PerThread> per_thread; // a host thread's masked copy of its read; the reads its length rule left out
 
-    explicit ColourSink(IndexBuild<KM>& st) : s(st), U(st.U), n_u(st.U.size()), failed(0), feeds(st.n_thr), cov(st.n_thr), ev(st.n_thr) {
+    explicit ColourSink(IndexBuild<KM>& st) : s(st), U(st.U), n_u(st.U.size()), failed(0), feeds(st.n_thr), cov(st.n_thr), ev(st.n_thr),
+                                              q_min(st.o.colour_min_conf >= 0.0 ? colour_q_min(st.o.colour_min_conf, st.o.colour_max_qual) : static_cast<unsigned char>(0)), min_len(st.o.colour_min_len), per_thread(st.n_thr) {
         HipLib::col_begin_fn begin_fn = nullptr;
         if (s.o.gpu && s.lib.get(begin_fn, "rtk_index_colour_begin") && s.lib.get(chunk_fn, "rtk_index_colour_chunk") && s.lib.get(end_fn, "rtk_index_colour_end") && !s.knobs.host_colours && n_u > 0) {
             if (s.o.merge && s.o.colour_files.empty() && !(s.lib.get(merge_fn, "rtk_index_colour_merge") && s.lib.get(merge_classes_fn, "rtk_index_colour_merge_classes"))) { // (the events are then fetched at once and every later step runs on the host threads)
@@ -43,18 +61,23 @@ template <class KM> struct ColourSink {
             if (s.o.subsample && host_merge) { cov_fn = nullptr; end_sub_fn = nullptr; }
             else if (s.o.subsample && !(s.lib.get(cov_fn, "rtk_index_colour_cov") && s.lib.get(end_sub_fn, "rtk_index_colour_end_subsampled"))) { // (the events are then fetched the old way, rtk_index_colour_end)
                 cov_fn = nullptr; end_sub_fn = nullptr; fprintf(stderr, "rtk_build_index: --gpu: %s lacks rtk_index_colour_cov / rtk_index_colour_end_subsampled: colours subsampled on the host threads\n", s.lib.path.c_str()); }
+            if (q_min && !s.lib.get(chunk_q_fn, "rtk_index_colour_chunk_q")) { // (the look-ups stay on the device)
+                chunk_q_fn = nullptr; fprintf(stderr, "rtk_build_index: --gpu: %s lacks rtk_index_colour_chunk_q: bases masked on the host threads\n", s.lib.path.c_str()); }
             std::vector<uint64_t> off(n_u + 1, 0); for (size_t u = 0; u < n_u; ++u) off[u + 1] = off[u] + s.U[u].seq.size();
             std::string pool(off[n_u], 'A');
             parallel_for(n_u, s.n_thr, [&](size_t b, size_t e, unsigned) { for (size_t u = b; u < e; ++u) memcpy(&pool[off[u]], s.U[u].seq.data(), s.U[u].seq.size()); });
             if (begin_fn(0, s.k, pool.data(), off.data(), n_u, &job) != 0) { fprintf(stderr, "rtk_build_index: --gpu: colours on the host threads (%s)\n", s.lib.last_error()); job = nullptr; }
             open_job = job != nullptr;
         }
-        for (unsigned t = 0; t < s.n_thr; ++t) { feeds[t].job = job; feeds[t].fn = chunk_fn; feeds[t].failed = &failed; if (!job) cov[t].assign(n_u, 0); }
+        for (unsigned t = 0; t < s.n_thr; ++t) { feeds[t].job = job; feeds[t].fn = chunk_fn; feeds[t].failed = &failed; feeds[t].fn_q = chunk_q_fn; feeds[t].q_min = q_min; if (!job) cov[t].assign(n_u, 0); }
     }
     ~ColourSink() { if (open_job) end_fn(job, nullptr, nullptr, nullptr); } // (left early: the job released)
     // one read, from thread t of the source: its k-mers looked up (the table is only read), or the read handed to the device
-    void read(unsigned t, const char* seq, size_t len, uint32_t id) {
-        if (job) { feeds[t].add(seq, len, id); return; }
+    // (qual: len quality bytes, or null; the sources see to it that a read has them when there is a confidence threshold)
+    void read(unsigned t, const char* seq, const char* qual, size_t len, uint32_t id) {
+        if (len < min_len) { ++per_thread[t].too_short; return; } // (the read keeps its id: the source has numbered it)
+        if (job) { feeds[t].add(seq, qual, len, id); return; }
+        if (q_min) { std::string& m = per_thread[t].masked; m.resize(len); colour_mask_bases(seq, qual, len, q_min, &m[0]); seq = m.data(); }
         std::vector<uint64_t>& c = cov[t]; std::vector<std::pair<uint32_t, uint32_t> >& e = ev[t];
         for_each_canonical_kmer<KM>(seq, len, s.k, s.mask, [&](KM km, size_t) {
             const uint64_t* v = s.km.slot(km, false);
@@ -69,6 +92,7 @@ template <class KM> struct ColourSink {
             for (size_t u = b; u < e; ++u) { const uint64_t* q = p; while (q < evs + n_ev && (*q >> 32) == u) ++q; U[u].colours.resize(static_cast<size_t>(q - p)); for (size_t i = 0; p + i < q; ++i) U[u].colours[i] = static_cast<uint32_t>(p[i] & 0xFFFFFFFFull); p = q; }
         });
     }
+    uint64_t too_short() const { uint64_t n = 0; for (size_t t = 0; t < per_thread.size(); ++t) n += per_thread[t].too_short; return n; }
     void take_cov(const uint64_t* cv) { parallel_for(n_u, s.n_thr, [&](size_t b, size_t e, unsigned) { for (size_t u = b; u < e; ++u) U[u].cov = cv[u]; }); }
     // --gpu: the distinct (unitig, id) events in sorted order and the coverages, back from the device
     bool finish_device() {
@@ -120,10 +144,14 @@ template <class KM> struct ColourSink {
     }
 };
 
+// a colouring record without a quality string of its own length under --colour-min-conf: the one message of all routes
+inline void colour_no_quality(const std::string& file) { fprintf(stderr, "rtk_build_index: --colour-min-conf: %s holds a record without a quality string of its own length (FASTQ input is needed)\n", file.c_str()); }
+
 // Source 1, any input: one reader parses the records and numbers them (a pair keeps one id: the id is the number of name changes before the read;
 // every read its own id with --colour-reads), worker threads take pieces of about 1 MB from a bounded queue.
 template <class KM> static bool colour_from_reader(IndexBuild<KM>& s, ColourSink<KM>& sink, const std::vector<std::string>& col_in, bool by_read) {
-    struct Chunk { std::vector<std::string> seq; std::vector<uint32_t> id; size_t bytes = 0; };
+    struct Chunk { std::vector<std::string> seq, qual; std::vector<uint32_t> id; size_t bytes = 0; }; // (qual: filled with a confidence threshold only)
+    const bool with_qual = sink.q_min != 0;
     std::mutex mq; std::condition_variable cv_put, cv_get; std::deque<std::unique_ptr<Chunk> > q; bool done = false, ok = true;
     std::vector<std::thread> th;
     for (unsigned t = 0; t < s.n_thr; ++t) th.emplace_back([&, t]() {
@@ -131,7 +159,7 @@ template <class KM> static bool colour_from_reader(IndexBuild<KM>& s, ColourSink
             std::unique_ptr<Chunk> c;
             { std::unique_lock<std::mutex> lk(mq); cv_get.wait(lk, [&]() { return !q.empty() || done; }); if (q.empty()) return; c = std::move(q.front()); q.pop_front(); }
             cv_put.notify_one();
-            for (size_t r = 0; r < c->seq.size(); ++r) sink.read(t, c->seq[r].data(), c->seq[r].size(), c->id[r]);
+            for (size_t r = 0; r < c->seq.size(); ++r) sink.read(t, c->seq[r].data(), with_qual ? c->qual[r].data() : nullptr, c->seq[r].size(), c->id[r]);
         }
     });
     std::string name, seq, qual, prev_name;
@@ -145,10 +173,11 @@ template <class KM> static bool colour_from_reader(IndexBuild<KM>& s, ColourSink
             name.erase(pair_name_len(name.data(), name.size()));
             if (first) { first = false; prev_name = name; }
             else if (by_read || name != prev_name) { ++pair_id; prev_name = name; }
+            if (with_qual) { if (qual.size() != seq.size()) { colour_no_quality(col_in[f]); ok = false; break; } cur->qual.push_back(std::string()); cur->qual.back().swap(qual); }
             cur->bytes += seq.size(); cur->seq.push_back(std::string()); cur->seq.back().swap(seq); cur->id.push_back(pair_id);
             if (cur->bytes >= (1u << 20)) flush();
         }
-        if (fr.failed()) { fprintf(stderr, "rtk_build_index: %s ends in a damaged or cut-short gzip stream\n", col_in[f].c_str()); ok = false; }
+        if (ok && fr.failed()) { fprintf(stderr, "rtk_build_index: %s ends in a damaged or cut-short gzip stream\n", col_in[f].c_str()); ok = false; }
     }
     flush();
     { std::lock_guard<std::mutex> lk(mq); done = true; }
@@ -172,7 +201,7 @@ template <class KM> static bool colour_from_samples(IndexBuild<KM>& s, ColourSin
             std::string m(2 * static_cast<size_t>(L), 'A');
             for (;;) { const uint64_t c = nx.fetch_add(1); if (c >= n_ch) break;
                 const uint64_t p0 = c * per, p1 = std::min<uint64_t>(ss->n_pairs(), p0 + per);
-                for (uint64_t p = p0; p < p1; ++p) { ss->pair(p, &m[0], &m[L]); for (int mate = 0; mate < 2; ++mate) sink.read(t, m.data() + mate * L, L, static_cast<uint32_t>(id_base + p)); }
+                for (uint64_t p = p0; p < p1; ++p) { ss->pair(p, &m[0], &m[L]); for (int mate = 0; mate < 2; ++mate) sink.read(t, m.data() + mate * L, nullptr, L, static_cast<uint32_t>(id_base + p)); }
             } });
         for (size_t t = 0; t < th.size(); ++t) th[t].join();
         id_base += ss->n_pairs();
@@ -190,19 +219,20 @@ template <class KM> static bool colour_from_plain_ranges(IndexBuild<KM>& s, Colo
         PlainChunks pc; if (!pc.open(col_in[f], 32u << 20)) { fprintf(stderr, "rtk_build_index: cannot open %s\n", col_in[f].c_str()); return false; }
         const size_t nc = pc.n_chunks();
         std::vector<RangeInfo> info(nc); std::vector<uint32_t> id0(nc, 0); // id0: id of the first read of every range
-        std::atomic<int> bad(0);
+        std::atomic<int> bad(0), no_quality(0); const bool with_qual = sink.q_min != 0;
         // sweep(map the reads, or only count): every range parsed by a thread; the names walked, the changes counted from id0 of the range
         auto sweep = [&](bool map) {
             std::atomic<size_t> nx(0); std::vector<std::thread> th;
             for (unsigned t = 0; t < s.n_thr; ++t) th.emplace_back([&, t]() {
                 for (;;) { const size_t i = nx.fetch_add(1); if (i >= nc) break;
-                    PackedReads r(false); if (!pc.parse_chunk(i, r)) { bad = 1; break; }
+                    PackedReads r(with_qual); if (!pc.parse_chunk(i, r)) { bad = 1; break; }
                     RangeInfo& ri = info[i]; uint32_t id = id0[i]; const char* pp = nullptr; size_t pn = 0;
                     for (size_t x = 0; x < r.size(); ++x) {
                         const char* p = r.name(x); const size_t n = pair_name_len(p, r.name_len(x));
                         if (x != 0 && (by_read || n != pn || memcmp(p, pp, n) != 0)) ++id;
                         pp = p; pn = n;
-                        if (map) sink.read(t, r.seq(x), r.seq_len(x), id);
+                        if (with_qual && !r.qual(x)) { no_quality = 1; bad = 1; break; }
+                        if (map) sink.read(t, r.seq(x), with_qual ? r.qual(x) : nullptr, r.seq_len(x), id);
                         else if (x == 0) ri.first.assign(p, n);
                     }
                     if (!map) { ri.n_reads = r.size(); ri.changes = id - id0[i]; if (r.size()) ri.last.assign(pp, pn); }
@@ -210,6 +240,7 @@ template <class KM> static bool colour_from_plain_ranges(IndexBuild<KM>& s, Colo
             for (size_t t = 0; t < th.size(); ++t) th[t].join();
         };
         sweep(false);
+        if (no_quality) colour_no_quality(col_in[f]);
         if (bad) return false;
         for (size_t i = 0; i < nc; ++i) {
             if (info[i].n_reads == 0) { id0[i] = next_id; continue; }
@@ -231,6 +262,12 @@ template <class KM> static bool colour_and_cover(IndexBuild<KM>& s) {
     bool all_sampled = s.o.fast && !by_read && !col_in.empty(), all_plain = s.o.fast;
     for (size_t f = 0; f < col_in.size(); ++f) { all_sampled = all_sampled && SampleSource::is_spec(col_in[f]); all_plain = all_plain && PlainChunks::is_plain(col_in[f]); }
     const bool ok = all_sampled ? colour_from_samples(s, sink, col_in) : (all_plain ? colour_from_plain_ranges(s, sink, col_in, by_read) : colour_from_reader(s, sink, col_in, by_read));
+    if (s.knobs.trace && (sink.q_min || sink.min_len)) { // (the same line on every route)
+        fprintf(stderr, "rtk_build_index: colour filter:");
+        if (sink.q_min) fprintf(stderr, " bases of the colouring reads with a quality byte below %u masked%s", static_cast<unsigned>(sink.q_min), sink.min_len ? ";" : "");
+        if (sink.min_len) fprintf(stderr, " %llu colouring reads shorter than %llu left out", static_cast<unsigned long long>(sink.too_short()), static_cast<unsigned long long>(sink.min_len));
+        fprintf(stderr, "\n");
+    }
     const bool sub_there = s.o.subsample && sink.job && sink.end_sub_fn, merge_there = sink.job && sink.merge_fn;
     if (sub_there || merge_there) { // the events wait on the device for the merging or the subsampling step
         if ((sub_there && !sink.cov_device()) || !ok) return false;

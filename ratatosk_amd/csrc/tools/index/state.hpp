@@ -32,12 +32,14 @@ struct IndexOptions {
     bool subsample = false; uint64_t subsample_seed = 1; // --subsample-colours [--subsample-seed N]: the colours thinned out by coverage (tools/index/subsample.hpp)
     bool merge = false; // --merge-duplicates: read pairs on the same unitigs share one colour id (tools/index/merge.hpp)
     std::vector<std::string> colour_files; // pass-2 index (`Ratatosk index -2`): colours = ids of these (pass-1 corrected long) reads, one id per read
+    // --colour-min-conf M / --colour-max-qual Q / --colour-min-len N (only with --colour-reads; tools/index/colour_filter.hpp has the rule): min_conf < 0 = not given
+    double colour_min_conf = -1.0; int colour_max_qual = 40; uint64_t colour_min_len = 0;
     std::string out_file(const char* ext) const { return prefix + ".index.k" + std::to_string(k) + ext; }
 };
 
 // 0, or the exit status (2: the message or the usage text is on stderr)
 inline int parse_options(int argc, char** argv, IndexOptions& o) {
-    bool seed_given = false;
+    bool seed_given = false; const char* filter_given = nullptr;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto need = [&](const char* n) -> const char* { if (i + 1 >= argc) { fprintf(stderr, "rtk_build_index: missing value for %s\n", n); exit(2); } return argv[++i]; };
@@ -55,11 +57,18 @@ inline int parse_options(int argc, char** argv, IndexOptions& o) {
         else if (a == "--merge-duplicates") o.merge = true;
         else if (a == "--subsample-seed") { const char* v = need("--subsample-seed"); char* end = nullptr; o.subsample_seed = strtoull(v, &end, 10); seed_given = true;
             if (*v < '0' || *v > '9' || *end) { fprintf(stderr, "rtk_build_index: --subsample-seed takes an unsigned number, not '%s'\n", v); return 2; } }
+        else if (a == "--colour-min-conf") { const char* v = need("--colour-min-conf"); char* end = nullptr; o.colour_min_conf = strtod(v, &end); filter_given = "--colour-min-conf";
+            if (end == v || *end || !(o.colour_min_conf >= 0.0 && o.colour_min_conf <= 1.0)) { fprintf(stderr, "rtk_build_index: --colour-min-conf takes a number in [0, 1], not '%s'\n", v); return 2; } }
+        else if (a == "--colour-max-qual") { const char* v = need("--colour-max-qual"); char* end = nullptr; const long q = strtol(v, &end, 10); filter_given = "--colour-max-qual";
+            if (end == v || *end || q < 1 || q > 93) { fprintf(stderr, "rtk_build_index: --colour-max-qual takes a number in 1 .. 93, not '%s'\n", v); return 2; } o.colour_max_qual = static_cast<int>(q); }
+        else if (a == "--colour-min-len") { const char* v = need("--colour-min-len"); char* end = nullptr; o.colour_min_len = strtoull(v, &end, 10); filter_given = "--colour-min-len";
+            if (*v < '0' || *v > '9' || *end) { fprintf(stderr, "rtk_build_index: --colour-min-len takes an unsigned number, not '%s'\n", v); return 2; } }
         else if (a == "--dump-input") o.dump_input = need("--dump-input");
         else { fprintf(stderr, "rtk_build_index: unknown option %s\n", a.c_str()); return 2; }
     }
     if (seed_given && !o.subsample) { fprintf(stderr, "rtk_build_index: --subsample-seed without --subsample-colours\n"); return 2; }
-    if (o.in_files.empty() || o.k < 3 || o.k > RTK_MAX_K || !(o.k & 1)) { fprintf(stderr, "usage: rtk_build_index -s reads.fq [-s ...] -o PREFIX [-k 31 (odd, <=63)] [--min-count 2] [--global-cov-factor 3.0] [--no-short-cycles] [--snps] [--fast | --gpu (k <= 63: same files, threads / the device for the heavy steps)] [--dump-input FILE] [--subsample-colours [--subsample-seed 1 (only with --subsample-colours)]: colours subsampled by coverage as the reference's index step does by default] [--merge-duplicates: read pairs that lie on the same unitigs share one colour id, as the reference's index step merges duplicated reads (no effect with --colour-reads)] [--colour-reads corrected_long_reads.fq: second-pass index, the graph comes from -s, colours and coverage from these reads]\n"); return 2; }
+    if (filter_given && o.colour_files.empty()) { fprintf(stderr, "rtk_build_index: %s without --colour-reads\n", filter_given); return 2; }
+    if (o.in_files.empty() || o.k < 3 || o.k > RTK_MAX_K || !(o.k & 1)) { fprintf(stderr, "usage: rtk_build_index -s reads.fq [-s ...] -o PREFIX [-k 31 (odd, <=63)] [--min-count 2] [--global-cov-factor 3.0] [--no-short-cycles] [--snps] [--fast | --gpu (k <= 63: same files, threads / the device for the heavy steps)] [--dump-input FILE] [--subsample-colours [--subsample-seed 1 (only with --subsample-colours)]: colours subsampled by coverage as the reference's index step does by default] [--merge-duplicates: read pairs that lie on the same unitigs share one colour id, as the reference's index step merges duplicated reads (no effect with --colour-reads)] [--colour-reads corrected_long_reads.fq: second-pass index, the graph comes from -s, colours and coverage from these reads [--colour-min-conf M (0 .. 1): a base of these reads whose quality is below that of confidence M colours nothing, as the reference's second-pass index does with -M (0: the '!' bases); needs FASTQ] [--colour-max-qual 40: the quality that stands for confidence 1 (-Q)] [--colour-min-len N: a read of fewer than N bases colours nothing (-C); these three only with --colour-reads]]\n"); return 2; }
     return 0;
 }
 
