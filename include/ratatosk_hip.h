@@ -253,6 +253,13 @@ int rtk_fix_snps(rtk_graph* g, const char* seq, uint32_t len, char* out);
 int rtk_seeds(rtk_graph* g, const rtk_opts* opts, const char* seq, uint32_t len,
               uint64_t* n_solid, int64_t* solid, uint64_t* n_weak, int64_t* weak, uint64_t cap);
 
+/* getSeeds of read `read` of a batch of SEVERAL reads: the anchors rtk_batch_run_seeds left for it, as the same (pos, unitig, dist, strand) quadruples as
+ * rtk_seeds, positions in the read's own coordinates (rtk_seeds is this call on a batch of one read). Valid after rtk_batch_run_seeds has completed and
+ * until the batch is run again (rtk_batch_run_regions consumes the anchors). *n_solid / *n_weak are the true counts; up to cap quadruples of each list are
+ * written. RTK_ERR_ARG for read >= the reads of the batch, for a batch whose seed stage has not completed, and -- after writing what fits, like rtk_seeds --
+ * for a cap below either count. Appended without a new revision number: see RTK_API_REVISION. */
+int rtk_batch_fetch_seeds(rtk_batch* b, uint32_t read, uint64_t* n_solid, int64_t* solid, uint64_t* n_weak, int64_t* weak, uint64_t cap);
+
 /* edlibAlign + edlibAlignmentToCigar (reference: src/edlib.cpp:141,298) with the IUPAC equality table of
  * src/Common.hpp:262-276 (use_iupac=0: edlibDefaultAlignConfig). mode 0 NW, 1 SHW, 2 HW; k<0 unbounded.
  * dist[i] = editDistance or -1; end_locs holds up to cap_locs locations per problem; cigars (standard format)
@@ -426,7 +433,7 @@ const char* rtk_version(void);
  * 8: rtk_stats fields n_fa_linked_*; 9: rtk_rescue_begin / _chunk / _end; still 9: rtk_stats fields n_strand2_* and n_park_*, the test-only rtk_myers_batch mode 5, appended at the end -- a library of revision 9
  * without them leaves them as the caller set them;
  * 10: rtk_sets_batch, rtk_stats fields n_colours_*; still 10: rtk_index_colour_cov, rtk_index_colour_end_subsampled, rtk_index_subsample_events, then rtk_index_colour_merge,
- * rtk_index_colour_merge_classes, rtk_index_merge_events, then rtk_index_colour_chunk_q, appended -- a library of revision 10 without them lacks the symbols, and callers look them up by name). */
+ * rtk_index_colour_merge_classes, rtk_index_merge_events, then rtk_index_colour_chunk_q, then rtk_batch_fetch_seeds, appended -- a library of revision 10 without them lacks the symbols, and callers look them up by name). */
 #define RTK_API_REVISION 10
 int rtk_api_revision(void);
 

@@ -128,6 +128,8 @@ def load_library(path=None):
         L.rtk_index_merge_events.argtypes = [C.c_int, C.POINTER(C.c_uint64), C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     if hasattr(L, "rtk_index_colour_chunk_q"):  # (still revision 10: appended; a library without it: index_colour_reads says so)
         L.rtk_index_colour_chunk_q.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_ubyte, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.c_uint32]
+    if hasattr(L, "rtk_batch_fetch_seeds"):  # (still revision 10: appended; a library without it: Batch.seeds says so)
+        L.rtk_batch_fetch_seeds.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_int64), C.POINTER(C.c_uint64), C.POINTER(C.c_int64), C.c_uint64]
     L.rtk_free.argtypes = [C.c_void_p]
     _libs[path] = L
     return L
@@ -234,7 +236,8 @@ class Batch:
             qual_arr = (C.c_char_p * n)(*bq)
         lens = (C.c_uint32 * n)(*[len(b) for b in bs])
         self.n = n
-        self.in_bases = sum(len(b) for b in bs)
+        self.lens = [len(b) for b in bs]
+        self.in_bases = sum(self.lens)
         self.h = C.c_void_p()
         if raw is not None:
             br = [_b(s) for s in raw]
@@ -257,6 +260,23 @@ class Batch:
         """Stage B (region correction + stitching); needs run_seeds of this batch."""
         o = opts or self.g.opts()
         self.g._check(self.L.rtk_batch_run_regions(self.h, C.byref(o)))
+
+    def seeds(self, i, cap=None):
+        """Anchors of read i after run_seeds, as Graph.seeds gives them for a single read: (solid, weak) lists of (pos, unitig, dist, strand) with positions
+        in the read's own coordinates (stage entry rtk_batch_fetch_seeds). Valid until the batch is run again."""
+        if not hasattr(self.L, "rtk_batch_fetch_seeds"):
+            raise RtkError("%s lacks rtk_batch_fetch_seeds (anchors of one read of a batch: appended at interface revision 10)" % self.L._name)
+        ns, nw = C.c_uint64(), C.c_uint64()
+        if cap is None:  # ask for the two counts first (the entry sets them before it refuses a capacity of 0): the lists are as long as they need to be
+            one = (C.c_int64 * 4)()
+            rc = self.L.rtk_batch_fetch_seeds(self.h, i, C.byref(ns), one, C.byref(nw), one, 0)
+            if rc != 0 and b"capacity" not in self.L.rtk_last_error():
+                self.g._check(rc)
+            cap = max(ns.value, nw.value)
+        so, we = (C.c_int64 * (4 * max(1, cap)))(), (C.c_int64 * (4 * max(1, cap)))()
+        self.g._check(self.L.rtk_batch_fetch_seeds(self.h, i, C.byref(ns), so, C.byref(nw), we, cap))
+        f = lambda a, n: [(a[4 * j], a[4 * j + 1], a[4 * j + 2], a[4 * j + 3]) for j in range(n)]
+        return f(so, ns.value), f(we, nw.value)
 
     def fetch(self):
         n = self.n

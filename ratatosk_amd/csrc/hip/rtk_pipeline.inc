@@ -328,6 +328,24 @@ static int seed_stage_checked(rtk_batch* b, const OptsView& ov) {
     return rtk_fail(RTK_ERR_DEVICE, "seed stage: scratch capacity exceeded after 3 attempts");
 }
 
+// The one reader of the seed stage's output layout (BatchView, rtk_seeds.h): the anchors of read `read` of a batch whose seed stage has completed, as
+// (pos, unitig, dist, strand) quadruples with positions in the read's own coordinates. Read r keeps its solid positions at s_pos[roff[r] .. + n_solid[r])
+// and looks their hits up in hits[roff[r] + pos]; its weak anchors are wk_pos / wk_hit[w_off[r] .. + w_cnt[r]). Up to `cap` quadruples of each list are
+// written; the counts are always the true ones, and a list longer than `cap` is an RTK_ERR_ARG in the name of the entry `who`.
+static int read_anchors(rtk_batch* b, uint32_t read, uint64_t* n_solid, int64_t* solid, uint64_t* n_weak, int64_t* weak, uint64_t cap, const char* who) {
+    const uint64_t base = b->roff[read]; const uint64_t len = b->roff[read + 1] - base;
+    uint32_t ns = 0, nw = 0; uint64_t woff = 0;
+    rtk_d2h(&ns, b->bv.n_solid + read, 4); rtk_d2h(&nw, b->bv.w_cnt + read, 4); rtk_d2h(&woff, b->bv.w_off + read, 8);
+    std::vector<uint32_t> sp(ns + 1), wp(nw + 1); std::vector<uint64_t> hits(len + 1), wh(nw + 1);
+    rtk_d2h(sp.data(), b->bv.s_pos + base, 4ull * ns); rtk_d2h(hits.data(), b->bv.hits + base, 8ull * len);
+    rtk_d2h(wp.data(), b->bv.wk_pos + woff, 4ull * nw); rtk_d2h(wh.data(), b->bv.wk_hit + woff, 8ull * nw);
+    *n_solid = ns; *n_weak = nw;
+    for (uint32_t i = 0; i < ns && i < cap; ++i) { const UMap u = rtk_unpack_hit(hits[sp[i]]); solid[4 * i] = sp[i]; solid[4 * i + 1] = u.unitig; solid[4 * i + 2] = u.dist; solid[4 * i + 3] = u.strand; }
+    for (uint32_t i = 0; i < nw && i < cap; ++i) { const UMap u = rtk_unpack_hit(wh[i]); weak[4 * i] = wp[i]; weak[4 * i + 1] = u.unitig; weak[4 * i + 2] = u.dist; weak[4 * i + 3] = u.strand; }
+    if (ns > cap || nw > cap) return rtk_fail(RTK_ERR_ARG, std::string(who) + ": output capacity too small");
+    return RTK_OK;
+}
+
 extern "C" int rtk_seeds(rtk_graph* g, const rtk_opts* opts, const char* seq, uint32_t len, uint64_t* n_solid, int64_t* solid, uint64_t* n_weak, int64_t* weak, uint64_t cap) {
     if (!g || !opts || !seq || !n_solid || !solid || !n_weak || !weak) return rtk_fail(RTK_ERR_ARG, "rtk_seeds: null argument");
     if (!opts_ok(opts)) return rtk_fail(RTK_ERR_ARG, "rtk_seeds: rtk_opts was not filled by this library's rtk_opts_default (struct_size does not match: older header, or a zero-filled struct)");
@@ -337,20 +355,20 @@ extern "C" int rtk_seeds(rtk_graph* g, const rtk_opts* opts, const char* seq, ui
     if (rc) return rc;
     try {
         rc = seed_stage_checked(b, opts_view(opts));
-        if (rc == RTK_OK) {
-            uint32_t ns = 0, nw = 0; uint64_t woff = 0;
-            rtk_d2h(&ns, b->bv.n_solid, 4); rtk_d2h(&nw, b->bv.w_cnt, 4); rtk_d2h(&woff, b->bv.w_off, 8);
-            std::vector<uint32_t> sp(ns + 1), wp(nw + 1); std::vector<uint64_t> hits(len + 1), wh(nw + 1);
-            rtk_d2h(sp.data(), b->bv.s_pos, 4ull * ns); rtk_d2h(hits.data(), b->bv.hits, 8ull * len);
-            rtk_d2h(wp.data(), b->bv.wk_pos + woff, 4ull * nw); rtk_d2h(wh.data(), b->bv.wk_hit + woff, 8ull * nw);
-            *n_solid = ns; *n_weak = nw;
-            for (uint32_t i = 0; i < ns && i < cap; ++i) { const UMap u = rtk_unpack_hit(hits[sp[i]]); solid[4 * i] = sp[i]; solid[4 * i + 1] = u.unitig; solid[4 * i + 2] = u.dist; solid[4 * i + 3] = u.strand; }
-            for (uint32_t i = 0; i < nw && i < cap; ++i) { const UMap u = rtk_unpack_hit(wh[i]); weak[4 * i] = wp[i]; weak[4 * i + 1] = u.unitig; weak[4 * i + 2] = u.dist; weak[4 * i + 3] = u.strand; }
-            if (ns > cap || nw > cap) rc = rtk_fail(RTK_ERR_ARG, "rtk_seeds: output capacity too small");
-        }
+        if (rc == RTK_OK) rc = read_anchors(b, 0, n_solid, solid, n_weak, weak, cap, "rtk_seeds");
     } catch (const std::exception& e) { rc = rtk_fail(RTK_ERR_DEVICE, e.what()); }
     delete b;
     return rc;
+}
+
+extern "C" int rtk_batch_fetch_seeds(rtk_batch* b, uint32_t read, uint64_t* n_solid, int64_t* solid, uint64_t* n_weak, int64_t* weak, uint64_t cap) {
+    if (!b || !n_solid || !solid || !n_weak || !weak) return rtk_fail(RTK_ERR_ARG, "rtk_batch_fetch_seeds: null argument");
+    if (!b->seeded) return rtk_fail(RTK_ERR_ARG, "rtk_batch_fetch_seeds: rtk_batch_run_seeds has not completed for this batch (or its region stage has run since)");
+    if (read >= b->n) return rtk_fail(RTK_ERR_ARG, "rtk_batch_fetch_seeds: the batch has no such read");
+    try {
+        rtk_set_device(b->g->device);
+        return read_anchors(b, read, n_solid, solid, n_weak, weak, cap, "rtk_batch_fetch_seeds");
+    } catch (const std::exception& e) { return rtk_fail(RTK_ERR_DEVICE, e.what()); }
 }
 
 extern "C" void rtk_batch_free(rtk_batch* b) { delete b; }

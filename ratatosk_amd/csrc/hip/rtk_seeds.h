@@ -324,7 +324,9 @@ RTK_FN void rtk_mask_read(const GraphView& g, const OptsView& o, const BatchView
                         return true; });
                     if (!ovf) unmask = rtk_set_inter_count(sc.set[3], nL, sc.set[cur], nR, o.min_cov_vertices) < o.min_cov_vertices;
                 }
-                if (unmask) rtk_wcopy(bv.masked + base + pv + k, bv.seq + base + pv + k, diff - k);
+                // two hits fewer than k windows apart (the rules above only let them through when the insert size is below 2 k): the reference's length diff - k
+                // wraps around and std::string::replace cuts it off at the end of the read (src/Graph.cpp:115,124,182) -- everything behind the first hit's k-mer is opened
+                if (unmask) rtk_wcopy(bv.masked + base + pv + k, bv.seq + base + pv + k, diff >= k ? diff - k : L - (pv + k));
             }
             if (first < 0) first = p;
         }
@@ -345,12 +347,15 @@ RTK_FN void rtk_mask_read(const GraphView& g, const OptsView& o, const BatchView
 #define RTK_EDIT_INS 2u
 #define RTK_EDIT_DEL 4u
 
-// variant v (0..245) of the window whose first k-1 / k / k+1 characters are (w_k1, w_ck, w_ck1): 2-bit code of the graph k-mer to look for
+// variant v (0..245) of the window whose first k-1 / k / k+1 characters are (w_k1, w_ck, w_ck1): 2-bit code of the graph k-mer to look for.
+// The numbering is that of k = 31 (rtk_variant_kind keys on it); at a smaller k the variants whose offset the window does not have -- substitution and
+// insertion offsets from k on, deletion offsets above k - 2 -- are not valid, so no shift count below goes negative.
 RTK_DEV bool rtk_variant_code(int v, int k, uint64_t w_k1, uint32_t w_ck, uint32_t w_ck1, uint64_t* code_out) {
     uint64_t code = 0; bool valid = false;
     if (v < 93) { // substitution: needs k characters
         if (w_ck <= 3) {
             const int oo = v / 3, j = v % 3;
+            if (oo >= k) { *code_out = 0; return false; }
             const uint64_t full = (w_k1 << 2) | w_ck;
             const int sh = 2 * (k - 1 - oo);
             const uint32_t orig = static_cast<uint32_t>((full >> sh) & 3ull);
@@ -359,6 +364,7 @@ RTK_DEV bool rtk_variant_code(int v, int k, uint64_t w_k1, uint32_t w_ck, uint32
         }
     } else if (v < 217) { // graph k-mer has one extra base: k-1 read characters + an inserted one
         const int vv = v - 93, oo = vv / 4; const uint64_t nb = static_cast<uint64_t>(vv % 4);
+        if (oo >= k) { *code_out = 0; return false; }
         const int rest = k - 1 - oo; // characters after the inserted base
         const uint64_t lo_mask = rest ? ((1ull << (2 * rest)) - 1ull) : 0ull;
         code = ((w_k1 >> (2 * rest)) << (2 * rest + 2)) | (nb << (2 * rest)) | (w_k1 & lo_mask); valid = true;
@@ -368,6 +374,7 @@ RTK_DEV bool rtk_variant_code(int v, int k, uint64_t w_k1, uint32_t w_ck, uint32
     } else if (v < RTK_N_VARIANTS) { // graph k-mer lacks one interior read base: k+1 read characters
         if (w_ck <= 3 && w_ck1 <= 3) {
             const int oo = v - 217 + 1; // deleted offset in [1, k-2]
+            if (oo > k - 2) { *code_out = 0; return false; }
             const uint64_t full2 = (w_k1 << 4) | (static_cast<uint64_t>(w_ck) << 2) | static_cast<uint64_t>(w_ck1); // k+1 characters (exactly 64 bits for k = 31)
             const int keep_lo = k - oo; // characters after the deleted one
             const uint64_t lo_mask = (1ull << (2 * keep_lo)) - 1ull;

@@ -18,9 +18,11 @@ def test_gpu_seeds_clean(ds_clean):
 
 def test_gpu_seeds_variant_enumeration_agrees(ds_small, ds_tandem, ds_k25, monkeypatch):
     assert _check(ds_tandem, 40, None) > 0
+    assert _check(ds_k25, 6, None, k=25) > 0
     monkeypatch.setenv("RTK_INEXACT_ENUM", "1")
     assert _check(ds_small, 12, None) > 0
     assert _check(ds_tandem, 40, None) > 0
+    assert _check(ds_k25, 6, None, k=25) > 0
 
 
 def test_gpu_seeds_mask_in_segments(ds_small, ds_clean, tmp_path, monkeypatch):

@@ -70,17 +70,18 @@ def _gap_reads(prefix, reps, seed=5):
     return reads
 
 
-def _check_gap_reads(prefixes, reps, segs, lib_path, monkeypatch):
+def _check_gap_reads(prefixes, reps, segs, lib_path, monkeypatch, opts=None):
+    """opts: option fields (insert_sz=...) given to the oracle and to the device alike; None = the defaults"""
     for prefix in prefixes:
         fa, rt = prefix + ".index.k31.fasta.gz", prefix + ".index.k31.rtsk"
         og = op.Graph(fa, rt, 31)
         reads = _gap_reads(prefix, reps)
-        want = [og.seeds(s) for s in reads]
+        want = [og.seeds(s, og.opts(**opts) if opts else None) for s in reads]
         for seg in segs:
             monkeypatch.setenv("RTK_MASK_SEG", seg)
             pg = api.Graph(fa, rt, 31, device=0, lib_path=lib_path)
             for s, w in zip(reads, want):
-                assert pg.seeds(s) == w, (prefix, seg, len(s))
+                assert pg.seeds(s, pg.opts(**opts) if opts else None) == w, (prefix, seg, len(s))
 
 
 def test_sim_seeds_mask_gaps_across_segment_borders(ds_clean, ds_small, monkeypatch):
