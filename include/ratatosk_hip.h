@@ -370,6 +370,24 @@ int rtk_index_colour_merge_classes(void* job, uint64_t* classes_above_one, uint6
 int rtk_index_merge_events(int device, const uint64_t* events, uint64_t n_events, uint32_t n_unitigs, uint64_t* events_out, uint64_t* n_out, uint64_t* n_ids_before,
                            uint64_t* n_ids_after);
 
+/* rtk_index_snp_candidates: the candidate search of the SNP annotations of an index build (rtk_build_index --gpu --snps; detectSNPs, src/Graph.cpp:484-720:
+ * searchSequence with one substitution over every window of a unitig) on the device. Unitig u = seq_pool[seq_off[u] .. seq_off[u + 1]) as for rtk_index_colour_begin
+ * (characters A/C/G/T, every unitig of at least k of them), odd k in 3 .. 63. searched[u] != 0: the windows of u are queried (NULL: those of every unitig); every
+ * unitig, searched or not, is found as a neighbour. For window p of a searched unitig u with the oriented k-mer x, a candidate is a k-mer y that differs from x at
+ * exactly one offset j (0 = the first base) with base alt there (A=0 C=1 G=2 T=3) and whose canonical form is a k-mer of a unitig w != u (w == u is what the host rule
+ * skips before it looks at anything, src/Graph.cpp:523: dropped here). *cand: two words per candidate, u << 32 | p then j << 40 | alt << 32 | w, ascending by
+ * (u, p, j, alt) -- the order in which the host rule visits them; *n_cand of them (rtk_free). A window has at most 3k candidates; no cap drops any.
+ * flags & RTK_SNP_FIRST_PER_SITE: of all candidates with equal (u, p + j, alt) only the one with the smallest p is kept, the kept ones again in (u, p, j, alt) order.
+ * That is exact for the host's replay: it marks (position p + j, alt) as tried at the first candidate it visits there and returns at once from every later one
+ * (`if (seq_tried[at] == ct) return`, csrc/tools/index/annotate.hpp), so only the first in visiting order -- the smallest p -- can have any effect.
+ * RTK_ERR_FORMAT when a canonical k-mer occurs twice in the unitigs (or a character is no base). The stage needs two sorted views of every window of the pool (key + unitig
+ * id each), a third such array for the sorts, the sort's temporary, two prefix tables and the candidates; the bytes are worked out before anything is allocated and
+ * compared with the free device memory (RTK_INDEX_SNP_MEM lowers that figure): RTK_ERR_DEVICE, with both numbers, when they do not fit -- the key space is not
+ * partitioned, the caller keeps its host route for that case. Appended without a new revision number: see RTK_API_REVISION. */
+#define RTK_SNP_FIRST_PER_SITE 1u
+int rtk_index_snp_candidates(int device, int k, const char* seq_pool, const uint64_t* seq_off, uint64_t n_unitigs, const uint8_t* searched, uint32_t flags,
+                             uint64_t** cand, uint64_t* n_cand);
+
 /* rtk_rescue_*: the rescue of unmapped short reads before the index build (`correct -u`; retrieveMissingReads, src/Graph.cpp:3857-4131, called at
  * src/Ratatosk.cpp:1040-1056), with exact sets where the reference has Bloom filters ([A11]). One-word k-mers (odd k <= 31).
  * begin (replaces buildBBF + the long-read graph build, src/Graph.cpp:3880-3884): lr / sr = the canonical k-mers seen at least twice in the long reads / in
@@ -433,7 +451,7 @@ const char* rtk_version(void);
  * 8: rtk_stats fields n_fa_linked_*; 9: rtk_rescue_begin / _chunk / _end; still 9: rtk_stats fields n_strand2_* and n_park_*, the test-only rtk_myers_batch mode 5, appended at the end -- a library of revision 9
  * without them leaves them as the caller set them;
  * 10: rtk_sets_batch, rtk_stats fields n_colours_*; still 10: rtk_index_colour_cov, rtk_index_colour_end_subsampled, rtk_index_subsample_events, then rtk_index_colour_merge,
- * rtk_index_colour_merge_classes, rtk_index_merge_events, then rtk_index_colour_chunk_q, then rtk_batch_fetch_seeds, appended -- a library of revision 10 without them lacks the symbols, and callers look them up by name). */
+ * rtk_index_colour_merge_classes, rtk_index_merge_events, then rtk_index_colour_chunk_q, then rtk_batch_fetch_seeds, then rtk_index_snp_candidates, appended -- a library of revision 10 without them lacks the symbols, and callers look them up by name). */
 #define RTK_API_REVISION 10
 int rtk_api_revision(void);
 

@@ -130,6 +130,9 @@ def load_library(path=None):
         L.rtk_index_colour_chunk_q.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_ubyte, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.c_uint32]
     if hasattr(L, "rtk_batch_fetch_seeds"):  # (still revision 10: appended; a library without it: Batch.seeds says so)
         L.rtk_batch_fetch_seeds.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_int64), C.POINTER(C.c_uint64), C.POINTER(C.c_int64), C.c_uint64]
+    if hasattr(L, "rtk_index_snp_candidates"):  # (still revision 10: appended; a library without it: index_snp_candidates says so)
+        L.rtk_index_snp_candidates.argtypes = [C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_ubyte), C.c_uint32,
+                                               C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_uint64)]
     L.rtk_free.argtypes = [C.c_void_p]
     _libs[path] = L
     return L
@@ -569,6 +572,41 @@ def index_colour_reads(unitigs, k, reads, ids=None, quals=None, q_min=0, device=
     finally:
         L.rtk_free(ev_p); L.rtk_free(cov_p)
     return events, cov
+
+
+SNP_FIRST_PER_SITE = 1
+
+
+def index_snp_candidates(unitigs, k, searched=None, first_per_site=False, device=0, lib_path=None):
+    """The candidate search of the SNP annotations of an index build, on the device (stage entry rtk_index_snp_candidates, include/ratatosk_hip.h; the split between
+    this search and the host's replay: DESIGN.md section 8). unitigs: sequences of A/C/G/T, each of at least k bases, no canonical k-mer twice; searched: None, or one
+    flag per unitig -- the windows of a flagged unitig are queried, every unitig is found as a neighbour. Returns the list of (u, p, j, alt, w): window p of unitig u with
+    base alt (A=0 .. T=3) at offset j is a k-mer of unitig w != u; ascending by (u, p, j, alt). first_per_site: of the candidates with equal (u, p + j, alt) only the
+    one with the smallest p."""
+    import numpy as np
+    L = load_library(lib_path)
+    if not hasattr(L, "rtk_index_snp_candidates"):
+        raise RtkError("%s lacks rtk_index_snp_candidates (SNP candidates: appended at interface revision 10)" % L._name)
+    seqs = [_b(u) for u in unitigs]
+    off = np.zeros(len(seqs) + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(u) for u in seqs], dtype=np.uint64)
+    flags = None
+    if searched is not None:
+        flags = np.ascontiguousarray([1 if f else 0 for f in searched], dtype=np.uint8)
+        if flags.size != len(seqs):
+            raise ValueError("index_snp_candidates: searched holds one flag per unitig")
+    u64p = C.POINTER(C.c_uint64)
+    cand, n = u64p(), C.c_uint64(0)
+    rc = L.rtk_index_snp_candidates(device, k, b"".join(seqs), off.ctypes.data_as(u64p), len(seqs), None if flags is None else flags.ctypes.data_as(C.POINTER(C.c_ubyte)),
+                                    SNP_FIRST_PER_SITE if first_per_site else 0, C.byref(cand), C.byref(n))
+    if rc != 0:
+        raise RtkError("rtk error %d: %s" % (rc, L.rtk_last_error().decode()))
+    try:
+        w = np.ctypeslib.as_array(cand, shape=(max(1, 2 * n.value),))[:2 * n.value].copy() if n.value else np.zeros(0, dtype=np.uint64)
+    finally:
+        L.rtk_free(cand)
+    w0, w1 = w[0::2], w[1::2]
+    return list(zip((w0 >> np.uint64(32)).tolist(), (w0 & np.uint64(0xFFFFFFFF)).tolist(), (w1 >> np.uint64(40)).tolist(), ((w1 >> np.uint64(32)) & np.uint64(3)).tolist(), (w1 & np.uint64(0xFFFFFFFF)).tolist()))
 
 
 def run_pipelined(batches, opts=None):

@@ -9,6 +9,7 @@
 //                           thinned out by coverage and their ids renumbered before they leave the device (k_sub_*); with rtk_index_colour_merge the ids of read
 //                           pairs on the same unitigs merged in place before that (k_merge_*); with rtk_index_colour_chunk_q the bases of a chunk whose quality
 //                           is below a threshold turned into N ahead of the mapping (k_col_mask)
+//   rtk_index_snp_candidates the candidate search of the SNP annotations: the graph k-mers one substitution away from every window of the searched unitigs (k_snp_*)
 // Every step serves one-word k-mers (k <= 31, key type uint64_t) and two-word k-mers (33 <= k <= 63, key type unsigned __int128: the 2k-bit code,
 // first base in the most significant bits; in memory the low word first). Own translation unit: rocPRIM's templates.
 #include <string.h>
@@ -1160,4 +1161,276 @@ extern "C" int rtk_index_merge_events(int device, const uint64_t* events, uint64
         *n_out = r.n_out; *n_ids_before = r.ids_before; *n_ids_after = r.ids_after;
     } catch (const std::exception& e) { return rtk_fail(RTK_ERR_DEVICE, std::string("rtk_index_merge_events: ") + e.what()); }
     return RTK_OK;
+}
+
+
+// ------------------------------------------------------------------------------------------------ SNP candidates (rtk_index_snp_candidates)
+// The candidate search of the SNP annotations (detectSNPs, src/Graph.cpp:484-720; the host rule and its two sorted views: csrc/tools/index/annotate.hpp,
+// NeighbourIndex) on the device. A graph k-mer ONE SUBSTITUTION away from a window shares its first k/2 bases or its last k - k/2 bases with it:
+//   k_snp_keys   one lane per window of every unitig: its canonical k-mer and the unitig's id
+//   view one     those pairs radix-sorted by the 2k-bit key (rocPRIM): the first half leads
+//   view two     the same keys rotated so that the last k - k/2 bases lead (k_snp_rot), sorted again. Both views carry the unitig id as payload.
+//   k_snp_table  in front of each view, the first entry of every value of the top min(24, 2k) key bits; on view one also the check that no key occurs twice
+//   k_snp_scan   one lane per window of a SEARCHED unitig: x and rc(x) from the text, four range scans (same first half in view one, same last half in view two, for x
+//                and for rc(x) with offset and base flipped back), the entries whose XOR with the query has exactly one non-zero base and that lie on another
+//                unitig are candidates. Run twice: the candidates of every window counted, an exclusive scan of the counts (rocPRIM), then written to their place
+//                (only the windows that have any search again). No cap: a window has at most 3k, and room is made for what was counted.
+//   order        with RTK_SNP_FIRST_PER_SITE the candidates sorted by (u, p + j, alt, p) and the first of every (u, p + j, alt) kept (rocPRIM sort + select); then, always,
+//                the candidates sorted by their two words (u << 32 | p, j << 40 | alt << 32 | w) as one 128-bit key: the order of the host rule's visits.
+// Bounds: a window index below the number of windows counted on the host from seq_off; a window of unitig u starts at most k bases before seq_off[u + 1]; table indices
+// are key >> shift <= 2^bits - 1 (+ 1 for the end of a range: the tables hold 2^bits + 1 entries); a candidate is written below the total that the count pass gave.
+namespace {
+
+// the entry of a list of unitigs that holds window g: woff[s] = the windows before entry s (n_s + 1 values, woff[0] = 0 <= g < woff[n_s]); the last s with woff[s] <= g
+__device__ __forceinline__ uint64_t snp_locate(const uint64_t* __restrict__ woff, uint64_t n_s, uint64_t g) {
+    uint64_t lo = 0, hi = n_s;
+    while (hi - lo > 1) { const uint64_t mid = lo + (hi - lo) / 2; if (woff[mid] <= g) lo = mid; else hi = mid; }
+    return lo;
+}
+template <class KM> __device__ __forceinline__ KM snp_window(const char* __restrict__ pool, uint64_t at, int k, bool* bad) {
+    KM x = 0;
+    for (int q = 0; q < k; ++q) { const uint32_t c = idx_code(static_cast<unsigned char>(pool[at + q])); if (c > 3u) *bad = true; x = (x << 2) | static_cast<KM>(c & 3u); }
+    return x;
+}
+__device__ __forceinline__ int snp_ctz(uint64_t m) { return __ffsll(static_cast<unsigned long long>(m)) - 1; }
+__device__ __forceinline__ int snp_ctz(km2_t m) { const uint64_t lo = static_cast<uint64_t>(m); return lo ? __ffsll(static_cast<unsigned long long>(lo)) - 1 : 63 + __ffsll(static_cast<unsigned long long>(static_cast<uint64_t>(m >> 64))); }
+inline dim3 snp_grid(uint64_t items) { const uint64_t b = (items + 255) / 256; return dim3(static_cast<unsigned>(b < 1 ? 1 : (b > 2048 ? 2048 : b))); }
+
+template <class KM>
+__global__ void k_snp_keys(const char* __restrict__ pool, const uint64_t* __restrict__ seq_off, const uint64_t* __restrict__ woff, uint64_t n_u, uint64_t n_win, int k,
+                           KM* __restrict__ keys, uint32_t* __restrict__ ids, uint32_t* __restrict__ flag) {
+    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
+    for (uint64_t g = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; g < n_win; g += stride) {
+        const uint64_t u = snp_locate(woff, n_u, g); bool bad = false;
+        const KM x = snp_window<KM>(pool, seq_off[u] + (g - woff[u]), k, &bad), rc = idx_revcomp(x, k);
+        keys[g] = x <= rc ? x : rc; ids[g] = static_cast<uint32_t>(u);
+        if (bad) atomicOr(flag, 1u); // a character that is no base
+    }
+}
+template <class KM> __global__ void k_snp_rot(const KM* __restrict__ a, const uint32_t* __restrict__ ia, uint64_t n, int k, KM* __restrict__ b, uint32_t* __restrict__ ib) {
+    const int hi_n = k / 2, lo_n = k - hi_n; const KM lomask = (static_cast<KM>(1) << (2 * lo_n)) - static_cast<KM>(1);
+    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
+    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += stride) { const KM x = a[i]; b[i] = ((x & lomask) << (2 * hi_n)) | (x >> (2 * lo_n)); ib[i] = ia[i]; }
+}
+// T[v] = the first entry whose top bits (key >> shift) are >= v, for v in 0 .. n_pref (n_pref = 2^bits: T[n_pref] = n). Lane i fills the values between the top bits of
+// entries i - 1 and i, so every T[v] is written once. flag != nullptr: bit 1 set when two neighbouring keys are equal.
+template <class KM> __global__ void k_snp_table(const KM* __restrict__ keys, uint64_t n, int shift, uint64_t n_pref, uint64_t* __restrict__ T, uint32_t* __restrict__ flag) {
+    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
+    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i <= n; i += stride) {
+        const uint64_t a = i == 0 ? 0 : static_cast<uint64_t>(keys[i - 1] >> shift) + 1, b = i == n ? n_pref : static_cast<uint64_t>(keys[i] >> shift);
+        for (uint64_t v = a; v <= b && v <= n_pref; ++v) T[v] = i;
+        if (flag && i != 0 && i < n && keys[i] == keys[i - 1]) atomicOr(flag, 2u);
+    }
+}
+
+template <class KM> struct SnpViews { const KM* a; const uint32_t* ia; const uint64_t* ta; const KM* b; const uint32_t* ib; const uint64_t* tb; int k, shift; };
+// The graph k-mers one substitution away from x (NeighbourIndex::scan): as (offset, base) of the ORIENTED neighbour of the window (flipped: x is the window's reverse
+// complement). Those on the window's own unitig u are dropped. out == nullptr: counted only; else candidate number c goes to out[2 (at + c)], below `end`. Returns the count.
+template <class KM>
+__device__ __forceinline__ uint32_t snp_scan(const SnpViews<KM>& V, KM x, bool flipped, uint32_t u, uint64_t word0, uint64_t* __restrict__ out, uint64_t at, uint64_t end) {
+    const int k = V.k, hi_n = k / 2, lo_n = k - hi_n;
+    const KM one = 1, lomask = (one << (2 * lo_n)) - one, himask = (one << (2 * hi_n)) - one, m55 = ~static_cast<KM>(0) / static_cast<KM>(3); // 0101...01
+    uint32_t c = 0;
+    auto entry = [&](KM y, uint32_t w) { // y: a canonical k-mer of unitig w
+        const KM d = y ^ x; if (d == 0 || w == u) return;
+        const KM m = (d | (d >> 1)) & m55; if (m & (m - one)) return; // more than one base differs
+        const int bit = snp_ctz(m); uint32_t j = static_cast<uint32_t>(k - 1 - bit / 2), base = static_cast<uint32_t>(y >> bit) & 3u;
+        if (flipped) { j = static_cast<uint32_t>(k - 1) - j; base = 3u - base; }
+        if (out && at + c < end) { out[2 * (at + c)] = word0; out[2 * (at + c) + 1] = (static_cast<uint64_t>(j) << 40) | (static_cast<uint64_t>(base) << 32) | w; }
+        ++c;
+    };
+    { // same first half: the differing base lies in the last lo_n bases
+        const KM lo_key = x & ~lomask, hi_key = x | lomask;
+        uint64_t i = V.ta[static_cast<uint64_t>(lo_key >> V.shift)]; const uint64_t e = V.ta[static_cast<uint64_t>(hi_key >> V.shift) + 1];
+        { uint64_t hi = e; while (i < hi) { const uint64_t mid = i + (hi - i) / 2; if (V.a[mid] < lo_key) i = mid + 1; else hi = mid; } }
+        for (; i < e; ++i) { const KM y = V.a[i]; if (y > hi_key) break; entry(y, V.ia[i]); }
+    }
+    { // same last half: the differing base lies in the first hi_n bases
+        const KM r = ((x & lomask) << (2 * hi_n)) | (x >> (2 * lo_n)), lo_key = r & ~himask, hi_key = r | himask;
+        uint64_t i = V.tb[static_cast<uint64_t>(lo_key >> V.shift)]; const uint64_t e = V.tb[static_cast<uint64_t>(hi_key >> V.shift) + 1];
+        { uint64_t hi = e; while (i < hi) { const uint64_t mid = i + (hi - i) / 2; if (V.b[mid] < lo_key) i = mid + 1; else hi = mid; } }
+        for (; i < e; ++i) { const KM y = V.b[i]; if (y > hi_key) break; entry(((y & himask) << (2 * lo_n)) | (y >> (2 * hi_n)), V.ib[i]); }
+    }
+    return c;
+}
+// list[s] = the s-th searched unitig, woff[s] = the windows of the searched unitigs before it. Count pass (out == nullptr): counts[g] = the candidates of window g.
+// Write pass: the candidates of window g at offs[g] .. offs[g + 1], in the order the scans find them.
+template <class KM>
+__global__ void k_snp_scan(const char* __restrict__ pool, const uint64_t* __restrict__ seq_off, const uint32_t* __restrict__ list, const uint64_t* __restrict__ woff, uint64_t n_s, uint64_t n_win,
+                           SnpViews<KM> V, uint32_t* __restrict__ counts, const uint64_t* __restrict__ offs, uint64_t* __restrict__ out) {
+    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
+    for (uint64_t g = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; g < n_win; g += stride) {
+        uint64_t at = 0, end = 0;
+        if (out) { at = offs[g]; end = offs[g + 1]; if (at == end) continue; }
+        const uint64_t s = snp_locate(woff, n_s, g), p = g - woff[s]; const uint32_t u = list[s]; bool bad = false;
+        const KM x = snp_window<KM>(pool, seq_off[u] + p, V.k, &bad), rc = idx_revcomp(x, V.k);
+        const uint64_t word0 = (static_cast<uint64_t>(u) << 32) | p;
+        const uint32_t c = snp_scan(V, x, false, u, word0, out, at, end);
+        const uint32_t c2 = snp_scan(V, rc, true, u, word0, out, at + c, end);
+        if (!out) counts[g] = c + c2;
+    }
+}
+struct SnpCountAt { const uint32_t* c; uint64_t n; __device__ uint64_t operator()(uint64_t i) const { return i < n ? static_cast<uint64_t>(c[i]) : 0ull; } };
+// candidates (two words each) -> keys (u, p + j, alt, p) with the unitig w beside them
+__global__ void k_snp_site_keys(const uint64_t* __restrict__ cand, uint64_t n, km2_t* __restrict__ keys, uint32_t* __restrict__ w) {
+    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
+    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const uint64_t w0 = cand[2 * i], w1 = cand[2 * i + 1], p = w0 & 0xFFFFFFFFull, j = w1 >> 40, alt = (w1 >> 32) & 3ull;
+        keys[i] = (static_cast<km2_t>(w0 >> 32) << 66) | (static_cast<km2_t>(p + j) << 34) | (static_cast<km2_t>(alt) << 32) | static_cast<km2_t>(p);
+        w[i] = static_cast<uint32_t>(w1);
+    }
+}
+struct SnpSiteHead { const km2_t* keys; __device__ bool operator()(uint64_t i) const { return i == 0 || (keys[i] >> 32) != (keys[i - 1] >> 32); } };
+// the order keys word0 << 64 | word1: of the kept site keys sel[0 .. n) (sel != nullptr), or of the candidates as they stand
+__global__ void k_snp_order_keys(const uint64_t* __restrict__ cand, const km2_t* __restrict__ site, const uint32_t* __restrict__ w, const uint64_t* __restrict__ sel, uint64_t n, km2_t* __restrict__ keys) {
+    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
+    for (uint64_t r = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; r < n; r += stride) {
+        uint64_t w0, w1;
+        if (sel) {
+            const uint64_t i = sel[r]; const km2_t sk = site[i];
+            const uint64_t u = static_cast<uint64_t>(sk >> 66), s = static_cast<uint64_t>(sk >> 34) & 0xFFFFFFFFull, alt = static_cast<uint64_t>(sk >> 32) & 3ull, p = static_cast<uint64_t>(sk) & 0xFFFFFFFFull;
+            w0 = (u << 32) | p; w1 = ((s - p) << 40) | (alt << 32) | w[i];
+        } else { w0 = cand[2 * r]; w1 = cand[2 * r + 1]; }
+        keys[r] = (static_cast<km2_t>(w0) << 64) | static_cast<km2_t>(w1);
+    }
+}
+
+template <class KM>
+int snp_candidates(int device, int k, const char* seq_pool, const uint64_t* seq_off, uint64_t n_unitigs, const uint8_t* searched, uint32_t flags, uint64_t** cand_out, uint64_t* n_cand) {
+    const bool trace = rtk_knob_index_trace();
+    try {
+        rtk_check(hipSetDevice(device), "hipSetDevice");
+        const auto t0 = std::chrono::steady_clock::now();
+        auto since = [&]() { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); };
+        // the windows of every unitig (the views) and of the searched ones (the queries)
+        const uint64_t n_bases = seq_off[n_unitigs];
+        std::vector<uint64_t> woff(n_unitigs + 1, 0), swoff(1, 0); std::vector<uint32_t> list;
+        for (uint64_t u = 0; u < n_unitigs; ++u) {
+            if (seq_off[u + 1] < seq_off[u] + static_cast<uint64_t>(k)) return rtk_fail(RTK_ERR_FORMAT, "rtk_index_snp_candidates: a unitig of fewer than k characters");
+            const uint64_t nw = seq_off[u + 1] - seq_off[u] - static_cast<uint64_t>(k) + 1;
+            if (nw + static_cast<uint64_t>(k) > (1ull << 32)) return rtk_fail(RTK_ERR_UNSUPPORTED, "rtk_index_snp_candidates: a unitig of 2^32 characters or more");
+            woff[u + 1] = woff[u] + nw;
+            if (!searched || searched[u]) { list.push_back(static_cast<uint32_t>(u)); swoff.push_back(swoff.back() + nw); }
+        }
+        const uint64_t N = woff[n_unitigs], n_s = list.size(), W = swoff.back();
+        if (N == 0 || W == 0) { // nothing to find, or nobody asks
+            if (trace) fprintf(stderr, "rtk_index_snps: %llu windows of %llu unitigs searched against %llu k-mers, 0 candidates (0 kept); views 0.00 s, scan 0.00 s\n", static_cast<unsigned long long>(W), static_cast<unsigned long long>(n_s), static_cast<unsigned long long>(N));
+            return RTK_OK;
+        }
+        // what the stage needs, before anything is allocated: text and offsets, three arrays of (key, id) -- two views and the sorts' other buffer --, the sort's
+        // temporary, two prefix tables, the counts and their running sums; the candidates come on top once they are counted (checked again there)
+        const int bits = 2 * k < 24 ? 2 * k : 24, shift = 2 * k - bits; const uint64_t n_pref = 1ull << bits;
+        size_t tb_sort = 0, tb_scan = 0;
+        { rocprim::double_buffer<KM> qk(nullptr, nullptr); rocprim::double_buffer<uint32_t> qv(nullptr, nullptr);
+          rtk_check(rocprim::radix_sort_pairs(nullptr, tb_sort, qk, qv, static_cast<size_t>(N), 0, 2 * k), "rocprim::radix_sort_pairs (size)"); }
+        SnpCountAt cnt_at; cnt_at.c = nullptr; cnt_at.n = W;
+        { auto it = rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint64_t>(0), cnt_at);
+          rtk_check(rocprim::exclusive_scan(nullptr, tb_scan, it, static_cast<uint64_t*>(nullptr), 0ull, static_cast<size_t>(W + 1), rocprim::plus<uint64_t>()), "rocprim::exclusive_scan (size)"); }
+        const uint64_t need = n_bases + 16 * (n_unitigs + 1) + 3 * N * (sizeof(KM) + 4) + std::max<uint64_t>(tb_sort, tb_scan) + 2 * 8 * (n_pref + 1) + 4 * n_s + 8 * (n_s + 1) + 4 * W + 8 * (W + 1) + 4096;
+        size_t fr = 0, tot = 0; rtk_check(hipMemGetInfo(&fr, &tot), "hipMemGetInfo");
+        const uint64_t room = rtk_knob_index_snp_mem(static_cast<uint64_t>(fr));
+        if (need > room) return rtk_fail(RTK_ERR_DEVICE, "rtk_index_snp_candidates: the two views of " + std::to_string(N) + " k-mers need " + std::to_string(need) + " bytes of device memory, " + std::to_string(room) + " are to be had (the key space is not partitioned)");
+
+        DevBuf d_pool, d_off, d_woff, d_k[3], d_v[3], d_tmp, d_ta, d_tb, d_flag;
+        d_pool.alloc(n_bases); d_off.alloc(8 * (n_unitigs + 1)); d_woff.alloc(8 * (n_unitigs + 1)); d_flag.alloc(8);
+        for (int i = 0; i < 3; ++i) { d_k[i].alloc(sizeof(KM) * N); d_v[i].alloc(4 * N); }
+        d_tmp.alloc(std::max<uint64_t>(tb_sort, tb_scan)); d_ta.alloc(8 * (n_pref + 1)); d_tb.alloc(8 * (n_pref + 1));
+        rtk_check(hipMemcpy(d_pool.p, seq_pool, n_bases, hipMemcpyHostToDevice), "hipMemcpy");
+        rtk_check(hipMemcpy(d_off.p, seq_off, 8 * (n_unitigs + 1), hipMemcpyHostToDevice), "hipMemcpy");
+        rtk_check(hipMemcpy(d_woff.p, woff.data(), 8 * (n_unitigs + 1), hipMemcpyHostToDevice), "hipMemcpy");
+        rtk_check(hipMemset(d_flag.p, 0, 8), "hipMemset");
+        uint32_t* flag = static_cast<uint32_t*>(d_flag.p);
+        const char* pool = static_cast<const char*>(d_pool.p); const uint64_t* off = static_cast<const uint64_t*>(d_off.p);
+        hipLaunchKernelGGL(k_snp_keys<KM>, snp_grid(N), dim3(256), 0, 0, pool, off, static_cast<const uint64_t*>(d_woff.p), n_unitigs, N, k, static_cast<KM*>(d_k[0].p), static_cast<uint32_t*>(d_v[0].p), flag);
+        rtk_check(hipGetLastError(), "kernel launch (k_snp_keys)");
+        // view one: (d_k[0], d_k[1]) sorted; view two: its rotated copy in d_k[2] sorted with the buffer view one left free
+        rocprim::double_buffer<KM> k1(static_cast<KM*>(d_k[0].p), static_cast<KM*>(d_k[1].p)); rocprim::double_buffer<uint32_t> v1(static_cast<uint32_t*>(d_v[0].p), static_cast<uint32_t*>(d_v[1].p));
+        rtk_check(rocprim::radix_sort_pairs(d_tmp.p, tb_sort, k1, v1, static_cast<size_t>(N), 0, 2 * k), "rocprim::radix_sort_pairs");
+        hipLaunchKernelGGL(k_snp_rot<KM>, snp_grid(N), dim3(256), 0, 0, static_cast<const KM*>(k1.current()), static_cast<const uint32_t*>(v1.current()), N, k, static_cast<KM*>(d_k[2].p), static_cast<uint32_t*>(d_v[2].p));
+        rtk_check(hipGetLastError(), "kernel launch (k_snp_rot)");
+        rocprim::double_buffer<KM> k2(static_cast<KM*>(d_k[2].p), k1.alternate()); rocprim::double_buffer<uint32_t> v2(static_cast<uint32_t*>(d_v[2].p), v1.alternate());
+        rtk_check(rocprim::radix_sort_pairs(d_tmp.p, tb_sort, k2, v2, static_cast<size_t>(N), 0, 2 * k), "rocprim::radix_sort_pairs");
+        hipLaunchKernelGGL(k_snp_table<KM>, snp_grid(N + 1), dim3(256), 0, 0, static_cast<const KM*>(k1.current()), N, shift, n_pref, static_cast<uint64_t*>(d_ta.p), flag);
+        hipLaunchKernelGGL(k_snp_table<KM>, snp_grid(N + 1), dim3(256), 0, 0, static_cast<const KM*>(k2.current()), N, shift, n_pref, static_cast<uint64_t*>(d_tb.p), static_cast<uint32_t*>(nullptr));
+        rtk_check(hipGetLastError(), "kernel launch (k_snp_table)"); rtk_check(hipDeviceSynchronize(), "views of the k-mers");
+        uint32_t fl = 0; rtk_check(hipMemcpy(&fl, d_flag.p, 4, hipMemcpyDeviceToHost), "hipMemcpy");
+        if (fl & 1u) return rtk_fail(RTK_ERR_FORMAT, "rtk_index_snp_candidates: a unitig holds a character that is no base");
+        if (fl & 2u) return rtk_fail(RTK_ERR_FORMAT, "rtk_index_snp_candidates: a k-mer occurs twice in the unitigs");
+        const double t_views = since();
+        // the buffer neither view ended up in is free again
+        for (int i = 0; i < 3; ++i) if (d_k[i].p != k1.current() && d_k[i].p != k2.current()) { (void)hipFree(d_k[i].p); d_k[i].p = nullptr; }
+        for (int i = 0; i < 3; ++i) if (d_v[i].p != v1.current() && d_v[i].p != v2.current()) { (void)hipFree(d_v[i].p); d_v[i].p = nullptr; }
+
+        DevBuf d_list, d_swoff, d_cnt, d_offs;
+        d_list.alloc(4 * n_s); d_swoff.alloc(8 * (n_s + 1)); d_cnt.alloc(4 * W); d_offs.alloc(8 * (W + 1));
+        rtk_check(hipMemcpy(d_list.p, list.data(), 4 * n_s, hipMemcpyHostToDevice), "hipMemcpy");
+        rtk_check(hipMemcpy(d_swoff.p, swoff.data(), 8 * (n_s + 1), hipMemcpyHostToDevice), "hipMemcpy");
+        SnpViews<KM> V; V.a = k1.current(); V.ia = v1.current(); V.ta = static_cast<const uint64_t*>(d_ta.p); V.b = k2.current(); V.ib = v2.current(); V.tb = static_cast<const uint64_t*>(d_tb.p); V.k = k; V.shift = shift;
+        hipLaunchKernelGGL(k_snp_scan<KM>, snp_grid(W), dim3(256), 0, 0, pool, off, static_cast<const uint32_t*>(d_list.p), static_cast<const uint64_t*>(d_swoff.p), n_s, W, V,
+                           static_cast<uint32_t*>(d_cnt.p), static_cast<const uint64_t*>(nullptr), static_cast<uint64_t*>(nullptr));
+        rtk_check(hipGetLastError(), "kernel launch (k_snp_scan)");
+        cnt_at.c = static_cast<const uint32_t*>(d_cnt.p);
+        { auto it = rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint64_t>(0), cnt_at);
+          rtk_check(rocprim::exclusive_scan(d_tmp.p, tb_scan, it, static_cast<uint64_t*>(d_offs.p), 0ull, static_cast<size_t>(W + 1), rocprim::plus<uint64_t>()), "rocprim::exclusive_scan"); }
+        rtk_check(hipDeviceSynchronize(), "candidates counted");
+        uint64_t C = 0; rtk_check(hipMemcpy(&C, static_cast<uint64_t*>(d_offs.p) + W, 8, hipMemcpyDeviceToHost), "hipMemcpy");
+        uint64_t R = C; uint64_t* res = static_cast<uint64_t*>(malloc(16 * (C ? C : 1)));
+        if (!res) return rtk_fail(RTK_ERR_IO, "rtk_index_snp_candidates: out of host memory");
+        std::unique_ptr<uint64_t, void (*)(void*)> res_guard(res, free);
+        if (C) {
+            // the candidates, their site keys and ids (both twice: the sort's other buffer), the kept indices, the order keys (twice)
+            const uint64_t need_c = C * (16 + 2 * 16 + 2 * 4 + 8 + 2 * 16) + (64u << 20);
+            rtk_check(hipMemGetInfo(&fr, &tot), "hipMemGetInfo");
+            const uint64_t room_c = rtk_knob_index_snp_mem(static_cast<uint64_t>(fr));
+            if (need_c > room_c) return rtk_fail(RTK_ERR_DEVICE, "rtk_index_snp_candidates: " + std::to_string(C) + " candidates need " + std::to_string(need_c) + " bytes of device memory, " + std::to_string(room_c) + " are to be had");
+            DevBuf d_cand, d_o[2], d_t2; d_cand.alloc(16 * C);
+            hipLaunchKernelGGL(k_snp_scan<KM>, snp_grid(W), dim3(256), 0, 0, pool, off, static_cast<const uint32_t*>(d_list.p), static_cast<const uint64_t*>(d_swoff.p), n_s, W, V,
+                               static_cast<uint32_t*>(nullptr), static_cast<const uint64_t*>(d_offs.p), static_cast<uint64_t*>(d_cand.p));
+            rtk_check(hipGetLastError(), "kernel launch (k_snp_scan)");
+            const uint64_t* raw = static_cast<const uint64_t*>(d_cand.p);
+            if (flags & RTK_SNP_FIRST_PER_SITE) {
+                DevBuf d_s[2], d_w[2], d_sel, d_nsel; d_s[0].alloc(16 * C); d_s[1].alloc(16 * C); d_w[0].alloc(4 * C); d_w[1].alloc(4 * C); d_sel.alloc(8 * C); d_nsel.alloc(8);
+                hipLaunchKernelGGL(k_snp_site_keys, snp_grid(C), dim3(256), 0, 0, raw, C, static_cast<km2_t*>(d_s[0].p), static_cast<uint32_t*>(d_w[0].p));
+                rtk_check(hipGetLastError(), "kernel launch (k_snp_site_keys)");
+                rocprim::double_buffer<km2_t> sk(static_cast<km2_t*>(d_s[0].p), static_cast<km2_t*>(d_s[1].p)); rocprim::double_buffer<uint32_t> sw(static_cast<uint32_t*>(d_w[0].p), static_cast<uint32_t*>(d_w[1].p));
+                size_t tb = 0; rtk_check(rocprim::radix_sort_pairs(nullptr, tb, sk, sw, static_cast<size_t>(C), 0, 98), "rocprim::radix_sort_pairs");
+                d_t2.alloc(tb); rtk_check(rocprim::radix_sort_pairs(d_t2.p, tb, sk, sw, static_cast<size_t>(C), 0, 98), "rocprim::radix_sort_pairs");
+                SnpSiteHead head; head.keys = sk.current();
+                auto idx = rocprim::make_counting_iterator<uint64_t>(0); auto heads = rocprim::make_transform_iterator(idx, head);
+                size_t sb = 0; rtk_check(rocprim::select(nullptr, sb, idx, heads, static_cast<uint64_t*>(d_sel.p), static_cast<unsigned long long*>(d_nsel.p), static_cast<size_t>(C)), "rocprim::select");
+                d_t2.alloc(sb); rtk_check(rocprim::select(d_t2.p, sb, idx, heads, static_cast<uint64_t*>(d_sel.p), static_cast<unsigned long long*>(d_nsel.p), static_cast<size_t>(C)), "rocprim::select");
+                rtk_check(hipDeviceSynchronize(), "first candidate of every site");
+                unsigned long long ns = 0; rtk_check(hipMemcpy(&ns, d_nsel.p, 8, hipMemcpyDeviceToHost), "hipMemcpy");
+                if (ns > C) return rtk_fail(RTK_ERR_DEVICE, "rtk_index_snp_candidates: more candidates kept than found");
+                R = ns; d_o[0].alloc(16 * R); d_o[1].alloc(16 * R);
+                hipLaunchKernelGGL(k_snp_order_keys, snp_grid(R), dim3(256), 0, 0, raw, static_cast<const km2_t*>(sk.current()), static_cast<const uint32_t*>(sw.current()), static_cast<const uint64_t*>(d_sel.p), R, static_cast<km2_t*>(d_o[0].p));
+                rtk_check(hipGetLastError(), "kernel launch (k_snp_order_keys)"); rtk_check(hipDeviceSynchronize(), "k_snp_order_keys");
+            } else {
+                d_o[0].alloc(16 * R); d_o[1].alloc(16 * R);
+                hipLaunchKernelGGL(k_snp_order_keys, snp_grid(R), dim3(256), 0, 0, raw, static_cast<const km2_t*>(nullptr), static_cast<const uint32_t*>(nullptr), static_cast<const uint64_t*>(nullptr), R, static_cast<km2_t*>(d_o[0].p));
+                rtk_check(hipGetLastError(), "kernel launch (k_snp_order_keys)");
+            }
+            rocprim::double_buffer<km2_t> ok(static_cast<km2_t*>(d_o[0].p), static_cast<km2_t*>(d_o[1].p));
+            size_t tb = 0; rtk_check(rocprim::radix_sort_keys(nullptr, tb, ok, static_cast<size_t>(R), 0, 128), "rocprim::radix_sort_keys");
+            d_t2.alloc(tb); rtk_check(rocprim::radix_sort_keys(d_t2.p, tb, ok, static_cast<size_t>(R), 0, 128), "rocprim::radix_sort_keys");
+            rtk_check(hipDeviceSynchronize(), "candidates ordered");
+            rtk_check(hipMemcpy(res, ok.current(), 16 * R, hipMemcpyDeviceToHost), "hipMemcpy");
+            for (uint64_t i = 0; i < R; ++i) std::swap(res[2 * i], res[2 * i + 1]); // (a 128-bit key lies low word first)
+        }
+        *cand_out = res_guard.release(); *n_cand = R;
+        if (trace) fprintf(stderr, "rtk_index_snps: %llu windows of %llu unitigs searched against %llu k-mers, %llu candidates (%llu kept); views %.2f s, scan %.2f s\n", static_cast<unsigned long long>(W), static_cast<unsigned long long>(n_s),
+                           static_cast<unsigned long long>(N), static_cast<unsigned long long>(C), static_cast<unsigned long long>(R), t_views, since() - t_views);
+    } catch (const std::exception& e) { return rtk_fail(RTK_ERR_DEVICE, std::string("rtk_index_snp_candidates: ") + e.what()); }
+    return RTK_OK;
+}
+} // namespace
+
+extern "C" int rtk_index_snp_candidates(int device, int k, const char* seq_pool, const uint64_t* seq_off, uint64_t n_unitigs, const uint8_t* searched, uint32_t flags, uint64_t** cand, uint64_t* n_cand) {
+    if (!cand || !n_cand || (n_unitigs && (!seq_pool || !seq_off))) return rtk_fail(RTK_ERR_ARG, "rtk_index_snp_candidates: null argument");
+    if (k < 3 || k > 63 || !(k & 1)) return rtk_fail(RTK_ERR_UNSUPPORTED, "rtk_index_snp_candidates: odd k <= 63 only");
+    if (rtk_device_count() <= device || device < 0) return rtk_fail(RTK_ERR_NO_DEVICE, "rtk_index_snp_candidates: no such HIP device (no CPU fallback)");
+    if (n_unitigs >= 0xFFFFFFFFull) return rtk_fail(RTK_ERR_UNSUPPORTED, "rtk_index_snp_candidates: more than 2^32 - 1 unitigs");
+    *cand = nullptr; *n_cand = 0;
+    if (n_unitigs == 0) return RTK_OK;
+    return k <= 31 ? snp_candidates<uint64_t>(device, k, seq_pool, seq_off, n_unitigs, searched, flags, cand, n_cand) : snp_candidates<km2_t>(device, k, seq_pool, seq_off, n_unitigs, searched, flags, cand, n_cand);
 }

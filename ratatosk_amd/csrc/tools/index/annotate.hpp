@@ -96,7 +96,8 @@ template <class KM> static void short_cycles(IndexBuild<KM>& s) {
 // its canonical form is, so the neighbours of x are the entries one substitution away from x plus the reverse complements of the entries one substitution
 // away from rc(x) (offset k-1-j, complemented base): a query scans the few entries that share a half with x, then with rc(x). Round 5: 8 bytes per
 // solid k-mer beside the k-mer set (26 GB at 3 Gb; the first version kept both orientations in both views, 103 GB + a sorting copy: `--snps` did not fit
-// a 3 Gb run). Used by the SNP search of --fast / --gpu (the plain path probes every variant in the k-mer table).
+// a 3 Gb run). Used by the SNP search of --fast, and of --gpu when the candidates are not found on the device (the plain path probes every variant in the k-mer table;
+// csrc/hip/rtk_index.hip builds the same two views in HBM for rtk_index_snp_candidates).
 template <class KM> struct NeighbourIndex { // KM: uint64_t, or u128 for two-word k-mers (16 bytes per solid k-mer beside the k-mer set)
     int k = 0, hi_n = 0, lo_n = 0; KM lomask = 0;
     const KM* a = nullptr; size_t n = 0; std::vector<KM> b; std::vector<uint64_t> ia, ib; int shift = 0; // ia / ib: first entry of every value of the top 24 bits of the 2k-bit key
@@ -163,8 +164,9 @@ template <class KM> struct SnpSearch {
     const std::vector<Unitig>& U; const std::vector<Nb>& adj; const std::vector<uint64_t>& shared; KTable<KM>& km; std::vector<std::vector<uint32_t> >& ambiguity;
     const std::vector<KM>& headk; const std::vector<KM>& tailk;
     std::unique_ptr<NeighbourIndex<KM> > nbx; // --fast: the neighbours from the two sorted views of the k-mer set; else every variant is probed in the table
-    explicit SnpSearch(IndexBuild<KM>& s) : k(s.k), mask(s.mask), min_cov_vertices(s.o.min_cov_vertices), U(s.U), adj(s.adj), shared(s.shared), km(s.km), ambiguity(s.ambiguity), headk(s.headk), tailk(s.tailk) {
-        if (s.o.fast) { nbx.reset(new NeighbourIndex<KM>()); nbx->build(s.solid, k, s.n_thr); s.lap("1-substitution neighbour index built"); }
+    // host_search: the candidates are enumerated here (false: they come as a list from the device, no neighbour index is built)
+    SnpSearch(IndexBuild<KM>& s, bool host_search) : k(s.k), mask(s.mask), min_cov_vertices(s.o.min_cov_vertices), U(s.U), adj(s.adj), shared(s.shared), km(s.km), ambiguity(s.ambiguity), headk(s.headk), tailk(s.tailk) {
+        if (s.o.fast && host_search) { nbx.reset(new NeighbourIndex<KM>()); nbx->build(s.solid, k, s.n_thr); s.lap("1-substitution neighbour index built"); }
     }
     struct Node { size_t u; bool fw; };
     // successors of (u, strand) in A,C,G,T order with the base that is appended
@@ -216,50 +218,117 @@ template <class KM> struct SnpSearch {
     static unsigned amb_bits(char c) { // getAmbiguityRev (src/Common.hpp:351-399): bit0 A, bit1 C, bit2 G, bit3 T
         switch (c) { case 'A': return 1; case 'C': return 2; case 'G': return 4; case 'T': return 8; case 'M': return 3; case 'R': return 5; case 'S': return 6; case 'V': return 7;
                      case 'W': return 9; case 'Y': return 10; case 'H': return 11; case 'K': return 12; case 'D': return 13; case 'B': return 14; case 'N': return 15; default: return 0; } }
-    void annotate(size_t u) {
+    // A candidate of unitig u: the graph holds window p with base `alt` at offset j, on unitig w != u (a SNP candidate cannot be on the same unitig, src/Graph.cpp:523).
+    struct Cand { size_t p; int j; uint64_t alt; size_t w; };
+    // The candidates of unitig u in the order of the visits: by (window, substituted offset, substituted base). --fast: the neighbours from the two sorted views; else
+    // every variant is probed in the table.
+    void enumerate(size_t u, std::vector<Cand>& out) {
+        out.clear();
         if (!(shared[u] & 0xffULL)) return; // hasSharedPids (src/Graph.cpp:500)
         const std::string& s = U[u].seq;
-        std::string seq_final = s, seq_tried = s;
-        std::set<size_t> ok, bad;
-        Walk lgt_fw, lgt_bw;
         KM fw = 0;
         for (size_t i = 0; i < s.size(); ++i) {
             fw = ((fw << 2) | static_cast<KM>(base2bits(s[i]))) & mask;
             if (i + 1 < static_cast<size_t>(k)) continue;
             const size_t p = i + 1 - static_cast<size_t>(k);
-            auto candidate = [&](int j, uint64_t alt) { // the graph holds the window with base `alt` at offset j
+            auto probe = [&](int j, uint64_t alt) { // is the window with base `alt` at offset j in the graph, on another unitig?
                 const int sh = 2 * (k - 1 - j);
                 const KM y = (fw & ~(static_cast<KM>(3) << sh)) | (static_cast<KM>(alt) << sh);
                 const uint64_t* v = km.slot(kmer_canonical(y, k), false);
                 if (!v) return;
                 const size_t w = (*v >> 32) - 1;
-                if (w == u) return; // a SNP candidate cannot be on the same unitig (src/Graph.cpp:523)
-                const size_t at = p + static_cast<size_t>(j); // pos_snp_km = first mismatch = the substituted offset
-                const unsigned f = amb_bits(seq_final[at]), t = amb_bits(seq_tried[at]), kk = 1u << alt;
-                const char cf = amb_char[f | kk], ct = amb_char[t | kk];
-                if (seq_tried[at] == ct) return; // that base was tried at this position before
-                seq_tried[at] = ct;
-                if (ok.count(w)) seq_final[at] = cf;
-                else if (!bad.count(w)) {
-                    if (is_valid(lgt_fw, lgt_bw, u, w)) { seq_final[at] = cf; ok.insert(w); } else bad.insert(w);
-                }
+                if (w == u) return;
+                Cand c; c.p = p; c.j = j; c.alt = alt; c.w = w; out.push_back(c);
             };
-            if (nbx) nbx->neighbours(fw, candidate); // (the same order)
+            if (nbx) nbx->neighbours(fw, probe); // (the same order)
             else for (int j = 0; j < k; ++j) {
                 const uint64_t cur = static_cast<uint64_t>(fw >> (2 * (k - 1 - j))) & 3ULL;
-                for (uint64_t alt = 0; alt < 4; ++alt) if (alt != cur) candidate(j, alt);
+                for (uint64_t alt = 0; alt < 4; ++alt) if (alt != cur) probe(j, alt);
+            }
+        }
+    }
+    // The rule over the candidates of unitig u, in the order given: the `tried` bases per position, the unitigs that answered before, the two walks that keep their state
+    // from candidate to candidate; then the ambiguity entries of u. A unitig without candidates keeps its bases and gets no entry.
+    void replay(size_t u, const Cand* cands, size_t n_cands) {
+        if (n_cands == 0) return;
+        const std::string& s = U[u].seq;
+        std::string seq_final = s, seq_tried = s;
+        std::set<size_t> ok, bad;
+        Walk lgt_fw, lgt_bw;
+        for (size_t c = 0; c < n_cands; ++c) {
+            const size_t w = cands[c].w; const uint64_t alt = cands[c].alt;
+            const size_t at = cands[c].p + static_cast<size_t>(cands[c].j); // pos_snp_km = first mismatch = the substituted offset
+            const unsigned f = amb_bits(seq_final[at]), t = amb_bits(seq_tried[at]), kk = 1u << alt;
+            const char cf = amb_char[f | kk], ct = amb_char[t | kk];
+            if (seq_tried[at] == ct) continue; // that base was tried at this position before
+            seq_tried[at] = ct;
+            if (ok.count(w)) seq_final[at] = cf;
+            else if (!bad.count(w)) {
+                if (is_valid(lgt_fw, lgt_bw, u, w)) { seq_final[at] = cf; ok.insert(w); } else bad.insert(w);
             }
         }
         for (size_t i = 0; i < seq_final.size(); ++i) if (seq_final[i] != 'A' && seq_final[i] != 'C' && seq_final[i] != 'G' && seq_final[i] != 'T') ambiguity[u].push_back(static_cast<uint32_t>((i << 4) + amb_bits(seq_final[i]))); // UnitigData.hpp:448-451
     }
 };
+
+// --gpu: the candidates of every unitig with an edge bit from the device (rtk_index_snp_candidates, csrc/hip/rtk_index.hip), first per (position, base) only -- the
+// later ones return at the `tried` check of the replay. Two words each: u << 32 | p, j << 40 | alt << 32 | w, by (u, p, j, alt). false with the reason in `why`: the
+// caller takes the host route.
+template <class KM> static bool snp_candidates_device(IndexBuild<KM>& s, std::vector<uint64_t>& cand, std::string& why) {
+    HipLib::snp_cand_fn fn = nullptr;
+    if (!s.lib.handle || !s.lib.get(fn, "rtk_index_snp_candidates")) { why = s.lib.path + " lacks rtk_index_snp_candidates"; return false; }
+    const size_t n_u = s.U.size();
+    if (n_u == 0) return true;
+    std::vector<uint64_t> off(n_u + 1, 0); for (size_t u = 0; u < n_u; ++u) off[u + 1] = off[u] + s.U[u].seq.size();
+    std::string pool(off[n_u], 'A'); std::vector<uint8_t> searched(n_u, 0);
+    parallel_for(n_u, s.n_thr, [&](size_t b, size_t e, unsigned) { for (size_t u = b; u < e; ++u) { memcpy(&pool[off[u]], s.U[u].seq.data(), s.U[u].seq.size()); searched[u] = (s.shared[u] & 0xffULL) ? 1 : 0; } });
+    uint64_t* list = nullptr; uint64_t n = 0;
+    if (fn(0, s.k, pool.data(), off.data(), n_u, searched.data(), 1u /* RTK_SNP_FIRST_PER_SITE */, &list, &n) != 0) { why = s.lib.last_error(); return false; }
+    cand.assign(list, list + 2 * n); s.lib.free(list);
+    return true;
+}
+
 template <class KM> static void snp_annotations(IndexBuild<KM>& s) {
-    SnpSearch<KM> search(s);
+    typedef typename SnpSearch<KM>::Cand Cand;
+    std::vector<uint64_t> dev; bool on_device = false;
+    if (s.o.gpu && s.knobs.snps_device) {
+        std::string why;
+        on_device = snp_candidates_device(s, dev, why);
+        if (!on_device) fprintf(stderr, "rtk_build_index: --gpu: SNP candidates on the host threads (%s)\n", why.c_str());
+    }
+    SnpSearch<KM> search(s, !on_device);
     const size_t n = s.U.size();
     // unitigs are independent and the k-mer table is only read: one strided slice per thread
     unsigned nt = std::thread::hardware_concurrency(); if (nt == 0) nt = 1; if (nt > std::max(64u, s.n_thr)) nt = std::max(64u, s.n_thr);
     std::vector<std::thread> th;
-    for (unsigned t = 0; t < nt; ++t) th.emplace_back([&, t]() { for (size_t u = t; u < n; u += nt) search.annotate(u); });
+    if (on_device) { // only the unitigs that have candidates are replayed: run r of the list = the candidates of one unitig
+        std::vector<size_t> run(1, 0); const size_t nc = dev.size() / 2;
+        for (size_t c = 1; c < nc; ++c) if ((dev[2 * c] >> 32) != (dev[2 * c - 2] >> 32)) run.push_back(c);
+        if (nc) run.push_back(nc);
+        for (unsigned t = 0; t < nt; ++t) th.emplace_back([&, t]() {
+            std::vector<Cand> cands;
+            for (size_t r = t; r + 1 < run.size(); r += nt) {
+                cands.clear();
+                for (size_t c = run[r]; c < run[r + 1]; ++c) { const uint64_t w0 = dev[2 * c], w1 = dev[2 * c + 1]; Cand x; x.p = static_cast<size_t>(w0 & 0xFFFFFFFFULL); x.j = static_cast<int>(w1 >> 40); x.alt = (w1 >> 32) & 3ULL; x.w = static_cast<size_t>(w1 & 0xFFFFFFFFULL); cands.push_back(x); }
+                search.replay(static_cast<size_t>(dev[2 * run[r]] >> 32), cands.data(), cands.size());
+            } });
+    } else {
+        std::vector<double> t_search(nt, 0.0), t_replay(nt, 0.0);
+        for (unsigned t = 0; t < nt; ++t) th.emplace_back([&, t]() {
+            std::vector<Cand> cands; double ts = 0.0, tr = 0.0;
+            for (size_t u = t; u < n; u += nt) {
+                const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+                search.enumerate(u, cands);
+                const std::chrono::steady_clock::time_point t1 = std::chrono::steady_clock::now();
+                search.replay(u, cands.data(), cands.size());
+                ts += std::chrono::duration<double>(t1 - t0).count(); tr += std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
+            }
+            t_search[t] = ts; t_replay[t] = tr; });
+        for (size_t t = 0; t < th.size(); ++t) th[t].join();
+        th.clear();
+        if (s.knobs.trace) { double ts = 0.0, tr = 0.0; for (unsigned t = 0; t < nt; ++t) { ts += t_search[t]; tr += t_replay[t]; }
+            fprintf(stderr, "rtk_build_index: SNP search on the host threads: candidate search %.2f s, replay %.2f s (summed over %u threads)\n", ts, tr, nt); }
+    }
     for (size_t t = 0; t < th.size(); ++t) th[t].join();
     size_t n_amb = 0, n_amb_unitigs = 0;
     for (size_t u = 0; u < n; ++u) { n_amb += s.ambiguity[u].size(); n_amb_unitigs += s.ambiguity[u].empty() ? 0 : 1; }

@@ -77,10 +77,12 @@ struct IndexKnobs {
     bool trace = getenv("RTK_INDEX_TRACE") != nullptr;                 // the laps and the step counts on stderr
     bool host_unitigs = getenv("RTK_INDEX_HOST_UNITIGS") != nullptr;   // --gpu: the chains on the host threads
     bool host_colours = getenv("RTK_INDEX_HOST_COLOURS") != nullptr;   // --gpu: the colours on the host threads
+    bool snps_device = true;                                           // RTK_INDEX_SNPS=device|host: --gpu --snps finds its candidates on the device (unset: device) or on the host threads; ignored without --gpu
     unsigned threads = 0;                                              // RTK_INDEX_THREADS (0: by the machine)
     size_t fasta_member_bytes = 32u << 20;                             // RTK_FASTA_MEMBER_BYTES (tests: many small members)
     IndexKnobs() {
         if (const char* e = getenv("RTK_INDEX_THREADS")) if (atoi(e) > 0) threads = static_cast<unsigned>(atoi(e));
+        if (const char* e = getenv("RTK_INDEX_SNPS")) { if (!strcmp(e, "host")) snps_device = false; else if (!strcmp(e, "device")) snps_device = true; }
         if (const char* e = getenv("RTK_FASTA_MEMBER_BYTES")) fasta_member_bytes = static_cast<size_t>(strtoull(e, nullptr, 10));
     }
 };
