@@ -1,5 +1,5 @@
 // Host-side count of the canonical k-mers (odd k <= 63; KM: uint64_t up to k = 31, u128 above) of FASTA/FASTQ files: the k-mers seen at least `min_count`
-// times, sorted ascending. What rtk_index_count_kmers (csrc/hip/rtk_index.hip) computes on the device, for the tools' plain paths (no GPU, no library).
+// times, sorted ascending. What rtk_index_count_kmers (csrc/hip/rtk_index_count.h) computes on the device, for the tools' plain paths (no GPU, no library).
 // The k-mer space is cut into one shard per thread by a hash; every thread reads the input itself (parsing is cheap next to the rest), collects the
 // k-mers of its shard, sorts them and keeps the first of every run of >= min_count equal ones.
 #ifndef RTK_COMMON_KMER_COUNT_HPP

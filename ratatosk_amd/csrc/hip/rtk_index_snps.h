@@ -1,0 +1,292 @@
+// rtk_index_snp_candidates: the graph k-mers one substitution away from every window of the searched unitigs (k_snp_*).
+#ifndef RTK_INDEX_SNPS_H
+#define RTK_INDEX_SNPS_H
+#include <cstdio>
+#include <initializer_list>
+#include <string>
+#include <vector>
+#include <rocprim/rocprim.hpp>
+#include "rtk_index_common.h"
+
+namespace {
+// ------------------------------------------------------------------------------------------------ SNP candidates (rtk_index_snp_candidates)
+// The candidate search of the SNP annotations (detectSNPs, src/Graph.cpp:484-720; the host rule and its two sorted views: csrc/tools/index/annotate.hpp,
+// NeighbourIndex) on the device. A graph k-mer ONE SUBSTITUTION away from a window shares its first k/2 bases or its last k - k/2 bases with it:
+//   k_snp_keys   one lane per window of every unitig: its canonical k-mer and the unitig's id
+//   view one     those pairs radix-sorted by the 2k-bit key (rocPRIM): the first half leads
+//   view two     the same keys rotated so that the last k - k/2 bases lead (k_snp_rot), sorted again. Both views carry the unitig id as payload.
+//   k_snp_table  in front of each view, the first entry of every value of the top min(24, 2k) key bits; on view one also the check that no key occurs twice
+//   k_snp_scan   one lane per window of a SEARCHED unitig: x and rc(x) from the text, four range scans (same first half in view one, same last half in view two, for x
+//                and for rc(x) with offset and base flipped back), the entries whose XOR with the query has exactly one non-zero base and that lie on another
+//                unitig are candidates. Run twice: the candidates of every window counted, an exclusive scan of the counts (rocPRIM), then written to their place
+//                (only the windows that have any search again). No cap: a window has at most 3k, and room is made for what was counted.
+//   order        with RTK_SNP_FIRST_PER_SITE the candidates sorted by (u, p + j, alt, p) and the first of every (u, p + j, alt) kept (rocPRIM sort + select); then, always,
+//                the candidates sorted by their two words (u << 32 | p, j << 40 | alt << 32 | w) as one 128-bit key: the order of the host rule's visits.
+// Bounds: a window index below the number of windows counted on the host from seq_off; a window of unitig u starts at most k bases before seq_off[u + 1]; table indices
+// are key >> shift <= 2^bits - 1 (+ 1 for the end of a range: the tables hold 2^bits + 1 entries); a candidate is written below the total that the count pass gave.
+// the entry of a list of unitigs that holds window g: woff[s] = the windows before entry s (n_s + 1 values, woff[0] = 0 <= g < woff[n_s]); the last s with woff[s] <= g
+__device__ __forceinline__ uint64_t snp_locate(const uint64_t* __restrict__ woff, uint64_t n_s, uint64_t g) {
+    uint64_t lo = 0, hi = n_s;
+    while (hi - lo > 1) { const uint64_t mid = lo + (hi - lo) / 2; if (woff[mid] <= g) lo = mid; else hi = mid; }
+    return lo;
+}
+template <class KM> __device__ __forceinline__ KM snp_window(const char* __restrict__ pool, uint64_t at, int k, bool* bad) {
+    KM x = 0;
+    for (int q = 0; q < k; ++q) { const uint32_t c = idx_code(static_cast<unsigned char>(pool[at + q])); if (c > 3u) *bad = true; x = (x << 2) | static_cast<KM>(c & 3u); }
+    return x;
+}
+__device__ __forceinline__ int snp_ctz(uint64_t m) { return __ffsll(static_cast<unsigned long long>(m)) - 1; }
+__device__ __forceinline__ int snp_ctz(km2_t m) { const uint64_t lo = static_cast<uint64_t>(m); return lo ? __ffsll(static_cast<unsigned long long>(lo)) - 1 : 63 + __ffsll(static_cast<unsigned long long>(static_cast<uint64_t>(m >> 64))); }
+
+template <class KM>
+__global__ void k_snp_keys(const char* __restrict__ pool, const uint64_t* __restrict__ seq_off, const uint64_t* __restrict__ woff, uint64_t n_u, uint64_t n_win, int k,
+                           KM* __restrict__ keys, uint32_t* __restrict__ ids, uint32_t* __restrict__ flag) {
+    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
+    for (uint64_t g = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; g < n_win; g += stride) {
+        const uint64_t u = snp_locate(woff, n_u, g); bool bad = false;
+        const KM x = snp_window<KM>(pool, seq_off[u] + (g - woff[u]), k, &bad), rc = idx_revcomp(x, k);
+        keys[g] = x <= rc ? x : rc; ids[g] = static_cast<uint32_t>(u);
+        if (bad) atomicOr(flag, 1u); // a character that is no base
+    }
+}
+template <class KM> __global__ void k_snp_rot(const KM* __restrict__ a, const uint32_t* __restrict__ ia, uint64_t n, int k, KM* __restrict__ b, uint32_t* __restrict__ ib) {
+    const int hi_n = k / 2, lo_n = k - hi_n; const KM lomask = (static_cast<KM>(1) << (2 * lo_n)) - static_cast<KM>(1);
+    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
+    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += stride) { const KM x = a[i]; b[i] = ((x & lomask) << (2 * hi_n)) | (x >> (2 * lo_n)); ib[i] = ia[i]; }
+}
+// T[v] = the first entry whose top bits (key >> shift) are >= v, for v in 0 .. n_pref (n_pref = 2^bits: T[n_pref] = n). Lane i fills the values between the top bits of
+// entries i - 1 and i, so every T[v] is written once. flag != nullptr: bit 1 set when two neighbouring keys are equal.
+template <class KM> __global__ void k_snp_table(const KM* __restrict__ keys, uint64_t n, int shift, uint64_t n_pref, uint64_t* __restrict__ T, uint32_t* __restrict__ flag) {
+    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
+    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i <= n; i += stride) {
+        const uint64_t a = i == 0 ? 0 : static_cast<uint64_t>(keys[i - 1] >> shift) + 1, b = i == n ? n_pref : static_cast<uint64_t>(keys[i] >> shift);
+        for (uint64_t v = a; v <= b && v <= n_pref; ++v) T[v] = i;
+        if (flag && i != 0 && i < n && keys[i] == keys[i - 1]) atomicOr(flag, 2u);
+    }
+}
+
+template <class KM> struct SnpViews { const KM* a; const uint32_t* ia; const uint64_t* ta; const KM* b; const uint32_t* ib; const uint64_t* tb; int k, shift; };
+// The graph k-mers one substitution away from x (NeighbourIndex::scan): as (offset, base) of the ORIENTED neighbour of the window (flipped: x is the window's reverse
+// complement). Those on the window's own unitig u are dropped. out == nullptr: counted only; else candidate number c goes to out[2 (at + c)], below `end`. Returns the count.
+template <class KM>
+__device__ __forceinline__ uint32_t snp_scan(const SnpViews<KM>& V, KM x, bool flipped, uint32_t u, uint64_t word0, uint64_t* __restrict__ out, uint64_t at, uint64_t end) {
+    const int k = V.k, hi_n = k / 2, lo_n = k - hi_n;
+    const KM one = 1, lomask = (one << (2 * lo_n)) - one, himask = (one << (2 * hi_n)) - one, m55 = ~static_cast<KM>(0) / static_cast<KM>(3); // 0101...01
+    uint32_t c = 0;
+    auto entry = [&](KM y, uint32_t w) { // y: a canonical k-mer of unitig w
+        const KM d = y ^ x; if (d == 0 || w == u) return;
+        const KM m = (d | (d >> 1)) & m55; if (m & (m - one)) return; // more than one base differs
+        const int bit = snp_ctz(m); uint32_t j = static_cast<uint32_t>(k - 1 - bit / 2), base = static_cast<uint32_t>(y >> bit) & 3u;
+        if (flipped) { j = static_cast<uint32_t>(k - 1) - j; base = 3u - base; }
+        if (out && at + c < end) { out[2 * (at + c)] = word0; out[2 * (at + c) + 1] = (static_cast<uint64_t>(j) << 40) | (static_cast<uint64_t>(base) << 32) | w; }
+        ++c;
+    };
+    { // same first half: the differing base lies in the last lo_n bases
+        const KM lo_key = x & ~lomask, hi_key = x | lomask;
+        uint64_t i = V.ta[static_cast<uint64_t>(lo_key >> V.shift)]; const uint64_t e = V.ta[static_cast<uint64_t>(hi_key >> V.shift) + 1];
+        { uint64_t hi = e; while (i < hi) { const uint64_t mid = i + (hi - i) / 2; if (V.a[mid] < lo_key) i = mid + 1; else hi = mid; } }
+        for (; i < e; ++i) { const KM y = V.a[i]; if (y > hi_key) break; entry(y, V.ia[i]); }
+    }
+    { // same last half: the differing base lies in the first hi_n bases
+        const KM r = ((x & lomask) << (2 * hi_n)) | (x >> (2 * lo_n)), lo_key = r & ~himask, hi_key = r | himask;
+        uint64_t i = V.tb[static_cast<uint64_t>(lo_key >> V.shift)]; const uint64_t e = V.tb[static_cast<uint64_t>(hi_key >> V.shift) + 1];
+        { uint64_t hi = e; while (i < hi) { const uint64_t mid = i + (hi - i) / 2; if (V.b[mid] < lo_key) i = mid + 1; else hi = mid; } }
+        for (; i < e; ++i) { const KM y = V.b[i]; if (y > hi_key) break; entry(((y & himask) << (2 * lo_n)) | (y >> (2 * hi_n)), V.ib[i]); }
+    }
+    return c;
+}
+// list[s] = the s-th searched unitig, woff[s] = the windows of the searched unitigs before it. Count pass (out == nullptr): counts[g] = the candidates of window g.
+// Write pass: the candidates of window g at offs[g] .. offs[g + 1], in the order the scans find them.
+template <class KM>
+__global__ void k_snp_scan(const char* __restrict__ pool, const uint64_t* __restrict__ seq_off, const uint32_t* __restrict__ list, const uint64_t* __restrict__ woff, uint64_t n_s, uint64_t n_win,
+                           SnpViews<KM> V, uint32_t* __restrict__ counts, const uint64_t* __restrict__ offs, uint64_t* __restrict__ out) {
+    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
+    for (uint64_t g = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; g < n_win; g += stride) {
+        uint64_t at = 0, end = 0;
+        if (out) { at = offs[g]; end = offs[g + 1]; if (at == end) continue; }
+        const uint64_t s = snp_locate(woff, n_s, g), p = g - woff[s]; const uint32_t u = list[s]; bool bad = false;
+        const KM x = snp_window<KM>(pool, seq_off[u] + p, V.k, &bad), rc = idx_revcomp(x, V.k);
+        const uint64_t word0 = (static_cast<uint64_t>(u) << 32) | p;
+        const uint32_t c = snp_scan(V, x, false, u, word0, out, at, end);
+        const uint32_t c2 = snp_scan(V, rc, true, u, word0, out, at + c, end);
+        if (!out) counts[g] = c + c2;
+    }
+}
+struct SnpCountAt { const uint32_t* c; uint64_t n; __device__ uint64_t operator()(uint64_t i) const { return i < n ? static_cast<uint64_t>(c[i]) : 0ull; } };
+// candidates (two words each) -> keys (u, p + j, alt, p) with the unitig w beside them
+__global__ void k_snp_site_keys(const uint64_t* __restrict__ cand, uint64_t n, km2_t* __restrict__ keys, uint32_t* __restrict__ w) {
+    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
+    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const uint64_t w0 = cand[2 * i], w1 = cand[2 * i + 1], p = w0 & 0xFFFFFFFFull, j = w1 >> 40, alt = (w1 >> 32) & 3ull;
+        keys[i] = (static_cast<km2_t>(w0 >> 32) << 66) | (static_cast<km2_t>(p + j) << 34) | (static_cast<km2_t>(alt) << 32) | static_cast<km2_t>(p);
+        w[i] = static_cast<uint32_t>(w1);
+    }
+}
+struct SnpSiteHead { const km2_t* keys; __device__ bool operator()(uint64_t i) const { return i == 0 || (keys[i] >> 32) != (keys[i - 1] >> 32); } };
+// the order keys word0 << 64 | word1: of the kept site keys sel[0 .. n) (sel != nullptr), or of the candidates as they stand
+__global__ void k_snp_order_keys(const uint64_t* __restrict__ cand, const km2_t* __restrict__ site, const uint32_t* __restrict__ w, const uint64_t* __restrict__ sel, uint64_t n, km2_t* __restrict__ keys) {
+    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
+    for (uint64_t r = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; r < n; r += stride) {
+        uint64_t w0, w1;
+        if (sel) {
+            const uint64_t i = sel[r]; const km2_t sk = site[i];
+            const uint64_t u = static_cast<uint64_t>(sk >> 66), s = static_cast<uint64_t>(sk >> 34) & 0xFFFFFFFFull, alt = static_cast<uint64_t>(sk >> 32) & 3ull, p = static_cast<uint64_t>(sk) & 0xFFFFFFFFull;
+            w0 = (u << 32) | p; w1 = ((s - p) << 40) | (alt << 32) | w[i];
+        } else { w0 = cand[2 * r]; w1 = cand[2 * r + 1]; }
+        keys[r] = (static_cast<km2_t>(w0) << 64) | static_cast<km2_t>(w1);
+    }
+}
+
+// A stage's device buffers as one list of (name, bytes): the memory the stage asks for is the sum over the list, and a buffer is allocated with the size the list
+// gives it, so the two cannot drift apart.
+template <int N> struct DevPlan {
+    struct Item { const char* name; uint64_t bytes; };
+    Item item[N]; DevArr<char> buf[N];
+    DevPlan(std::initializer_list<Item> l) { int i = 0; for (const Item& it : l) if (i < N) item[i++] = it; for (; i < N; ++i) item[i] = Item{"", 0}; }
+    uint64_t bytes() const { uint64_t s = 0; for (int i = 0; i < N; ++i) s += item[i].bytes; return s; }
+    template <class T> T* alloc(int i) { buf[i].alloc(item[i].bytes); return reinterpret_cast<T*>(buf[i].p); }
+    void release(int i) { buf[i].release(); }
+};
+enum { SNP_POOL, SNP_OFF, SNP_WOFF, SNP_K0, SNP_K1, SNP_K2, SNP_V0, SNP_V1, SNP_V2, SNP_TMP, SNP_TA, SNP_TB, SNP_LIST, SNP_SWOFF, SNP_CNT, SNP_OFFS, SNP_BUFS };
+enum { SNPC_CAND, SNPC_S0, SNPC_S1, SNPC_W0, SNPC_W1, SNPC_SEL, SNPC_O0, SNPC_O1, SNPC_BUFS };
+#define RTK_SNP_SLACK 4096ull          // on top of the views' list: the flag word, the granularity of the allocations
+#define RTK_SNP_CAND_SLACK (64ull << 20) // on top of the candidates' list: the temporaries of its sorts and selection
+
+// room for `need` bytes? what is to be had: the free device memory, or RTK_INDEX_SNP_MEM
+inline bool snp_room(uint64_t need, uint64_t* room) {
+    size_t fr = 0, tot = 0; rtk_check(hipMemGetInfo(&fr, &tot), "hipMemGetInfo");
+    *room = rtk_knob_index_snp_mem(static_cast<uint64_t>(fr));
+    return need <= *room;
+}
+
+// the windows of every unitig (the views: woff) and of the searched ones (the queries: list, swoff)
+struct SnpWindows { std::vector<uint64_t> woff, swoff; std::vector<uint32_t> list; uint64_t N = 0, n_s = 0, W = 0; };
+inline int snp_windows(int k, const uint64_t* seq_off, uint64_t n_unitigs, const uint8_t* searched, SnpWindows* w) {
+    w->woff.assign(n_unitigs + 1, 0); w->swoff.assign(1, 0);
+    for (uint64_t u = 0; u < n_unitigs; ++u) {
+        if (seq_off[u + 1] < seq_off[u] + static_cast<uint64_t>(k)) return rtk_fail(RTK_ERR_FORMAT, "rtk_index_snp_candidates: a unitig of fewer than k characters");
+        const uint64_t nw = seq_off[u + 1] - seq_off[u] - static_cast<uint64_t>(k) + 1;
+        if (nw + static_cast<uint64_t>(k) > (1ull << 32)) return rtk_fail(RTK_ERR_UNSUPPORTED, "rtk_index_snp_candidates: a unitig of 2^32 characters or more");
+        w->woff[u + 1] = w->woff[u] + nw;
+        if (!searched || searched[u]) { w->list.push_back(static_cast<uint32_t>(u)); w->swoff.push_back(w->swoff.back() + nw); }
+    }
+    w->N = w->woff[n_unitigs]; w->n_s = w->list.size(); w->W = w->swoff.back();
+    return RTK_OK;
+}
+
+// The C candidates at `raw` (two words each) in the order of the host rule's visits, first_per_site: only the first of every (u, p + j, alt). They are left as
+// 128-bit keys word0 << 64 | word1 in plan buffer SNPC_O0 or SNPC_O1: *keys. Returns how many are kept, or a count above C: more kept than found.
+inline uint64_t snp_order(DevPlan<SNPC_BUFS>& plan, const uint64_t* raw, uint64_t C, bool first_per_site, const km2_t** keys) {
+    uint64_t R = C; DevArr<char> tmp;
+    const km2_t* site = nullptr; const uint32_t* site_w = nullptr; const uint64_t* sel = nullptr;
+    if (first_per_site) {
+        rocprim::double_buffer<km2_t> sk(plan.alloc<km2_t>(SNPC_S0), plan.alloc<km2_t>(SNPC_S1)); rocprim::double_buffer<uint32_t> sw(plan.alloc<uint32_t>(SNPC_W0), plan.alloc<uint32_t>(SNPC_W1));
+        uint64_t* kept = plan.alloc<uint64_t>(SNPC_SEL); DevArr<unsigned long long> n_kept; n_kept.alloc(1);
+        launch("k_snp_site_keys", k_snp_site_keys, idx_grid(C, 2048), 0, raw, C, sk.current(), sw.current());
+        prim(tmp, "rocprim::radix_sort_pairs", [&](void* t, size_t& b) { return rocprim::radix_sort_pairs(t, b, sk, sw, C, 0, 98); });
+        SnpSiteHead head; head.keys = sk.current();
+        auto idx = rocprim::make_counting_iterator<uint64_t>(0); auto heads = rocprim::make_transform_iterator(idx, head);
+        prim(tmp, "rocprim::select", [&](void* t, size_t& b) { return rocprim::select(t, b, idx, heads, kept, n_kept.p, C); });
+        R = read_word(n_kept.p, "first candidate of every site");
+        if (R > C) return R;
+        site = sk.current(); site_w = sw.current(); sel = kept;
+    }
+    plan.item[SNPC_O0].bytes = plan.item[SNPC_O1].bytes = 16 * R; // (asked for at 16 C each: R <= C)
+    rocprim::double_buffer<km2_t> ok(plan.alloc<km2_t>(SNPC_O0), plan.alloc<km2_t>(SNPC_O1));
+    launch("k_snp_order_keys", k_snp_order_keys, idx_grid(R, 2048), 0, raw, site, site_w, sel, R, ok.current());
+    if (first_per_site) { rtk_check(hipDeviceSynchronize(), "k_snp_order_keys"); for (int i = SNPC_S0; i <= SNPC_SEL; ++i) plan.release(i); } // (the site keys have served)
+    prim(tmp, "rocprim::radix_sort_keys", [&](void* t, size_t& b) { return rocprim::radix_sort_keys(t, b, ok, R, 0, 128); });
+    rtk_check(hipDeviceSynchronize(), "candidates ordered");
+    *keys = ok.current();
+    return R;
+}
+
+template <class KM>
+int snp_candidates(int k, const char* seq_pool, const uint64_t* seq_off, uint64_t n_unitigs, const uint8_t* searched, uint32_t flags, uint64_t** cand_out, uint64_t* n_cand) {
+    const StageClock clk;
+    SnpWindows win;
+    if (const int rc = snp_windows(k, seq_off, n_unitigs, searched, &win)) return rc;
+    const uint64_t n_bases = seq_off[n_unitigs], N = win.N, n_s = win.n_s, W = win.W;
+    if (N == 0 || W == 0) { // nothing to find, or nobody asks
+        if (clk.trace) fprintf(stderr, "rtk_index_snps: %llu windows of %llu unitigs searched against %llu k-mers, 0 candidates (0 kept); views 0.00 s, scan 0.00 s\n", static_cast<unsigned long long>(W), static_cast<unsigned long long>(n_s), static_cast<unsigned long long>(N));
+        return RTK_OK;
+    }
+    // The two rocPRIM primitives of the views, each spelt once: sized here on null buffers, run below on the real ones.
+    auto sort_view = [&](rocprim::double_buffer<KM>& keys, rocprim::double_buffer<uint32_t>& ids) {
+        return [&keys, &ids, N, k](void* t, size_t& b) { return rocprim::radix_sort_pairs(t, b, keys, ids, N, 0, 2 * k); };
+    };
+    auto scan_counts = [&](const uint32_t* counts, uint64_t* offs) {
+        return [counts, offs, W](void* t, size_t& b) {
+            SnpCountAt at; at.c = counts; at.n = W;
+            auto it = rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint64_t>(0), at);
+            return rocprim::exclusive_scan(t, b, it, offs, 0ull, W + 1, rocprim::plus<uint64_t>());
+        };
+    };
+    rocprim::double_buffer<KM> no_keys(nullptr, nullptr); rocprim::double_buffer<uint32_t> no_ids(nullptr, nullptr);
+    const size_t tb_sort = prim_bytes("rocprim::radix_sort_pairs (size)", sort_view(no_keys, no_ids)), tb_scan = prim_bytes("rocprim::exclusive_scan (size)", scan_counts(nullptr, nullptr));
+    // What the stage needs, before anything is allocated: text and offsets, three arrays of (key, id) -- two views and the sorts' other buffer --, the primitives'
+    // temporary, two prefix tables, the searched unitigs, the counts and their running sums. The candidates come on top once they are counted (checked again there).
+    const int bits = 2 * k < 24 ? 2 * k : 24, shift = 2 * k - bits; const uint64_t n_pref = 1ull << bits;
+    DevPlan<SNP_BUFS> plan({{"unitig text", n_bases}, {"unitig offsets", 8 * (n_unitigs + 1)}, {"window offsets", 8 * (n_unitigs + 1)},
+                            {"keys 0", sizeof(KM) * N}, {"keys 1", sizeof(KM) * N}, {"keys 2", sizeof(KM) * N}, {"ids 0", 4 * N}, {"ids 1", 4 * N}, {"ids 2", 4 * N},
+                            {"temporary", std::max<uint64_t>(tb_sort, tb_scan)}, {"prefix table one", 8 * (n_pref + 1)}, {"prefix table two", 8 * (n_pref + 1)},
+                            {"searched unitigs", 4 * n_s}, {"searched window offsets", 8 * (n_s + 1)}, {"counts", 4 * W}, {"candidate offsets", 8 * (W + 1)}});
+    const uint64_t need = plan.bytes() + RTK_SNP_SLACK; uint64_t room = 0;
+    if (!snp_room(need, &room)) return rtk_fail(RTK_ERR_DEVICE, "rtk_index_snp_candidates: the two views of " + std::to_string(N) + " k-mers need " + std::to_string(need) + " bytes of device memory, " + std::to_string(room) + " are to be had (the key space is not partitioned)");
+
+    // the keys of all windows; view one: (keys 0, keys 1) sorted; view two: its rotated copy in keys 2 sorted with the buffer view one left free
+    const char* pool = plan.alloc<char>(SNP_POOL); const uint64_t* off = plan.alloc<uint64_t>(SNP_OFF); const uint64_t* d_woff = plan.alloc<uint64_t>(SNP_WOFF);
+    DevArr<uint32_t> flag; flag.alloc(2);
+    KM* d_k[3]; uint32_t* d_v[3];
+    for (int i = 0; i < 3; ++i) { d_k[i] = plan.alloc<KM>(SNP_K0 + i); d_v[i] = plan.alloc<uint32_t>(SNP_V0 + i); }
+    void* tmp = plan.alloc<char>(SNP_TMP); uint64_t* ta = plan.alloc<uint64_t>(SNP_TA); uint64_t* tb = plan.alloc<uint64_t>(SNP_TB);
+    rtk_check(hipMemcpy(plan.buf[SNP_POOL].p, seq_pool, n_bases, hipMemcpyHostToDevice), "hipMemcpy");
+    rtk_check(hipMemcpy(plan.buf[SNP_OFF].p, seq_off, 8 * (n_unitigs + 1), hipMemcpyHostToDevice), "hipMemcpy");
+    rtk_check(hipMemcpy(plan.buf[SNP_WOFF].p, win.woff.data(), 8 * (n_unitigs + 1), hipMemcpyHostToDevice), "hipMemcpy");
+    rtk_check(hipMemset(flag.p, 0, 8), "hipMemset");
+    launch("k_snp_keys", k_snp_keys<KM>, idx_grid(N, 2048), 0, pool, off, d_woff, n_unitigs, N, k, d_k[0], d_v[0], flag.p);
+    rocprim::double_buffer<KM> k1(d_k[0], d_k[1]); rocprim::double_buffer<uint32_t> v1(d_v[0], d_v[1]);
+    prim(tmp, tb_sort, "rocprim::radix_sort_pairs", sort_view(k1, v1));
+    launch("k_snp_rot", k_snp_rot<KM>, idx_grid(N, 2048), 0, k1.current(), v1.current(), N, k, d_k[2], d_v[2]);
+    rocprim::double_buffer<KM> k2(d_k[2], k1.alternate()); rocprim::double_buffer<uint32_t> v2(d_v[2], v1.alternate());
+    prim(tmp, tb_sort, "rocprim::radix_sort_pairs", sort_view(k2, v2));
+    launch("k_snp_table", k_snp_table<KM>, idx_grid(N + 1, 2048), 0, k1.current(), N, shift, n_pref, ta, flag.p);
+    launch("k_snp_table", k_snp_table<KM>, idx_grid(N + 1, 2048), 0, k2.current(), N, shift, n_pref, tb, nullptr);
+    const uint32_t fl = read_word(flag.p, "views of the k-mers");
+    if (fl & 1u) return rtk_fail(RTK_ERR_FORMAT, "rtk_index_snp_candidates: a unitig holds a character that is no base");
+    if (fl & 2u) return rtk_fail(RTK_ERR_FORMAT, "rtk_index_snp_candidates: a k-mer occurs twice in the unitigs");
+    const double t_views = clk.since();
+    // the buffer neither view ended up in is free again
+    for (int i = 0; i < 3; ++i) if (d_k[i] != k1.current() && d_k[i] != k2.current()) plan.release(SNP_K0 + i);
+    for (int i = 0; i < 3; ++i) if (d_v[i] != v1.current() && d_v[i] != v2.current()) plan.release(SNP_V0 + i);
+
+    // the candidates of every window counted, and their places
+    uint32_t* list = plan.alloc<uint32_t>(SNP_LIST); uint64_t* swoff = plan.alloc<uint64_t>(SNP_SWOFF); uint32_t* counts = plan.alloc<uint32_t>(SNP_CNT); uint64_t* offs = plan.alloc<uint64_t>(SNP_OFFS);
+    rtk_check(hipMemcpy(list, win.list.data(), 4 * n_s, hipMemcpyHostToDevice), "hipMemcpy");
+    rtk_check(hipMemcpy(swoff, win.swoff.data(), 8 * (n_s + 1), hipMemcpyHostToDevice), "hipMemcpy");
+    SnpViews<KM> V; V.a = k1.current(); V.ia = v1.current(); V.ta = ta; V.b = k2.current(); V.ib = v2.current(); V.tb = tb; V.k = k; V.shift = shift;
+    launch("k_snp_scan", k_snp_scan<KM>, idx_grid(W, 2048), 0, pool, off, list, swoff, n_s, W, V, counts, nullptr, nullptr);
+    prim(tmp, tb_scan, "rocprim::exclusive_scan", scan_counts(counts, offs));
+    const uint64_t C = read_word(offs + W, "candidates counted");
+    uint64_t R = C; HostOut<uint64_t> res;
+    if (!res.alloc(2 * C)) return rtk_fail(RTK_ERR_IO, "rtk_index_snp_candidates: out of host memory");
+    if (C) {
+        // the candidates, their site keys and ids (both twice: the sort's other buffer), the kept indices, the order keys (twice)
+        DevPlan<SNPC_BUFS> cplan({{"candidates", 16 * C}, {"site keys 0", 16 * C}, {"site keys 1", 16 * C}, {"site ids 0", 4 * C}, {"site ids 1", 4 * C}, {"kept", 8 * C}, {"order keys 0", 16 * C}, {"order keys 1", 16 * C}});
+        const uint64_t need_c = cplan.bytes() + RTK_SNP_CAND_SLACK; uint64_t room_c = 0;
+        if (!snp_room(need_c, &room_c)) return rtk_fail(RTK_ERR_DEVICE, "rtk_index_snp_candidates: " + std::to_string(C) + " candidates need " + std::to_string(need_c) + " bytes of device memory, " + std::to_string(room_c) + " are to be had");
+        uint64_t* raw = cplan.alloc<uint64_t>(SNPC_CAND);
+        launch("k_snp_scan", k_snp_scan<KM>, idx_grid(W, 2048), 0, pool, off, list, swoff, n_s, W, V, nullptr, offs, raw);
+        const km2_t* ordered = nullptr;
+        R = snp_order(cplan, raw, C, (flags & RTK_SNP_FIRST_PER_SITE) != 0, &ordered);
+        if (R > C) return rtk_fail(RTK_ERR_DEVICE, "rtk_index_snp_candidates: more candidates kept than found");
+        rtk_check(hipMemcpy(res.p, ordered, 16 * R, hipMemcpyDeviceToHost), "hipMemcpy");
+        for (uint64_t i = 0; i < R; ++i) std::swap(res.p[2 * i], res.p[2 * i + 1]); // (a 128-bit key lies low word first)
+    }
+    *cand_out = res.release(); *n_cand = R;
+    if (clk.trace) fprintf(stderr, "rtk_index_snps: %llu windows of %llu unitigs searched against %llu k-mers, %llu candidates (%llu kept); views %.2f s, scan %.2f s\n", static_cast<unsigned long long>(W), static_cast<unsigned long long>(n_s),
+                           static_cast<unsigned long long>(N), static_cast<unsigned long long>(C), static_cast<unsigned long long>(R), t_views, clk.since() - t_views);
+    return RTK_OK;
+}
+} // namespace
+#endif

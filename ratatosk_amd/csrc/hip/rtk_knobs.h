@@ -24,7 +24,7 @@ inline int rtk_knob_trace_class(int dflt) { return rtk_env_int("RTK_TRACE_CLASS"
 inline bool rtk_knob_lane_cost() { return rtk_env_set("RTK_LANE_COST"); }          // flag, simulator only: one line per region of the lane kernel
 inline bool rtk_knob_myers_prof() { return rtk_env_set("RTK_MYERS_PROF"); }        // flag: rtk_myers_batch prints the cycle counters of the Hirschberg drivers
 inline bool rtk_knob_myers_time() { return rtk_env_set("RTK_MYERS_TIME"); }        // flag: rtk_myers_batch prints its kernel times
-inline bool rtk_knob_index_trace() { return rtk_env_set("RTK_INDEX_TRACE"); }      // flag: progress lines of the index build (rtk_index.hip)
+inline bool rtk_knob_index_trace() { return rtk_env_set("RTK_INDEX_TRACE"); }      // flag: progress lines of the index build (rtk_index.hip and its stages rtk_index_*.h)
 inline bool rtk_knob_load_trace() { return rtk_env_set("RTK_LOAD_TRACE"); }        // flag: progress lines of the graph upload (rtk_graph_tables.hip)
 
 // ---- seed stage: read on every call
@@ -70,7 +70,7 @@ inline uint64_t rtk_knob_coalesce_bases() { static const uint64_t v = rtk_env_u6
 inline long rtk_knob_coalesce_wait_us() { static const long v = [] { const char* e = getenv("RTK_COALESCE_WAIT_US"); return e ? atol(e) : 1500L; }(); return v; } // long, 1500: how long a call waits for company
 inline uint32_t rtk_knob_coalesce_split() { static const uint32_t v = static_cast<uint32_t>(rtk_env_pos_int("RTK_COALESCE_SPLIT", 2)); return v; } // u32 >= 1, 2: parts a merged batch is cut into
 
-// ---- index build and graph upload (rtk_index.hip, rtk_graph_tables.hip): read on every call
+// ---- index build and graph upload (rtk_index.hip and its stages rtk_index_*.h, rtk_graph_tables.hip): read on every call
 inline uint64_t rtk_knob_index_cap(uint64_t dflt) { return rtk_env_u64("RTK_INDEX_CAP", dflt); }         // u64: slots of the k-mer count table (default: from the input size)
 inline uint64_t rtk_knob_index_chunk(uint64_t dflt) { const uint64_t v = rtk_env_u64("RTK_INDEX_CHUNK", 0); return v >= 1024 ? v : dflt; } // u64 >= 1024: bytes of input per chunk (tests: small chunks cut long records)
 inline int rtk_knob_index_keep_text() { return rtk_env_int("RTK_INDEX_KEEP_TEXT", -1); }                 // 0 | non-zero | unset (-1: decided from the free memory): keep the packed input on the device

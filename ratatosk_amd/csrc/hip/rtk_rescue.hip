@@ -16,13 +16,7 @@
 #include <mutex>
 #include <string>
 
-#include <hip/hip_runtime.h>
-
-#include "../../../include/ratatosk_hip.h"
-#include "rtk_mem.h"
-#include "rtk_types.h"
-
-int rtk_fail(int code, const std::string& msg); // (rtk_device.hip)
+#include "rtk_index_common.h" // the owners, launch and entry helpers of the index build's device side
 
 namespace {
 
@@ -109,19 +103,65 @@ __global__ void k_rescue(const char* __restrict__ chars, uint64_t n, const uint6
     if (lane < 2 && (n_probed | n_hits)) atomicAdd(counters + lane, static_cast<unsigned long long>(lane == 0 ? n_probed : n_hits));
 }
 
-struct DevBuf { void* p = nullptr; ~DevBuf() { release(); } void release() { if (p) (void)hipFree(p); p = nullptr; } void alloc(uint64_t bytes) { release(); rtk_check(hipMalloc(&p, bytes ? bytes : 8), "hipMalloc (rescue)"); } };
-struct PinBuf { void* p = nullptr; ~PinBuf() { if (p) (void)hipHostFree(p); } void alloc(uint64_t bytes) { rtk_check(hipHostMalloc(&p, bytes, hipHostMallocDefault), "hipHostMalloc (rescue)"); } };
+struct Rescue { static const char* dev() { return "hipMalloc (rescue)"; } static const char* pin() { return "hipHostMalloc (rescue)"; } };
+template <class T> using RscDev = DevArr<T, Rescue>;
+template <class T> using RscPin = PinArr<T, Rescue>;
 
 struct RescueJob {
     int device = 0, k = 31; uint32_t min_positions = 31;
-    DevBuf table, counters; uint64_t slots = 0, n_d = 0;
+    RscDev<uint64_t> table; RscDev<unsigned long long> counters; uint64_t slots = 0, n_d = 0; // counters: positions probed, hits, |D|
     // two chunks in flight (callers on two threads overlap the copies of one with the kernel of the other); a slot is one caller's from its copy in to its copy out
-    DevBuf d_chars[2], d_starts[2], d_keep[2]; PinBuf h_chars[2], h_starts[2], h_keep[2]; hipStream_t st[2] = {nullptr, nullptr}; std::mutex m[2]; std::atomic<unsigned> next{0};
-    std::atomic<uint64_t> chars{0}, chunks{0}; double t_table = 0.0; std::chrono::steady_clock::time_point t0;
-    ~RescueJob() { if (st[0]) (void)hipStreamDestroy(st[0]); if (st[1]) (void)hipStreamDestroy(st[1]); }
-};
+    RscDev<char> d_chars[2]; RscDev<uint64_t> d_starts[2]; RscDev<unsigned char> d_keep[2]; RscPin<char> h_chars[2]; RscPin<uint64_t> h_starts[2]; RscPin<unsigned char> h_keep[2];
+    Stream st[2]; std::mutex m[2]; std::atomic<unsigned> next{0};
+    std::atomic<uint64_t> chars{0}, chunks{0}; double t_table = 0.0; StageClock clk;
 
-dim3 rsc_grid(uint64_t items) { const uint64_t b = (items + 255) / 256; return dim3(static_cast<unsigned>(b < 1 ? 1 : (b > 65536 ? 65536 : b))); }
+    // D = the long-read k-mers that are no short-read k-mers, counted and then inserted into the table
+    void build_table(const uint64_t* lr, uint64_t n_lr, const uint64_t* sr, uint64_t n_sr) {
+        counters.alloc(3); rtk_check(hipMemset(counters.p, 0, 24), "hipMemset");
+        unsigned long long* d_nd = counters.p + 2;
+        RscDev<uint64_t> d_lr, d_sr; d_lr.alloc(n_lr); d_sr.alloc(n_sr); // released when D exists
+        if (n_lr) rtk_check(hipMemcpy(d_lr.p, lr, 8 * n_lr, hipMemcpyHostToDevice), "hipMemcpy");
+        if (n_sr) rtk_check(hipMemcpy(d_sr.p, sr, 8 * n_sr, hipMemcpyHostToDevice), "hipMemcpy");
+        if (n_lr) { launch("k_rescue_diff", k_rescue_diff, idx_grid(n_lr), 0, d_lr.p, n_lr, d_sr.p, n_sr, nullptr, 0ull, d_nd); rtk_check(hipDeviceSynchronize(), "k_rescue_diff"); }
+        n_d = read_word(d_nd); slots = 2 * n_d + 64; // load <= 0.5: a probe ends in its first slot more often than not
+        table.alloc(slots);
+        launch("k_rescue_fill", k_rescue_fill, idx_grid(slots), 0, table.p, slots);
+        if (n_d) launch("k_rescue_diff", k_rescue_diff, idx_grid(n_lr), 0, d_lr.p, n_lr, d_sr.p, n_sr, table.p, slots, d_nd);
+        rtk_check(hipDeviceSynchronize(), "rescue table");
+    }
+    void begin(int device_, int k_, const uint64_t* lr, uint64_t n_lr, const uint64_t* sr, uint64_t n_sr, uint32_t min_positions_) {
+        device = device_; k = k_; min_positions = min_positions_;
+        build_table(lr, n_lr, sr, n_sr);
+        for (int i = 0; i < 2; ++i) {
+            d_chars[i].alloc(RTK_RESCUE_CHUNK); d_starts[i].alloc(RTK_RESCUE_READS); d_keep[i].alloc(RTK_RESCUE_READS);
+            h_chars[i].alloc(RTK_RESCUE_CHUNK); h_starts[i].alloc(RTK_RESCUE_READS); h_keep[i].alloc(RTK_RESCUE_READS);
+            st[i].create();
+        }
+        t_table = clk.since();
+        if (clk.trace) fprintf(stderr, "rtk_rescue_begin: %llu long-read k-mers, %llu short-read k-mers -> %llu in the long reads only, table of %llu slots in %.2f s\n", static_cast<unsigned long long>(n_lr),
+                               static_cast<unsigned long long>(n_sr), static_cast<unsigned long long>(n_d), static_cast<unsigned long long>(slots), t_table);
+    }
+    void chunk(const char* text, uint64_t n_chars, const uint64_t* starts, uint32_t n_reads, unsigned char* keep) {
+        const int sl = static_cast<int>(next.fetch_add(1) & 1u);
+        std::lock_guard<std::mutex> lk(m[sl]);
+        memcpy(h_chars[sl].p, text, n_chars); memcpy(h_starts[sl].p, starts, 8ull * n_reads);
+        rtk_check(hipMemcpyAsync(d_chars[sl].p, h_chars[sl].p, n_chars, hipMemcpyHostToDevice, st[sl]), "hipMemcpyAsync");
+        rtk_check(hipMemcpyAsync(d_starts[sl].p, h_starts[sl].p, 8ull * n_reads, hipMemcpyHostToDevice, st[sl]), "hipMemcpyAsync");
+        const unsigned blocks = static_cast<unsigned>(std::min<uint64_t>((static_cast<uint64_t>(n_reads) + 3) / 4, 2048)); // 4 waves per block, one read per wave and round
+        launch("k_rescue", k_rescue, dim3(blocks), st[sl], d_chars[sl].p, n_chars, d_starts[sl].p, n_reads, k, min_positions, table.p, slots, d_keep[sl].p, counters.p);
+        rtk_check(hipMemcpyAsync(h_keep[sl].p, d_keep[sl].p, n_reads, hipMemcpyDeviceToHost, st[sl]), "hipMemcpyAsync");
+        rtk_check(hipStreamSynchronize(st[sl]), "k_rescue");
+        memcpy(keep, h_keep[sl].p, n_reads);
+        chars += n_chars; ++chunks;
+    }
+    void end(uint64_t* n_positions_probed, uint64_t* n_hits) {
+        rtk_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+        unsigned long long c[2] = {0, 0}; rtk_check(hipMemcpy(c, counters.p, 16, hipMemcpyDeviceToHost), "hipMemcpy");
+        *n_positions_probed = c[0]; *n_hits = c[1];
+        if (clk.trace) fprintf(stderr, "rtk_rescue: %llu characters in %llu chunks, %llu positions probed, %llu hits; table %.2f s, all %.2f s\n", static_cast<unsigned long long>(chars.load()),
+                               static_cast<unsigned long long>(chunks.load()), c[0], c[1], t_table, clk.since());
+    }
+};
 
 } // namespace
 
@@ -129,45 +169,11 @@ extern "C" int rtk_rescue_begin(int device, int k, const uint64_t* lr, uint64_t 
     if (!job_out || (!lr && n_lr) || (!sr && n_sr)) return rtk_fail(RTK_ERR_ARG, "rtk_rescue_begin: null argument");
     if (k < 3 || k > 31 || !(k & 1)) return rtk_fail(RTK_ERR_UNSUPPORTED, "rtk_rescue_begin: odd k <= 31 only (one-word k-mers)");
     if (min_positions < 1) return rtk_fail(RTK_ERR_ARG, "rtk_rescue_begin: min_positions must be at least 1");
-    if (rtk_device_count() <= device || device < 0) return rtk_fail(RTK_ERR_NO_DEVICE, "rtk_rescue_begin: no such HIP device (no CPU fallback)");
+    if (const int rc = check_device("rtk_rescue_begin", device)) return rc;
     *job_out = nullptr;
     for (uint64_t i = 1; i < n_lr; ++i) if (lr[i - 1] >= lr[i]) return rtk_fail(RTK_ERR_ARG, "rtk_rescue_begin: the long-read k-mers are not sorted and distinct");
     for (uint64_t i = 1; i < n_sr; ++i) if (sr[i - 1] >= sr[i]) return rtk_fail(RTK_ERR_ARG, "rtk_rescue_begin: the short-read k-mers are not sorted and distinct");
-    std::unique_ptr<RescueJob> J(new RescueJob());
-    try {
-        rtk_check(hipSetDevice(device), "hipSetDevice");
-        J->t0 = std::chrono::steady_clock::now();
-        J->device = device; J->k = k; J->min_positions = min_positions;
-        J->counters.alloc(24); rtk_check(hipMemset(J->counters.p, 0, 24), "hipMemset"); // positions probed, hits, |D|
-        unsigned long long* d_nd = static_cast<unsigned long long*>(J->counters.p) + 2;
-        { DevBuf d_lr, d_sr; d_lr.alloc(8 * n_lr); d_sr.alloc(8 * n_sr); // released when D exists
-          if (n_lr) rtk_check(hipMemcpy(d_lr.p, lr, 8 * n_lr, hipMemcpyHostToDevice), "hipMemcpy");
-          if (n_sr) rtk_check(hipMemcpy(d_sr.p, sr, 8 * n_sr, hipMemcpyHostToDevice), "hipMemcpy");
-          if (n_lr) {
-              hipLaunchKernelGGL(k_rescue_diff, rsc_grid(n_lr), dim3(256), 0, 0, static_cast<const uint64_t*>(d_lr.p), n_lr, static_cast<const uint64_t*>(d_sr.p), n_sr, static_cast<uint64_t*>(nullptr), 0ull, d_nd);
-              rtk_check(hipGetLastError(), "kernel launch (k_rescue_diff)"); rtk_check(hipDeviceSynchronize(), "k_rescue_diff");
-          }
-          unsigned long long nd = 0; rtk_check(hipMemcpy(&nd, d_nd, 8, hipMemcpyDeviceToHost), "hipMemcpy");
-          J->n_d = nd; J->slots = 2 * J->n_d + 64; // load <= 0.5: a probe ends in its first slot more often than not
-          J->table.alloc(8 * J->slots);
-          hipLaunchKernelGGL(k_rescue_fill, rsc_grid(J->slots), dim3(256), 0, 0, static_cast<uint64_t*>(J->table.p), J->slots);
-          rtk_check(hipGetLastError(), "kernel launch (k_rescue_fill)");
-          if (J->n_d) {
-              hipLaunchKernelGGL(k_rescue_diff, rsc_grid(n_lr), dim3(256), 0, 0, static_cast<const uint64_t*>(d_lr.p), n_lr, static_cast<const uint64_t*>(d_sr.p), n_sr, static_cast<uint64_t*>(J->table.p), J->slots, d_nd);
-              rtk_check(hipGetLastError(), "kernel launch (k_rescue_diff)");
-          }
-          rtk_check(hipDeviceSynchronize(), "rescue table"); }
-        for (int i = 0; i < 2; ++i) {
-            J->d_chars[i].alloc(RTK_RESCUE_CHUNK); J->d_starts[i].alloc(8 * RTK_RESCUE_READS); J->d_keep[i].alloc(RTK_RESCUE_READS);
-            J->h_chars[i].alloc(RTK_RESCUE_CHUNK); J->h_starts[i].alloc(8 * RTK_RESCUE_READS); J->h_keep[i].alloc(RTK_RESCUE_READS);
-            rtk_check(hipStreamCreate(&J->st[i]), "hipStreamCreate");
-        }
-        J->t_table = std::chrono::duration<double>(std::chrono::steady_clock::now() - J->t0).count();
-        if (rtk_knob_index_trace()) fprintf(stderr, "rtk_rescue_begin: %llu long-read k-mers, %llu short-read k-mers -> %llu in the long reads only, table of %llu slots in %.2f s\n", static_cast<unsigned long long>(n_lr),
-                                           static_cast<unsigned long long>(n_sr), static_cast<unsigned long long>(J->n_d), static_cast<unsigned long long>(J->slots), J->t_table);
-    } catch (const std::exception& e) { return rtk_fail(RTK_ERR_DEVICE, std::string("rtk_rescue_begin: ") + e.what()); }
-    *job_out = J.release();
-    return RTK_OK;
+    return entry("rtk_rescue_begin", device, [&]() { std::unique_ptr<RescueJob> J(new RescueJob()); J->begin(device, k, lr, n_lr, sr, n_sr, min_positions); *job_out = J.release(); return RTK_OK; });
 }
 
 extern "C" int rtk_rescue_chunk(void* job, const char* chars, uint64_t n_chars, const uint64_t* starts, uint32_t n_reads, unsigned char* keep) {
@@ -176,23 +182,7 @@ extern "C" int rtk_rescue_chunk(void* job, const char* chars, uint64_t n_chars, 
     if (n_reads == 0) return RTK_OK;
     if (n_chars > RTK_RESCUE_CHUNK || n_reads > RTK_RESCUE_READS) return rtk_fail(RTK_ERR_ARG, "rtk_rescue_chunk: chunk larger than 64 MB of characters / 4 M reads");
     for (uint32_t r = 0; r < n_reads; ++r) if (starts[r] > n_chars || (r && starts[r] < starts[r - 1])) return rtk_fail(RTK_ERR_ARG, "rtk_rescue_chunk: read starts must ascend and lie inside the chunk");
-    try {
-        const int sl = static_cast<int>(J->next.fetch_add(1) & 1u);
-        std::lock_guard<std::mutex> lk(J->m[sl]);
-        rtk_check(hipSetDevice(J->device), "hipSetDevice");
-        memcpy(J->h_chars[sl].p, chars, n_chars); memcpy(J->h_starts[sl].p, starts, 8ull * n_reads);
-        rtk_check(hipMemcpyAsync(J->d_chars[sl].p, J->h_chars[sl].p, n_chars, hipMemcpyHostToDevice, J->st[sl]), "hipMemcpyAsync");
-        rtk_check(hipMemcpyAsync(J->d_starts[sl].p, J->h_starts[sl].p, 8ull * n_reads, hipMemcpyHostToDevice, J->st[sl]), "hipMemcpyAsync");
-        const unsigned blocks = static_cast<unsigned>(std::min<uint64_t>((static_cast<uint64_t>(n_reads) + 3) / 4, 2048)); // 4 waves per block, one read per wave and round
-        hipLaunchKernelGGL(k_rescue, dim3(blocks), dim3(256), 0, J->st[sl], static_cast<const char*>(J->d_chars[sl].p), n_chars, static_cast<const uint64_t*>(J->d_starts[sl].p), n_reads, J->k, J->min_positions,
-                           static_cast<const uint64_t*>(J->table.p), J->slots, static_cast<unsigned char*>(J->d_keep[sl].p), static_cast<unsigned long long*>(J->counters.p));
-        rtk_check(hipGetLastError(), "kernel launch (k_rescue)");
-        rtk_check(hipMemcpyAsync(J->h_keep[sl].p, J->d_keep[sl].p, n_reads, hipMemcpyDeviceToHost, J->st[sl]), "hipMemcpyAsync");
-        rtk_check(hipStreamSynchronize(J->st[sl]), "k_rescue");
-        memcpy(keep, J->h_keep[sl].p, n_reads);
-        J->chars += n_chars; ++J->chunks;
-    } catch (const std::exception& e) { return rtk_fail(RTK_ERR_DEVICE, std::string("rtk_rescue_chunk: ") + e.what()); }
-    return RTK_OK;
+    return entry("rtk_rescue_chunk", J->device, [&]() { J->chunk(chars, n_chars, starts, n_reads, keep); return RTK_OK; });
 }
 
 extern "C" int rtk_rescue_end(void* job, uint64_t* n_positions_probed, uint64_t* n_hits) {
@@ -200,13 +190,5 @@ extern "C" int rtk_rescue_end(void* job, uint64_t* n_positions_probed, uint64_t*
     if (!J) return rtk_fail(RTK_ERR_ARG, "rtk_rescue_end: null job");
     if (!n_positions_probed || !n_hits) return RTK_OK; // (abandoned job: released)
     *n_positions_probed = 0; *n_hits = 0;
-    try {
-        rtk_check(hipSetDevice(J->device), "hipSetDevice");
-        rtk_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
-        unsigned long long c[2] = {0, 0}; rtk_check(hipMemcpy(c, J->counters.p, 16, hipMemcpyDeviceToHost), "hipMemcpy");
-        *n_positions_probed = c[0]; *n_hits = c[1];
-        if (rtk_knob_index_trace()) fprintf(stderr, "rtk_rescue: %llu characters in %llu chunks, %llu positions probed, %llu hits; table %.2f s, all %.2f s\n", static_cast<unsigned long long>(J->chars.load()),
-                                           static_cast<unsigned long long>(J->chunks.load()), c[0], c[1], J->t_table, std::chrono::duration<double>(std::chrono::steady_clock::now() - J->t0).count());
-    } catch (const std::exception& e) { return rtk_fail(RTK_ERR_DEVICE, std::string("rtk_rescue_end: ") + e.what()); }
-    return RTK_OK;
+    return entry("rtk_rescue_end", J->device, [&]() { J->end(n_positions_probed, n_hits); return RTK_OK; });
 }

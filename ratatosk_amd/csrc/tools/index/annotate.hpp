@@ -97,7 +97,7 @@ template <class KM> static void short_cycles(IndexBuild<KM>& s) {
 // away from rc(x) (offset k-1-j, complemented base): a query scans the few entries that share a half with x, then with rc(x). Round 5: 8 bytes per
 // solid k-mer beside the k-mer set (26 GB at 3 Gb; the first version kept both orientations in both views, 103 GB + a sorting copy: `--snps` did not fit
 // a 3 Gb run). Used by the SNP search of --fast, and of --gpu when the candidates are not found on the device (the plain path probes every variant in the k-mer table;
-// csrc/hip/rtk_index.hip builds the same two views in HBM for rtk_index_snp_candidates).
+// csrc/hip/rtk_index_snps.h builds the same two views in HBM for rtk_index_snp_candidates).
 template <class KM> struct NeighbourIndex { // KM: uint64_t, or u128 for two-word k-mers (16 bytes per solid k-mer beside the k-mer set)
     int k = 0, hi_n = 0, lo_n = 0; KM lomask = 0;
     const KM* a = nullptr; size_t n = 0; std::vector<KM> b; std::vector<uint64_t> ia, ib; int shift = 0; // ia / ib: first entry of every value of the top 24 bits of the 2k-bit key
@@ -271,7 +271,7 @@ template <class KM> struct SnpSearch {
     }
 };
 
-// --gpu: the candidates of every unitig with an edge bit from the device (rtk_index_snp_candidates, csrc/hip/rtk_index.hip), first per (position, base) only -- the
+// --gpu: the candidates of every unitig with an edge bit from the device (rtk_index_snp_candidates, csrc/hip/rtk_index_snps.h), first per (position, base) only -- the
 // later ones return at the `tried` check of the replay. Two words each: u << 32 | p, j << 40 | alt << 32 | w, by (u, p, j, alt). false with the reason in `why`: the
 // caller takes the host route.
 template <class KM> static bool snp_candidates_device(IndexBuild<KM>& s, std::vector<uint64_t>& cand, std::string& why) {

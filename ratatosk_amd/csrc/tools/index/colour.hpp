@@ -16,7 +16,7 @@ namespace rtk {
 // mates share a name up to a trailing /1 or /2: the length of the name without it
 inline size_t pair_name_len(const char* p, size_t n) { return (n > 2 && p[n - 2] == '/' && (p[n - 1] == '1' || p[n - 1] == '2')) ? n - 2 : n; }
 
-// --gpu: the reads are handed to the device chunk by chunk (csrc/hip/rtk_index.hip rtk_index_colour_*: the k-mer table of the unitigs in HBM, one lane per
+// --gpu: the reads are handed to the device chunk by chunk (csrc/hip/rtk_index_colour.h rtk_index_colour_*: the k-mer table of the unitigs in HBM, one lane per
 // read position); this tool keeps what is its own -- reading, and the numbering of the reads. Every thread fills a chunk of its own.
 // With a confidence threshold (q_min != 0; tools/index/colour_filter.hpp) the quality bytes travel beside the characters and the device masks (fn_q); a library without
 // that entry gets characters masked here.

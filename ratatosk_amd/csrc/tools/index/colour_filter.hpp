@@ -1,6 +1,6 @@
 // rtk_build_index --colour-reads with --colour-min-conf / --colour-max-qual / --colour-min-len: which bases and which reads colour a second-pass index (restates the
 // part of addCoverage that runs with long_read_correct == true, src/Ratatosk.cpp:1228: the graph of the second pass is coloured by the reads of the first; DESIGN.md
-// section 4 [A14]). One rule for the host routes here and for the device route (csrc/hip/rtk_index.hip rtk_index_colour_chunk_q, k_col_mask), which give the same bytes:
+// section 4 [A14]). One rule for the host routes here and for the device route (csrc/hip/rtk_index_colour.h rtk_index_colour_chunk_q, k_col_mask), which give the same bytes:
 //   c_min  = (unsigned char)(min(M, 1.0) * (Q - 1) + 34.0): getQual(min_confidence_2nd_pass, out_qual = 1, max_qual) (src/Common.hpp:410-418, called at
 //            src/Graph.cpp:1573) with its double-to-char truncation. Q = 40: M = 0 gives 34 ('"'), M = 0.5 gives 53 ('5'), M = 1 gives 73 ('I').
 //   A base of a colouring read whose quality byte is below c_min (bytes compare unsigned) is no base (src/Graph.cpp:1806-1814, 1872-1880 write 'N' over it before the

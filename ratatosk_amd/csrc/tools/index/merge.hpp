@@ -1,7 +1,7 @@
 // rtk_build_index --merge-duplicates: short-read pairs that lie on the same unitigs share one colour id (restates the block the reference announces as "Detecting
 // and removing duplicated reads", src/Graph.cpp:1630-1705 and 2089-2134: every pair gets a signature, the sum of the hashes of the unitigs its reads map to, and
 // pairs of equal signature that meet on a unitig receive the same read id; DESIGN.md section 4 [A13]). One rule for the host route here and for the device route
-// (csrc/hip/rtk_index.hip rtk_index_colour_merge), which give the same bytes:
+// (csrc/hip/rtk_index_merge.h rtk_index_colour_merge), which give the same bytes:
 //   U(i)   the unitigs of id i (an id without events takes no part); g(u) = subsample_hash(u + 1, 0), the splitmix64 finalizer of u + 1;
 //   S(i)   the sum of g(u) over U(i) modulo 2^64; low(i) = min U(i).
 //   Ids with equal (S, low) are one class; its leader is its smallest id; the leaders, ascending, are numbered from 0; every id takes its leader's number; the

@@ -1,6 +1,6 @@
 // rtk_build_index --subsample-colours: the colours thinned out by coverage before they are final (restates the subsampling of addCoverage,
 // src/Graph.cpp:2312-2870, with estimateHaplotypeCoverage, src/Graph.cpp:4185-4234; DESIGN.md section 4 [A12]). One rule for the host route here and
-// for the device route (csrc/hip/rtk_index.hip rtk_index_colour_end_subsampled), which give the same bytes:
+// for the device route (csrc/hip/rtk_index_subsample.h rtk_index_colour_end_subsampled), which give the same bytes:
 //   H     per-haplotype k-mer coverage from the simple bubbles of the graph; below 10 nothing is subsampled. rate = 5.0 / H.
 //   bins  the rounded k-mer coverages of the unitigs, sorted descending, cut at twenty quantiles; bin j (lowest coverage first) is the half-open range
 //         [s[p_j], s[p_j+1]) of coverages, an empty one is skipped, unitigs at the maximum fall into none.

@@ -165,7 +165,7 @@ template <class KM> static void build_unitigs(IndexBuild<KM>& s) {
     bool fast_done = false, have_dev = false;
     DeviceUnitigs dev;
     HipLib::unitigs_fn fn = nullptr;
-    if (s.o.gpu && s.lib.get(fn, "rtk_index_unitigs") && !s.knobs.host_unitigs) { // the chains walked and written on the device (csrc/hip/rtk_index.hip rtk_index_unitigs)
+    if (s.o.gpu && s.lib.get(fn, "rtk_index_unitigs") && !s.knobs.host_unitigs) { // the chains walked and written on the device (csrc/hip/rtk_index_unitigs.h rtk_index_unitigs)
         have_dev = fn(0, s.k, reinterpret_cast<const uint64_t*>(s.solid.data()), s.solid.size(), &dev.pool, &dev.off, &dev.seeds, &dev.n, &dev.left, &dev.n_left) == 0;
         if (!have_dev) fprintf(stderr, "rtk_build_index: --gpu: unitigs on the host threads (%s)\n", s.lib.last_error ? s.lib.last_error() : "?");
     }
