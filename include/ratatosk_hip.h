@@ -380,13 +380,24 @@ int rtk_index_merge_events(int device, const uint64_t* events, uint64_t n_events
  * flags & RTK_SNP_FIRST_PER_SITE: of all candidates with equal (u, p + j, alt) only the one with the smallest p is kept, the kept ones again in (u, p, j, alt) order.
  * That is exact for the host's replay: it marks (position p + j, alt) as tried at the first candidate it visits there and returns at once from every later one
  * (`if (seq_tried[at] == ct) return`, csrc/tools/index/annotate.hpp), so only the first in visiting order -- the smallest p -- can have any effect.
- * RTK_ERR_FORMAT when a canonical k-mer occurs twice in the unitigs (or a character is no base). The stage needs two sorted views of every window of the pool (key + unitig
- * id each), a third such array for the sorts, the sort's temporary, two prefix tables and the candidates; the bytes are worked out before anything is allocated and
- * compared with the free device memory (RTK_INDEX_SNP_MEM lowers that figure): RTK_ERR_DEVICE, with both numbers, when they do not fit -- the key space is not
- * partitioned, the caller keeps its host route for that case. Appended without a new revision number: see RTK_API_REVISION. */
+ * RTK_ERR_FORMAT when a canonical k-mer occurs twice in the unitigs (or a character is no base). The stage needs two sorted views of the windows of the pool (key + unitig
+ * id each), a third such array for the sorts, the sort's temporary, two prefix tables, the counts and offsets of the searched windows, and the candidates; the bytes are
+ * worked out before anything is allocated and compared with the room: the free device memory, or RTK_INDEX_SNP_MEM when that is lower. When the views of all windows do
+ * not fit, the key space is partitioned: the search runs in P passes, each against views of one range of the keys' leading min(24, 2k) bits (balanced from a histogram of
+ * those bits, so that a pass holds about 1/P of the keys), and the candidates of all passes are ordered together at the end -- the same output for every P. P is the
+ * smallest number of passes whose plan fits, at most min(256, 2^min(24, 2k)); the environment variable RTK_INDEX_SNP_PASSES (read at the call, 0 or unset: as few as fit)
+ * forces exactly that many, clamped to the same cap. RTK_ERR_DEVICE, `need <bytes> bytes of device memory, <room> are to be had`, when not even the most passes fit (or the
+ * forced number does not): `need` is the smallest plan -- text, offsets, counts, candidate offsets, tables, temporaries and the views of the smallest partitions --, nothing
+ * was allocated, and the caller keeps its host route for that case. Appended without a new revision number: see RTK_API_REVISION.
+ * rtk_index_snp_plan: what rtk_index_snp_candidates would do for these unitigs (their offsets are all it needs) with `room` bytes (0: the figure the stage itself would
+ * use now), worked out by the same code and without allocating anything. *passes: the number of passes, 0 when nothing fits; *need_one_pass: the bytes of the single pass;
+ * *need_min: the bytes of the smallest plan. The figures take every partition at its even share of the keys; the stage, once it has seen the histogram, takes more passes
+ * when a partition is heavier than that. */
 #define RTK_SNP_FIRST_PER_SITE 1u
 int rtk_index_snp_candidates(int device, int k, const char* seq_pool, const uint64_t* seq_off, uint64_t n_unitigs, const uint8_t* searched, uint32_t flags,
                              uint64_t** cand, uint64_t* n_cand);
+int rtk_index_snp_plan(int device, int k, const uint64_t* seq_off, uint64_t n_unitigs, const uint8_t* searched, uint64_t room, uint32_t* passes,
+                       uint64_t* need_one_pass, uint64_t* need_min);
 
 /* rtk_rescue_*: the rescue of unmapped short reads before the index build (`correct -u`; retrieveMissingReads, src/Graph.cpp:3857-4131, called at
  * src/Ratatosk.cpp:1040-1056), with exact sets where the reference has Bloom filters ([A11]). One-word k-mers (odd k <= 31).
@@ -451,7 +462,7 @@ const char* rtk_version(void);
  * 8: rtk_stats fields n_fa_linked_*; 9: rtk_rescue_begin / _chunk / _end; still 9: rtk_stats fields n_strand2_* and n_park_*, the test-only rtk_myers_batch mode 5, appended at the end -- a library of revision 9
  * without them leaves them as the caller set them;
  * 10: rtk_sets_batch, rtk_stats fields n_colours_*; still 10: rtk_index_colour_cov, rtk_index_colour_end_subsampled, rtk_index_subsample_events, then rtk_index_colour_merge,
- * rtk_index_colour_merge_classes, rtk_index_merge_events, then rtk_index_colour_chunk_q, then rtk_batch_fetch_seeds, then rtk_index_snp_candidates, appended -- a library of revision 10 without them lacks the symbols, and callers look them up by name). */
+ * rtk_index_colour_merge_classes, rtk_index_merge_events, then rtk_index_colour_chunk_q, then rtk_batch_fetch_seeds, then rtk_index_snp_candidates, then rtk_index_snp_plan, appended -- a library of revision 10 without them lacks the symbols, and callers look them up by name). */
 #define RTK_API_REVISION 10
 int rtk_api_revision(void);
 

@@ -133,6 +133,9 @@ def load_library(path=None):
     if hasattr(L, "rtk_index_snp_candidates"):  # (still revision 10: appended; a library without it: index_snp_candidates says so)
         L.rtk_index_snp_candidates.argtypes = [C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_ubyte), C.c_uint32,
                                                C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_uint64)]
+    if hasattr(L, "rtk_index_snp_plan"):  # (still revision 10: appended; a library without it: index_snp_plan says so)
+        L.rtk_index_snp_plan.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_ubyte), C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
+                                         C.POINTER(C.c_uint64)]
     L.rtk_free.argtypes = [C.c_void_p]
     _libs[path] = L
     return L
@@ -607,6 +610,30 @@ def index_snp_candidates(unitigs, k, searched=None, first_per_site=False, device
         L.rtk_free(cand)
     w0, w1 = w[0::2], w[1::2]
     return list(zip((w0 >> np.uint64(32)).tolist(), (w0 & np.uint64(0xFFFFFFFF)).tolist(), (w1 >> np.uint64(40)).tolist(), ((w1 >> np.uint64(32)) & np.uint64(3)).tolist(), (w1 & np.uint64(0xFFFFFFFF)).tolist()))
+
+
+def index_snp_plan(unitigs, k, searched=None, room=0, device=0, lib_path=None):
+    """What index_snp_candidates would do for these unitigs with `room` bytes of device memory (0: what the stage itself would go by now -- the free memory, or
+    RTK_INDEX_SNP_MEM when that is lower), worked out by the stage's own code without allocating anything (rtk_index_snp_plan, include/ratatosk_hip.h). Only the lengths
+    of the unitigs count. Returns (passes, need_one_pass, need_min): the number of passes over partitions of the key space (0: nothing fits; RTK_INDEX_SNP_PASSES forces
+    it), the bytes of the single pass, the bytes of the smallest plan."""
+    import numpy as np
+    L = load_library(lib_path)
+    if not hasattr(L, "rtk_index_snp_plan"):
+        raise RtkError("%s lacks rtk_index_snp_plan (SNP candidates in passes: appended at interface revision 10)" % L._name)
+    off = np.zeros(len(unitigs) + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(u) for u in unitigs], dtype=np.uint64)
+    flags = None
+    if searched is not None:
+        flags = np.ascontiguousarray([1 if f else 0 for f in searched], dtype=np.uint8)
+        if flags.size != len(unitigs):
+            raise ValueError("index_snp_plan: searched holds one flag per unitig")
+    passes, one, least = C.c_uint32(0), C.c_uint64(0), C.c_uint64(0)
+    rc = L.rtk_index_snp_plan(device, k, off.ctypes.data_as(C.POINTER(C.c_uint64)), len(unitigs), None if flags is None else flags.ctypes.data_as(C.POINTER(C.c_ubyte)), room,
+                              C.byref(passes), C.byref(one), C.byref(least))
+    if rc != 0:
+        raise RtkError("rtk error %d: %s" % (rc, L.rtk_last_error().decode()))
+    return passes.value, one.value, least.value
 
 
 def run_pipelined(batches, opts=None):

@@ -9,7 +9,8 @@
 //     ..._end_subsampled    (rtk_index_subsample.h) the events thinned out by coverage and their ids renumbered before they leave the device (k_sub_*)
 //     ..._merge             (rtk_index_merge.h)     the ids of read pairs on the same unitigs merged in place before that (k_merge_*)
 //   rtk_index_snp_candidates (rtk_index_snps.h)     the candidate search of the SNP annotations: the graph k-mers one substitution away from every window of the
-//                                                   searched unitigs (k_snp_*)
+//                                                   searched unitigs (k_snp_*), in passes over partitions of the key space when the views of all
+//                                                   windows do not fit; rtk_index_snp_plan: what it would do, from the offsets alone
 // Every step serves one-word k-mers (k <= 31, key type uint64_t) and two-word k-mers (33 <= k <= 63, key type unsigned __int128: the 2k-bit code,
 // first base in the most significant bits; in memory the low word first). Own translation unit: rocPRIM's templates.
 // An entry is: the checks of its arguments, entry(...) -- the device set, what is thrown turned into the entry's error --, one call into the stage.
@@ -195,4 +196,13 @@ extern "C" int rtk_index_snp_candidates(int device, int k, const char* seq_pool,
     *cand = nullptr; *n_cand = 0;
     if (n_unitigs == 0) return RTK_OK;
     return entry("rtk_index_snp_candidates", device, [&]() { return by_key_type(k, [&](auto km) { return snp_candidates<decltype(km)>(k, seq_pool, seq_off, n_unitigs, searched, flags, cand, n_cand); }); });
+}
+
+extern "C" int rtk_index_snp_plan(int device, int k, const uint64_t* seq_off, uint64_t n_unitigs, const uint8_t* searched, uint64_t room, uint32_t* passes, uint64_t* need_one_pass, uint64_t* need_min) {
+    if (!passes || !need_one_pass || !need_min || (n_unitigs && !seq_off)) return rtk_fail(RTK_ERR_ARG, "rtk_index_snp_plan: null argument");
+    if (const int rc = check_k_and_device("rtk_index_snp_plan", k, device)) return rc;
+    if (n_unitigs >= 0xFFFFFFFFull) return rtk_fail(RTK_ERR_UNSUPPORTED, "rtk_index_snp_plan: more than 2^32 - 1 unitigs");
+    *passes = 0; *need_one_pass = 0; *need_min = 0;
+    const uint64_t none[1] = {0};
+    return entry("rtk_index_snp_plan", device, [&]() { return by_key_type(k, [&](auto km) { return snp_plan<decltype(km)>(k, n_unitigs ? seq_off : none, n_unitigs, searched, room, passes, need_one_pass, need_min); }); });
 }

@@ -76,6 +76,7 @@ inline uint64_t rtk_knob_index_chunk(uint64_t dflt) { const uint64_t v = rtk_env
 inline int rtk_knob_index_keep_text() { return rtk_env_int("RTK_INDEX_KEEP_TEXT", -1); }                 // 0 | non-zero | unset (-1: decided from the free memory): keep the packed input on the device
 inline uint64_t rtk_knob_index_events(uint64_t dflt) { return rtk_env_u64("RTK_INDEX_EVENTS", dflt); }   // u64: capacity of the (unitig, read) event buffer of the colouring
 inline uint64_t rtk_knob_index_snp_mem(uint64_t dflt) { return std::min(dflt, rtk_env_u64("RTK_INDEX_SNP_MEM", dflt)); } // u64 bytes: rtk_index_snp_candidates compares its need with this instead of the free device memory when it is lower (tests: the refusal)
+inline uint32_t rtk_knob_index_snp_passes() { return static_cast<uint32_t>(std::min<uint64_t>(rtk_env_u64("RTK_INDEX_SNP_PASSES", 0), 0xFFFFFFFFull)); } // u32, 0 = as few as fit: rtk_index_snp_candidates searches in exactly this many passes over partitions of the key space (clamped to min(256, prefix values); tests: the partitioned path on small inputs)
 inline uint64_t rtk_knob_hx_part_keys(uint64_t dflt) { return rtk_env_u64("RTK_HX_PART_KEYS", dflt); }   // u64: keys per partition when the signature table is built
 
 // ---- simulator only

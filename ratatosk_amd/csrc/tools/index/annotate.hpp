@@ -272,7 +272,7 @@ template <class KM> struct SnpSearch {
 };
 
 // --gpu: the candidates of every unitig with an edge bit from the device (rtk_index_snp_candidates, csrc/hip/rtk_index_snps.h), first per (position, base) only -- the
-// later ones return at the `tried` check of the replay. Two words each: u << 32 | p, j << 40 | alt << 32 | w, by (u, p, j, alt). false with the reason in `why`: the
+// later ones return at the `tried` check of the replay (the entry searches in as many passes over the key space as the device's memory asks for). Two words each: u << 32 | p, j << 40 | alt << 32 | w, by (u, p, j, alt). false with the reason in `why`: the
 // caller takes the host route.
 template <class KM> static bool snp_candidates_device(IndexBuild<KM>& s, std::vector<uint64_t>& cand, std::string& why) {
     HipLib::snp_cand_fn fn = nullptr;
