@@ -51,12 +51,19 @@ template <class KM> struct SolidHead {
 template <class KM> struct KeyAt { const KM* keys; __device__ KM operator()(uint64_t i) const { return keys[i]; } };
 
 // bytes of the inputs (a sampled source: of the text it stands for); false: *err
-inline bool count_input_bytes(const std::vector<std::string>& files, uint64_t* total, std::string* err) {
-    *total = 0;
+// *fasta_kmers: of those bytes, the ones of FASTA files (records start with '>': a unitig file handed in as the graph), left OUT of *total and given as the k-mers
+// they stand for: nearly every byte of FASTA text starts a window, and gzip packs such text to a quarter (2 bits a base), where half of a FASTQ file's bytes are bases.
+inline bool count_input_bytes(const std::vector<std::string>& files, uint64_t* total, uint64_t* fasta_kmers, std::string* err) {
+    *total = 0; *fasta_kmers = 0;
     for (size_t f = 0; f < files.size(); ++f) {
         if (rtk::SampleSource::is_spec(files[f])) { std::shared_ptr<rtk::SampleSource> ss = rtk::SampleSource::get(files[f], err); if (!ss) return false; *total += 2 * ss->n_bases(); continue; }
         FILE* fp = fopen(files[f].c_str(), "rb"); if (!fp) { *err = "cannot open " + files[f]; return false; }
-        fseek(fp, 0, SEEK_END); *total += static_cast<uint64_t>(ftell(fp)); fclose(fp);
+        unsigned char m[2] = {0, 0}; const size_t n_m = fread(m, 1, 2, fp);
+        fseek(fp, 0, SEEK_END); const uint64_t bytes = static_cast<uint64_t>(ftell(fp)); fclose(fp);
+        const bool gz = n_m == 2 && m[0] == 0x1f && m[1] == 0x8b;
+        char first = n_m ? static_cast<char>(m[0]) : 0;
+        if (gz) { gzFile g = gzopen(files[f].c_str(), "rb"); if (g) { if (gzread(g, &first, 1) != 1) first = 0; gzclose(g); } }
+        if (first == '>') *fasta_kmers += gz ? 4 * bytes : bytes; else *total += bytes;
     }
     return true;
 }
@@ -116,11 +123,11 @@ template <class KM> int count_kmers(int k, const char* const* files, int n_files
     const std::vector<std::string> fl(files, files + n_files);
     std::string err;
     // passes: the k-mers of one pass (one hash partition of the k-mer space) must fit twice (radix sort) next to what else lives on the device
-    uint64_t total_bytes = 0;
-    if (!count_input_bytes(fl, &total_bytes, &err)) return rtk_fail(RTK_ERR_IO, "rtk_index_count_kmers: " + err);
+    uint64_t total_bytes = 0, fasta_kmers = 0;
+    if (!count_input_bytes(fl, &total_bytes, &fasta_kmers, &err)) return rtk_fail(RTK_ERR_IO, "rtk_index_count_kmers: " + err);
     size_t fr = 0, tot = 0; rtk_check(hipMemGetInfo(&fr, &tot), "hipMemGetInfo");
-    if (rtk_knob_index_trace()) fprintf(stderr, "rtk_index_count_kmers: inputs sized (%.1f GB), %.1f GB of device memory free\n", total_bytes / 1e9, fr / 1e9);
-    const uint64_t est_kmers = total_bytes / 2 + (1u << 20); // FASTQ: half of the bytes are bases (gzip input: a multiple of it; the capacity test below catches that)
+    if (rtk_knob_index_trace()) fprintf(stderr, "rtk_index_count_kmers: inputs sized (%.1f GB), %.1f GB of device memory free\n", (total_bytes + fasta_kmers) / 1e9, fr / 1e9);
+    const uint64_t est_kmers = total_bytes / 2 + fasta_kmers + (1u << 20); // FASTQ: half of the bytes are bases (gzip FASTQ: a multiple of it; the capacity test below catches that); FASTA: see count_input_bytes
     uint64_t cap = static_cast<uint64_t>(fr) / 10 * 7 / (2 * sizeof(KM)); // 70 % of the free memory for keys + their sort buffer (the rest: two chunks of text, the sort's histograms)
     cap = rtk_knob_index_cap(cap);
     if (cap < (1u << 20)) cap = 1u << 20;

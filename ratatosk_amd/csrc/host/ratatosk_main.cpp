@@ -58,6 +58,7 @@ struct Opt {
     double min_conf_snp = 0.9;
     size_t insert_sz = 500, w1 = 1000, w2 = 5000, batch_bases = 0; // 0: not given (64 Mi for the first pass, 32 Mi for the second)
     bool merge_duplicates = false; // --merge-duplicates: handed to both index steps of `correct -s` (the second colours by long reads and leaves them alone)
+    bool k1_from_k2 = false; // --k1-from-k2: `correct -s` builds the k2 graph once (rtk_build_index --graph-only) and both indexes from its unitig file (--graph-from)
     bool subsample = false; std::string subsample_seed; // --subsample-colours [--subsample-seed N]: handed to both index steps of `correct -s`
     // -M / -C / -Q as given: `correct -s` hands them to the index step of the second pass (rtk_build_index --colour-min-conf / --colour-min-len / --colour-max-qual)
     std::string min_conf_colour2, min_len_colour2, max_qual_given;
@@ -74,6 +75,9 @@ static void usage() {
                     "      --subsample-seed N  seed of the hash that stands in for the reference's random draws (default 1; only with --subsample-colours)\n"
                     "      --merge-duplicates  short-read pairs that lie on the same unitigs share one colour id, as the reference's index step merges duplicated reads;\n"
                     "                        handed to both index steps (the second colours by long reads, one id each, and says so)\n"
+                    "      --k1-from-k2      the short reads are counted once, at k2: the k1 graph is built from the unitigs of the k2 graph (every k1-mer of their text), as the reference's\n"
+                    "                        one-command run does, and the second-pass index takes the same k2 graph instead of counting again (rtk_build_index --graph-only, then --graph-from twice).\n"
+                    "                        Without it the k1 graph is built from the short reads; the two k1 graphs differ in the k1-mers that recur only in erroneous k2-mers. With -2 alone: accepted, the chain of before\n"
                     "  -M, --min-conf-color2  a base of a first-pass read whose quality is below that of this confidence (0 .. 1; 0: the '!' bases) does not colour the graph of the\n"
                     "                        second pass; -C, --min-len-color2: a first-pass read of fewer bases colours nothing. Handed to the k2 index step, with -Q if given\n"
                     "                        (rtk_build_index --colour-min-conf / --colour-min-len / --colour-max-qual). The reference applies -M 0 -C 3000 by default; here neither\n"
@@ -131,6 +135,9 @@ static bool gzip_member(const std::string& in, std::string& out) { out.clear(); 
 // -1 / -2: the index of that pass, then that pass. The first step that fails ends the run (non-zero exit, the step named); nothing is tried again.
 // With -u the chain starts with the rescue (src/Ratatosk.cpp:1040-1056: every run without an index, also -1 / -2 alone): rtk_rescue_reads --gpu writes
 // OUT_extra_sr.fasta, which is a further -s of BOTH index steps (both graphs are built from the short reads here) and is removed at the end of the run.
+// With --k1-from-k2 the short reads are counted once, as the reference does (src/Ratatosk.cpp:1062-1068, 1092-1101, 1194): step 1a builds the k2 graph alone
+// (rtk_build_index --graph-only, OUT.tmp.g2.index.kK2.fasta.gz, removed at the end), step 1 takes the k1 graph from the text of its unitigs and colours it with the
+// short reads, step 3 takes the k2 graph from the same file and colours it with the reads of the first pass, without -s.
 static int run_step(const char* what, const std::vector<std::string>& args, bool verbose) {
     std::vector<char*> av; for (size_t i = 0; i < args.size(); ++i) av.push_back(const_cast<char*>(args[i].c_str())); av.push_back(nullptr);
     if (verbose) { fprintf(stderr, "Ratatosk::correct: %s:", what); for (size_t i = 0; i < args.size(); ++i) fprintf(stderr, " %s", args[i].c_str()); fprintf(stderr, "\n"); }
@@ -165,10 +172,12 @@ static int correct_from_short_reads(const Opt& opt, const char* argv0) {
     const std::string dir = self.find('/') == std::string::npos ? std::string(".") : self.substr(0, self.rfind('/')), tool = dir + "/rtk_build_index", rescue_tool = dir + "/rtk_rescue_reads";
     if (opt.cores > 0 && std::find(opt.fwd1.begin(), opt.fwd1.end(), std::string("-c")) != opt.fwd1.end()) setenv("RTK_INDEX_THREADS", std::to_string(opt.cores).c_str(), 1); // (else the tool sizes itself by the machine)
     std::string extra_sr; // OUT_extra_sr.fasta, when the rescue kept reads
-    auto index_args = [&](int k, const std::string& prefix, const std::vector<std::string>& colour) {
+    // graph_from: the unitig file the graph is taken from (--k1-from-k2), else it is counted from the short reads; with_short: the short reads given (-s: they count, or colour a graph given)
+    auto index_args = [&](int k, const std::string& prefix, const std::vector<std::string>& colour, const std::string& graph_from, bool with_short) {
         std::vector<std::string> a; a.push_back(tool); a.push_back("--gpu"); a.push_back("-k"); a.push_back(std::to_string(k));
-        for (size_t i = 0; i < opt.in_short.size(); ++i) { a.push_back("-s"); a.push_back(opt.in_short[i]); }
-        if (!extra_sr.empty()) { a.push_back("-s"); a.push_back(extra_sr); }
+        if (!graph_from.empty()) { a.push_back("--graph-from"); a.push_back(graph_from); }
+        for (size_t i = 0; with_short && i < opt.in_short.size(); ++i) { a.push_back("-s"); a.push_back(opt.in_short[i]); }
+        if (with_short && !extra_sr.empty()) { a.push_back("-s"); a.push_back(extra_sr); }
         for (size_t i = 0; i < colour.size(); ++i) { a.push_back("--colour-reads"); a.push_back(colour[i]); }
         if (!colour.empty() && (!opt.min_conf_colour2.empty() || !opt.min_len_colour2.empty())) { // the second-pass index alone (DESIGN.md section 4 [A14]); neither given: the command line of before
             if (!opt.min_conf_colour2.empty()) { a.push_back("--colour-min-conf"); a.push_back(opt.min_conf_colour2); }
@@ -183,6 +192,10 @@ static int correct_from_short_reads(const Opt& opt, const char* argv0) {
     auto index_files = [&](int k, const std::string& prefix) { const std::string p = prefix + ".index.k" + std::to_string(k); return std::make_pair(p + ".fasta.gz", p + ".rtsk"); };
     const std::string pre1 = opt.out + ".tmp.k1", pre2 = opt.out + ".tmp.k2", mid = opt.out + ".2.fastq";
     const std::pair<std::string, std::string> f1 = index_files(opt.k1, pre1), f2 = index_files(opt.k2, pre2);
+    // --k1-from-k2 (both passes, or -1): the k2 graph of the short reads, built once (step 1a); both indexes take their graph from its unitig file. -2 alone: the graph
+    // of that pass is built from the short reads in the reference as well (src/Ratatosk.cpp:1176), the chain of before
+    const bool reuse = opt.k1_from_k2 && !opt.pass2;
+    const std::string pre_g = opt.out + ".tmp.g2", graph2 = index_files(opt.k2, pre_g).first, no_graph;
     std::vector<std::string> tmp_files;
     auto cleanup = [&]() { for (size_t i = 0; i < tmp_files.size(); ++i) unlink(tmp_files[i].c_str()); };
     const auto t0 = std::chrono::steady_clock::now();
@@ -206,8 +219,17 @@ static int correct_from_short_reads(const Opt& opt, const char* argv0) {
     }
     if (both || opt.pass1) {
         if (v) fprintf(stderr, "Ratatosk::Ratatosk(): Building graph from short reads (1/2).\n");
+        if (reuse) {
+            std::vector<std::string> a; a.push_back(tool); a.push_back("--gpu"); a.push_back("--graph-only"); a.push_back("-k"); a.push_back(std::to_string(opt.k2));
+            for (size_t i = 0; i < opt.in_short.size(); ++i) { a.push_back("-s"); a.push_back(opt.in_short[i]); }
+            if (!extra_sr.empty()) { a.push_back("-s"); a.push_back(extra_sr); }
+            a.push_back("-o"); a.push_back(pre_g);
+            rescued.push_back(graph2); // (outlives the files of the first pass: removed when the run ends)
+            if (run_step("step 1a (k2 graph, rtk_build_index)", a, v)) { cleanup_all(); return 1; }
+            if (v) fprintf(stderr, "Ratatosk::Ratatosk(): k2 graph built, k1 graph from its unitigs. [%.1f s]\n", since());
+        }
         tmp_files.push_back(f1.first); tmp_files.push_back(f1.second);
-        if (run_step("step 1 (k1 index, rtk_build_index)", index_args(opt.k1, pre1, std::vector<std::string>()), v)) { cleanup_all(); return 1; }
+        if (run_step("step 1 (k1 index, rtk_build_index)", index_args(opt.k1, pre1, std::vector<std::string>(), reuse ? graph2 : no_graph, true), v)) { cleanup_all(); return 1; }
         if (v) fprintf(stderr, "Ratatosk::Ratatosk(): Correcting long reads (1/2). [%.1f s]\n", since());
         std::vector<std::string> a; a.push_back(self); a.push_back("correct"); a.push_back("-1"); a.push_back("-g"); a.push_back(f1.first); a.push_back("-d"); a.push_back(f1.second);
         for (size_t i = 0; i < opt.in_long.size(); ++i) { a.push_back("-l"); a.push_back(opt.in_long[i]); }
@@ -220,7 +242,7 @@ static int correct_from_short_reads(const Opt& opt, const char* argv0) {
         if (both) tmp_files.push_back(mid);
         if (v) fprintf(stderr, "Ratatosk::Ratatosk(): Building graph from short reads (2/2). [%.1f s]\n", since());
         tmp_files.push_back(f2.first); tmp_files.push_back(f2.second);
-        if (run_step("step 3 (k2 index, rtk_build_index)", index_args(opt.k2, pre2, p1_reads), v)) { cleanup_all(); return 1; }
+        if (run_step("step 3 (k2 index, rtk_build_index)", index_args(opt.k2, pre2, p1_reads, both && reuse ? graph2 : no_graph, !(both && reuse)), v)) { cleanup_all(); return 1; }
         if (v) fprintf(stderr, "Ratatosk::Ratatosk(): Correcting long reads (2/2). [%.1f s]\n", since());
         std::vector<std::string> a; a.push_back(self); a.push_back("correct"); a.push_back("-2"); a.push_back("-g"); a.push_back(f2.first); a.push_back("-d"); a.push_back(f2.second);
         for (size_t i = 0; i < p1_reads.size(); ++i) { a.push_back("-l"); a.push_back(p1_reads[i]); }
@@ -251,7 +273,7 @@ int main(int argc, char** argv) {
         {"correction-rounds", required_argument, 0, 'r'}, {"no-snp-correction", no_argument, 0, 'F'}, {"force-io-order", no_argument, 0, 'O'}, {"no-graph-index", no_argument, 0, 'I'},
         {"in-unmapped-short", required_argument, 0, 'u'}, {"in-accurate-long", required_argument, 0, 'a'}, {"in-short-phase", required_argument, 0, 'p'}, {"in-long-phase", required_argument, 0, 'P'}, {"force-correct-snp", no_argument, 0, 'f'},
         {"sampling", required_argument, 0, 'S'}, {"min-conf-color2", required_argument, 0, 'M'}, {"min-len-color2", required_argument, 0, 'C'},
-        {"batch-bases", required_argument, 0, 'B'}, {"strip-annotations", no_argument, 0, 1001}, {"gpus", required_argument, 0, 1002}, {"workers-per-gpu", required_argument, 0, 1003}, {"parse-only", no_argument, 0, 1004}, {"allow-tinybitmap", no_argument, 0, 1005}, {"subsample-colours", no_argument, 0, 1006}, {"subsample-seed", required_argument, 0, 1007}, {"merge-duplicates", no_argument, 0, 1008}, {"verbose", no_argument, 0, 'v'}, {0, 0, 0, 0}};
+        {"batch-bases", required_argument, 0, 'B'}, {"strip-annotations", no_argument, 0, 1001}, {"gpus", required_argument, 0, 1002}, {"workers-per-gpu", required_argument, 0, 1003}, {"parse-only", no_argument, 0, 1004}, {"allow-tinybitmap", no_argument, 0, 1005}, {"subsample-colours", no_argument, 0, 1006}, {"subsample-seed", required_argument, 0, 1007}, {"merge-duplicates", no_argument, 0, 1008}, {"k1-from-k2", no_argument, 0, 1009}, {"verbose", no_argument, 0, 'v'}, {0, 0, 0, 0}};
     int c, idx = 0;
     while ((c = getopt_long(argc - 1, argv + 1, "s:l:o:c:g:d:i:k:w:Q:m:B:L:K:W:t:r:u:a:p:P:S:M:C:GFOIf12v", lo, &idx)) != -1) {
         { // what `correct -s` hands on to its correction steps: the option as given (long options by their long name)
@@ -301,6 +323,7 @@ int main(int argc, char** argv) {
             case 1007: { opt.subsample_seed = optarg; char* end = nullptr; (void)strtoull(optarg, &end, 10); // (on its own it switches nothing on: refused below, as rtk_build_index does)
                 if (*optarg < '0' || *optarg > '9' || *end) { fprintf(stderr, "Ratatosk::correct: --subsample-seed takes an unsigned number, not '%s'\n", optarg); return 1; } break; }
             case 1008: opt.merge_duplicates = true; break; // (with -g / -d: refused below)
+            case 1009: opt.k1_from_k2 = true; break; // (with -g / -d: refused below)
             case 's': opt.in_short.push_back(optarg); break; // (with -g / -d: ignored, said below)
             default: usage(); return 0; // the reference returns 0 on option errors too (src/Ratatosk.cpp:1018)
         }
@@ -321,6 +344,10 @@ int main(int argc, char** argv) {
     }
     if (opt.merge_duplicates) { // likewise
         fprintf(stderr, "Ratatosk::correct: --merge-duplicates belongs to the index build (correct -s SHORT --merge-duplicates -l LONG -o OUT, or rtk_build_index --merge-duplicates): not accepted next to a pre-built index (-g, -d)\n");
+        return 1;
+    }
+    if (opt.k1_from_k2) { // likewise: the graphs of a pre-built index are what they are
+        fprintf(stderr, "Ratatosk::correct: --k1-from-k2 belongs to the index build (correct -s SHORT --k1-from-k2 -l LONG -o OUT, or rtk_build_index --graph-only / --graph-from): not accepted next to a pre-built index (-g, -d)\n");
         return 1;
     }
     for (size_t i = 0; i < opt.in_short.size(); ++i) fprintf(stderr, "Ratatosk::correct: short reads are only needed by `index` (not in scope); ignored\n");

@@ -17,6 +17,8 @@
 //   * short cycles   = restatement of detectShortCycles (src/Graph.cpp:4660-4735), so that fixRepeats has inputs
 //   * SNP annotations (--snps only) = restatement of detectSNPs (src/Graph.cpp:484-720) with the breadth-first bubble walk of
 //     isValidSNPcandidate (src/GraphTraversal.cpp:1057-1147); haplotype ids stay empty (no phasing input).
+//   * graph reuse    (--graph-only / --graph-from) = the graph of one build's unitig FASTA taken as the graph of another, of any k: the reference builds its k1 graph
+//     from the text of the k2 unitigs and reads the k2 graph back for the second pass (src/Ratatosk.cpp:1092-1101, 1194); DESIGN.md section 4 [A15]
 // The build is a list of steps over one state (tools/index/state.hpp): run<KM>() below names them in order.
 #include <zlib.h>
 
@@ -46,20 +48,33 @@ static int dump_input(const IndexOptions& o) {
 // with --gpu on the device (csrc/hip/rtk_index.hip, through the C ABI of libratatosk_hip.so next to this executable) ----
 template <class KM> static bool count_kmers(IndexBuild<KM>& s) {
     const IndexOptions& o = s.o;
+    // the graph of the reads (-s, k-mers seen >= --min-count times), or with --graph-from the graph of a unitig file: every k-mer of its text, once
+    // (a compacted graph survives its own FASTA: the unitigs depend on the k-mer set alone). The same route either way.
+    const bool from_graph = !o.graph_files.empty();
+    const std::vector<std::string>& files = o.graph_inputs(); const unsigned min_count = o.graph_min_count();
+    if (s.knobs.trace) { fprintf(stderr, "rtk_build_index: graph from %s", from_graph ? "--graph-from" : "the reads of -s"); for (size_t f = 0; f < files.size(); ++f) fprintf(stderr, " %s", files[f].c_str());
+        fprintf(stderr, from_graph ? " (every k-mer of the text is a vertex)\n" : " (k-mers seen >= %u times)\n", min_count); }
+    auto nothing_there = [&]() { // a graph file without a window of k bases: no graph to colour, nothing written
+        if (!from_graph || !s.solid.empty()) return false;
+        std::string names; for (size_t f = 0; f < files.size(); ++f) names += (f ? ", " : "") + files[f];
+        fprintf(stderr, "rtk_build_index: no k-mer of length %d in %s\n", s.k, names.c_str()); return true;
+    };
     if (!o.gpu) {
-        const int bad = count_kmers_host<KM>(o.in_files, s.k, o.min_count, s.n_thr, s.solid, nullptr);
-        if (bad) fprintf(stderr, bad == 2 ? "rtk_build_index: an input file ends in a damaged or cut-short gzip stream\n" : "rtk_build_index: cannot open an input file\n");
-        return !bad;
+        size_t bad_file = 0;
+        const int bad = count_kmers_host<KM>(files, s.k, min_count, s.n_thr, s.solid, &bad_file);
+        if (bad && from_graph) fprintf(stderr, bad == 2 ? "rtk_build_index: %s ends in a damaged or cut-short gzip stream\n" : "rtk_build_index: cannot open %s\n", files[bad_file].c_str());
+        else if (bad) fprintf(stderr, bad == 2 ? "rtk_build_index: an input file ends in a damaged or cut-short gzip stream\n" : "rtk_build_index: cannot open an input file\n");
+        return !bad && !nothing_there();
     }
     if (!s.lib.open("rtk_build_index")) return false;
     if (!s.lib.count_kmers || !s.lib.last_error || !s.lib.free) { fprintf(stderr, "rtk_build_index: --gpu: %s lacks the index entry points\n", s.lib.path.c_str()); return false; }
-    std::vector<const char*> fp; for (size_t f = 0; f < o.in_files.size(); ++f) fp.push_back(o.in_files[f].c_str());
+    std::vector<const char*> fp; for (size_t f = 0; f < files.size(); ++f) fp.push_back(files[f].c_str());
     uint64_t* sk = nullptr; uint64_t ns = 0;
-    if (s.lib.count_kmers(0, s.k, fp.data(), static_cast<int>(fp.size()), o.min_count, static_cast<int>(s.n_thr), &sk, &ns) != 0) { fprintf(stderr, "rtk_build_index: --gpu: %s\n", s.lib.last_error()); return false; }
+    if (s.lib.count_kmers(0, s.k, fp.data(), static_cast<int>(fp.size()), min_count, static_cast<int>(s.n_thr), &sk, &ns) != 0) { fprintf(stderr, "rtk_build_index: --gpu: %s\n", s.lib.last_error()); return false; }
     s.solid.resize(ns);
     if (ns) memcpy(s.solid.data(), sk, sizeof(KM) * ns); // (two-word k-mers: two words each, low word first)
     s.lib.free(sk);
-    return true;
+    return !nothing_there();
 }
 
 // The unitig FASTA only needs the sequences: with --fast it is compressed on threads of its own while the colours, annotations and records are worked out.
@@ -130,6 +145,12 @@ template <class KM> static int run(const IndexOptions& o) {
     s.lap("k-mer table filled");
     build_unitigs(s);
     s.lap("unitigs built");
+    if (o.graph_only) { // the unitig FASTA of the full build, and no .rtsk (an earlier one at that path is not touched)
+        start_fasta_writer(s);
+        if (!finish_fasta_writer(s)) return 1;
+        s.lap("files written");
+        return 0;
+    }
     start_fasta_writer(s);
     if (!colour_and_cover(s)) return 1;
     s.lap("colours and coverage done");

@@ -34,19 +34,27 @@ struct IndexOptions {
     std::vector<std::string> colour_files; // pass-2 index (`Ratatosk index -2`): colours = ids of these (pass-1 corrected long) reads, one id per read
     // --colour-min-conf M / --colour-max-qual Q / --colour-min-len N (only with --colour-reads; tools/index/colour_filter.hpp has the rule): min_conf < 0 = not given
     double colour_min_conf = -1.0; int colour_max_qual = 40; uint64_t colour_min_len = 0;
+    // --graph-from FILE: the graph is every k-mer of the text of these FASTA files (the unitig file of an earlier build, of any k), each once; -s then only colours and covers
+    std::vector<std::string> graph_files;
+    bool graph_only = false; // --graph-only: count, table, unitigs, the unitig FASTA written, nothing else
+    // what the graph is counted from, and how often a k-mer must be seen there
+    const std::vector<std::string>& graph_inputs() const { return graph_files.empty() ? in_files : graph_files; }
+    unsigned graph_min_count() const { return graph_files.empty() ? min_count : 1u; }
     std::string out_file(const char* ext) const { return prefix + ".index.k" + std::to_string(k) + ext; }
 };
 
 // 0, or the exit status (2: the message or the usage text is on stderr)
 inline int parse_options(int argc, char** argv, IndexOptions& o) {
-    bool seed_given = false; const char* filter_given = nullptr;
+    bool seed_given = false, min_count_given = false; const char* filter_given = nullptr;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto need = [&](const char* n) -> const char* { if (i + 1 >= argc) { fprintf(stderr, "rtk_build_index: missing value for %s\n", n); exit(2); } return argv[++i]; };
         if (a == "-s") o.in_files.push_back(need("-s"));
         else if (a == "-o") o.prefix = need("-o");
         else if (a == "-k") o.k = atoi(need("-k"));
-        else if (a == "--min-count") o.min_count = static_cast<unsigned>(atoi(need("--min-count")));
+        else if (a == "--min-count") { o.min_count = static_cast<unsigned>(atoi(need("--min-count"))); min_count_given = true; }
+        else if (a == "--graph-from") o.graph_files.push_back(need("--graph-from"));
+        else if (a == "--graph-only") o.graph_only = true;
         else if (a == "--global-cov-factor") o.global_cov_factor = atof(need("--global-cov-factor"));
         else if (a == "--no-short-cycles") o.detect_cycles = false;
         else if (a == "--snps") o.detect_snps = true;
@@ -66,9 +74,16 @@ inline int parse_options(int argc, char** argv, IndexOptions& o) {
         else if (a == "--dump-input") o.dump_input = need("--dump-input");
         else { fprintf(stderr, "rtk_build_index: unknown option %s\n", a.c_str()); return 2; }
     }
+    if (o.graph_only) { // the graph and nothing else: whatever colours, annotates or takes the graph from elsewhere clashes with it
+        const char* clash = o.detect_snps ? "--snps" : !o.colour_files.empty() ? "--colour-reads" : filter_given ? filter_given : o.merge ? "--merge-duplicates" : (o.subsample || seed_given) ? "--subsample-colours" : !o.graph_files.empty() ? "--graph-from" : nullptr;
+        if (clash) { fprintf(stderr, "rtk_build_index: --graph-only writes the unitig FASTA and stops: %s does not go with it\n", clash); return 2; }
+    }
+    if (!o.graph_files.empty() && min_count_given) { fprintf(stderr, "rtk_build_index: --min-count next to --graph-from: every k-mer of a graph file is a vertex (the reads of -s only colour), so there is nothing it could count\n"); return 2; }
+    if (!o.graph_files.empty() && o.in_files.empty() && o.colour_files.empty()) { fprintf(stderr, "rtk_build_index: --graph-from needs reads that colour the graph: -s or --colour-reads\n"); return 2; }
     if (seed_given && !o.subsample) { fprintf(stderr, "rtk_build_index: --subsample-seed without --subsample-colours\n"); return 2; }
     if (filter_given && o.colour_files.empty()) { fprintf(stderr, "rtk_build_index: %s without --colour-reads\n", filter_given); return 2; }
-    if (o.in_files.empty() || o.k < 3 || o.k > RTK_MAX_K || !(o.k & 1)) { fprintf(stderr, "usage: rtk_build_index -s reads.fq [-s ...] -o PREFIX [-k 31 (odd, <=63)] [--min-count 2] [--global-cov-factor 3.0] [--no-short-cycles] [--snps] [--fast | --gpu (k <= 63: same files, threads / the device for the heavy steps)] [--dump-input FILE] [--subsample-colours [--subsample-seed 1 (only with --subsample-colours)]: colours subsampled by coverage as the reference's index step does by default] [--merge-duplicates: read pairs that lie on the same unitigs share one colour id, as the reference's index step merges duplicated reads (no effect with --colour-reads)] [--colour-reads corrected_long_reads.fq: second-pass index, the graph comes from -s, colours and coverage from these reads [--colour-min-conf M (0 .. 1): a base of these reads whose quality is below that of confidence M colours nothing, as the reference's second-pass index does with -M (0: the '!' bases); needs FASTQ] [--colour-max-qual 40: the quality that stands for confidence 1 (-Q)] [--colour-min-len N: a read of fewer than N bases colours nothing (-C); these three only with --colour-reads]]\n"); return 2; }
+    const bool graph_given = !o.graph_files.empty() && !o.colour_files.empty(); // (the one case without -s: the graph from a file, the colours from --colour-reads)
+    if ((o.in_files.empty() && !graph_given) || o.k < 3 || o.k > RTK_MAX_K || !(o.k & 1)) { fprintf(stderr, "usage: rtk_build_index -s reads.fq [-s ...] -o PREFIX [-k 31 (odd, <=63)] [--min-count 2] [--global-cov-factor 3.0] [--no-short-cycles] [--snps] [--fast | --gpu (k <= 63: same files, threads / the device for the heavy steps)] [--dump-input FILE] [--subsample-colours [--subsample-seed 1 (only with --subsample-colours)]: colours subsampled by coverage as the reference's index step does by default] [--merge-duplicates: read pairs that lie on the same unitigs share one colour id, as the reference's index step merges duplicated reads (no effect with --colour-reads)] [--colour-reads corrected_long_reads.fq: second-pass index, the graph comes from -s, colours and coverage from these reads [--colour-min-conf M (0 .. 1): a base of these reads whose quality is below that of confidence M colours nothing, as the reference's second-pass index does with -M (0: the '!' bases); needs FASTQ] [--colour-max-qual 40: the quality that stands for confidence 1 (-Q)] [--colour-min-len N: a read of fewer than N bases colours nothing (-C); these three only with --colour-reads]] [--graph-only: the unitig FASTA (PREFIX.index.kK.fasta.gz, the bytes of the full build) and nothing else, no .rtsk; not with --snps, --colour-reads, --merge-duplicates, --subsample-colours, --graph-from] [--graph-from unitigs.fasta.gz (may be repeated; FASTA as -s reads it): the graph is every all-A/C/G/T window of length k of these records, each once, whatever the k the file was written with (a k above the file's own: the windows of that length inside its unitigs); -s then only colours and covers, and is not needed next to --colour-reads; not with --min-count]\n"); return 2; }
     return 0;
 }
 
