@@ -399,6 +399,26 @@ int rtk_index_snp_candidates(int device, int k, const char* seq_pool, const uint
 int rtk_index_snp_plan(int device, int k, const uint64_t* seq_off, uint64_t n_unitigs, const uint8_t* searched, uint64_t room, uint32_t* passes,
                        uint64_t* need_one_pass, uint64_t* need_min);
 
+/* rtk_index_cover_*: where the text of other sequences (the unitigs of the k2 graph) crosses an edge of these unitigs that too few colours share -- the search of
+ * the last block of the reference's first-pass addCoverage, "Covering low coverage edges." (src/Graph.cpp:3085-3363; DESIGN.md section 4 [A16]; the stage:
+ * csrc/hip/rtk_index_cover.h). Any odd k <= 63.
+ * begin: the unitigs as for rtk_index_colour_begin (packed, with their k-mer table in HBM), at most 2^30 of them (RTK_ERR_UNSUPPORTED above); low_bits[u]: the
+ * recorded edges of unitig u -- bit 1, 2, 4, 8 for the successor of its forward strand that appends A, C, G, T, the same bits << 4 for the successors of its
+ * reverse strand. chunk (calls are serialised): pieces of sequences separated by '\n', n_chars characters (at most 64 MB and 4 M pieces per call); piece r starts at
+ * starts[r] (starts[0] = 0, ascending), belongs to sequence seq_numbers[r] and begins at position first_positions[r] of that sequence. A sequence longer than a chunk
+ * is cut by the caller so that every k + 1 consecutive characters lie whole inside exactly one piece (a piece starts k characters before the end of the one before);
+ * a sequence of more than 2^32 characters is refused (RTK_ERR_UNSUPPORTED). end: the crossings of all chunks, two words each, ascending by the first word -- the order
+ * of the sequence numbers, left to right inside a sequence --, *n of them (rtk_free); releases the job (also on error; with null outputs: only that).
+ * A crossing: position p of a sequence where the k characters at p and at p + 1 are all A/C/G/T (either case), the k-mer at p is the last k-mer of its unitig u in
+ * the direction the text walks it, the k-mer at p + 1 lies in the graph (on unitig v, which may be u), and the recorded bit of u for that direction and character
+ * p + k is set. word 0 = sequence number << 32 | p; word 1 = u << 33 | v << 3 | direction << 2 | base (direction 1: u walked on its reverse strand; base: A=0 .. T=3
+ * of character p + k). The bits are only read: testing, clearing and handing out ids in order is the caller's. The capacity of the survivor buffer is counted
+ * (RTK_INDEX_COVER_CAP, default 2^20 crossings): a chunk that finds more is mapped a second time into a larger one. Appended without a new revision number: see
+ * RTK_API_REVISION. */
+int rtk_index_cover_begin(int device, int k, const char* seq_pool, const uint64_t* seq_off, uint64_t n_unitigs, const uint8_t* low_bits, void** job);
+int rtk_index_cover_chunk(void* job, const char* chars, uint64_t n_chars, const uint64_t* starts, const uint32_t* seq_numbers, const uint64_t* first_positions, uint32_t n_seqs);
+int rtk_index_cover_end(void* job, uint64_t** crossings, uint64_t* n);
+
 /* rtk_rescue_*: the rescue of unmapped short reads before the index build (`correct -u`; retrieveMissingReads, src/Graph.cpp:3857-4131, called at
  * src/Ratatosk.cpp:1040-1056), with exact sets where the reference has Bloom filters ([A11]). One-word k-mers (odd k <= 31).
  * begin (replaces buildBBF + the long-read graph build, src/Graph.cpp:3880-3884): lr / sr = the canonical k-mers seen at least twice in the long reads / in
@@ -462,7 +482,7 @@ const char* rtk_version(void);
  * 8: rtk_stats fields n_fa_linked_*; 9: rtk_rescue_begin / _chunk / _end; still 9: rtk_stats fields n_strand2_* and n_park_*, the test-only rtk_myers_batch mode 5, appended at the end -- a library of revision 9
  * without them leaves them as the caller set them;
  * 10: rtk_sets_batch, rtk_stats fields n_colours_*; still 10: rtk_index_colour_cov, rtk_index_colour_end_subsampled, rtk_index_subsample_events, then rtk_index_colour_merge,
- * rtk_index_colour_merge_classes, rtk_index_merge_events, then rtk_index_colour_chunk_q, then rtk_batch_fetch_seeds, then rtk_index_snp_candidates, then rtk_index_snp_plan, appended -- a library of revision 10 without them lacks the symbols, and callers look them up by name). */
+ * rtk_index_colour_merge_classes, rtk_index_merge_events, then rtk_index_colour_chunk_q, then rtk_batch_fetch_seeds, then rtk_index_snp_candidates, then rtk_index_snp_plan, then rtk_index_cover_begin / _chunk / _end, appended -- a library of revision 10 without them lacks the symbols, and callers look them up by name). */
 #define RTK_API_REVISION 10
 int rtk_api_revision(void);
 

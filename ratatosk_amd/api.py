@@ -136,6 +136,10 @@ def load_library(path=None):
     if hasattr(L, "rtk_index_snp_plan"):  # (still revision 10: appended; a library without it: index_snp_plan says so)
         L.rtk_index_snp_plan.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_ubyte), C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
                                          C.POINTER(C.c_uint64)]
+    if hasattr(L, "rtk_index_cover_begin"):  # (still revision 10: appended; a library without them: index_cover_crossings says so)
+        L.rtk_index_cover_begin.argtypes = [C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_ubyte), C.POINTER(C.c_void_p)]
+        L.rtk_index_cover_chunk.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.c_uint32]
+        L.rtk_index_cover_end.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_uint64)]
     L.rtk_free.argtypes = [C.c_void_p]
     _libs[path] = L
     return L
@@ -634,6 +638,84 @@ def index_snp_plan(unitigs, k, searched=None, room=0, device=0, lib_path=None):
     if rc != 0:
         raise RtkError("rtk error %d: %s" % (rc, L.rtk_last_error().decode()))
     return passes.value, one.value, least.value
+
+
+def index_cover_layout(sequences, k, chunks=None):
+    """The chunks index_cover_crossings hands to the device for `sequences`, as (chars, starts, seq_numbers, first_positions) each: what rtk_index_cover_chunk
+    takes. A sequence shorter than k + 1 characters holds no pair of windows and is left out (the numbers of the others stay those of the list). chunks: None
+    (every sequence whole, all in one chunk), or the largest number of characters of a chunk, separators included: the sequences are then packed into chunks of
+    that size in their order, and a sequence longer than a chunk is cut into pieces that overlap by k characters, so that every k + 1 consecutive characters lie
+    whole inside exactly one piece. Character starts[r] + j of a chunk is position first_positions[r] + j of sequence seq_numbers[r]."""
+    import numpy as np
+    if chunks is not None and chunks < k + 3:
+        raise ValueError("index_cover_crossings: a chunk holds at least k + 2 characters and a separator")
+    pieces = []  # (sequence number, first position, characters)
+    for n, s in enumerate(_b(x) for x in sequences):
+        if len(s) < k + 1:
+            continue
+        a, room = 0, len(s) if chunks is None else chunks - 1
+        while True:
+            e = min(len(s), a + room)
+            pieces.append((n, a, s[a:e]))
+            if e == len(s):
+                break
+            a = e - k
+    parts, cur, size = [], [], 0
+    for pc in pieces:
+        if cur and chunks is not None and size + len(pc[2]) + 1 > chunks:
+            parts.append(cur); cur, size = [], 0
+        cur.append(pc); size += len(pc[2]) + 1
+    if cur:
+        parts.append(cur)
+    out = []
+    for part in parts:
+        starts = np.zeros(len(part), dtype=np.uint64)
+        starts[1:] = np.cumsum([len(c) + 1 for _, _, c in part[:-1]], dtype=np.uint64)
+        out.append((b"".join(c + b"\n" for _, _, c in part), starts, np.ascontiguousarray([n for n, _, _ in part], dtype=np.uint32),
+                    np.ascontiguousarray([a for _, a, _ in part], dtype=np.uint64)))
+    return out
+
+
+def index_cover_crossings(unitigs, k, low_bits, sequences, device=0, lib_path=None, chunks=None):
+    """Where `sequences` cross the recorded low-coverage edges of `unitigs`, on the device: one job over rtk_index_cover_begin, one rtk_index_cover_chunk per
+    chunk, rtk_index_cover_end (include/ratatosk_hip.h; the rule: DESIGN.md section 4 [A16]). low_bits: one byte per unitig -- bit 1, 2, 4, 8 for the successor of
+    the forward strand that appends A, C, G, T, the same << 4 for the reverse strand. chunks: how the sequences are cut and packed (index_cover_layout). Returns the
+    list of (sequence number, p, u, v, direction, base), ascending by (sequence number, p): the bits are only read, nothing is cleared."""
+    import numpy as np
+    L = load_library(lib_path)
+    if not hasattr(L, "rtk_index_cover_begin"):
+        raise RtkError("%s lacks rtk_index_cover_begin / _chunk / _end (low-coverage edges covered: appended at interface revision 10)" % L._name)
+    u64p, u32p = C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)
+    seqs = [_b(u) for u in unitigs]
+    off = np.zeros(len(seqs) + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(u) for u in seqs], dtype=np.uint64)
+    low = np.ascontiguousarray(low_bits, dtype=np.uint8)
+    if low.size != len(seqs):
+        raise ValueError("index_cover_crossings: low_bits holds one byte per unitig")
+    parts = index_cover_layout(sequences, k, chunks)
+
+    def ok(rc):
+        if rc != 0:
+            raise RtkError("rtk error %d: %s" % (rc, L.rtk_last_error().decode()))
+
+    job = C.c_void_p()
+    ok(L.rtk_index_cover_begin(device, k, b"".join(seqs), off.ctypes.data_as(u64p), len(seqs), low.ctypes.data_as(C.POINTER(C.c_ubyte)), C.byref(job)))
+    try:
+        for chars, starts, numbers, first in parts:
+            ok(L.rtk_index_cover_chunk(job, chars, len(chars), starts.ctypes.data_as(u64p), numbers.ctypes.data_as(u32p), first.ctypes.data_as(u64p), len(numbers)))
+    except BaseException:
+        L.rtk_index_cover_end(job, None, None)
+        raise
+    out, n = u64p(), C.c_uint64(0)
+    ok(L.rtk_index_cover_end(job, C.byref(out), C.byref(n)))
+    try:
+        w = np.ctypeslib.as_array(out, shape=(max(1, 2 * n.value),))[:2 * n.value].copy() if n.value else np.zeros(0, dtype=np.uint64)
+    finally:
+        L.rtk_free(out)
+    w0, w1 = w[0::2], w[1::2]
+    one = np.uint64(1)
+    return list(zip((w0 >> np.uint64(32)).tolist(), (w0 & np.uint64(0xFFFFFFFF)).tolist(), (w1 >> np.uint64(33)).tolist(), ((w1 >> np.uint64(3)) & np.uint64(0x3FFFFFFF)).tolist(),
+                    ((w1 >> np.uint64(2)) & one).tolist(), (w1 & np.uint64(3)).tolist()))
 
 
 def run_pipelined(batches, opts=None):

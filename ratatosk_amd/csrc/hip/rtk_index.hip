@@ -11,6 +11,8 @@
 //   rtk_index_snp_candidates (rtk_index_snps.h)     the candidate search of the SNP annotations: the graph k-mers one substitution away from every window of the
 //                                                   searched unitigs (k_snp_*), in passes over partitions of the key space when the views of all
 //                                                   windows do not fit; rtk_index_snp_plan: what it would do, from the offsets alone
+//   rtk_index_cover_*       (rtk_index_cover.h)     the text of other sequences (the k2 unitigs) walked over the k-mer table: where it crosses an edge recorded as
+//                                                   shared by too few colours (k_cover_map); the crossings in the order of the file for the caller's serial walk
 // Every step serves one-word k-mers (k <= 31, key type uint64_t) and two-word k-mers (33 <= k <= 63, key type unsigned __int128: the 2k-bit code,
 // first base in the most significant bits; in memory the low word first). Own translation unit: rocPRIM's templates.
 // An entry is: the checks of its arguments, entry(...) -- the device set, what is thrown turned into the entry's error --, one call into the stage.
@@ -25,6 +27,7 @@
 #include "rtk_index_subsample.h"
 #include "rtk_index_merge.h"
 #include "rtk_index_snps.h"
+#include "rtk_index_cover.h"
 
 extern "C" int rtk_index_count_kmers(int device, int k, const char* const* files, int n_files, uint32_t min_count, int n_threads, uint64_t** solid_out, uint64_t* n_solid) {
     if (!files || n_files <= 0 || !solid_out || !n_solid) return rtk_fail(RTK_ERR_ARG, "rtk_index_count_kmers: null argument");
@@ -185,6 +188,41 @@ extern "C" int rtk_index_merge_events(int device, const uint64_t* events, uint64
         if (r.n_out > n_events) return rtk_fail(RTK_ERR_DEVICE, "rtk_index_merge_events: more events after the merge than before");
         if (r.n_out) rtk_check(hipMemcpy(events_out, out, 8 * r.n_out, hipMemcpyDeviceToHost), "hipMemcpy");
         *n_out = r.n_out; *n_ids_before = r.ids_before; *n_ids_after = r.ids_after;
+        return RTK_OK;
+    });
+}
+
+extern "C" int rtk_index_cover_begin(int device, int k, const char* seq_pool, const uint64_t* seq_off, uint64_t n_unitigs, const uint8_t* low_bits, void** job_out) {
+    if (!seq_pool || !seq_off || !low_bits || !job_out || n_unitigs == 0) return rtk_fail(RTK_ERR_ARG, "rtk_index_cover_begin: null argument");
+    if (n_unitigs > RTK_COVER_MAX_UNITIGS) return rtk_fail(RTK_ERR_UNSUPPORTED, "rtk_index_cover_begin: more than 2^30 unitigs (a crossing names two unitigs in one word)");
+    if (const int rc = check_k_and_device("rtk_index_cover_begin", k, device)) return rc;
+    *job_out = nullptr;
+    return entry("rtk_index_cover_begin", device, [&]() { std::unique_ptr<CoverJob> J(new CoverJob()); J->begin(device, k, seq_pool, seq_off, n_unitigs, low_bits); *job_out = J.release(); return RTK_OK; });
+}
+
+extern "C" int rtk_index_cover_chunk(void* job, const char* chars, uint64_t n_chars, const uint64_t* starts, const uint32_t* seq_numbers, const uint64_t* first_positions, uint32_t n_seqs) {
+    CoverJob* J = static_cast<CoverJob*>(job);
+    if (!J || !chars || !starts || !seq_numbers || !first_positions) return rtk_fail(RTK_ERR_ARG, "rtk_index_cover_chunk: null argument");
+    if (n_seqs == 0 || n_chars == 0) return RTK_OK;
+    if (n_chars > RTK_COVER_MAX_CHUNK || n_seqs > RTK_COVER_MAX_CHUNK / 16) return rtk_fail(RTK_ERR_ARG, "rtk_index_cover_chunk: chunk larger than 64 MB of characters / 4 M pieces");
+    for (uint32_t r = 0; r < n_seqs; ++r) { // (the kernel finds the piece of a position by bisection over starts, and a position has 32 bits in a crossing)
+        if (starts[r] >= n_chars || (r == 0 ? starts[0] != 0 : starts[r] <= starts[r - 1])) return rtk_fail(RTK_ERR_ARG, "rtk_index_cover_chunk: starts begin at 0, ascend and lie inside the chunk");
+        if (first_positions[r] + ((r + 1 < n_seqs ? starts[r + 1] : n_chars) - starts[r]) > (1ull << 32)) return rtk_fail(RTK_ERR_UNSUPPORTED, "rtk_index_cover_chunk: a sequence of more than 2^32 characters");
+    }
+    std::lock_guard<std::mutex> lk(J->m);
+    return entry("rtk_index_cover_chunk", J->device, [&]() { J->chunk(chars, n_chars, starts, seq_numbers, first_positions, n_seqs); return RTK_OK; });
+}
+
+extern "C" int rtk_index_cover_end(void* job, uint64_t** crossings, uint64_t* n) {
+    std::unique_ptr<CoverJob> J(static_cast<CoverJob*>(job));
+    if (!J) return rtk_fail(RTK_ERR_ARG, "rtk_index_cover_end: null job");
+    if (!crossings || !n) return RTK_OK; // (abandoned job: released)
+    *crossings = nullptr; *n = 0;
+    return entry("rtk_index_cover_end", J->device, [&]() {
+        HostOut<uint64_t> out;
+        if (!J->end(out)) return rtk_fail(RTK_ERR_IO, "rtk_index_cover_end: out of host memory");
+        *crossings = out.release(); *n = J->n_found;
+        J->trace_end();
         return RTK_OK;
     });
 }

@@ -28,16 +28,24 @@ __global__ void k_col_pack(const char* __restrict__ pool, uint64_t n_bases, uint
 // One lane per character position of a chunk of reads (sequences separated by '\n'): its k-mer looked up in the unitig table. A run of consecutive
 // positions of one read on one unitig is one EVENT (unitig << 32 | id of the read) and one addition of its length to the unitig's coverage, made by
 // the first lane of the run inside its wave (a run that crosses a wave boundary gives two events: duplicates go when the events are sorted).
-// the unitig of a one-word k-mer: 16-byte slots {canonical k-mer, unitig << 32 | ...}
-__device__ __forceinline__ uint32_t col_find(const GraphView& g, uint64_t km, int k) {
+// Where a k-mer lies: its unitig (0xFFFFFFFF: not in the graph), its offset there, and whether the unitig spells it as given (fw) or its reverse complement. The slot's
+// value holds all three (unitig << 32 | offset << 1 | the unitig spells the canonical form): nothing is searched a second time.
+struct ColPlace { uint32_t u, off; bool fw; };
+// a one-word k-mer: 16-byte slots {canonical k-mer, value}
+__device__ __forceinline__ ColPlace col_place(const GraphView& g, uint64_t km, int k) {
     const uint64_t rc = idx_revcomp(km, k), can = km <= rc ? km : rc;
     const uint64_t* __restrict__ ht = g.ht; const uint64_t slots = g.ht_slots;
     uint64_t s = __umul64hi(idx_hash(can), slots);
-    for (;;) { const uint64_t key = ht[2 * s]; if (key == can) return static_cast<uint32_t>(ht[2 * s + 1] >> 32); if (key == RTK_IDX_SENTINEL) return 0xFFFFFFFFu; s = s + 1 == slots ? 0 : s + 1; }
+    for (;;) {
+        const uint64_t key = ht[2 * s];
+        if (key == can) { const uint64_t v = ht[2 * s + 1]; ColPlace r; r.u = static_cast<uint32_t>(v >> 32); r.off = static_cast<uint32_t>((v & 0xFFFFFFFFull) >> 1); r.fw = ((v & 1ull) != 0) == (km <= rc); return r; }
+        if (key == RTK_IDX_SENTINEL) { ColPlace r; r.u = 0xFFFFFFFFu; r.off = 0; r.fw = true; return r; }
+        s = s + 1 == slots ? 0 : s + 1;
+    }
 }
 // the unitig of a two-word k-mer: the slots keep a fingerprint of the canonical k-mer, a match is confirmed against the unitig's bases
 // (rtk_find_kmer_wide without the presence filters, which the index build's table does not have)
-__device__ __forceinline__ uint32_t col_find(const GraphView& g, km2_t km, int k) {
+__device__ __forceinline__ ColPlace col_place(const GraphView& g, km2_t km, int k) {
     const RtkKm fw = idx_words(km), rc = rtk_km_revcomp(fw, k), can = rtk_km_less(fw, rc) ? fw : rc;
     const uint64_t fp = rtk_km_fingerprint(can); const uint64_t* __restrict__ ht = g.ht; const uint64_t slots = g.ht_slots;
     for (uint64_t s = rtk_ht_slot(rtk_km_hash(can), slots);; s = rtk_ht_next(s, slots)) {
@@ -45,11 +53,14 @@ __device__ __forceinline__ uint32_t col_find(const GraphView& g, km2_t km, int k
         if (key == fp) {
             const uint64_t v = ht[2 * s + 1]; const uint32_t u = static_cast<uint32_t>(v >> 32);
             const RtkKm urc = rtk_km_rc_of_unitig(g, g.uoff[u] + ((v & 0xFFFFFFFFull) >> 1), k);
-            if (rtk_km_eq(urc, rc) || rtk_km_eq(urc, fw)) return u;
+            const bool same = rtk_km_eq(urc, rc); // (the reverse complement of the unitig's window is that of the k-mer: the unitig spells it as given)
+            if (same || rtk_km_eq(urc, fw)) { ColPlace r; r.u = u; r.off = static_cast<uint32_t>((v & 0xFFFFFFFFull) >> 1); r.fw = same; return r; }
         }
-        if (key == RTK_EMPTY_KEY) return 0xFFFFFFFFu;
+        if (key == RTK_EMPTY_KEY) { ColPlace r; r.u = 0xFFFFFFFFu; r.off = 0; r.fw = true; return r; }
     }
 }
+// the unitig alone
+template <class KM> __device__ __forceinline__ uint32_t col_find(const GraphView& g, KM km, int k) { return col_place(g, km, k).u; }
 template <class KM>
 __global__ void k_col_map(const char* __restrict__ chars, uint64_t n, int k, const uint64_t* __restrict__ starts, const uint32_t* __restrict__ ids, uint32_t n_reads,
                           GraphView g, unsigned long long* __restrict__ cov, uint64_t* __restrict__ events, unsigned long long* __restrict__ top, uint64_t cap) {
@@ -110,10 +121,26 @@ uint64_t* sort_unique_events(uint64_t* cur, uint64_t* other, uint64_t n, DevArr<
     *n_out = read_word(d_n.p, "events sorted"); return out;
 }
 
+// The unitigs of a job in HBM: packed to 2 bits, their offsets, and their k-mer table (rtk_graph_tables.hip); g holds the fields the mapping kernels read
+// (k_col_map here, k_cover_map of rtk_index_cover.h).
+struct DeviceUnitigs : Owner {
+    DevArr<uint64_t> useq, uoff, ht; uint64_t slots = 0; GraphView g;
+    void build(int k, uint32_t n_unitigs, const char* seq_pool, const uint64_t* seq_off) {
+        const uint64_t n_bases = seq_off[n_unitigs], n_kmers = n_bases - n_unitigs * static_cast<uint64_t>(k - 1), n_words = (n_bases + 31) / 32;
+        { DevArr<char> d_pool; d_pool.alloc(n_bases); rtk_check(hipMemcpy(d_pool.p, seq_pool, n_bases, hipMemcpyHostToDevice), "hipMemcpy");
+          useq.alloc(n_words + 2); rtk_check(hipMemset(useq.p, 0, 8 * (n_words + 2)), "hipMemset");
+          launch("k_col_pack", k_col_pack, dim3(4096), 0, d_pool.p, n_bases, useq.p, n_words); rtk_check(hipDeviceSynchronize(), "k_col_pack"); }
+        uoff.alloc(n_unitigs + 1ull); rtk_check(hipMemcpy(uoff.p, seq_off, 8 * (n_unitigs + 1ull), hipMemcpyHostToDevice), "hipMemcpy");
+        void* table = nullptr; rtk::device_kmer_table(useq.p, uoff.p, n_unitigs, n_bases, n_kmers, k, &table, &slots);
+        ht.adopt(table);
+        memset(&g, 0, sizeof(g)); g.k = k; g.n_unitigs = n_unitigs; g.ht_slots = slots; g.ht = ht.p; g.useq = useq.p; g.uoff = uoff.p;
+    }
+};
+
 struct ColourJob {
-    int device = 0, k = 31; uint32_t n_unitigs = 0; GraphView g; // g: the k-mer table and the packed unitigs (the only fields k_col_map reads)
-    DevArr<uint64_t> useq, uoff, ht, events, alt; DevArr<unsigned long long> cov, top; DevArr<char> tmp;
-    uint64_t slots = 0, cap = 0, n_events = 0; // n_events: sorted, distinct events at the front of `events`
+    int device = 0, k = 31; uint32_t n_unitigs = 0; DeviceUnitigs du; GraphView& g = du.g; // g: the k-mer table and the packed unitigs (the only fields k_col_map reads)
+    DevArr<uint64_t> events, alt; DevArr<unsigned long long> cov, top; DevArr<char> tmp;
+    uint64_t cap = 0, n_events = 0; // n_events: sorted, distinct events at the front of `events`
     uint64_t n_ids = 0;                        // largest id fed + 1 (after rtk_index_colour_merge: the number of merged ids): the size of the id tables of the subsampling
     uint64_t merge_classes_above_one = 0, merge_largest = 0; // what the last rtk_index_colour_merge found
     DevArr<char> d_chars[2]; DevArr<uint64_t> d_starts[2]; DevArr<uint32_t> d_ids[2]; PinArr<char> h_chars[2]; PinArr<uint64_t> h_starts[2]; PinArr<uint32_t> h_ids[2]; uint64_t chunk_cap = 0, reads_cap = 0;
@@ -139,14 +166,7 @@ struct ColourJob {
 
     // the unitigs packed to 2 bits, their k-mer table, the coverage counters
     void build_graph(const char* seq_pool, const uint64_t* seq_off) {
-        const uint64_t n_bases = seq_off[n_unitigs], n_kmers = n_bases - n_unitigs * static_cast<uint64_t>(k - 1), n_words = (n_bases + 31) / 32;
-        { DevArr<char> d_pool; d_pool.alloc(n_bases); rtk_check(hipMemcpy(d_pool.p, seq_pool, n_bases, hipMemcpyHostToDevice), "hipMemcpy");
-          useq.alloc(n_words + 2); rtk_check(hipMemset(useq.p, 0, 8 * (n_words + 2)), "hipMemset");
-          launch("k_col_pack", k_col_pack, dim3(4096), 0, d_pool.p, n_bases, useq.p, n_words); rtk_check(hipDeviceSynchronize(), "k_col_pack"); }
-        uoff.alloc(n_unitigs + 1ull); rtk_check(hipMemcpy(uoff.p, seq_off, 8 * (n_unitigs + 1ull), hipMemcpyHostToDevice), "hipMemcpy");
-        void* table = nullptr; rtk::device_kmer_table(useq.p, uoff.p, n_unitigs, n_bases, n_kmers, k, &table, &slots);
-        ht.adopt(table);
-        memset(&g, 0, sizeof(g)); g.k = k; g.n_unitigs = n_unitigs; g.ht_slots = slots; g.ht = ht.p; g.useq = useq.p; g.uoff = uoff.p;
+        du.build(k, n_unitigs, seq_pool, seq_off);
         cov.alloc(n_unitigs); rtk_check(hipMemset(cov.p, 0, 8ull * n_unitigs), "hipMemset");
         top.alloc(1); rtk_check(hipMemset(top.p, 0, 8), "hipMemset");
     }

@@ -59,6 +59,7 @@ struct Opt {
     size_t insert_sz = 500, w1 = 1000, w2 = 5000, batch_bases = 0; // 0: not given (64 Mi for the first pass, 32 Mi for the second)
     bool merge_duplicates = false; // --merge-duplicates: handed to both index steps of `correct -s` (the second colours by long reads and leaves them alone)
     bool k1_from_k2 = false; // --k1-from-k2: `correct -s` builds the k2 graph once (rtk_build_index --graph-only) and both indexes from its unitig file (--graph-from)
+    bool cover_edges = false; // --cover-edges (only with --k1-from-k2): the k1 index step of `correct -s` covers its low-coverage edges from the k2 unitig file (rtk_build_index --cover-edges-from)
     bool subsample = false; std::string subsample_seed; // --subsample-colours [--subsample-seed N]: handed to both index steps of `correct -s`
     // -M / -C / -Q as given: `correct -s` hands them to the index step of the second pass (rtk_build_index --colour-min-conf / --colour-min-len / --colour-max-qual)
     std::string min_conf_colour2, min_len_colour2, max_qual_given;
@@ -78,6 +79,8 @@ static void usage() {
                     "      --k1-from-k2      the short reads are counted once, at k2: the k1 graph is built from the unitigs of the k2 graph (every k1-mer of their text), as the reference's\n"
                     "                        one-command run does, and the second-pass index takes the same k2 graph instead of counting again (rtk_build_index --graph-only, then --graph-from twice).\n"
                     "                        Without it the k1 graph is built from the short reads; the two k1 graphs differ in the k1-mers that recur only in erroneous k2-mers. With -2 alone: accepted, the chain of before\n"
+                    "      --cover-edges     (only with --k1-from-k2; with -1 or both passes) the k1 index step covers the edges whose two unitigs share fewer than 2 colours wherever a k2 unitig walks\n"
+                    "                        over them, with two fresh colour ids per crossing, as the reference's first-pass index does (rtk_build_index --cover-edges-from the k2 unitig file)\n"
                     "  -M, --min-conf-color2  a base of a first-pass read whose quality is below that of this confidence (0 .. 1; 0: the '!' bases) does not colour the graph of the\n"
                     "                        second pass; -C, --min-len-color2: a first-pass read of fewer bases colours nothing. Handed to the k2 index step, with -Q if given\n"
                     "                        (rtk_build_index --colour-min-conf / --colour-min-len / --colour-max-qual). The reference applies -M 0 -C 3000 by default; here neither\n"
@@ -156,6 +159,8 @@ static int correct_from_short_reads(const Opt& opt, const char* argv0) {
     const bool both = !opt.pass1 && !opt.pass2;
     if (opt.pass1 && opt.pass2) { fprintf(stderr, "Ratatosk::correct: -1 and -2 exclude each other (neither: both passes)\n"); return 1; }
     if (opt.in_long.empty() || opt.out.empty()) { fprintf(stderr, "Ratatosk::correct: -s, -l and -o are required\n"); return 1; }
+    if (opt.cover_edges && !opt.k1_from_k2) { fprintf(stderr, "Ratatosk::correct: --cover-edges needs --k1-from-k2: the edges of the k1 graph are covered from the unitigs of the k2 graph, which is only there at that step when it is built first\n"); return 1; }
+    if (opt.cover_edges && opt.pass2) { fprintf(stderr, "Ratatosk::correct: --cover-edges belongs to the k1 index step (both passes, or -1): -2 alone builds no k1 index\n"); return 1; }
     if (opt.pass2 && opt.in_long_raw.empty()) { fprintf(stderr, "Ratatosk::correct: -2 needs the uncorrected long reads (-L) next to the pass-1 reads (-l)\n"); return 1; }
     if (opt.k1 < 3 || opt.k1 > 31 || !(opt.k1 & 1) || opt.k2 < 3 || opt.k2 > 63 || !(opt.k2 & 1)) { fprintf(stderr, "Ratatosk::correct: k1 must be odd and <= 31, k2 odd and <= 63\n"); return 1; }
     if (!opt.min_conf_colour2.empty()) { // src/Ratatosk.cpp:378-388
@@ -173,9 +178,11 @@ static int correct_from_short_reads(const Opt& opt, const char* argv0) {
     if (opt.cores > 0 && std::find(opt.fwd1.begin(), opt.fwd1.end(), std::string("-c")) != opt.fwd1.end()) setenv("RTK_INDEX_THREADS", std::to_string(opt.cores).c_str(), 1); // (else the tool sizes itself by the machine)
     std::string extra_sr; // OUT_extra_sr.fasta, when the rescue kept reads
     // graph_from: the unitig file the graph is taken from (--k1-from-k2), else it is counted from the short reads; with_short: the short reads given (-s: they count, or colour a graph given)
-    auto index_args = [&](int k, const std::string& prefix, const std::vector<std::string>& colour, const std::string& graph_from, bool with_short) {
+    // cover_from: the unitig file whose sequences cover the low-coverage edges (--cover-edges: the k1 index step alone)
+    auto index_args = [&](int k, const std::string& prefix, const std::vector<std::string>& colour, const std::string& graph_from, bool with_short, const std::string& cover_from) {
         std::vector<std::string> a; a.push_back(tool); a.push_back("--gpu"); a.push_back("-k"); a.push_back(std::to_string(k));
         if (!graph_from.empty()) { a.push_back("--graph-from"); a.push_back(graph_from); }
+        if (!cover_from.empty()) { a.push_back("--cover-edges-from"); a.push_back(cover_from); }
         for (size_t i = 0; with_short && i < opt.in_short.size(); ++i) { a.push_back("-s"); a.push_back(opt.in_short[i]); }
         if (with_short && !extra_sr.empty()) { a.push_back("-s"); a.push_back(extra_sr); }
         for (size_t i = 0; i < colour.size(); ++i) { a.push_back("--colour-reads"); a.push_back(colour[i]); }
@@ -229,7 +236,7 @@ static int correct_from_short_reads(const Opt& opt, const char* argv0) {
             if (v) fprintf(stderr, "Ratatosk::Ratatosk(): k2 graph built, k1 graph from its unitigs. [%.1f s]\n", since());
         }
         tmp_files.push_back(f1.first); tmp_files.push_back(f1.second);
-        if (run_step("step 1 (k1 index, rtk_build_index)", index_args(opt.k1, pre1, std::vector<std::string>(), reuse ? graph2 : no_graph, true), v)) { cleanup_all(); return 1; }
+        if (run_step("step 1 (k1 index, rtk_build_index)", index_args(opt.k1, pre1, std::vector<std::string>(), reuse ? graph2 : no_graph, true, reuse && opt.cover_edges ? graph2 : no_graph), v)) { cleanup_all(); return 1; }
         if (v) fprintf(stderr, "Ratatosk::Ratatosk(): Correcting long reads (1/2). [%.1f s]\n", since());
         std::vector<std::string> a; a.push_back(self); a.push_back("correct"); a.push_back("-1"); a.push_back("-g"); a.push_back(f1.first); a.push_back("-d"); a.push_back(f1.second);
         for (size_t i = 0; i < opt.in_long.size(); ++i) { a.push_back("-l"); a.push_back(opt.in_long[i]); }
@@ -242,7 +249,7 @@ static int correct_from_short_reads(const Opt& opt, const char* argv0) {
         if (both) tmp_files.push_back(mid);
         if (v) fprintf(stderr, "Ratatosk::Ratatosk(): Building graph from short reads (2/2). [%.1f s]\n", since());
         tmp_files.push_back(f2.first); tmp_files.push_back(f2.second);
-        if (run_step("step 3 (k2 index, rtk_build_index)", index_args(opt.k2, pre2, p1_reads, both && reuse ? graph2 : no_graph, !(both && reuse)), v)) { cleanup_all(); return 1; }
+        if (run_step("step 3 (k2 index, rtk_build_index)", index_args(opt.k2, pre2, p1_reads, both && reuse ? graph2 : no_graph, !(both && reuse), no_graph), v)) { cleanup_all(); return 1; }
         if (v) fprintf(stderr, "Ratatosk::Ratatosk(): Correcting long reads (2/2). [%.1f s]\n", since());
         std::vector<std::string> a; a.push_back(self); a.push_back("correct"); a.push_back("-2"); a.push_back("-g"); a.push_back(f2.first); a.push_back("-d"); a.push_back(f2.second);
         for (size_t i = 0; i < p1_reads.size(); ++i) { a.push_back("-l"); a.push_back(p1_reads[i]); }
@@ -273,7 +280,7 @@ int main(int argc, char** argv) {
         {"correction-rounds", required_argument, 0, 'r'}, {"no-snp-correction", no_argument, 0, 'F'}, {"force-io-order", no_argument, 0, 'O'}, {"no-graph-index", no_argument, 0, 'I'},
         {"in-unmapped-short", required_argument, 0, 'u'}, {"in-accurate-long", required_argument, 0, 'a'}, {"in-short-phase", required_argument, 0, 'p'}, {"in-long-phase", required_argument, 0, 'P'}, {"force-correct-snp", no_argument, 0, 'f'},
         {"sampling", required_argument, 0, 'S'}, {"min-conf-color2", required_argument, 0, 'M'}, {"min-len-color2", required_argument, 0, 'C'},
-        {"batch-bases", required_argument, 0, 'B'}, {"strip-annotations", no_argument, 0, 1001}, {"gpus", required_argument, 0, 1002}, {"workers-per-gpu", required_argument, 0, 1003}, {"parse-only", no_argument, 0, 1004}, {"allow-tinybitmap", no_argument, 0, 1005}, {"subsample-colours", no_argument, 0, 1006}, {"subsample-seed", required_argument, 0, 1007}, {"merge-duplicates", no_argument, 0, 1008}, {"k1-from-k2", no_argument, 0, 1009}, {"verbose", no_argument, 0, 'v'}, {0, 0, 0, 0}};
+        {"batch-bases", required_argument, 0, 'B'}, {"strip-annotations", no_argument, 0, 1001}, {"gpus", required_argument, 0, 1002}, {"workers-per-gpu", required_argument, 0, 1003}, {"parse-only", no_argument, 0, 1004}, {"allow-tinybitmap", no_argument, 0, 1005}, {"subsample-colours", no_argument, 0, 1006}, {"subsample-seed", required_argument, 0, 1007}, {"merge-duplicates", no_argument, 0, 1008}, {"k1-from-k2", no_argument, 0, 1009}, {"cover-edges", no_argument, 0, 1010}, {"verbose", no_argument, 0, 'v'}, {0, 0, 0, 0}};
     int c, idx = 0;
     while ((c = getopt_long(argc - 1, argv + 1, "s:l:o:c:g:d:i:k:w:Q:m:B:L:K:W:t:r:u:a:p:P:S:M:C:GFOIf12v", lo, &idx)) != -1) {
         { // what `correct -s` hands on to its correction steps: the option as given (long options by their long name)
@@ -324,6 +331,7 @@ int main(int argc, char** argv) {
                 if (*optarg < '0' || *optarg > '9' || *end) { fprintf(stderr, "Ratatosk::correct: --subsample-seed takes an unsigned number, not '%s'\n", optarg); return 1; } break; }
             case 1008: opt.merge_duplicates = true; break; // (with -g / -d: refused below)
             case 1009: opt.k1_from_k2 = true; break; // (with -g / -d: refused below)
+            case 1010: opt.cover_edges = true; break; // (with -g / -d, or without --k1-from-k2: refused below)
             case 's': opt.in_short.push_back(optarg); break; // (with -g / -d: ignored, said below)
             default: usage(); return 0; // the reference returns 0 on option errors too (src/Ratatosk.cpp:1018)
         }
@@ -344,6 +352,10 @@ int main(int argc, char** argv) {
     }
     if (opt.merge_duplicates) { // likewise
         fprintf(stderr, "Ratatosk::correct: --merge-duplicates belongs to the index build (correct -s SHORT --merge-duplicates -l LONG -o OUT, or rtk_build_index --merge-duplicates): not accepted next to a pre-built index (-g, -d)\n");
+        return 1;
+    }
+    if (opt.cover_edges) { // likewise: the colours of a pre-built index are what they are
+        fprintf(stderr, "Ratatosk::correct: --cover-edges belongs to the index build (correct -s SHORT --k1-from-k2 --cover-edges -l LONG -o OUT, or rtk_build_index --cover-edges-from): not accepted next to a pre-built index (-g, -d)\n");
         return 1;
     }
     if (opt.k1_from_k2) { // likewise: the graphs of a pre-built index are what they are

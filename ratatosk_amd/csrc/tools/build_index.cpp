@@ -19,6 +19,8 @@
 //     isValidSNPcandidate (src/GraphTraversal.cpp:1057-1147); haplotype ids stay empty (no phasing input).
 //   * graph reuse    (--graph-only / --graph-from) = the graph of one build's unitig FASTA taken as the graph of another, of any k: the reference builds its k1 graph
 //     from the text of the k2 unitigs and reads the k2 graph back for the second pass (src/Ratatosk.cpp:1092-1101, 1194); DESIGN.md section 4 [A15]
+//   covered edges  (--cover-edges-from only) = the edges that too few colours share get two fresh ids on both ends where a k2 unitig walks over them, as the last
+//     block of addCoverage does (src/Graph.cpp:3085-3363; index/cover.hpp; DESIGN.md section 4 [A16])
 // The build is a list of steps over one state (tools/index/state.hpp): run<KM>() below names them in order.
 #include <zlib.h>
 
@@ -29,6 +31,7 @@
 #include "../common/rtsk_io.hpp"
 #include "index/annotate.hpp"
 #include "index/colour.hpp"
+#include "index/cover.hpp"
 #include "index/merge.hpp"
 #include "index/subsample.hpp"
 #include "index/unitigs.hpp"
@@ -159,6 +162,8 @@ template <class KM> static int run(const IndexOptions& o) {
     if (o.subsample) { if (!subsample_colours(s)) return 1; s.lap("colours subsampled"); }
     edge_bits(s);
     s.lap("adjacency and edge bits done");
+    const bool cover = !o.cover_files.empty();
+    if (cover) { if (!cover_edges(s)) return 1; s.lap("low-coverage edges covered"); }
     if (o.detect_cycles) { short_cycles(s); s.lap("short cycles done"); }
     if (o.detect_snps) { snp_annotations(s); s.lap("SNP annotations done"); }
     colour_split(s);

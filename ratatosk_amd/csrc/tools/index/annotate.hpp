@@ -336,11 +336,15 @@ template <class KM> static void snp_annotations(IndexBuild<KM>& s) {
 }
 
 // ---- global / local colour split (simplified restatement of src/Graph.cpp:2874-2985) ----
+// The split is made on the read colours alone: the last s.cover_ids[u].size() colours of unitig u are the ids --cover-edges-from added (cover.hpp); they are
+// left out of every set compared here and join the local set at the end (SharedPairID::add puts a fresh id there).
 template <class KM> static void colour_split(IndexBuild<KM>& s) {
     const int k = s.k; const size_t n = s.U.size(); const std::vector<Unitig>& U = s.U; const std::vector<Nb>& adj = s.adj; const std::vector<uint64_t>& kmcov = s.kmcov;
     const double global_cov_factor = s.o.global_cov_factor, min_color_sharing = s.o.min_color_sharing;
     std::vector<std::vector<uint32_t> >& global_ids = s.global_ids; std::vector<std::vector<uint32_t> >& local_ids = s.local_ids;
     global_ids.assign(n, std::vector<uint32_t>()); local_ids.assign(n, std::vector<uint32_t>());
+    auto n_read = [&](size_t u) { return U[u].colours.size() - (s.cover_ids.empty() ? 0 : s.cover_ids[u].size()); }; // the read colours of u: colours[0 .. n_read(u))
+    auto read_end = [&](size_t u) { return U[u].colours.begin() + static_cast<std::ptrdiff_t>(n_read(u)); };
     double tot_cov = 0, tot_km = 0;
     for (size_t u = 0; u < n; ++u) { tot_cov += static_cast<double>(U[u].cov); tot_km += static_cast<double>(U[u].seq.size() - k + 1); }
     const double est_cov = tot_km > 0 ? tot_cov / tot_km : 0.0;
@@ -352,7 +356,7 @@ template <class KM> static void colour_split(IndexBuild<KM>& s) {
     for (size_t si = 0; si < seeds.size(); ++si) {
         const size_t u0 = seeds[si].second;
         if (visited[u0]) continue;
-        std::vector<uint32_t> inter = U[u0].colours;
+        std::vector<uint32_t> inter(U[u0].colours.begin(), read_end(u0));
         size_t max_card_inter = static_cast<size_t>(static_cast<double>(inter.size()) * min_color_sharing);
         std::set<size_t> seen, valid; seen.insert(u0);
         std::queue<size_t> q; q.push(u0);
@@ -364,10 +368,10 @@ template <class KM> static void colour_split(IndexBuild<KM>& s) {
             for (size_t j = 0; j < nbs.size(); ++j) {
                 const size_t w = nbs[j].second;
                 std::vector<uint32_t> li;
-                std::set_intersection(inter.begin(), inter.end(), U[w].colours.begin(), U[w].colours.end(), std::back_inserter(li));
-                if (static_cast<double>(li.size()) >= static_cast<double>(U[w].colours.size()) * min_color_sharing && li.size() >= max_card_inter && !li.empty()) {
+                std::set_intersection(inter.begin(), inter.end(), U[w].colours.begin(), read_end(w), std::back_inserter(li));
+                if (static_cast<double>(li.size()) >= static_cast<double>(n_read(w)) * min_color_sharing && li.size() >= max_card_inter && !li.empty()) {
                     inter.swap(li);
-                    max_card_inter = std::max(max_card_inter, static_cast<size_t>(static_cast<double>(U[w].colours.size()) * min_color_sharing));
+                    max_card_inter = std::max(max_card_inter, static_cast<size_t>(static_cast<double>(n_read(w)) * min_color_sharing));
                     valid.insert(w); q.push(w);
                 }
             }
@@ -376,12 +380,13 @@ template <class KM> static void colour_split(IndexBuild<KM>& s) {
             valid.insert(u0);
             for (std::set<size_t>::const_iterator it = valid.begin(); it != valid.end(); ++it) {
                 global_ids[*it] = inter; visited[*it] = 1;
-                std::set_difference(U[*it].colours.begin(), U[*it].colours.end(), inter.begin(), inter.end(), std::back_inserter(local_ids[*it]));
+                std::set_difference(U[*it].colours.begin(), read_end(*it), inter.begin(), inter.end(), std::back_inserter(local_ids[*it]));
             }
         }
     }
     size_t ng = 0;
-    for (size_t u = 0; u < n; ++u) { if (global_ids[u].empty()) local_ids[u] = U[u].colours; else ++ng; }
+    for (size_t u = 0; u < n; ++u) { if (global_ids[u].empty()) local_ids[u].assign(U[u].colours.begin(), read_end(u)); else ++ng; }
+    if (!s.cover_ids.empty()) for (size_t u = 0; u < n; ++u) local_ids[u].insert(local_ids[u].end(), s.cover_ids[u].begin(), s.cover_ids[u].end()); // (larger than every read id: the sets stay sorted)
     fprintf(stderr, "rtk_build_index: est. k-mer coverage %.2f, %zu unitigs carry a global colour set\n", est_cov, ng);
 }
 

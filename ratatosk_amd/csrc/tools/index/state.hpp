@@ -36,6 +36,8 @@ struct IndexOptions {
     double colour_min_conf = -1.0; int colour_max_qual = 40; uint64_t colour_min_len = 0;
     // --graph-from FILE: the graph is every k-mer of the text of these FASTA files (the unitig file of an earlier build, of any k), each once; -s then only colours and covers
     std::vector<std::string> graph_files;
+    // --cover-edges-from FILE: the edges that fewer than min_cov_vertices colours share get two fresh ids on both ends wherever a sequence of these FASTA files (the unitigs of the k2 graph) walks over them (tools/index/cover.hpp)
+    std::vector<std::string> cover_files;
     bool graph_only = false; // --graph-only: count, table, unitigs, the unitig FASTA written, nothing else
     // what the graph is counted from, and how often a k-mer must be seen there
     const std::vector<std::string>& graph_inputs() const { return graph_files.empty() ? in_files : graph_files; }
@@ -55,6 +57,7 @@ inline int parse_options(int argc, char** argv, IndexOptions& o) {
         else if (a == "--min-count") { o.min_count = static_cast<unsigned>(atoi(need("--min-count"))); min_count_given = true; }
         else if (a == "--graph-from") o.graph_files.push_back(need("--graph-from"));
         else if (a == "--graph-only") o.graph_only = true;
+        else if (a == "--cover-edges-from") o.cover_files.push_back(need("--cover-edges-from"));
         else if (a == "--global-cov-factor") o.global_cov_factor = atof(need("--global-cov-factor"));
         else if (a == "--no-short-cycles") o.detect_cycles = false;
         else if (a == "--snps") o.detect_snps = true;
@@ -75,15 +78,17 @@ inline int parse_options(int argc, char** argv, IndexOptions& o) {
         else { fprintf(stderr, "rtk_build_index: unknown option %s\n", a.c_str()); return 2; }
     }
     if (o.graph_only) { // the graph and nothing else: whatever colours, annotates or takes the graph from elsewhere clashes with it
-        const char* clash = o.detect_snps ? "--snps" : !o.colour_files.empty() ? "--colour-reads" : filter_given ? filter_given : o.merge ? "--merge-duplicates" : (o.subsample || seed_given) ? "--subsample-colours" : !o.graph_files.empty() ? "--graph-from" : nullptr;
+        const char* clash = o.detect_snps ? "--snps" : !o.colour_files.empty() ? "--colour-reads" : filter_given ? filter_given : o.merge ? "--merge-duplicates" : (o.subsample || seed_given) ? "--subsample-colours" : !o.graph_files.empty() ? "--graph-from" : !o.cover_files.empty() ? "--cover-edges-from" : nullptr;
         if (clash) { fprintf(stderr, "rtk_build_index: --graph-only writes the unitig FASTA and stops: %s does not go with it\n", clash); return 2; }
     }
+    if (!o.cover_files.empty() && !o.colour_files.empty()) { fprintf(stderr, "rtk_build_index: --cover-edges-from next to --colour-reads: the low-coverage edges are covered in a first-pass index only (the reference skips the step when the long reads colour)\n"); return 2; }
+    for (size_t f = 0; f < o.cover_files.size(); ++f) { FILE* fp = fopen(o.cover_files[f].c_str(), "rb"); if (!fp) { fprintf(stderr, "rtk_build_index: --cover-edges-from: cannot open %s\n", o.cover_files[f].c_str()); return 2; } fclose(fp); }
     if (!o.graph_files.empty() && min_count_given) { fprintf(stderr, "rtk_build_index: --min-count next to --graph-from: every k-mer of a graph file is a vertex (the reads of -s only colour), so there is nothing it could count\n"); return 2; }
     if (!o.graph_files.empty() && o.in_files.empty() && o.colour_files.empty()) { fprintf(stderr, "rtk_build_index: --graph-from needs reads that colour the graph: -s or --colour-reads\n"); return 2; }
     if (seed_given && !o.subsample) { fprintf(stderr, "rtk_build_index: --subsample-seed without --subsample-colours\n"); return 2; }
     if (filter_given && o.colour_files.empty()) { fprintf(stderr, "rtk_build_index: %s without --colour-reads\n", filter_given); return 2; }
     const bool graph_given = !o.graph_files.empty() && !o.colour_files.empty(); // (the one case without -s: the graph from a file, the colours from --colour-reads)
-    if ((o.in_files.empty() && !graph_given) || o.k < 3 || o.k > RTK_MAX_K || !(o.k & 1)) { fprintf(stderr, "usage: rtk_build_index -s reads.fq [-s ...] -o PREFIX [-k 31 (odd, <=63)] [--min-count 2] [--global-cov-factor 3.0] [--no-short-cycles] [--snps] [--fast | --gpu (k <= 63: same files, threads / the device for the heavy steps)] [--dump-input FILE] [--subsample-colours [--subsample-seed 1 (only with --subsample-colours)]: colours subsampled by coverage as the reference's index step does by default] [--merge-duplicates: read pairs that lie on the same unitigs share one colour id, as the reference's index step merges duplicated reads (no effect with --colour-reads)] [--colour-reads corrected_long_reads.fq: second-pass index, the graph comes from -s, colours and coverage from these reads [--colour-min-conf M (0 .. 1): a base of these reads whose quality is below that of confidence M colours nothing, as the reference's second-pass index does with -M (0: the '!' bases); needs FASTQ] [--colour-max-qual 40: the quality that stands for confidence 1 (-Q)] [--colour-min-len N: a read of fewer than N bases colours nothing (-C); these three only with --colour-reads]] [--graph-only: the unitig FASTA (PREFIX.index.kK.fasta.gz, the bytes of the full build) and nothing else, no .rtsk; not with --snps, --colour-reads, --merge-duplicates, --subsample-colours, --graph-from] [--graph-from unitigs.fasta.gz (may be repeated; FASTA as -s reads it): the graph is every all-A/C/G/T window of length k of these records, each once, whatever the k the file was written with (a k above the file's own: the windows of that length inside its unitigs); -s then only colours and covers, and is not needed next to --colour-reads; not with --min-count]\n"); return 2; }
+    if ((o.in_files.empty() && !graph_given) || o.k < 3 || o.k > RTK_MAX_K || !(o.k & 1)) { fprintf(stderr, "usage: rtk_build_index -s reads.fq [-s ...] -o PREFIX [-k 31 (odd, <=63)] [--min-count 2] [--global-cov-factor 3.0] [--no-short-cycles] [--snps] [--fast | --gpu (k <= 63: same files, threads / the device for the heavy steps)] [--dump-input FILE] [--subsample-colours [--subsample-seed 1 (only with --subsample-colours)]: colours subsampled by coverage as the reference's index step does by default] [--merge-duplicates: read pairs that lie on the same unitigs share one colour id, as the reference's index step merges duplicated reads (no effect with --colour-reads)] [--colour-reads corrected_long_reads.fq: second-pass index, the graph comes from -s, colours and coverage from these reads [--colour-min-conf M (0 .. 1): a base of these reads whose quality is below that of confidence M colours nothing, as the reference's second-pass index does with -M (0: the '!' bases); needs FASTQ] [--colour-max-qual 40: the quality that stands for confidence 1 (-Q)] [--colour-min-len N: a read of fewer than N bases colours nothing (-C); these three only with --colour-reads]] [--graph-only: the unitig FASTA (PREFIX.index.kK.fasta.gz, the bytes of the full build) and nothing else, no .rtsk; not with --snps, --colour-reads, --merge-duplicates, --subsample-colours, --graph-from] [--graph-from unitigs.fasta.gz (may be repeated; FASTA as -s reads it): the graph is every all-A/C/G/T window of length k of these records, each once, whatever the k the file was written with (a k above the file's own: the windows of that length inside its unitigs); -s then only colours and covers, and is not needed next to --colour-reads; not with --min-count] [--cover-edges-from k2_unitigs.fasta.gz (may be repeated; FASTA, plain or gzip, of any k): every edge whose two unitigs share fewer than 2 colours gets two fresh colour ids on both unitigs wherever a sequence of the file walks over it, in the order of the file, as the reference's first-pass index covers its low-coverage edges from the k2 unitigs; the annotations see the ids, the edge bits and the coverage stay; not with --colour-reads, --graph-only]\n"); return 2; }
     return 0;
 }
 
@@ -152,6 +157,7 @@ template <class KM> struct IndexBuild { // KM: uint64_t for k <= 31, u128 for k 
     std::vector<Nb> adj; std::vector<uint64_t> kmcov, shared; // neighbours, coverage + branching bit, edge bits (+ 0x100: in a short cycle)
     std::vector<std::string> cycles;
     std::vector<std::vector<uint32_t> > ambiguity, global_ids, local_ids;
+    std::vector<std::vector<uint32_t> > cover_ids; // --cover-edges-from: the ids the covering step added, per unitig (also the last of its colours: colour_split leaves that many out and puts them into the local set)
     std::shared_ptr<void> colour_sink; // --gpu --subsample-colours / --merge-duplicates: the ColourSink whose job still holds the events on the device
     std::thread fasta_thread; std::atomic<int> fasta_rc; // --fast: the unitig FASTA is compressed beside the other steps
     explicit IndexBuild(const IndexOptions& opt) : o(opt), k(opt.k), mask(km_mask<KM>(opt.k)), km(16), fasta_rc(0) {
