@@ -134,6 +134,11 @@ typedef struct rtk_stats {
      * do not fit the LDS buffer is handed on (n_colours_declined_fit) and answered -- and counted -- by one of the other two programs. Appended without a new
      * revision number, like the fields above. */
     uint64_t n_colours_declined_fit;
+    /* The forward trim of a gap region keeps only the last column of its sweep, which holds all that the rule of the skip reads (distance, last move). Where the
+     * region goes on to its second strand after all, rtk_park_walk sweeps the trimmed string against the raw region a second time, stored, and walks that
+     * (n_park_resweeps == n_park_walked then). The second sweep is no alignment of the reference's and is not part of n_align / n_align_cells.
+     * RTK_TRIM_STORE=1 stores the table at the trim, as before: 0 second sweeps. Appended without a new revision number, like the fields above. */
+    uint64_t n_park_resweeps;
 } rtk_stats;
 
 /* dbg.read(G.fasta.gz) + readGraphData(G.rtsk) (reference: src/Ratatosk.cpp:1087-1089; src/Graph.cpp:722-784).
@@ -284,12 +289,15 @@ int rtk_myers_batch_waves(uint32_t n, const char* const* query, const uint32_t* 
  *   RTK_MYERS_MODE_NW_PREFIX_LAST: 0 <= k <= qlen. The NW distance of (query[0, k), target) and in end_locs[0] the LAST move of the path mode 4 walks (0 match,
  *     1 insert, 2 delete, 3 mismatch), read off the stored sweep without a walk (rtk_myers_last_move: what the deferred park of the forward trim keeps of its
  *     path); -1 where there is no path (k = 0 or an empty target). No path is returned.
+ *   RTK_MYERS_MODE_NW_PREFIX_LAST_COLUMN: as mode 5, from a sweep that stores no table: the answer is derived from the delta vectors of the sweep's last
+ *     column alone (rtk_myers_last_move_column: what the forward trim of a gap region keeps). Same problems taken, same answers.
  * A problem the route does not take (a target byte other than A C G T -- the sweep's target: the query in mode 3 --, more than 4096 characters in the swept
  * query, a table or move list too big for the in-memory traceback, an empty string) is answered by the calls the route replaces. How the calling thread's last
  * rtk_myers_batch call split its problems of these modes: rtk_myers_column_last_routes (a route that took nothing would pass on the fallback's results). */
 #define RTK_MYERS_MODE_SHW_BY_COLUMN 3
 #define RTK_MYERS_MODE_NW_PREFIX 4
 #define RTK_MYERS_MODE_NW_PREFIX_LAST 5
+#define RTK_MYERS_MODE_NW_PREFIX_LAST_COLUMN 6
 void rtk_myers_column_last_routes(uint64_t* column_route, uint64_t* fallback);
 
 /* rtk_myers_batch with ONE PROBLEM PER LANE: queries of up to 512 characters against targets of up to 2048 over A, C, G, T, N are computed column by column in a
@@ -482,7 +490,9 @@ const char* rtk_version(void);
  * 8: rtk_stats fields n_fa_linked_*; 9: rtk_rescue_begin / _chunk / _end; still 9: rtk_stats fields n_strand2_* and n_park_*, the test-only rtk_myers_batch mode 5, appended at the end -- a library of revision 9
  * without them leaves them as the caller set them;
  * 10: rtk_sets_batch, rtk_stats fields n_colours_*; still 10: rtk_index_colour_cov, rtk_index_colour_end_subsampled, rtk_index_subsample_events, then rtk_index_colour_merge,
- * rtk_index_colour_merge_classes, rtk_index_merge_events, then rtk_index_colour_chunk_q, then rtk_batch_fetch_seeds, then rtk_index_snp_candidates, then rtk_index_snp_plan, then rtk_index_cover_begin / _chunk / _end, appended -- a library of revision 10 without them lacks the symbols, and callers look them up by name). */
+ * rtk_index_colour_merge_classes, rtk_index_merge_events, then rtk_index_colour_chunk_q, then rtk_batch_fetch_seeds, then rtk_index_snp_candidates, then rtk_index_snp_plan, then rtk_index_cover_begin / _chunk / _end, appended -- a library of revision 10 without them lacks the symbols, and callers look them up by name;
+ * then the rtk_stats field n_park_resweeps and the test-only rtk_myers_batch mode 6, which are no symbols: a library of revision 10 without them leaves the field as the
+ * caller set it and answers mode 6 with RTK_ERR_ARG). */
 #define RTK_API_REVISION 10
 int rtk_api_revision(void);
 

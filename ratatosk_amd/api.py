@@ -40,7 +40,8 @@ class RtkStats(C.Structure):
                                          "n_fa_linked_run", "n_fa_linked_skipped", "n_fa_linked_entries",
                                          "n_strand2_run", "n_strand2_skipped", "n_strand2_audit_mismatch",
                                          "n_park_walked", "n_park_deferred",
-                                         "n_colours_small", "n_colours_wide", "n_colours_bits", "n_colours_general", "n_colours_audit_mismatch", "n_colours_declined_fit")]
+                                         "n_colours_small", "n_colours_wide", "n_colours_bits", "n_colours_general", "n_colours_audit_mismatch", "n_colours_declined_fit",
+                                         "n_park_resweeps")]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -401,7 +402,7 @@ def rescue_reads(lr_kmers, sr_kmers, seqs, k=31, min_positions=31, device=0, sta
     return out
 
 
-MODE_SHW_BY_COLUMN, MODE_NW_PREFIX, MODE_NW_PREFIX_LAST = 3, 4, 5  # test-only modes of myers_batch (include/ratatosk_hip.h)
+MODE_SHW_BY_COLUMN, MODE_NW_PREFIX, MODE_NW_PREFIX_LAST, MODE_NW_PREFIX_LAST_COLUMN = 3, 4, 5, 6  # test-only modes of myers_batch (include/ratatosk_hip.h)
 
 
 def myers_column_last_routes(lib_path=None):

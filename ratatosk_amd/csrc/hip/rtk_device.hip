@@ -529,12 +529,13 @@ RTK_FN void rtk_myers_column_item(const MyersScratch& sc, const MyersProb& p, ui
         if (r.nloc > 1 && static_cast<uint32_t>(r.nloc) <= cap_locs) end_locs[static_cast<uint64_t>(i) * cap_locs + (r.nloc - 1)] = r.last;
         n_loc[i] = r.nloc;
     } else { // RTK_MYERS_MODE_NW_PREFIX, RTK_MYERS_MODE_NW_PREFIX_LAST: (q[0, k), t)
-        const int k = p.k; const bool last_only = p.mode == RTK_MYERS_MODE_NW_PREFIX_LAST;
+        const int k = p.k; const bool from_column = p.mode == RTK_MYERS_MODE_NW_PREFIX_LAST_COLUMN, last_only = from_column || p.mode == RTK_MYERS_MODE_NW_PREFIX_LAST;
         int at = 0, last = -1;
-        if (k > 0 && rtk_myers_shw_by_column(sc, q, m, t, n, iupac, 1, k, &r, &at)) {
+        if (k > 0 && rtk_myers_shw_by_column(sc, q, m, t, n, iupac, from_column ? 2 : 1, k, &r, &at)) {
             const long long W = (k + 63) >> 6;
             if (static_cast<uint32_t>(k) <= sc.r_cap && static_cast<uint32_t>(k + n) <= sc.mv_cap && (2LL * 8 + 4) * W * n + 8LL * n < 1024 * 1024) {
-                if (last_only) last = rtk_myers_last_move(sc, k, n, n, at); // the trim's look at the table, in place of the walk
+                if (from_column) last = rtk_myers_last_move_column(sc, k); // the trim's look at the last column of a sweep that stored no table
+                else if (last_only) last = rtk_myers_last_move(sc, k, n, n, at); // the same look at a stored table, in place of the walk
                 else rtk_myers_walk(sc, k, n, n, at, &nm);
                 r.dist = at; route = 1;
             }
@@ -616,9 +617,9 @@ extern "C" int rtk_myers_batch_waves(uint32_t n, const char* const* query, const
             probs[i].t_off = pool.size(); pool.append(target[i], tlen[i]);
             probs[i].qlen = qlen[i]; probs[i].tlen = tlen[i]; probs[i].k = k[i]; probs[i].mode = mode[i];
             if (mode[i] == RTK_MODE_HW && want_path) return rtk_fail(RTK_ERR_UNSUPPORTED, "rtk_myers_batch: HW path alignment is not on the hot path");
-            if (mode[i] < 0 || mode[i] > RTK_MYERS_MODE_NW_PREFIX_LAST || (mode[i] > RTK_MODE_HW && waves > 1)) return rtk_fail(RTK_ERR_ARG, "rtk_myers_batch: unknown mode (the test-only modes 3 to 5 run on one wave)");
+            if (mode[i] < 0 || mode[i] > RTK_MYERS_MODE_NW_PREFIX_LAST_COLUMN || (mode[i] > RTK_MODE_HW && waves > 1)) return rtk_fail(RTK_ERR_ARG, "rtk_myers_batch: unknown mode (the test-only modes 3 to 6 run on one wave)");
             if ((mode[i] == RTK_MYERS_MODE_SHW_BY_COLUMN && k[i] >= 0) || (mode[i] >= RTK_MYERS_MODE_NW_PREFIX && (k[i] < 0 || static_cast<uint32_t>(k[i]) > qlen[i])))
-                return rtk_fail(RTK_ERR_ARG, "rtk_myers_batch: mode 3 takes k < 0, modes 4 and 5 a query row 0 <= k <= qlen");
+                return rtk_fail(RTK_ERR_ARG, "rtk_myers_batch: mode 3 takes k < 0, modes 4 to 6 a query row 0 <= k <= qlen");
             max_q = std::max(max_q, qlen[i]); max_t = std::max(max_t, tlen[i]);
         }
         for (uint32_t i = 0; i < n; ++i) if (mode[i] > RTK_MODE_HW) { max_q = max_t = std::max(max_q, max_t); break; } // the column route sweeps (target, query) in mode 3

@@ -60,6 +60,7 @@ inline bool rtk_knob_strand2_audit() { return rtk_env_is1("RTK_STRAND2_AUDIT"); 
 inline uint32_t rtk_knob_colours_route() { return rtk_env_eq("RTK_COLOURS_ROUTE", "bits") ? 1u : (rtk_env_eq("RTK_COLOURS_ROUTE", "general") ? 2u : 0u); } // "bits": rtk_choose_colors skips its small program; "general": the general program answers every call (same results; tests/test_colour_routes.py)
 inline uint32_t rtk_knob_colours_audit() { return rtk_env_is1("RTK_COLOURS_AUDIT") ? (rtk_env_is1("RTK_TEST_COLOURS_FAULT") ? 3u : 1u) : 0u; } // RTK_COLOURS_AUDIT '1': the general program repeats every selection another program answered, differences are counted (rtk_stats::n_colours_audit_mismatch); with the test hook RTK_TEST_COLOURS_FAULT '1' (3) the first answer loses its largest id before the comparison
 inline bool rtk_knob_park_eager() { return rtk_env_is1("RTK_PARK_EAGER"); }         // '1': the forward trim of a gap region walks and parks its alignment right away, also where no consensus will read it (same results; parity test, A/B timing)
+inline bool rtk_knob_trim_store() { return rtk_env_is1("RTK_TRIM_STORE"); }         // '1': the forward trim of a gap region stores the whole table of its sweep, instead of keeping the delta vectors of the last column alone (same results; parity test, A/B timing)
 inline bool rtk_knob_test_coalesce_fail() { return rtk_env_set("RTK_TEST_COALESCE_FAIL"); } // flag, test hook: a merged batch is reported as failed (its members must come through on their own)
 
 // ---- region stage and rtk_correct_batch: read ONCE per process (the first call fixes the value)

@@ -311,6 +311,7 @@ __device__ __forceinline__ SweepStat rtk_myers_fast(const char* __restrict__ qp,
     int hout_prev = 0; unsigned tc_prev = 0;
     int score = m;
     int best = 0x7fffffff, first = -1, last = -1, cnt = 0, fin = m;
+    uint64_t lastPh = 0, lastMh = 0; // STORE == 2: the horizontal deltas of this word's latest column
     const int steps = n + W - 1;
     for (int c0 = 0; c0 < steps; c0 += 64) {
         const int cj = c0 + lane;
@@ -332,7 +333,8 @@ __device__ __forceinline__ SweepStat rtk_myers_fast(const char* __restrict__ qp,
             const int hout = rtk_myers_step(nPv, nMv, Eq, hin, bit, Ph, Mh);
             const int col = s - lane;
             const bool active = has_word && col >= 0 && col < n;
-            if (STORE) { if (active) { rtk_tb_put(tb + 4ull * RTK_TB(col, w, n), nPv, nMv, Ph, Mh); } }
+            if (STORE == 1) { if (active) { rtk_tb_put(tb + 4ull * RTK_TB(col, w, n), nPv, nMv, Ph, Mh); } }
+            if (STORE == 2) { lastPh = active ? Ph : lastPh; lastMh = active ? Mh : lastMh; }
             Pv = active ? nPv : Pv; Mv = active ? nMv : Mv;
             hout_prev = active ? hout : hout_prev;
             score += (active && lane == W - 1) ? hout : 0;
@@ -346,6 +348,7 @@ __device__ __forceinline__ SweepStat rtk_myers_fast(const char* __restrict__ qp,
             }
         }
     }
+    if (STORE == 2 && has_word) rtk_tb_put(tb + 4ull * w, Pv, Mv, lastPh, lastMh); // the last column, as a table of one column
     if (COLUMN) { rtk_last_column_stat(has_word ? Pv : 0ull, has_word ? Mv : 0ull, 64, m, n, at, st); return st; }
     st.final_score = fin; st.best = best; st.first = first; st.last = last; st.cnt = cnt;
     return st;
@@ -372,6 +375,8 @@ RTK_DEV int rtk_myers_step32(uint32_t& Pv, uint32_t& Mv, uint32_t Eq, int hin, i
 
 // TRACK = 0: only the final score is wanted (NW); 1: minimum of the last row with its first / last position and count (SHW, HW);
 // 2: the same of the last COLUMN, read once the sweep is done (rtk_last_column_stat, row `at`).
+// STORE = 0: nothing is written; 1: the traceback table; 2: the table entries of the LAST column only, as a table of one column at the start of tb
+// (entry w = Pv, Mv, Ph, Mh of word w at column n - 1: what rtk_myers_last_move_column reads) -- no store inside the sweep.
 template <int STORE, int TRACK>
 __device__ __forceinline__ SweepStat rtk_myers_fast32(const char* __restrict__ qp, int m, const char* __restrict__ tp, int n, int top_h, bool iupac, uint64_t* __restrict__ tb, int at = 0) {
     SweepStat st; st.final_score = m; st.best = 0x7fffffff; st.first = -1; st.last = -1; st.cnt = 0; st.plain = true; st.at_score = 0;
@@ -414,6 +419,7 @@ __device__ __forceinline__ SweepStat rtk_myers_fast32(const char* __restrict__ q
     const int bit = (w == W - 1) ? last_bit : 31;
     uint32_t Pv = ~0u, Mv = 0u;
     int hout_prev = 0; uint32_t m1_prev = 0, m2_prev = 0;
+    uint32_t lastPh = 0, lastMh = 0; // STORE == 2: the horizontal deltas of this word's latest column
     int score = m;
     int vbest = 0x7fffffff, vfirst = -1, vlast = -1, vcnt = 0;
     const int steps = n + W - 1;
@@ -437,12 +443,14 @@ __device__ __forceinline__ SweepStat rtk_myers_fast32(const char* __restrict__ q
         const int col = s - lane;                                                                                                            \
         if (MASKED) {                                                                                                                        \
             const bool active = has_word && col >= 0 && col < n;                                                                             \
-            if (STORE) { if (active) { RtkTbHalf hv; hv.pv = nPv; hv.mv = nMv; hv.ph = Ph; hv.mh = Mh; tbh[2ull * static_cast<uint64_t>(col)] = hv; } } \
+            if (STORE == 1) { if (active) { RtkTbHalf hv; hv.pv = nPv; hv.mv = nMv; hv.ph = Ph; hv.mh = Mh; tbh[2ull * static_cast<uint64_t>(col)] = hv; } } \
+            if (STORE == 2) { lastPh = active ? Ph : lastPh; lastMh = active ? Mh : lastMh; }                                                \
             Pv = active ? nPv : Pv; Mv = active ? nMv : Mv;                                                                                  \
             hout_prev = active ? hout : hout_prev;                                                                                           \
             score += active ? hout : 0;                                                                                                      \
         } else {                                                                                                                             \
-            if (STORE) { if (has_word) { RtkTbHalf hv; hv.pv = nPv; hv.mv = nMv; hv.ph = Ph; hv.mh = Mh; tbh[2ull * static_cast<uint64_t>(col)] = hv; } } \
+            if (STORE == 1) { if (has_word) { RtkTbHalf hv; hv.pv = nPv; hv.mv = nMv; hv.ph = Ph; hv.mh = Mh; tbh[2ull * static_cast<uint64_t>(col)] = hv; } } \
+            if (STORE == 2) { lastPh = Ph; lastMh = Mh; }                                                                                    \
             Pv = nPv; Mv = nMv; hout_prev = hout; score += hout;                                                                             \
         }                                                                                                                                    \
         m1_prev = m1; m2_prev = m2;                                                                                                          \
@@ -471,6 +479,7 @@ __device__ __forceinline__ SweepStat rtk_myers_fast32(const char* __restrict__ q
         for (; j < lim; ++j) RTK_STEP32(1)
     }
 #undef RTK_STEP32
+    if (STORE == 2 && has_word) { RtkTbHalf hv; hv.pv = Pv; hv.mv = Mv; hv.ph = lastPh; hv.mh = lastMh; reinterpret_cast<RtkTbHalf*>(tb)[w] = hv; } // the last column, as a table of one column
     st.final_score = __builtin_amdgcn_readlane(score, W - 1);
     if (TRACK == 2) rtk_last_column_stat(has_word ? Pv : 0u, has_word ? Mv : 0u, 32, m, n, at, st);
     if (TRACK == 1) { st.best = __builtin_amdgcn_readlane(vbest, W - 1); st.first = __builtin_amdgcn_readlane(vfirst, W - 1); st.last = __builtin_amdgcn_readlane(vlast, W - 1); st.cnt = __builtin_amdgcn_readlane(vcnt, W - 1); }
@@ -1189,7 +1198,14 @@ RTK_FN bool rtk_myers_shw_by_column(const MyersScratch& sc_, const char* corr_, 
 #ifdef RTK_SIM
     for (int j = 0; j < n; ++j) { const char ch = raw[j]; if (!(ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T')) return false; } // the device sweep's own test
     uint64_t* fin = new uint64_t[2 * W];
-    rtk_myers_pass(sc, rtk_seq(corr, m), rtk_seq(raw, n), 1, iupac, store, fin, fin + W);
+    rtk_myers_pass(sc, rtk_seq(corr, m), rtk_seq(raw, n), 1, iupac, store ? 1 : 0, fin, fin + W);
+    if (store == 2) { // what the device sweep leaves behind: the entries of the last column at the start of the table, and no other entry that can be read
+        uint64_t* const tb = rtk_ld(&sc.tb); uint64_t* const lastc = new uint64_t[4 * W];
+        for (long long w = 0; w < W; ++w) memcpy(lastc + 4 * w, tb + 4ull * RTK_TB(n - 1, w, n), 32);
+        memset(tb, 0xA5, 32ull * static_cast<uint64_t>(W) * static_cast<uint64_t>(n));
+        memcpy(tb, lastc, 32ull * static_cast<uint64_t>(W));
+        delete[] lastc;
+    }
     best = 0x7fffffff; first = -1; last = -1; cnt = 0; atv = n;
     for (int i = 0, v = n; i < m; ++i) {
         v += static_cast<int>((fin[i >> 6] >> (i & 63)) & 1ull) - static_cast<int>((fin[W + (i >> 6)] >> (i & 63)) & 1ull);
@@ -1198,7 +1214,8 @@ RTK_FN bool rtk_myers_shw_by_column(const MyersScratch& sc_, const char* corr_, 
     }
     delete[] fin;
 #else
-    const SweepStat st = store ? rtk_myers_fast_any<1, 2>(corr, m, raw, n, 1, iupac, rtk_ld(&sc.tb), at) : rtk_myers_fast_any<0, 2>(corr, m, raw, n, 1, iupac, nullptr, at);
+    const SweepStat st = store == 2 ? rtk_myers_fast_any<2, 2>(corr, m, raw, n, 1, iupac, rtk_ld(&sc.tb), at)
+                       : store ? rtk_myers_fast_any<1, 2>(corr, m, raw, n, 1, iupac, rtk_ld(&sc.tb), at) : rtk_myers_fast_any<0, 2>(corr, m, raw, n, 1, iupac, nullptr, at);
     rtk_sync();
     if (!st.plain) return false;
     best = st.best; first = st.first; last = st.last; cnt = st.cnt; atv = st.at_score;
@@ -1209,7 +1226,7 @@ RTK_FN bool rtk_myers_shw_by_column(const MyersScratch& sc_, const char* corr_, 
     r.dist = best;
     if (pseudo && n == best) { r.first = -1; r.last = (colbest == best) ? last : -1; r.nloc = 1 + ((colbest == best) ? cnt : 0); }
     else { r.first = first; r.last = last; r.nloc = cnt; }
-    *out = r;
+    if (out) *out = r;
     if (at_score) *at_score = atv;
     return true;
 }
@@ -1340,6 +1357,26 @@ RTK_DEV uint8_t rtk_myers_last_move(const MyersScratch& sc_, int m_, int n_, int
     int diag = m - 1; // column 0: D[m - 1][0]
     if (c > 0) { uint64_t l0, l1, l2, l3; rtk_tb_get(tbp + 4ull * RTK_TB(c - 1, w, ncols), l0, l1, l2, l3); diag = cur - hd - (static_cast<int>((l0 >> b) & 1ull) - static_cast<int>((l1 >> b) & 1ull)); }
     return (diag == cur) ? 0 : 3;
+}
+
+// The same move from the LAST COLUMN alone, as a sweep with store = 2 leaves it (rtk_myers_shw_by_column: entry w at the start of the table holds Pv, Mv, Ph, Mh
+// of word w at column n - 1): the last move of the NW path of (query[0, m), target). The
+// vertical delta of cell (m, n) is bit m - 1 of Pv / Mv, its horizontal delta the same bit of Ph / Mh; the diagonal neighbour is reached over the cell above,
+// D[m - 1][n - 1] = D[m][n] - vertical delta - horizontal delta of row m - 1, and that delta is bit m - 2 of Ph / Mh (the word before when m - 1 is the first
+// row of its word; +1 in the matrix's row 0). Same preferences, same values as rtk_myers_last_move. Wave-uniform; one entry read, two at a word boundary.
+RTK_DEV uint8_t rtk_myers_last_move_column(const MyersScratch& sc_, int m_) {
+    const MyersScratch& sc = *rtk_u(&sc_); RTK_ASSUME_LDS(&sc);
+    const int m = rtk_u(m_);
+    const uint64_t* const tbp = rtk_ld(&sc.tb);
+    const int r = m - 1, w = r >> 6, b = r & 63;
+    uint64_t a0, a1, a2, a3; rtk_tb_get(tbp + 4ull * static_cast<uint64_t>(w), a0, a1, a2, a3);
+    const int vd = static_cast<int>((a0 >> b) & 1ull) - static_cast<int>((a1 >> b) & 1ull);
+    if (vd == 1) return 1; // up
+    if (static_cast<int>((a2 >> b) & 1ull) - static_cast<int>((a3 >> b) & 1ull) == 1) return 2; // left
+    int hu = 1; // row 0 of the matrix: D[0][n] - D[0][n - 1]
+    if (b > 0) hu = static_cast<int>((a2 >> (b - 1)) & 1ull) - static_cast<int>((a3 >> (b - 1)) & 1ull);
+    else if (w > 0) { uint64_t u0, u1, u2, u3; rtk_tb_get(tbp + 4ull * static_cast<uint64_t>(w - 1), u0, u1, u2, u3); hu = static_cast<int>((u2 >> 63) & 1ull) - static_cast<int>((u3 >> 63) & 1ull); }
+    return (vd + hu == 0) ? 0 : 3; // diagonal neighbour D[m - 1][n - 1] = D[m][n] - vd - hu: a match keeps the score
 }
 
 RTK_FN void rtk_myers_traceback(const MyersScratch& sc_, MySeq q_, MySeq t_, bool iupac_, uint32_t* n_moves_) {

@@ -139,6 +139,7 @@ static OptsView opts_view(const rtk_opts* o) {
     v.strand2_mode = rtk_knob_strand2_always() ? 1u : (rtk_knob_strand2_audit() ? 2u : 0u); // (knobs as well: the bytes are the same under all three)
     v.colours_mode = rtk_knob_colours_route() | (rtk_knob_colours_audit() << 2); // RTK_CM_* (the selection is the same under every setting)
     v.park_eager = rtk_knob_park_eager() ? 1u : 0u;
+    v.trim_store = rtk_knob_trim_store() ? 1u : 0u;
     v.long_read_correct = o->long_read_correct ? 1 : 0; v.max_len_weak_region2 = static_cast<uint32_t>(o->max_len_weak_region2 > 0xFFFFFFFFull ? 0xFFFFFFFFull : o->max_len_weak_region2);
     return v;
 }

@@ -362,7 +362,8 @@ RTK_GLOBAL void k_regions(const LaunchCtx* L, GraphView g, OptsView o, BatchView
         for (int i = RTK_RC_FA_LINKED_RUN; i < RTK_RC_STRAND2_RUN; ++i) rtk_atomic_add(bv.counters + RTK_CNT_FA_LINKED + (i - RTK_RC_FA_LINKED_RUN), sc->cnt[i]);
         for (int i = RTK_RC_STRAND2_RUN; i < RTK_RC_PARK_WALKED; ++i) rtk_atomic_add(bv.counters + RTK_CNT_STRAND2 + (i - RTK_RC_STRAND2_RUN), sc->cnt[i]);
         for (int i = RTK_RC_PARK_WALKED; i < RTK_RC_COLOURS_SMALL; ++i) rtk_atomic_add(bv.counters + RTK_CNT_PARK + (i - RTK_RC_PARK_WALKED), sc->cnt[i]);
-        for (int i = RTK_RC_COLOURS_SMALL; i < RTK_RC_N; ++i) rtk_atomic_add(bv.counters + RTK_CNT_COLOURS + (i - RTK_RC_COLOURS_SMALL), sc->cnt[i]);
+        for (int i = RTK_RC_COLOURS_SMALL; i < RTK_RC_PARK_RESWEEPS; ++i) rtk_atomic_add(bv.counters + RTK_CNT_COLOURS + (i - RTK_RC_COLOURS_SMALL), sc->cnt[i]);
+        rtk_atomic_add(bv.counters + RTK_CNT_PARK_RESWEEPS, sc->cnt[RTK_RC_PARK_RESWEEPS]);
         for (int i = 0; i < RTK_H_N; ++i) rtk_atomic_add(bv.counters + RTK_CNT_HIST + i, static_cast<unsigned long long>(RTK_HIST_GET(*sc, i)));
 #ifdef RTK_PROF
         for (int i = 0; i < RTK_LAP_N; ++i) rtk_atomic_add(bv.counters + RTK_CNT_PROF + i, static_cast<unsigned long long>(sc->prof[i]));
@@ -789,7 +790,7 @@ static void region_trace_report(const unsigned long long* cnt) {
     fprintf(stderr, "[rtk trace] fixAmbiguity linked-allele searches: run %llu, skipped %llu, entries produced %llu, cycles %.3g\n", cnt[RTK_CNT_FA_LINKED + 0], cnt[RTK_CNT_FA_LINKED + 1],
             cnt[RTK_CNT_FA_LINKED + 2], double(cnt[RTK_CNT_FINE + RTK_FINE_FA_LINKED]));
     fprintf(stderr, "[rtk trace] second strand of gap regions: run %llu, skipped %llu (the forward result decides), audit mismatches %llu\n", cnt[RTK_CNT_STRAND2 + 0], cnt[RTK_CNT_STRAND2 + 1], cnt[RTK_CNT_STRAND2 + 2]);
-    fprintf(stderr, "[rtk trace] stored sweeps of the forward trims: walked for a consensus %llu, never walked %llu\n", cnt[RTK_CNT_PARK + 0], cnt[RTK_CNT_PARK + 1]);
+    fprintf(stderr, "[rtk trace] stored sweeps of the forward trims: walked for a consensus %llu (from a second sweep %llu), never walked %llu\n", cnt[RTK_CNT_PARK + 0], cnt[RTK_CNT_PARK_RESWEEPS], cnt[RTK_CNT_PARK + 1]);
     fprintf(stderr, "[rtk trace] colour selections answered by: small %llu, wide %llu, bits %llu, general %llu; audit mismatches %llu; handed on by the register program for room %llu\n", cnt[RTK_CNT_COLOURS + 0], cnt[RTK_CNT_COLOURS + 1], cnt[RTK_CNT_COLOURS + 2],
             cnt[RTK_CNT_COLOURS + 3], cnt[RTK_CNT_COLOURS + 4], cnt[RTK_CNT_COLOURS + 5]);
     fprintf(stderr, "[rtk trace] walks %llu moves %llu reloads %llu scalar steps %llu cycles %.3g tail cycles %.3g\n", cnt[RTK_CNT_WALK_CALLS], cnt[RTK_CNT_WALK_MOVES],
@@ -811,7 +812,7 @@ static void region_stats(RegionRun& R, const unsigned long long* cnt) {
     st.n_consensus_resumed = cnt[RTK_CNT_ROUTES + 3]; st.n_consensus_swept = cnt[RTK_CNT_ROUTES + 4];
     st.n_fa_linked_run = cnt[RTK_CNT_FA_LINKED + 0]; st.n_fa_linked_skipped = cnt[RTK_CNT_FA_LINKED + 1]; st.n_fa_linked_entries = cnt[RTK_CNT_FA_LINKED + 2];
     st.n_strand2_run = cnt[RTK_CNT_STRAND2 + 0]; st.n_strand2_skipped = cnt[RTK_CNT_STRAND2 + 1]; st.n_strand2_audit_mismatch = cnt[RTK_CNT_STRAND2 + 2];
-    st.n_park_walked = cnt[RTK_CNT_PARK + 0]; st.n_park_deferred = cnt[RTK_CNT_PARK + 1];
+    st.n_park_walked = cnt[RTK_CNT_PARK + 0]; st.n_park_deferred = cnt[RTK_CNT_PARK + 1]; st.n_park_resweeps = cnt[RTK_CNT_PARK_RESWEEPS];
     st.n_colours_small = cnt[RTK_CNT_COLOURS + 0]; st.n_colours_wide = cnt[RTK_CNT_COLOURS + 1]; st.n_colours_bits = cnt[RTK_CNT_COLOURS + 2]; st.n_colours_general = cnt[RTK_CNT_COLOURS + 3];
     st.n_colours_audit_mismatch = cnt[RTK_CNT_COLOURS + 4]; st.n_colours_declined_fit = cnt[RTK_CNT_COLOURS + 5];
     st.ms_stitch = R.t_st.elapsed(); st.ms_total = b->t_all.elapsed();

@@ -444,7 +444,7 @@ RTK_FN_DRIVER void rtk_region_program(const RCtx& c_, RegionDesc* rd_) {
                 emit_minus_k(fw.seq, fw.seq_len, fw.qual, fw.qual_len);
             } else {
                 s.cnt[skippable ? RTK_RC_STRAND2_SKIPPED : RTK_RC_STRAND2_RUN] += 1; // (the audit counts the rule's verdicts and runs both kinds)
-                rtk_park_walk(c); // the consensus may run now (rbuf[RTK_RB_PARK_MOVES], hand-over H2): the forward alignment is walked from the trim's sweep before the second strand overwrites the table
+                rtk_park_walk(c, fw.seq, s_fw + pa); // the consensus may run now (rbuf[RTK_RB_PARK_MOVES], hand-over H2): the forward alignment is swept again, stored, and walked before the second strand overwrites the table
                 auto audit = [&](const char* seq, uint32_t sl, const char* q, uint32_t ql) { // what the full route is about to emit against the forward strings
                     if (skippable && !(sl == fw.seq_len && ql == fw.qual_len && rtk_str_equal(seq, fw.seq, sl) && rtk_str_equal(q, fw.qual, ql))) s.cnt[RTK_RC_STRAND2_AUDIT_MISMATCH] += 1;
                 };

@@ -37,14 +37,23 @@ RTK_FN_HOT MyersResult rtk_align_path(const RCtx& c_, const char* q_, uint32_t m
 // The walk of a pending park (TrimPark, rtk_trim_by_column below) and its copy to rbuf[RTK_RB_PARK_MOVES]; no park pending: nothing. Between the trim and this call nothing may write the Myers table: the trim is
 // the last alignment of rtk_correct_region, and rtk_region_program calls this at its decision about the second strand, with rtk_strand2_skippable -- which
 // aligns nothing -- in between. (s.my.moves is written here and copied at once, so what it held does not matter.)
-RTK_FN void rtk_park_walk(const RCtx& c_) {
-    const RCtx& c = *rtk_u(&c_); RegionScratch& s = rtk_hdr(c);
+// A trim that kept only the last column of its sweep (pending == RTK_PARK_NO_TABLE) has no table to walk: the sweep of (corr[0, len), raw) is run again here, stored
+// this time -- rows up to len of the trim's own sweep, so the walk is the same. The few regions that come here pay a second sweep (rtk_stats::n_park_resweeps; not
+// an alignment of n_align / n_align_cells: the reference makes none); the many that do not have stored no table. corr, raw: the strings of the trim.
+RTK_FN void rtk_park_walk(const RCtx& c_, const char* corr_, const char* raw_) {
+    const RCtx& c = *rtk_u(&c_); RegionScratch& s = rtk_hdr(c); const char* corr = rtk_u(corr_); const char* raw = rtk_u(raw_);
     TrimPark& pk = s.loc.park;
     if (!pk.pending) return;
+    const unsigned long long t1 = rtk_clock();
+    if (pk.pending == RTK_PARK_NO_TABLE) {
+        const bool ok = rtk_myers_shw_by_column(s.my, corr, static_cast<int>(pk.len), raw, static_cast<int>(pk.n), true, 1, 0, nullptr, nullptr);
+        s.cnt[RTK_RC_PARK_RESWEEPS] += 1;
+        if (!ok) { pk.pending = 0; pk.nm = 0; s.cnt[RTK_RC_CYC_MYERS] += rtk_clock() - t1; return; } // (cannot happen: the trim's sweep of a longer string passed the same tests) nothing parked, the consensus sweeps the pair itself
+        pk.gen = rtk_ld(&s.my.tb_gen);
+    }
 #ifdef RTK_SIM
     assert(pk.gen == s.my.tb_gen); // the table still holds the sweep of the trim
 #endif
-    const unsigned long long t1 = rtk_clock();
     pk.pending = 0;
     uint32_t& nm = pk.nm; nm = 0;
     rtk_myers_walk(s.my, static_cast<int>(pk.len), static_cast<int>(pk.n), static_cast<int>(pk.n), pk.dist, &nm);
@@ -55,19 +64,24 @@ RTK_FN void rtk_park_walk(const RCtx& c_) {
 }
 
 // The trim of rtk_correct_region, edlibAlign(raw, corr, SHW), read off the last column of ONE NW sweep of (corr, raw) (rtk_myers_shw_by_column): a plain
-// NW step instead of the distance call's step with last-row tracking. park: the sweep is stored, and when the consensus's forward alignment -- NW path of the
-// trimmed string corr[0, keep) against this raw region (rtk_generate_consensus) -- would take the in-memory traceback of rtk_myers_path, its moves are walked
-// from row keep (D[keep][|raw|] is the minimum the trim found) and parked in rbuf[RTK_RB_PARK_MOVES], which otherwise only the consensus writes (as RTK_RB_CONS_QUAL), after it has read them (hand-over H2, rtk_region_types.h). Most gap regions
-// never run a consensus (rtk_strand2_skippable), and the rule that decides so asks three things of the park: that it exists, its distance and its LAST move. So
-// the trim only notes those (rtk_myers_last_move: one look at the table) and leaves the park pending; rtk_region_program has rtk_park_walk make the walk and the
-// copy where the region does go on to its second strand. RTK_PARK_EAGER=1 (tests, A/B runs) walks right here; so does a pair whose
-// moves might not fit the string buffers (the walk then clears the park; the consensus sweeps the pair itself and reports the overflow).
+// NW step instead of the distance call's step with last-row tracking.
+// park: the same sweep also holds the consensus's forward alignment, the NW path of the trimmed string corr[0, keep) against this raw region
+// (rtk_generate_consensus): its moves can be walked from row keep (D[keep][|raw|] is the minimum the trim found) and parked in rbuf[RTK_RB_PARK_MOVES], which
+// otherwise only the consensus writes (as RTK_RB_CONS_QUAL), after it has read them (hand-over H2, rtk_region_types.h). Most gap regions never run a consensus
+// (rtk_strand2_skippable), and the rule that decides so asks three things of the park: that it exists, its distance and its LAST move. All three are in the
+// last column of the sweep. So the sweep of a park stores no table: it keeps the delta vectors of that column (store 2 of rtk_myers_shw_by_column), the trim
+// notes the three things (rtk_myers_last_move_column) and leaves the park pending. Where the region does go on to its second strand, rtk_region_program calls
+// rtk_park_walk, which sweeps corr[0, keep) against the raw region again, stored this time, walks the path and copies the moves. RTK_TRIM_STORE=1 stores the
+// table at the trim and walks that. RTK_PARK_EAGER=1 (tests, A/B runs) walks right here; so does a pair whose moves might not fit the string buffers (the walk
+// then clears the park; the consensus sweeps the pair itself and reports the overflow).
 // false: the route does not apply (no result, no alignment counted) and the caller makes the distance call.
 RTK_FN bool rtk_trim_by_column(const RCtx& c_, const char* raw_, uint32_t n_, const char* corr_, uint32_t m_, bool park_, MyersResult* out_) {
     const RCtx& c = *rtk_u(&c_); RegionScratch& s = rtk_hdr(c); const char* raw = rtk_u(raw_); const char* corr = rtk_u(corr_);
     const uint32_t n = rtk_u(n_), m = rtk_u(m_); const bool park = rtk_u(park_); MyersResult* out = rtk_u(out_);
     const unsigned long long t0 = rtk_clock();
-    const bool ok = rtk_myers_shw_by_column(s.my, corr, static_cast<int>(m), raw, static_cast<int>(n), true, park ? 1 : 0, 0, out, nullptr);
+    // park: the sweep keeps its last column (store 2), which holds what the rule of the skip asks; RTK_TRIM_STORE=1 (rtk_knobs.h): the whole table (store 1), as before
+    const bool table = rtk_u(c.o.trim_store) != 0u;
+    const bool ok = rtk_myers_shw_by_column(s.my, corr, static_cast<int>(m), raw, static_cast<int>(n), true, park ? (table ? 1 : 2) : 0, 0, out, nullptr);
     s.cnt[RTK_RC_CYC_MYERS] += rtk_clock() - t0;
     if (!ok) return false;
     s.cnt[RTK_RC_ALIGN] += 1; s.cnt[RTK_RC_CELLS] += static_cast<unsigned long long>((m + 63) / 64) * n;
@@ -81,10 +95,10 @@ RTK_FN bool rtk_trim_by_column(const RCtx& c_, const char* raw_, uint32_t n_, co
     if (keep == 0 || keep > s.my.r_cap || keep + n > s.my.mv_cap || !((2LL * 8 + 4) * W * n + 8LL * n < 1024 * 1024)) return true;
     const unsigned long long t1 = rtk_clock();
     TrimPark& pk = s.loc.park;
-    pk.nm = 0; pk.len = keep; pk.dist = out->dist; pk.n = n; pk.gen = rtk_ld(&s.my.tb_gen); pk.pending = 1;
-    pk.last_move = rtk_myers_last_move(s.my, static_cast<int>(keep), static_cast<int>(n), static_cast<int>(n), out->dist);
+    pk.nm = 0; pk.len = keep; pk.dist = out->dist; pk.n = n; pk.gen = rtk_ld(&s.my.tb_gen); pk.pending = table ? RTK_PARK_TABLE : RTK_PARK_NO_TABLE;
+    pk.last_move = table ? rtk_myers_last_move(s.my, static_cast<int>(keep), static_cast<int>(n), static_cast<int>(n), out->dist) : rtk_myers_last_move_column(s.my, static_cast<int>(keep));
     s.cnt[RTK_RC_CYC_MYERS] += rtk_clock() - t1;
-    if (rtk_u(c.o.park_eager) || keep + n > s.str_cap) rtk_park_walk(c);
+    if (rtk_u(c.o.park_eager) || keep + n > s.str_cap) rtk_park_walk(c, corr, raw);
     return true;
 }
 

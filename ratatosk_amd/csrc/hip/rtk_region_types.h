@@ -229,9 +229,11 @@ struct ResCorr { char* seq; char* qual; uint32_t seq_len, qual_len; uint64_t* bm
 // state of one rtk_correct_region call that its three parts hand on (side lists + colours | path search | assembly + trim)
 struct RegionCall { const char* s_read; const char* q_read; uint64_t complete; UMap um1, um2; uint32_t s_len, p1, p2, first_pos, len_weak_region, lw_lo, lw_hi, n_all, n_partial, n_amb, has_end_pt, found_first, lrc; };
 // the forward trim of a gap region, kept for the consensus (rtk_trim_by_column): the alignment NW(rbuf[RTK_RB_FW_SEQ][0, len), raw region of n characters), distance dist, whose
-// path ends in last_move. pending: the path is still in the stored sweep (table generation gen) and rtk_park_walk makes it when a consensus is going to run; else
+// path ends in last_move. pending: nobody has walked the path yet, and rtk_park_walk makes it when a consensus is going to run -- from the stored sweep (RTK_PARK_TABLE,
+// table generation gen), or, where the trim kept only the last column of its sweep (RTK_PARK_NO_TABLE), from a second, stored sweep of the same pair; else
 // nm moves are parked in rbuf[RTK_RB_PARK_MOVES] (nm = 0 and not pending: nothing parked)
 struct TrimPark { uint32_t nm, len; int32_t dist; uint32_t n, last_move, pending, gen; };
+enum { RTK_PARK_TABLE = 1u, RTK_PARK_NO_TABLE = 2u };
 struct DriverLocals { Anchors an[RTK_AN_N]; ResCorr rc[RTK_RES_N]; SideList side[RTK_SIDE_N]; uint32_t len[RTK_LEN_N]; int best[RTK_BEST_N]; MyersSaved saved; RegionCall call; TrimPark park; MyersResult trim; };
 
 struct RegionScratch {

@@ -26,6 +26,7 @@ struct OptsView {
     U<uint32_t> strand2_mode; // RTK_STRAND2_ALWAYS / RTK_STRAND2_AUDIT (rtk_knobs.h): 0 = a gap region whose forward result decides the bytes skips its second strand (rtk_strand2_skippable, rtk_region.h), 1 = every second strand runs, 2 = they run where the rule says skip, and the two results are compared
     U<uint32_t> colours_mode; // RTK_COLOURS_ROUTE / RTK_COLOURS_AUDIT / RTK_TEST_COLOURS_FAULT (rtk_knobs.h): RTK_CM_* (rtk_types.h). 0 = rtk_choose_colors (rtk_colours.h) asks its programs in their usual order and nothing is compared
     U<uint32_t> park_eager; // RTK_PARK_EAGER (rtk_knobs.h): 1 = the forward trim of a gap region walks its alignment at once (rtk_trim_by_column, rtk_region_align.h), 0 = only where a consensus is going to run
+    U<uint32_t> trim_store; // RTK_TRIM_STORE (rtk_knobs.h): 1 = the forward trim of a gap region stores the table of its sweep (rtk_trim_by_column, rtk_region_align.h), 0 = it keeps the last column alone
 };
 
 struct BatchView {

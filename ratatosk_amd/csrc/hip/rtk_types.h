@@ -196,7 +196,8 @@ enum RtkCounterSlot {
     RTK_CNT_PARK_END = 219,
     RTK_CNT_COLOURS = 219,          // [6] k_regions, calls of rtk_choose_colors by the program that answered: small, wide, bits, general; audit mismatches; calls the register program declined for room (RTK_RC_COLOURS_SMALL ..) -> rtk_stats
     RTK_CNT_COLOURS_END = 225,
-    RTK_CNT_USED_END = RTK_CNT_COLOURS_END,
+    RTK_CNT_PARK_RESWEEPS = 225,    // k_regions, forward trims without a table whose path was walked from a second sweep (RTK_RC_PARK_RESWEEPS) -> rtk_stats
+    RTK_CNT_USED_END = 226,
     RTK_CNT_TOTAL = (RTK_CNT_USED_END + 31) / 32 * 32 // words in the block: what is used, rounded up to 256 bytes (the tail is free)
 };
 static_assert(RTK_CNT_TOTAL == 256, "counter map: the size of the block changed (it is part of what the kernels and the host agree on)");
@@ -235,12 +236,14 @@ enum RtkRegionCnt { RTK_RC_EXPAND = 0, RTK_RC_COLOUR = 1, RTK_RC_PATHBASE = 2, R
     // calls of rtk_choose_colors (rtk_colours.h) by the program that answered -> RTK_CNT_COLOURS + 0 .. 5: rtk_choose_colors_small with at most RTK_CS_MAX_IDS ids
     // (repeats counted) / with more ("wide"), rtk_choose_colors_bits, rtk_choose_colors_general; -- RTK_COLOURS_AUDIT=1 -- calls whose first answer differed from the
     // general program's; and calls rtk_choose_colors_small handed on because universe and bit vectors did not fit its LDS buffer (they are answered, and counted, further on)
-    RTK_RC_COLOURS_SMALL = 29, RTK_RC_COLOURS_WIDE = 30, RTK_RC_COLOURS_BITS = 31, RTK_RC_COLOURS_GENERAL = 32, RTK_RC_COLOURS_AUDIT_MISMATCH = 33, RTK_RC_COLOURS_DECLINED_FIT = 34, RTK_RC_N = 35 };
+    RTK_RC_COLOURS_SMALL = 29, RTK_RC_COLOURS_WIDE = 30, RTK_RC_COLOURS_BITS = 31, RTK_RC_COLOURS_GENERAL = 32, RTK_RC_COLOURS_AUDIT_MISMATCH = 33, RTK_RC_COLOURS_DECLINED_FIT = 34,
+    // forward trims that kept only the last column of their sweep and whose path was walked after all, from a second, stored sweep (rtk_park_walk) -> RTK_CNT_PARK_RESWEEPS
+    RTK_RC_PARK_RESWEEPS = 35, RTK_RC_N = 36 };
 static_assert(RTK_CNT_ROUTES_END - RTK_CNT_ROUTES == static_cast<int>(RTK_RC_FA_LINKED_RUN) - static_cast<int>(RTK_RC_TRIM_STORED), "counter map: one slot per route counter");
 static_assert(RTK_CNT_FA_LINKED_END - RTK_CNT_FA_LINKED == static_cast<int>(RTK_RC_STRAND2_RUN) - static_cast<int>(RTK_RC_FA_LINKED_RUN), "counter map: one slot per fixAmbiguity counter");
 static_assert(RTK_CNT_STRAND2_END - RTK_CNT_STRAND2 == static_cast<int>(RTK_RC_PARK_WALKED) - static_cast<int>(RTK_RC_STRAND2_RUN), "counter map: one slot per second-strand counter");
 static_assert(RTK_CNT_PARK_END - RTK_CNT_PARK == static_cast<int>(RTK_RC_COLOURS_SMALL) - static_cast<int>(RTK_RC_PARK_WALKED), "counter map: one slot per park counter");
-static_assert(RTK_CNT_COLOURS_END - RTK_CNT_COLOURS == static_cast<int>(RTK_RC_N) - static_cast<int>(RTK_RC_COLOURS_SMALL), "counter map: one slot per colour-route counter");
+static_assert(RTK_CNT_COLOURS_END - RTK_CNT_COLOURS == static_cast<int>(RTK_RC_PARK_RESWEEPS) - static_cast<int>(RTK_RC_COLOURS_SMALL), "counter map: one slot per colour-route counter");
 // OptsView::colours_mode (rtk_seeds.h; RTK_COLOURS_ROUTE, RTK_COLOURS_AUDIT, RTK_TEST_COLOURS_FAULT of rtk_knobs.h): route in bits 0 .. 1, the audit and its test hook above
 #define RTK_CM_ROUTE 3u
 #define RTK_CM_ROUTE_BITS 1u
