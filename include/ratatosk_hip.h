@@ -440,6 +440,20 @@ int rtk_rescue_begin(int device, int k, const uint64_t* lr, uint64_t n_lr, const
 int rtk_rescue_chunk(void* job, const char* chars, uint64_t n_chars, const uint64_t* starts, uint32_t n_reads, unsigned char* keep);
 int rtk_rescue_end(void* job, uint64_t* n_positions_probed, uint64_t* n_hits);
 
+/* rtk_qv_*: the k-mer QV of reads against a set of k-mers (rtk_qv, `correct --qv`; DESIGN.md section 4, [A17]; no counterpart in the reference). One-word k-mers
+ * (odd k <= 31). begin: solid = canonical k-mers, sorted ascending and distinct, as rtk_index_count_kmers returns them (may be empty: nothing is ever found); they
+ * are put into a table in HBM, the input is not kept. chunk (any thread, two calls run side by side): pieces separated by '\n' as for rtk_rescue_chunk, piece p =
+ * chars[starts[p] .. starts[p + 1]) (starts[0] = 0, ascending; the last piece ends at n_chars; at most 64 MB and 4 M pieces per call); windows[p] = the start
+ * positions of piece p whose k characters are all A/C/G/T (either case), found[p] = those whose canonical k-mer is in the set. A window that holds the separator
+ * or any other character is not valid, so the text alone decides and no window reaches into the next piece. A piece is a whole read or part of one: a read longer
+ * than a chunk is cut by the caller with an overlap of k - 1 characters, so that every window lies whole in exactly one piece, and the caller adds the pieces up.
+ * The device cuts the work by position (spans of rtk_qv_span() start positions), not by piece: no read sets the launch time. end: valid windows and found ones
+ * over all chunks; releases the job (also on error; with null outputs: only that). Appended without a new revision number: see RTK_API_REVISION. */
+int rtk_qv_begin(int device, int k, const uint64_t* solid, uint64_t n_solid, void** job);
+int rtk_qv_chunk(void* job, const char* chars, uint64_t n_chars, const uint64_t* starts, uint32_t n_pieces, uint32_t* windows, uint32_t* found);
+int rtk_qv_end(void* job, uint64_t* n_windows, uint64_t* n_found);
+uint32_t rtk_qv_span(void); /* start positions one wave takes at a time (for tests) */
+
 /* Stage entry for tests (revision 10): the wave-cooperative set primitives of the region stage (csrc/hip/rtk_sets.h, rtk_colours.h), one problem per wavefront
  * in ONE launch, each wave with the LDS buffer to itself as in the region kernel. Problem i: the operation op[i], two arrays of 32-bit words a[i][0 .. na[i]) and
  * b[i][0 .. nb[i]) and scalar[i]; its output words go to out_pool[out_off[i] .. out_off[i + 1]) (the caller sizes the slices), out_n[i] says how many were
@@ -490,7 +504,7 @@ const char* rtk_version(void);
  * 8: rtk_stats fields n_fa_linked_*; 9: rtk_rescue_begin / _chunk / _end; still 9: rtk_stats fields n_strand2_* and n_park_*, the test-only rtk_myers_batch mode 5, appended at the end -- a library of revision 9
  * without them leaves them as the caller set them;
  * 10: rtk_sets_batch, rtk_stats fields n_colours_*; still 10: rtk_index_colour_cov, rtk_index_colour_end_subsampled, rtk_index_subsample_events, then rtk_index_colour_merge,
- * rtk_index_colour_merge_classes, rtk_index_merge_events, then rtk_index_colour_chunk_q, then rtk_batch_fetch_seeds, then rtk_index_snp_candidates, then rtk_index_snp_plan, then rtk_index_cover_begin / _chunk / _end, appended -- a library of revision 10 without them lacks the symbols, and callers look them up by name;
+ * rtk_index_colour_merge_classes, rtk_index_merge_events, then rtk_index_colour_chunk_q, then rtk_batch_fetch_seeds, then rtk_index_snp_candidates, then rtk_index_snp_plan, then rtk_index_cover_begin / _chunk / _end, then rtk_qv_begin / _chunk / _end / _span, appended -- a library of revision 10 without them lacks the symbols, and callers look them up by name;
  * then the rtk_stats field n_park_resweeps and the test-only rtk_myers_batch mode 6, which are no symbols: a library of revision 10 without them leaves the field as the
  * caller set it and answers mode 6 with RTK_ERR_ARG). */
 #define RTK_API_REVISION 10

@@ -141,6 +141,11 @@ def load_library(path=None):
         L.rtk_index_cover_begin.argtypes = [C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_ubyte), C.POINTER(C.c_void_p)]
         L.rtk_index_cover_chunk.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.c_uint32]
         L.rtk_index_cover_end.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_uint64)]
+    if hasattr(L, "rtk_qv_begin"):  # (still revision 10: appended; a library without them: qv_reads says so)
+        L.rtk_qv_begin.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_void_p)]
+        L.rtk_qv_chunk.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        L.rtk_qv_end.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.rtk_qv_span.argtypes = []; L.rtk_qv_span.restype = C.c_uint32
     L.rtk_free.argtypes = [C.c_void_p]
     _libs[path] = L
     return L
@@ -400,6 +405,104 @@ def rescue_reads(lr_kmers, sr_kmers, seqs, k=31, min_positions=31, device=0, sta
     if stats is not None:
         stats["n_positions_probed"], stats["n_hits"] = probed.value, hits.value
     return out
+
+
+QV_CHUNK_CHARS = 48 << 20  # characters per rtk_qv_chunk call of qv_reads, separators included (the entry takes 64 MB)
+
+
+def qv_span(lib_path=None):
+    """Start positions one wave of k_qv takes at a time (rtk_qv_span): tests place read lengths and piece sizes around it."""
+    L = load_library(lib_path)
+    if not hasattr(L, "rtk_qv_begin"):
+        raise RtkError("%s has no rtk_qv entries" % L._name)
+    return int(L.rtk_qv_span())
+
+
+def qv_reads(solid_kmers, seqs, k=31, device=0, max_piece=None, lib_path=None, threads=1, stats=None):
+    """The k-mer QV counts of rtk_qv (DESIGN.md section 4 [A17]) over rtk_qv_begin / _chunk / _end: solid_kmers = sorted distinct canonical k-mers (as
+    rtk_index_count_kmers returns them); returns ([windows], [found]) per read of seqs: the start positions whose k characters are all A/C/G/T (either case) and
+    those whose canonical k-mer is in the set. Chunks are laid out as rescue_reads lays them out; a read longer than max_piece characters (default: what a chunk
+    holds) is cut into pieces that overlap by k - 1 characters and added up again, and a chunk holds max_piece + 1 characters at the most (tests lower it to get many
+    chunks from little text). threads=2 feeds the chunks from two threads. stats (a dict) receives n_chunks, n_windows and n_found."""
+    L = load_library(lib_path)
+    if not hasattr(L, "rtk_qv_begin"):
+        raise RtkError("%s has no rtk_qv entries" % L._name)
+    if max_piece is None:
+        max_piece = QV_CHUNK_CHARS - 1
+    if max_piece < k or max_piece > QV_CHUNK_CHARS - 1:
+        raise ValueError("max_piece must lie in k .. %d" % (QV_CHUNK_CHARS - 1))
+    keep_solid, p_solid, n_solid = _u64_array(solid_kmers)
+    bs = [_b(s) for s in seqs]
+    pieces = []  # (read, piece text)
+    for r, s in enumerate(bs):
+        a = 0
+        while True:
+            pieces.append((r, s[a:a + max_piece]))
+            if a + max_piece >= len(s):
+                break
+            a += max_piece - (k - 1)
+    chunks, i = [], 0  # [i, j) of pieces: at most max_piece + 1 characters and 2 M pieces
+    while i < len(pieces):
+        j, size = i, 0
+        while j < len(pieces) and size + len(pieces[j][1]) + 1 <= max_piece + 1 and j - i < (2 << 20):
+            size += len(pieces[j][1]) + 1; j += 1
+        chunks.append((i, j)); i = j
+    job = C.c_void_p()
+
+    def check(rc):
+        if rc != 0:
+            raise RtkError("rtk error %d: %s" % (rc, L.rtk_last_error().decode()))
+
+    check(L.rtk_qv_begin(device, k, p_solid, n_solid, C.byref(job)))
+    windows, found = [0] * len(bs), [0] * len(bs)
+    results = [None] * len(chunks)
+
+    def run(c):
+        i, j = chunks[c]
+        starts, at = (C.c_uint64 * (j - i))(), 0
+        for p in range(i, j):
+            starts[p - i] = at; at += len(pieces[p][1]) + 1
+        chars = b"\n".join(t for _, t in pieces[i:j]) + b"\n"
+        w, f = (C.c_uint32 * (j - i))(), (C.c_uint32 * (j - i))()
+        check(L.rtk_qv_chunk(job, chars, len(chars), starts, j - i, w, f))
+        results[c] = (list(w), list(f))
+
+    try:
+        if threads <= 1:
+            for c in range(len(chunks)):
+                run(c)
+        else:
+            import threading
+            errors = []
+
+            def feed(t):
+                try:
+                    for c in range(t, len(chunks), threads):
+                        run(c)
+                except Exception as e:  # noqa: BLE001 (handed to the caller below)
+                    errors.append(e)
+
+            th = [threading.Thread(target=feed, args=(t,)) for t in range(threads)]
+            for t in th:
+                t.start()
+            for t in th:
+                t.join()
+            if errors:
+                raise errors[0]
+    except Exception:
+        L.rtk_qv_end(job, None, None)
+        raise
+    n_windows, n_found = C.c_uint64(), C.c_uint64()
+    check(L.rtk_qv_end(job, C.byref(n_windows), C.byref(n_found)))
+    for c, (i, j) in enumerate(chunks):
+        w, f = results[c]
+        for p in range(i, j):
+            windows[pieces[p][0]] += w[p - i]; found[pieces[p][0]] += f[p - i]
+    if (sum(windows), sum(found)) != (n_windows.value, n_found.value):
+        raise RtkError("rtk_qv: the pieces add up to %d windows / %d found, the device counted %d / %d" % (sum(windows), sum(found), n_windows.value, n_found.value))
+    if stats is not None:
+        stats["n_chunks"], stats["n_windows"], stats["n_found"] = len(chunks), n_windows.value, n_found.value
+    return windows, found
 
 
 MODE_SHW_BY_COLUMN, MODE_NW_PREFIX, MODE_NW_PREFIX_LAST, MODE_NW_PREFIX_LAST_COLUMN = 3, 4, 5, 6  # test-only modes of myers_batch (include/ratatosk_hip.h)

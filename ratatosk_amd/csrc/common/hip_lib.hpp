@@ -33,6 +33,9 @@ struct HipLib {
     typedef int (*rescue_begin_fn)(int, int, const uint64_t*, uint64_t, const uint64_t*, uint64_t, uint32_t, void**);                        // rtk_rescue_begin
     typedef int (*rescue_chunk_fn)(void*, const char*, uint64_t, const uint64_t*, uint32_t, unsigned char*);                                 // rtk_rescue_chunk
     typedef int (*rescue_end_fn)(void*, uint64_t*, uint64_t*);                                                                               // rtk_rescue_end
+    typedef int (*qv_begin_fn)(int, int, const uint64_t*, uint64_t, void**);                                                                 // rtk_qv_begin
+    typedef int (*qv_chunk_fn)(void*, const char*, uint64_t, const uint64_t*, uint32_t, uint32_t*, uint32_t*);                               // rtk_qv_chunk
+    typedef int (*qv_end_fn)(void*, uint64_t*, uint64_t*);                                                                                   // rtk_qv_end
 
     std::string path = "libratatosk_hip.so";
     void* handle = nullptr;

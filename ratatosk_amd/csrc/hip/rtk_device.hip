@@ -269,6 +269,10 @@ extern "C" int rtk_index_unitigs(int, int, const uint64_t*, uint64_t, char**, ui
 extern "C" int rtk_rescue_begin(int, int, const uint64_t*, uint64_t, const uint64_t*, uint64_t, uint32_t, void**) { return rtk_fail(RTK_ERR_UNSUPPORTED, "rtk_rescue_begin: not part of the simulator build"); }
 extern "C" int rtk_rescue_chunk(void*, const char*, uint64_t, const uint64_t*, uint32_t, unsigned char*) { return rtk_fail(RTK_ERR_UNSUPPORTED, "rtk_rescue_chunk: not part of the simulator build"); }
 extern "C" int rtk_rescue_end(void*, uint64_t*, uint64_t*) { return rtk_fail(RTK_ERR_UNSUPPORTED, "rtk_rescue_end: not part of the simulator build"); }
+extern "C" int rtk_qv_begin(int, int, const uint64_t*, uint64_t, void**) { return rtk_fail(RTK_ERR_UNSUPPORTED, "rtk_qv_begin: not part of the simulator build"); }
+extern "C" int rtk_qv_chunk(void*, const char*, uint64_t, const uint64_t*, uint32_t, uint32_t*, uint32_t*) { return rtk_fail(RTK_ERR_UNSUPPORTED, "rtk_qv_chunk: not part of the simulator build"); }
+extern "C" int rtk_qv_end(void*, uint64_t*, uint64_t*) { return rtk_fail(RTK_ERR_UNSUPPORTED, "rtk_qv_end: not part of the simulator build"); }
+extern "C" uint32_t rtk_qv_span(void) { return 0; } // (no k_qv here)
 #endif
 extern "C" int rtk_device_memory(int device, uint64_t* free_bytes, uint64_t* total_bytes) {
     if (!free_bytes || !total_bytes) return rtk_fail(RTK_ERR_ARG, "rtk_device_memory: null argument");

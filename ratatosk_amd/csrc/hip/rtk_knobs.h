@@ -91,6 +91,7 @@ inline int rtk_knob_sim_devices() { return std::max(1, rtk_env_int("RTK_SIM_DEVI
 //   csrc/tools (rtk_build_index): RTK_FASTA_MEMBER_BYTES, RTK_INDEX_HOST_COLOURS, RTK_INDEX_HOST_UNITIGS, RTK_INDEX_SNPS (device | host: where --gpu --snps finds its candidates),
 //     RTK_INDEX_THREADS, RTK_INDEX_TRACE, RTK_INDEX_CHUNK (--gpu --cover-edges-from: characters of cover text per chunk)
 //   csrc/tools (rtk_rescue_reads): RTK_INDEX_CHUNK (characters of -u text per batch), RTK_INDEX_THREADS, RTK_INDEX_TRACE
+//   csrc/tools (rtk_qv): RTK_INDEX_CHUNK (characters of -l text per chunk; a longer read is cut into pieces), RTK_INDEX_THREADS, RTK_INDEX_TRACE (--gpu: also the time of k_qv alone)
 //   ratatosk_amd/api.py: RTK_LIB_OVERRIDE (another build of the library), RTK_HOST_TABLES
 
 #endif

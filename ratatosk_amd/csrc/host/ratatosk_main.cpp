@@ -59,6 +59,7 @@ struct Opt {
     size_t insert_sz = 500, w1 = 1000, w2 = 5000, batch_bases = 0; // 0: not given (64 Mi for the first pass, 32 Mi for the second)
     bool merge_duplicates = false; // --merge-duplicates: handed to both index steps of `correct -s` (the second colours by long reads and leaves them alone)
     bool k1_from_k2 = false; // --k1-from-k2: `correct -s` builds the k2 graph once (rtk_build_index --graph-only) and both indexes from its unitig file (--graph-from)
+    bool qv = false; // --qv: `correct -s` ends with rtk_qv --gpu on the -l reads and on its own output (OUT.qv.tsv; DESIGN.md section 4 [A17])
     bool cover_edges = false; // --cover-edges (only with --k1-from-k2): the k1 index step of `correct -s` covers its low-coverage edges from the k2 unitig file (rtk_build_index --cover-edges-from)
     bool subsample = false; std::string subsample_seed; // --subsample-colours [--subsample-seed N]: handed to both index steps of `correct -s`
     // -M / -C / -Q as given: `correct -s` hands them to the index step of the second pass (rtk_build_index --colour-min-conf / --colour-min-len / --colour-max-qual)
@@ -85,6 +86,7 @@ static void usage() {
                     "                        second pass; -C, --min-len-color2: a first-pass read of fewer bases colours nothing. Handed to the k2 index step, with -Q if given\n"
                     "                        (rtk_build_index --colour-min-conf / --colour-min-len / --colour-max-qual). The reference applies -M 0 -C 3000 by default; here neither\n"
                     "                        applies unless given. Next to a pre-built index (-g, -d) they are ignored\n"
+                    "      --qv              after the last step: the k-mer QV of the -l reads and of the output of the run against the k1-mers seen twice in the -s reads (rtk_qv --gpu, <out_prefix>.qv.tsv)\n"
                     "  -u, --in-unmapped-short  unmapped short reads (may be repeated; or a text file of paths): those with enough k1-mers that the long reads hold and the -s reads\n"
                     "                        do not are rescued first (rtk_rescue_reads --gpu, <out_prefix>_extra_sr.fasta, removed at the end) and join the short reads of the index builds\n\n"
                     "       Ratatosk correct -1 -g <graph.fasta.gz> -d <unitig_data.rtsk> -l <long_reads> -o <out_prefix> [options]\n"
@@ -259,6 +261,16 @@ static int correct_from_short_reads(const Opt& opt, const char* argv0) {
         cleanup();
     }
     cleanup_all();
+    if (opt.qv) { // the reads before and after, against the short-read k1-mers: a fresh child like every step; the corrected output stays whatever becomes of it
+        const std::string result = opt.pass1 ? mid : opt.out + (opt.gzip ? ".fastq.gz" : ".fastq");
+        std::vector<std::string> a; a.push_back(dir + "/rtk_qv"); a.push_back("--gpu"); a.push_back("-k"); a.push_back(std::to_string(opt.k1));
+        for (size_t i = 0; i < opt.in_short.size(); ++i) { a.push_back("-s"); a.push_back(opt.in_short[i]); }
+        for (size_t i = 0; i < opt.in_long.size(); ++i) { a.push_back("-l"); a.push_back(opt.in_long[i]); }
+        a.push_back("-l"); a.push_back(result);
+        if (v) a.push_back("-v");
+        a.push_back("-o"); a.push_back(opt.out);
+        if (run_step("step 5 (k-mer QV of the reads before and after, rtk_qv)", a, v)) return 1;
+    }
     if (v) fprintf(stderr, "Ratatosk::Ratatosk(): Done. [%.1f s]\n", since());
     return 0;
 }
@@ -280,7 +292,7 @@ int main(int argc, char** argv) {
         {"correction-rounds", required_argument, 0, 'r'}, {"no-snp-correction", no_argument, 0, 'F'}, {"force-io-order", no_argument, 0, 'O'}, {"no-graph-index", no_argument, 0, 'I'},
         {"in-unmapped-short", required_argument, 0, 'u'}, {"in-accurate-long", required_argument, 0, 'a'}, {"in-short-phase", required_argument, 0, 'p'}, {"in-long-phase", required_argument, 0, 'P'}, {"force-correct-snp", no_argument, 0, 'f'},
         {"sampling", required_argument, 0, 'S'}, {"min-conf-color2", required_argument, 0, 'M'}, {"min-len-color2", required_argument, 0, 'C'},
-        {"batch-bases", required_argument, 0, 'B'}, {"strip-annotations", no_argument, 0, 1001}, {"gpus", required_argument, 0, 1002}, {"workers-per-gpu", required_argument, 0, 1003}, {"parse-only", no_argument, 0, 1004}, {"allow-tinybitmap", no_argument, 0, 1005}, {"subsample-colours", no_argument, 0, 1006}, {"subsample-seed", required_argument, 0, 1007}, {"merge-duplicates", no_argument, 0, 1008}, {"k1-from-k2", no_argument, 0, 1009}, {"cover-edges", no_argument, 0, 1010}, {"verbose", no_argument, 0, 'v'}, {0, 0, 0, 0}};
+        {"batch-bases", required_argument, 0, 'B'}, {"strip-annotations", no_argument, 0, 1001}, {"gpus", required_argument, 0, 1002}, {"workers-per-gpu", required_argument, 0, 1003}, {"parse-only", no_argument, 0, 1004}, {"allow-tinybitmap", no_argument, 0, 1005}, {"subsample-colours", no_argument, 0, 1006}, {"subsample-seed", required_argument, 0, 1007}, {"merge-duplicates", no_argument, 0, 1008}, {"k1-from-k2", no_argument, 0, 1009}, {"cover-edges", no_argument, 0, 1010}, {"qv", no_argument, 0, 1011}, {"verbose", no_argument, 0, 'v'}, {0, 0, 0, 0}};
     int c, idx = 0;
     while ((c = getopt_long(argc - 1, argv + 1, "s:l:o:c:g:d:i:k:w:Q:m:B:L:K:W:t:r:u:a:p:P:S:M:C:GFOIf12v", lo, &idx)) != -1) {
         { // what `correct -s` hands on to its correction steps: the option as given (long options by their long name)
@@ -332,6 +344,7 @@ int main(int argc, char** argv) {
             case 1008: opt.merge_duplicates = true; break; // (with -g / -d: refused below)
             case 1009: opt.k1_from_k2 = true; break; // (with -g / -d: refused below)
             case 1010: opt.cover_edges = true; break; // (with -g / -d, or without --k1-from-k2: refused below)
+            case 1011: opt.qv = true; break; // (with -g / -d: refused below)
             case 's': opt.in_short.push_back(optarg); break; // (with -g / -d: ignored, said below)
             default: usage(); return 0; // the reference returns 0 on option errors too (src/Ratatosk.cpp:1018)
         }
@@ -341,6 +354,10 @@ int main(int argc, char** argv) {
     for (int i = optind; i < argc - 1; ++i) fprintf(stderr, "Ratatosk::correct: argument '%s' belongs to no option and is ignored (several input files: one -l each, or a text file of paths)\n", argv[1 + i]);
     if (!opt.subsample_seed.empty() && !opt.subsample && opt.graph.empty() && opt.udata.empty()) { fprintf(stderr, "Ratatosk::correct: --subsample-seed without --subsample-colours\n"); return 1; }
     if (!opt.in_short.empty() && opt.graph.empty() && opt.udata.empty()) return correct_from_short_reads(opt, argv[0]);
+    if (opt.qv) { // the set is counted from the -s reads, which a run on a pre-built index does not have
+        fprintf(stderr, "Ratatosk::correct: --qv belongs to the run that builds its indexes from the short reads (correct -s SHORT -l LONG -o OUT --qv): next to a pre-built index (-g, -d) use rtk_qv -g GRAPH.fasta.gz -l READS -l OUT.fastq -k K1 -o OUT\n");
+        return 1;
+    }
     if (!opt.in_unmapped.empty() && opt.graph.empty() && opt.udata.empty()) { fprintf(stderr, "Ratatosk::correct: -u needs the mapped short reads (-s) it is compared with\n"); return 1; }
     if (!opt.in_unmapped.empty()) { // the reference ignores -u when it is given an index (src/Ratatosk.cpp:1040: !hasIndex); said aloud here
         fprintf(stderr, "Ratatosk::correct: -u (unmapped-read rescue) next to a pre-built index (-g, -d) is not in scope of this build: the rescue belongs to the index build (correct -s SHORT -u UNMAPPED -l LONG -o OUT)\n");
