@@ -407,6 +407,24 @@ int rtk_index_snp_candidates(int device, int k, const char* seq_pool, const uint
 int rtk_index_snp_plan(int device, int k, const uint64_t* seq_off, uint64_t n_unitigs, const uint8_t* searched, uint64_t room, uint32_t* passes,
                        uint64_t* need_one_pass, uint64_t* need_min);
 
+/* rtk_index_pair_ids: the colour ids of the read pairs BY NAME (rtk_build_index --pair-by-name; DESIGN.md section 4 [A18]; the stage: csrc/hip/rtk_index_pairs.h) -- the
+ * reference's name_hmap (addCoverage, src/Graph.cpp:1595-1608, 1800-1804): a name gets the next id when it is first seen, every later record of that name the same id.
+ * name_hash[r]: the hash of the name of record r of the input, records in input order (the caller hashes: 64-bit FNV-1a over the name, then the mixer of the k-mer
+ * tables, csrc/common/name_hash.hpp; two names are the same when their hashes are). ids[r] (room for n words, the caller's) = the number of distinct hashes whose first
+ * record precedes the first record of hash name_hash[r]; *n_ids = the number of distinct hashes. n = 0: RTK_OK and nothing written; n >= 2^32: RTK_ERR_UNSUPPORTED
+ * before anything is allocated. The stage sorts (hash, ordinal), marks the first of every run and ranks the firsts; the bytes are worked out before anything is allocated
+ * and compared with the room: the free device memory, or RTK_INDEX_PAIR_MEM when that is lower. When the sort's buffers for all records do not fit, the hash space is cut
+ * into P equal ranges and the stage runs in P passes, each over the records of one range in their input order (the hashes stay on the host and are streamed through
+ * a staging buffer every pass); 4 bytes per record live across the passes. P is the smallest number whose plan fits, at most 256; RTK_INDEX_PAIR_PASSES (read at the call,
+ * 0 or unset: as few as fit) forces exactly that many, clamped to 256. The same ids for every P. RTK_ERR_DEVICE, `need <bytes> bytes of device memory, <room> are to be
+ * had`, when not even the most passes fit (or the forced number does not): the caller keeps its host route for that case. Appended without a new revision number: see
+ * RTK_API_REVISION.
+ * rtk_index_pair_plan: what rtk_index_pair_ids would do for n records with `room` bytes (0: the figure the stage itself would use now), worked out by the same code and
+ * without allocating anything. *passes: the number of passes, 0 when nothing fits; *need_one_pass: the bytes of the single pass; *need_min: the bytes of the smallest plan.
+ * The figures take every pass at its even share of the records; the stage, once it has counted them, takes more passes when a range is heavier than that. */
+int rtk_index_pair_ids(int device, const uint64_t* name_hash, uint64_t n, uint32_t* ids, uint64_t* n_ids);
+int rtk_index_pair_plan(int device, uint64_t n, uint64_t room, uint32_t* passes, uint64_t* need_one_pass, uint64_t* need_min);
+
 /* rtk_index_cover_*: where the text of other sequences (the unitigs of the k2 graph) crosses an edge of these unitigs that too few colours share -- the search of
  * the last block of the reference's first-pass addCoverage, "Covering low coverage edges." (src/Graph.cpp:3085-3363; DESIGN.md section 4 [A16]; the stage:
  * csrc/hip/rtk_index_cover.h). Any odd k <= 63.
@@ -504,7 +522,7 @@ const char* rtk_version(void);
  * 8: rtk_stats fields n_fa_linked_*; 9: rtk_rescue_begin / _chunk / _end; still 9: rtk_stats fields n_strand2_* and n_park_*, the test-only rtk_myers_batch mode 5, appended at the end -- a library of revision 9
  * without them leaves them as the caller set them;
  * 10: rtk_sets_batch, rtk_stats fields n_colours_*; still 10: rtk_index_colour_cov, rtk_index_colour_end_subsampled, rtk_index_subsample_events, then rtk_index_colour_merge,
- * rtk_index_colour_merge_classes, rtk_index_merge_events, then rtk_index_colour_chunk_q, then rtk_batch_fetch_seeds, then rtk_index_snp_candidates, then rtk_index_snp_plan, then rtk_index_cover_begin / _chunk / _end, then rtk_qv_begin / _chunk / _end / _span, appended -- a library of revision 10 without them lacks the symbols, and callers look them up by name;
+ * rtk_index_colour_merge_classes, rtk_index_merge_events, then rtk_index_colour_chunk_q, then rtk_batch_fetch_seeds, then rtk_index_snp_candidates, then rtk_index_snp_plan, then rtk_index_cover_begin / _chunk / _end, then rtk_qv_begin / _chunk / _end / _span, then rtk_index_pair_ids / rtk_index_pair_plan, appended -- a library of revision 10 without them lacks the symbols, and callers look them up by name;
  * then the rtk_stats field n_park_resweeps and the test-only rtk_myers_batch mode 6, which are no symbols: a library of revision 10 without them leaves the field as the
  * caller set it and answers mode 6 with RTK_ERR_ARG). */
 #define RTK_API_REVISION 10

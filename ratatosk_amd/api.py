@@ -146,6 +146,9 @@ def load_library(path=None):
         L.rtk_qv_chunk.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.rtk_qv_end.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.rtk_qv_span.argtypes = []; L.rtk_qv_span.restype = C.c_uint32
+    if hasattr(L, "rtk_index_pair_ids"):  # (still revision 10: appended; a library without them: index_pair_ids / index_pair_plan say so)
+        L.rtk_index_pair_ids.argtypes = [C.c_int, C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+        L.rtk_index_pair_plan.argtypes = [C.c_int, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.rtk_free.argtypes = [C.c_void_p]
     _libs[path] = L
     return L
@@ -739,6 +742,51 @@ def index_snp_plan(unitigs, k, searched=None, room=0, device=0, lib_path=None):
     passes, one, least = C.c_uint32(0), C.c_uint64(0), C.c_uint64(0)
     rc = L.rtk_index_snp_plan(device, k, off.ctypes.data_as(C.POINTER(C.c_uint64)), len(unitigs), None if flags is None else flags.ctypes.data_as(C.POINTER(C.c_ubyte)), room,
                               C.byref(passes), C.byref(one), C.byref(least))
+    if rc != 0:
+        raise RtkError("rtk error %d: %s" % (rc, L.rtk_last_error().decode()))
+    return passes.value, one.value, least.value
+
+
+def name_hash(name):
+    """The hash of a read name for --pair-by-name (DESIGN.md section 4 [A18]; csrc/common/name_hash.hpp): 64-bit FNV-1a over the bytes of the name (what the readers
+    hand over: the header up to the first blank, without a trailing /1 or /2), then the mixer of the k-mer tables. Pure Python."""
+    m, h = (1 << 64) - 1, 0xcbf29ce484222325
+    for c in _b(name):
+        h = ((h ^ c) * 0x100000001b3) & m
+    h ^= h >> 33
+    h = (h * 0xff51afd7ed558ccd) & m
+    h ^= h >> 33
+    h = (h * 0xc4ceb9fe1a85ec53) & m
+    return h ^ (h >> 33)
+
+
+def index_pair_ids(hashes, device=0, lib_path=None):
+    """The colour ids of the read pairs by name, on the device (stage entry rtk_index_pair_ids, include/ratatosk_hip.h): hashes[r] = the name hash of record r of the
+    colouring input, in input order. Returns (ids, n_ids): ids[r] = the number of distinct hashes first seen before the first record of hashes[r] (a list), and the
+    number of distinct hashes. RTK_INDEX_PAIR_PASSES / RTK_INDEX_PAIR_MEM are read at the call."""
+    import numpy as np
+    L = load_library(lib_path)
+    if not hasattr(L, "rtk_index_pair_ids"):
+        raise RtkError("%s lacks rtk_index_pair_ids (read pairs by name: appended at interface revision 10)" % L._name)
+    h = np.ascontiguousarray(hashes, dtype=np.uint64)
+    ids = np.zeros(max(1, h.size), dtype=np.uint32)
+    n_ids = C.c_uint64(0)
+    rc = L.rtk_index_pair_ids(device, h.ctypes.data_as(C.POINTER(C.c_uint64)) if h.size else None, h.size, ids.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(n_ids))
+    if rc != 0:
+        raise RtkError("rtk error %d: %s" % (rc, L.rtk_last_error().decode()))
+    return ids[:h.size].tolist(), n_ids.value
+
+
+def index_pair_plan(n, room=0, device=0, lib_path=None):
+    """What index_pair_ids would do for n records with `room` bytes of device memory (0: what the stage itself would go by now -- the free memory, or
+    RTK_INDEX_PAIR_MEM when that is lower), worked out by the stage's own code without allocating anything (rtk_index_pair_plan). Returns (passes, need_one_pass,
+    need_min): the number of passes over equal ranges of the hash space (0: nothing fits; RTK_INDEX_PAIR_PASSES forces it), the bytes of the single pass, the bytes
+    of the smallest plan."""
+    L = load_library(lib_path)
+    if not hasattr(L, "rtk_index_pair_plan"):
+        raise RtkError("%s lacks rtk_index_pair_plan (read pairs by name: appended at interface revision 10)" % L._name)
+    passes, one, least = C.c_uint32(0), C.c_uint64(0), C.c_uint64(0)
+    rc = L.rtk_index_pair_plan(device, n, room, C.byref(passes), C.byref(one), C.byref(least))
     if rc != 0:
         raise RtkError("rtk error %d: %s" % (rc, L.rtk_last_error().decode()))
     return passes.value, one.value, least.value

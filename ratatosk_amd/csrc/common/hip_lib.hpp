@@ -27,6 +27,7 @@ struct HipLib {
     typedef int (*col_merge_fn)(void*, uint64_t*, uint64_t*, uint64_t*, uint64_t*);                                                          // rtk_index_colour_merge
     typedef int (*col_merge_classes_fn)(void*, uint64_t*, uint64_t*);                                                                        // rtk_index_colour_merge_classes
     typedef int (*snp_cand_fn)(int, int, const char*, const uint64_t*, uint64_t, const uint8_t*, uint32_t, uint64_t**, uint64_t*);                          // rtk_index_snp_candidates
+    typedef int (*pair_ids_fn)(int, const uint64_t*, uint64_t, uint32_t*, uint64_t*);                                                        // rtk_index_pair_ids
     typedef int (*cover_begin_fn)(int, int, const char*, const uint64_t*, uint64_t, const uint8_t*, void**);                                 // rtk_index_cover_begin
     typedef int (*cover_chunk_fn)(void*, const char*, uint64_t, const uint64_t*, const uint32_t*, const uint64_t*, uint32_t);                // rtk_index_cover_chunk
     typedef int (*cover_end_fn)(void*, uint64_t**, uint64_t*);                                                                               // rtk_index_cover_end

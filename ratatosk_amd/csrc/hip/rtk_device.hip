@@ -262,6 +262,8 @@ extern "C" int rtk_index_colour_merge_classes(void*, uint64_t*, uint64_t*) { ret
 extern "C" int rtk_index_merge_events(int, const uint64_t*, uint64_t, uint32_t, uint64_t*, uint64_t*, uint64_t*, uint64_t*) { return rtk_fail(RTK_ERR_UNSUPPORTED, "rtk_index_merge_events: not part of the simulator build"); }
 extern "C" int rtk_index_snp_candidates(int, int, const char*, const uint64_t*, uint64_t, const uint8_t*, uint32_t, uint64_t**, uint64_t*) { return rtk_fail(RTK_ERR_UNSUPPORTED, "rtk_index_snp_candidates: not part of the simulator build"); }
 extern "C" int rtk_index_snp_plan(int, int, const uint64_t*, uint64_t, const uint8_t*, uint64_t, uint32_t*, uint64_t*, uint64_t*) { return rtk_fail(RTK_ERR_UNSUPPORTED, "rtk_index_snp_plan: not part of the simulator build"); }
+extern "C" int rtk_index_pair_ids(int, const uint64_t*, uint64_t, uint32_t*, uint64_t*) { return rtk_fail(RTK_ERR_UNSUPPORTED, "rtk_index_pair_ids: not part of the simulator build"); }
+extern "C" int rtk_index_pair_plan(int, uint64_t, uint64_t, uint32_t*, uint64_t*, uint64_t*) { return rtk_fail(RTK_ERR_UNSUPPORTED, "rtk_index_pair_plan: not part of the simulator build"); }
 extern "C" int rtk_index_cover_begin(int, int, const char*, const uint64_t*, uint64_t, const uint8_t*, void**) { return rtk_fail(RTK_ERR_UNSUPPORTED, "rtk_index_cover_begin: not part of the simulator build"); }
 extern "C" int rtk_index_cover_chunk(void*, const char*, uint64_t, const uint64_t*, const uint32_t*, const uint64_t*, uint32_t) { return rtk_fail(RTK_ERR_UNSUPPORTED, "rtk_index_cover_chunk: not part of the simulator build"); }
 extern "C" int rtk_index_cover_end(void*, uint64_t**, uint64_t*) { return rtk_fail(RTK_ERR_UNSUPPORTED, "rtk_index_cover_end: not part of the simulator build"); }

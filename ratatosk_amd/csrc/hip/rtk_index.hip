@@ -13,6 +13,8 @@
 //                                                   windows do not fit; rtk_index_snp_plan: what it would do, from the offsets alone
 //   rtk_index_cover_*       (rtk_index_cover.h)     the text of other sequences (the k2 unitigs) walked over the k-mer table: where it crosses an edge recorded as
 //                                                   shared by too few colours (k_cover_map); the crossings in the order of the file for the caller's serial walk
+//   rtk_index_pair_ids      (rtk_index_pairs.h)     the ids of the read pairs by name: the rank of every record's name hash by first appearance (k_pair_*), in passes
+//                                                   over equal ranges of the hash space when sort buffers for all records do not fit; rtk_index_pair_plan: what it would do
 // Every step serves one-word k-mers (k <= 31, key type uint64_t) and two-word k-mers (33 <= k <= 63, key type unsigned __int128: the 2k-bit code,
 // first base in the most significant bits; in memory the low word first). Own translation unit: rocPRIM's templates.
 // An entry is: the checks of its arguments, entry(...) -- the device set, what is thrown turned into the entry's error --, one call into the stage.
@@ -28,6 +30,7 @@
 #include "rtk_index_merge.h"
 #include "rtk_index_snps.h"
 #include "rtk_index_cover.h"
+#include "rtk_index_pairs.h"
 
 extern "C" int rtk_index_count_kmers(int device, int k, const char* const* files, int n_files, uint32_t min_count, int n_threads, uint64_t** solid_out, uint64_t* n_solid) {
     if (!files || n_files <= 0 || !solid_out || !n_solid) return rtk_fail(RTK_ERR_ARG, "rtk_index_count_kmers: null argument");
@@ -243,4 +246,22 @@ extern "C" int rtk_index_snp_plan(int device, int k, const uint64_t* seq_off, ui
     *passes = 0; *need_one_pass = 0; *need_min = 0;
     const uint64_t none[1] = {0};
     return entry("rtk_index_snp_plan", device, [&]() { return by_key_type(k, [&](auto km) { return snp_plan<decltype(km)>(k, n_unitigs ? seq_off : none, n_unitigs, searched, room, passes, need_one_pass, need_min); }); });
+}
+
+extern "C" int rtk_index_pair_ids(int device, const uint64_t* name_hash, uint64_t n, uint32_t* ids, uint64_t* n_ids) {
+    if (!n_ids || (n && (!name_hash || !ids))) return rtk_fail(RTK_ERR_ARG, "rtk_index_pair_ids: null argument");
+    if (n >= (1ull << 32)) return rtk_fail(RTK_ERR_UNSUPPORTED, "rtk_index_pair_ids: 2^32 records or more (an id has 32 bits)");
+    if (const int rc = check_device("rtk_index_pair_ids", device)) return rc;
+    *n_ids = 0;
+    if (n == 0) return RTK_OK;
+    return entry("rtk_index_pair_ids", device, [&]() { return pair_ids_device(name_hash, n, ids, n_ids); });
+}
+
+extern "C" int rtk_index_pair_plan(int device, uint64_t n, uint64_t room, uint32_t* passes, uint64_t* need_one_pass, uint64_t* need_min) {
+    if (!passes || !need_one_pass || !need_min) return rtk_fail(RTK_ERR_ARG, "rtk_index_pair_plan: null argument");
+    if (n >= (1ull << 32)) return rtk_fail(RTK_ERR_UNSUPPORTED, "rtk_index_pair_plan: 2^32 records or more (an id has 32 bits)");
+    if (const int rc = check_device("rtk_index_pair_plan", device)) return rc;
+    *passes = 1; *need_one_pass = 0; *need_min = 0;
+    if (n == 0) return RTK_OK; // (nothing is allocated for no records)
+    return entry("rtk_index_pair_plan", device, [&]() { return pair_plan_entry(n, room, passes, need_one_pass, need_min); });
 }

@@ -79,6 +79,8 @@ inline uint64_t rtk_knob_index_events(uint64_t dflt) { return rtk_env_u64("RTK_I
 inline uint64_t rtk_knob_index_cover_cap(uint64_t dflt) { return rtk_env_u64("RTK_INDEX_COVER_CAP", dflt); } // u64 >= 1: crossings the buffer of rtk_index_cover_* has room for at first (tests: 1, every chunk with a crossing is mapped a second time)
 inline uint64_t rtk_knob_index_snp_mem(uint64_t dflt) { return std::min(dflt, rtk_env_u64("RTK_INDEX_SNP_MEM", dflt)); } // u64 bytes: rtk_index_snp_candidates compares its need with this instead of the free device memory when it is lower (tests: the refusal)
 inline uint32_t rtk_knob_index_snp_passes() { return static_cast<uint32_t>(std::min<uint64_t>(rtk_env_u64("RTK_INDEX_SNP_PASSES", 0), 0xFFFFFFFFull)); } // u32, 0 = as few as fit: rtk_index_snp_candidates searches in exactly this many passes over partitions of the key space (clamped to min(256, prefix values); tests: the partitioned path on small inputs)
+inline uint64_t rtk_knob_index_pair_mem(uint64_t dflt) { return std::min(dflt, rtk_env_u64("RTK_INDEX_PAIR_MEM", dflt)); } // u64 bytes: rtk_index_pair_ids compares its need with this instead of the free device memory when it is lower (tests: the refusal)
+inline uint32_t rtk_knob_index_pair_passes() { return static_cast<uint32_t>(std::min<uint64_t>(rtk_env_u64("RTK_INDEX_PAIR_PASSES", 0), 0xFFFFFFFFull)); } // u32, 0 = as few as fit: rtk_index_pair_ids pairs in exactly this many passes over equal ranges of the hash space (clamped to 256; tests: the partitioned path on small inputs)
 inline uint64_t rtk_knob_hx_part_keys(uint64_t dflt) { return rtk_env_u64("RTK_HX_PART_KEYS", dflt); }   // u64: keys per partition when the signature table is built
 
 // ---- simulator only
@@ -89,7 +91,7 @@ inline int rtk_knob_sim_devices() { return std::max(1, rtk_env_int("RTK_SIM_DEVI
 //   csrc/host (graph file -> flat tables, the Ratatosk driver): RTK_BF1_LOG2BITS, RTK_BF1_OFF, RTK_BF_KEYS_PER_WORD, RTK_HT_DENSE_KMERS, RTK_HX_MAX_GB, RTK_INEXACT_ENUM,
 //     RTK_LOAD_TRACE, RTK_CLI_STATS, RTK_CLI_TRACE, RTK_SERIAL_READER
 //   csrc/tools (rtk_build_index): RTK_FASTA_MEMBER_BYTES, RTK_INDEX_HOST_COLOURS, RTK_INDEX_HOST_UNITIGS, RTK_INDEX_SNPS (device | host: where --gpu --snps finds its candidates),
-//     RTK_INDEX_THREADS, RTK_INDEX_TRACE, RTK_INDEX_CHUNK (--gpu --cover-edges-from: characters of cover text per chunk)
+//     RTK_INDEX_THREADS, RTK_INDEX_TRACE, RTK_INDEX_CHUNK (--gpu --cover-edges-from: characters of cover text per chunk; --pair-by-name --fast: bytes per range of a plain file)
 //   csrc/tools (rtk_rescue_reads): RTK_INDEX_CHUNK (characters of -u text per batch), RTK_INDEX_THREADS, RTK_INDEX_TRACE
 //   csrc/tools (rtk_qv): RTK_INDEX_CHUNK (characters of -l text per chunk; a longer read is cut into pieces), RTK_INDEX_THREADS, RTK_INDEX_TRACE (--gpu: also the time of k_qv alone)
 //   ratatosk_amd/api.py: RTK_LIB_OVERRIDE (another build of the library), RTK_HOST_TABLES

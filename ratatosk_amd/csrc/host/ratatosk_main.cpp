@@ -59,6 +59,7 @@ struct Opt {
     size_t insert_sz = 500, w1 = 1000, w2 = 5000, batch_bases = 0; // 0: not given (64 Mi for the first pass, 32 Mi for the second)
     bool merge_duplicates = false; // --merge-duplicates: handed to both index steps of `correct -s` (the second colours by long reads and leaves them alone)
     bool k1_from_k2 = false; // --k1-from-k2: `correct -s` builds the k2 graph once (rtk_build_index --graph-only) and both indexes from its unitig file (--graph-from)
+    bool pair_by_name = false; // --pair-by-name: handed to the index step whose colours come from the short reads (step 1); rtk_build_index --pair-by-name
     bool qv = false; // --qv: `correct -s` ends with rtk_qv --gpu on the -l reads and on its own output (OUT.qv.tsv; DESIGN.md section 4 [A17])
     bool cover_edges = false; // --cover-edges (only with --k1-from-k2): the k1 index step of `correct -s` covers its low-coverage edges from the k2 unitig file (rtk_build_index --cover-edges-from)
     bool subsample = false; std::string subsample_seed; // --subsample-colours [--subsample-seed N]: handed to both index steps of `correct -s`
@@ -77,6 +78,9 @@ static void usage() {
                     "      --subsample-seed N  seed of the hash that stands in for the reference's random draws (default 1; only with --subsample-colours)\n"
                     "      --merge-duplicates  short-read pairs that lie on the same unitigs share one colour id, as the reference's index step merges duplicated reads;\n"
                     "                        handed to both index steps (the second colours by long reads, one id each, and says so)\n"
+                    "      --pair-by-name    the colour id of a short read is the rank of its name by first appearance over all -s files, as the reference numbers its pairs: mates in\n"
+                    "                        separate files (-s R1.fastq -s R2.fastq) share one id. Handed to the k1 index step (rtk_build_index --pair-by-name), whose colours come from the\n"
+                    "                        short reads; the second-pass index colours by long reads and does not get it. With -2 alone: accepted, changes nothing\n"
                     "      --k1-from-k2      the short reads are counted once, at k2: the k1 graph is built from the unitigs of the k2 graph (every k1-mer of their text), as the reference's\n"
                     "                        one-command run does, and the second-pass index takes the same k2 graph instead of counting again (rtk_build_index --graph-only, then --graph-from twice).\n"
                     "                        Without it the k1 graph is built from the short reads; the two k1 graphs differ in the k1-mers that recur only in erroneous k2-mers. With -2 alone: accepted, the chain of before\n"
@@ -195,6 +199,7 @@ static int correct_from_short_reads(const Opt& opt, const char* argv0) {
         }
         if (!opt.no_snps) a.push_back("--snps");
         if (opt.merge_duplicates) a.push_back("--merge-duplicates");
+        if (opt.pair_by_name && colour.empty()) a.push_back("--pair-by-name"); // (only where the short reads colour: step 1)
         if (opt.subsample) { a.push_back("--subsample-colours"); if (!opt.subsample_seed.empty()) { a.push_back("--subsample-seed"); a.push_back(opt.subsample_seed); } }
         a.push_back("-o"); a.push_back(prefix); return a;
     };
@@ -292,7 +297,7 @@ int main(int argc, char** argv) {
         {"correction-rounds", required_argument, 0, 'r'}, {"no-snp-correction", no_argument, 0, 'F'}, {"force-io-order", no_argument, 0, 'O'}, {"no-graph-index", no_argument, 0, 'I'},
         {"in-unmapped-short", required_argument, 0, 'u'}, {"in-accurate-long", required_argument, 0, 'a'}, {"in-short-phase", required_argument, 0, 'p'}, {"in-long-phase", required_argument, 0, 'P'}, {"force-correct-snp", no_argument, 0, 'f'},
         {"sampling", required_argument, 0, 'S'}, {"min-conf-color2", required_argument, 0, 'M'}, {"min-len-color2", required_argument, 0, 'C'},
-        {"batch-bases", required_argument, 0, 'B'}, {"strip-annotations", no_argument, 0, 1001}, {"gpus", required_argument, 0, 1002}, {"workers-per-gpu", required_argument, 0, 1003}, {"parse-only", no_argument, 0, 1004}, {"allow-tinybitmap", no_argument, 0, 1005}, {"subsample-colours", no_argument, 0, 1006}, {"subsample-seed", required_argument, 0, 1007}, {"merge-duplicates", no_argument, 0, 1008}, {"k1-from-k2", no_argument, 0, 1009}, {"cover-edges", no_argument, 0, 1010}, {"qv", no_argument, 0, 1011}, {"verbose", no_argument, 0, 'v'}, {0, 0, 0, 0}};
+        {"batch-bases", required_argument, 0, 'B'}, {"strip-annotations", no_argument, 0, 1001}, {"gpus", required_argument, 0, 1002}, {"workers-per-gpu", required_argument, 0, 1003}, {"parse-only", no_argument, 0, 1004}, {"allow-tinybitmap", no_argument, 0, 1005}, {"subsample-colours", no_argument, 0, 1006}, {"subsample-seed", required_argument, 0, 1007}, {"merge-duplicates", no_argument, 0, 1008}, {"k1-from-k2", no_argument, 0, 1009}, {"cover-edges", no_argument, 0, 1010}, {"qv", no_argument, 0, 1011}, {"pair-by-name", no_argument, 0, 1012}, {"verbose", no_argument, 0, 'v'}, {0, 0, 0, 0}};
     int c, idx = 0;
     while ((c = getopt_long(argc - 1, argv + 1, "s:l:o:c:g:d:i:k:w:Q:m:B:L:K:W:t:r:u:a:p:P:S:M:C:GFOIf12v", lo, &idx)) != -1) {
         { // what `correct -s` hands on to its correction steps: the option as given (long options by their long name)
@@ -345,6 +350,7 @@ int main(int argc, char** argv) {
             case 1009: opt.k1_from_k2 = true; break; // (with -g / -d: refused below)
             case 1010: opt.cover_edges = true; break; // (with -g / -d, or without --k1-from-k2: refused below)
             case 1011: opt.qv = true; break; // (with -g / -d: refused below)
+            case 1012: opt.pair_by_name = true; break; // (with -g / -d: refused below)
             case 's': opt.in_short.push_back(optarg); break; // (with -g / -d: ignored, said below)
             default: usage(); return 0; // the reference returns 0 on option errors too (src/Ratatosk.cpp:1018)
         }
@@ -373,6 +379,10 @@ int main(int argc, char** argv) {
     }
     if (opt.cover_edges) { // likewise: the colours of a pre-built index are what they are
         fprintf(stderr, "Ratatosk::correct: --cover-edges belongs to the index build (correct -s SHORT --k1-from-k2 --cover-edges -l LONG -o OUT, or rtk_build_index --cover-edges-from): not accepted next to a pre-built index (-g, -d)\n");
+        return 1;
+    }
+    if (opt.pair_by_name) { // likewise
+        fprintf(stderr, "Ratatosk::correct: --pair-by-name belongs to the index build (correct -s R1 -s R2 --pair-by-name -l LONG -o OUT, or rtk_build_index --pair-by-name): not accepted next to a pre-built index (-g, -d)\n");
         return 1;
     }
     if (opt.k1_from_k2) { // likewise: the graphs of a pre-built index are what they are

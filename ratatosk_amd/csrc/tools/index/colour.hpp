@@ -8,6 +8,7 @@
 #include <memory>
 #include <mutex>
 
+#include "../../common/name_hash.hpp"
 #include "colour_filter.hpp"
 #include "state.hpp"
 
@@ -147,9 +148,100 @@ template <class KM> struct ColourSink {
 // a colouring record without a quality string of its own length under --colour-min-conf: the one message of all routes
 inline void colour_no_quality(const std::string& file) { fprintf(stderr, "rtk_build_index: --colour-min-conf: %s holds a record without a quality string of its own length (FASTQ input is needed)\n", file.c_str()); }
 
+// ---- --pair-by-name (DESIGN.md section 4 [A18]): the id of a record is the rank of its NAME by first appearance over the whole colouring input -- the -s files in
+// the order given, records in file order --, as the reference's name_hmap hands ids out (src/Graph.cpp:1595-1608, 1800-1804): mates in separate files share one id.
+// Every record counts, so an interleaved file gets the ids of the name-change rule. A name sweep ahead of the colouring notes the hash of every record's name
+// (common/name_hash.hpp) under the record's ordinal; pair_ids() turns the hashes into ids (--gpu: rtk_index_pair_ids, csrc/hip/rtk_index_pairs.h; else pair_ids_host);
+// the mapping sweep of the source then feeds record r with ids[r]. Sink, events and every later step see ids as before.
+struct PairNames {
+    std::vector<uint64_t> hash; // [ordinal]
+    std::vector<uint32_t> ids;  // [ordinal]
+    uint64_t n_ids = 0;
+    size_t chunk_bytes = 32u << 20; // source 3: bytes per range (RTK_INDEX_CHUNK: tests, many ranges)
+    std::vector<std::vector<uint64_t> > range_first; // source 3, per file: the ordinal of the first record of every range, and past the last
+    PairNames() { const char* e = getenv("RTK_INDEX_CHUNK"); if (e && strtoull(e, nullptr, 10) >= 1024) chunk_bytes = static_cast<size_t>(strtoull(e, nullptr, 10)); }
+};
+
+// ids[r] = the number of distinct hashes whose first record precedes the first record of hash[r]. The records go into 256 buckets by the top byte of the hash, in
+// ordinal order; a bucket is sorted by (hash, ordinal) on a thread, the first of a run is its leader; the ids are the ranks of the leaders.
+inline void pair_ids_host(const std::vector<uint64_t>& hash, unsigned n_thr, std::vector<uint32_t>& ids, uint64_t* n_ids) {
+    const size_t n = hash.size();
+    std::vector<size_t> start(257, 0);
+    for (size_t i = 0; i < n; ++i) ++start[(hash[i] >> 56) + 1];
+    for (size_t b = 0; b < 256; ++b) start[b + 1] += start[b];
+    std::vector<std::pair<uint64_t, uint32_t> > rec(n); std::vector<uint32_t> leader(n);
+    { std::vector<size_t> at(start.begin(), start.end() - 1); for (size_t i = 0; i < n; ++i) rec[at[hash[i] >> 56]++] = std::make_pair(hash[i], static_cast<uint32_t>(i)); }
+    parallel_for(256, n_thr, [&](size_t b, size_t e, unsigned) {
+        for (size_t bk = b; bk < e; ++bk) {
+            std::sort(rec.begin() + start[bk], rec.begin() + start[bk + 1]);
+            uint32_t head = 0;
+            for (size_t i = start[bk]; i < start[bk + 1]; ++i) { if (i == start[bk] || rec[i].first != rec[i - 1].first) head = rec[i].second; leader[rec[i].second] = head; }
+        }
+    });
+    uint32_t next = 0; ids.assign(n, 0);
+    for (size_t j = 0; j < n; ++j) ids[j] = leader[j] == j ? next++ : ids[leader[j]]; // (leader[j] <= j)
+    *n_ids = next;
+}
+
+template <class KM> static bool pair_ids(IndexBuild<KM>& s, PairNames& pn, const char** where) {
+    const size_t n = pn.hash.size(); *where = "host threads";
+    if (n >= (1ull << 32)) { fprintf(stderr, "rtk_build_index: --pair-by-name: 2^32 records or more (an id has 32 bits)\n"); return false; }
+    if (s.o.gpu && n) { // a library without the entry, or a device without the room: said, and paired here
+        HipLib::pair_ids_fn fn = nullptr; pn.ids.assign(n, 0);
+        if (!s.lib.handle || !s.lib.get(fn, "rtk_index_pair_ids")) fprintf(stderr, "rtk_build_index: --gpu: %s lacks rtk_index_pair_ids: read names paired on the host threads\n", s.lib.path.c_str());
+        else if (fn(0, pn.hash.data(), n, pn.ids.data(), &pn.n_ids) == 0) { *where = "device"; return true; }
+        else fprintf(stderr, "rtk_build_index: --gpu: read names paired on the host threads (%s)\n", s.lib.last_error());
+    }
+    pair_ids_host(pn.hash, s.n_thr, pn.ids, &pn.n_ids);
+    return true;
+}
+
+// the name sweep of source 1: the input read once more, for the names only
+template <class KM> static bool pair_names_from_reader(IndexBuild<KM>& s, const std::vector<std::string>& col_in, PairNames& pn) {
+    std::string name, seq, qual;
+    for (size_t f = 0; f < col_in.size(); ++f) {
+        FastxReader fr; if (!fr.open(col_in[f], s.o.fast ? static_cast<int>(s.n_thr < 8 ? s.n_thr : 8) : 0)) { fprintf(stderr, "rtk_build_index: cannot open %s\n", col_in[f].c_str()); return false; }
+        while (fr.next(name, seq, qual)) pn.hash.push_back(name_hash(name.data(), pair_name_len(name.data(), name.size())));
+        if (fr.failed()) { fprintf(stderr, "rtk_build_index: %s ends in a damaged or cut-short gzip stream\n", col_in[f].c_str()); return false; }
+    }
+    return true;
+}
+// the name sweep of source 3 (it takes the place of the counting sweep): every range parsed by a thread keeps the hashes of its records; the running sums of the
+// ranges' record counts stitch them together and give every range the ordinal of its first record
+template <class KM> static bool pair_names_from_plain_ranges(IndexBuild<KM>& s, const std::vector<std::string>& col_in, PairNames& pn) {
+    pn.range_first.assign(col_in.size(), std::vector<uint64_t>());
+    for (size_t f = 0; f < col_in.size(); ++f) {
+        PlainChunks pc; if (!pc.open(col_in[f], pn.chunk_bytes)) { fprintf(stderr, "rtk_build_index: cannot open %s\n", col_in[f].c_str()); return false; }
+        const size_t nc = pc.n_chunks();
+        std::vector<std::vector<uint64_t> > h(nc); std::atomic<int> bad(0); std::atomic<size_t> nx(0); std::vector<std::thread> th;
+        for (unsigned t = 0; t < s.n_thr; ++t) th.emplace_back([&]() {
+            for (;;) { const size_t i = nx.fetch_add(1); if (i >= nc) break;
+                PackedReads r(false); if (!pc.parse_chunk(i, r)) { bad = 1; break; }
+                h[i].resize(r.size());
+                for (size_t x = 0; x < r.size(); ++x) h[i][x] = name_hash(r.name(x), pair_name_len(r.name(x), r.name_len(x)));
+            } });
+        for (size_t t = 0; t < th.size(); ++t) th[t].join();
+        if (bad) return false;
+        std::vector<uint64_t>& first = pn.range_first[f]; first.assign(nc + 1, pn.hash.size());
+        for (size_t i = 0; i < nc; ++i) { first[i] = pn.hash.size(); pn.hash.insert(pn.hash.end(), h[i].begin(), h[i].end()); std::vector<uint64_t>().swap(h[i]); }
+        first[nc] = pn.hash.size();
+    }
+    return true;
+}
+// the line a user of split files must see: how the names paired up; and the warning when they did not
+inline void pair_summary(const PairNames& pn, bool several_files) {
+    std::vector<uint32_t> per(pn.n_ids, 0); uint64_t one = 0, two = 0, more = 0;
+    for (size_t r = 0; r < pn.ids.size(); ++r) ++per[pn.ids[r]];
+    for (size_t i = 0; i < per.size(); ++i) { if (per[i] == 1) ++one; else if (per[i] == 2) ++two; else ++more; }
+    fprintf(stderr, "rtk_build_index: --pair-by-name: %llu records, %llu names: %llu with one record, %llu with two, %llu with more\n", static_cast<unsigned long long>(pn.ids.size()),
+            static_cast<unsigned long long>(pn.n_ids), static_cast<unsigned long long>(one), static_cast<unsigned long long>(two), static_cast<unsigned long long>(more));
+    if (several_files && !pn.ids.empty() && two == 0 && more == 0)
+        fprintf(stderr, "rtk_build_index: --pair-by-name: warning: no name has two records: the mates do not seem to share their names (a name is the header up to the first blank, without a trailing /1 or /2), every read is coloured on its own\n");
+}
+
 // Source 1, any input: one reader parses the records and numbers them (a pair keeps one id: the id is the number of name changes before the read;
-// every read its own id with --colour-reads), worker threads take pieces of about 1 MB from a bounded queue.
-template <class KM> static bool colour_from_reader(IndexBuild<KM>& s, ColourSink<KM>& sink, const std::vector<std::string>& col_in, bool by_read) {
+// every read its own id with --colour-reads; pn != nullptr, --pair-by-name: record r gets pn->ids[r]), worker threads take pieces of about 1 MB from a bounded queue.
+template <class KM> static bool colour_from_reader(IndexBuild<KM>& s, ColourSink<KM>& sink, const std::vector<std::string>& col_in, bool by_read, const PairNames* pn) {
     struct Chunk { std::vector<std::string> seq, qual; std::vector<uint32_t> id; size_t bytes = 0; }; // (qual: filled with a confidence threshold only)
     const bool with_qual = sink.q_min != 0;
     std::mutex mq; std::condition_variable cv_put, cv_get; std::deque<std::unique_ptr<Chunk> > q; bool done = false, ok = true;
@@ -163,7 +255,7 @@ template <class KM> static bool colour_from_reader(IndexBuild<KM>& s, ColourSink
         }
     });
     std::string name, seq, qual, prev_name;
-    uint32_t pair_id = 0; bool first = true;
+    uint32_t pair_id = 0; bool first = true; size_t ordinal = 0;
     std::unique_ptr<Chunk> cur(new Chunk());
     auto flush = [&]() { if (cur->seq.empty()) return; { std::unique_lock<std::mutex> lk(mq); cv_put.wait(lk, [&]() { return q.size() < 4u * s.n_thr; }); q.push_back(std::move(cur)); } cv_get.notify_one(); cur.reset(new Chunk()); };
     for (size_t f = 0; f < col_in.size() && ok; ++f) {
@@ -171,7 +263,8 @@ template <class KM> static bool colour_from_reader(IndexBuild<KM>& s, ColourSink
         while (fr.next(name, seq, qual)) {
             for (size_t x = 0; x < seq.size(); ++x) seq[x] = static_cast<char>(seq[x] & 0xDF);
             name.erase(pair_name_len(name.data(), name.size()));
-            if (first) { first = false; prev_name = name; }
+            if (pn) { if (ordinal >= pn->ids.size()) { fprintf(stderr, "rtk_build_index: --pair-by-name: %s holds more records than the name sweep saw\n", col_in[f].c_str()); ok = false; break; } pair_id = pn->ids[ordinal++]; }
+            else if (first) { first = false; prev_name = name; }
             else if (by_read || name != prev_name) { ++pair_id; prev_name = name; }
             if (with_qual) { if (qual.size() != seq.size()) { colour_no_quality(col_in[f]); ok = false; break; } cur->qual.push_back(std::string()); cur->qual.back().swap(qual); }
             cur->bytes += seq.size(); cur->seq.push_back(std::string()); cur->seq.back().swap(seq); cur->id.push_back(pair_id);
@@ -211,13 +304,15 @@ template <class KM> static bool colour_from_samples(IndexBuild<KM>& s, ColourSin
 
 // Source 3, --fast on plain files: byte ranges of the files parsed and looked up by all threads. The id of a read is the number of name changes
 // before it (every read with --colour-reads), so a first sweep over the ranges counts the changes inside each and notes its first and last
-// name; the running sums give every range the id of its first read; the second sweep maps the reads.
-template <class KM> static bool colour_from_plain_ranges(IndexBuild<KM>& s, ColourSink<KM>& sink, const std::vector<std::string>& col_in, bool by_read) {
+// name; the running sums give every range the id of its first read; the second sweep maps the reads. pn != nullptr (--pair-by-name): the name sweep
+// (pair_names_from_plain_ranges, over the same ranges) has taken the place of the first sweep, and record x of range i gets pn->ids[range_first[i] + x].
+template <class KM> static bool colour_from_plain_ranges(IndexBuild<KM>& s, ColourSink<KM>& sink, const std::vector<std::string>& col_in, bool by_read, const PairNames* pn) {
     struct RangeInfo { uint32_t changes = 0; uint64_t n_reads = 0; std::string first, last; };
     uint32_t next_id = 0; bool have_prev = false; std::string prev_last;
     for (size_t f = 0; f < col_in.size(); ++f) {
-        PlainChunks pc; if (!pc.open(col_in[f], 32u << 20)) { fprintf(stderr, "rtk_build_index: cannot open %s\n", col_in[f].c_str()); return false; }
+        PlainChunks pc; if (!pc.open(col_in[f], pn ? pn->chunk_bytes : 32u << 20)) { fprintf(stderr, "rtk_build_index: cannot open %s\n", col_in[f].c_str()); return false; }
         const size_t nc = pc.n_chunks();
+        if (pn && pn->range_first[f].size() != nc + 1) { fprintf(stderr, "rtk_build_index: --pair-by-name: %s is not the file the name sweep saw\n", col_in[f].c_str()); return false; }
         std::vector<RangeInfo> info(nc); std::vector<uint32_t> id0(nc, 0); // id0: id of the first read of every range
         std::atomic<int> bad(0), no_quality(0); const bool with_qual = sink.q_min != 0;
         // sweep(map the reads, or only count): every range parsed by a thread; the names walked, the changes counted from id0 of the range
@@ -226,23 +321,25 @@ template <class KM> static bool colour_from_plain_ranges(IndexBuild<KM>& s, Colo
             for (unsigned t = 0; t < s.n_thr; ++t) th.emplace_back([&, t]() {
                 for (;;) { const size_t i = nx.fetch_add(1); if (i >= nc) break;
                     PackedReads r(with_qual); if (!pc.parse_chunk(i, r)) { bad = 1; break; }
-                    RangeInfo& ri = info[i]; uint32_t id = id0[i]; const char* pp = nullptr; size_t pn = 0;
+                    RangeInfo& ri = info[i]; uint32_t id = id0[i]; const char* pp = nullptr; size_t pl = 0;
+                    if (pn && pn->range_first[f][i + 1] - pn->range_first[f][i] != r.size()) { bad = 1; break; } // (the file changed under the two sweeps)
                     for (size_t x = 0; x < r.size(); ++x) {
                         const char* p = r.name(x); const size_t n = pair_name_len(p, r.name_len(x));
-                        if (x != 0 && (by_read || n != pn || memcmp(p, pp, n) != 0)) ++id;
-                        pp = p; pn = n;
+                        if (pn) id = pn->ids[pn->range_first[f][i] + x];
+                        else if (x != 0 && (by_read || n != pl || memcmp(p, pp, n) != 0)) ++id;
+                        pp = p; pl = n;
                         if (with_qual && !r.qual(x)) { no_quality = 1; bad = 1; break; }
                         if (map) sink.read(t, r.seq(x), with_qual ? r.qual(x) : nullptr, r.seq_len(x), id);
                         else if (x == 0) ri.first.assign(p, n);
                     }
-                    if (!map) { ri.n_reads = r.size(); ri.changes = id - id0[i]; if (r.size()) ri.last.assign(pp, pn); }
+                    if (!map) { ri.n_reads = r.size(); ri.changes = id - id0[i]; if (r.size()) ri.last.assign(pp, pl); }
                 } });
             for (size_t t = 0; t < th.size(); ++t) th[t].join();
         };
-        sweep(false);
+        if (!pn) sweep(false);
         if (no_quality) colour_no_quality(col_in[f]);
         if (bad) return false;
-        for (size_t i = 0; i < nc; ++i) {
+        for (size_t i = 0; i < nc && !pn; ++i) {
             if (info[i].n_reads == 0) { id0[i] = next_id; continue; }
             if (have_prev && (by_read || info[i].first != prev_last)) ++next_id;
             id0[i] = next_id; next_id += info[i].changes; have_prev = true; prev_last = info[i].last;
@@ -258,10 +355,24 @@ template <class KM> static bool colour_and_cover(IndexBuild<KM>& s) {
     // (addCoverage(dbg, opt_pass2, ..., long_read_correct = true), src/Ratatosk.cpp:1218)
     const bool by_read = !s.o.colour_files.empty();
     const std::vector<std::string>& col_in = by_read ? s.o.colour_files : s.o.in_files;
-    std::shared_ptr<ColourSink<KM> > sink_p = std::make_shared<ColourSink<KM> >(s); ColourSink<KM>& sink = *sink_p;
     bool all_sampled = s.o.fast && !by_read && !col_in.empty(), all_plain = s.o.fast;
     for (size_t f = 0; f < col_in.size(); ++f) { all_sampled = all_sampled && SampleSource::is_spec(col_in[f]); all_plain = all_plain && PlainChunks::is_plain(col_in[f]); }
-    const bool ok = all_sampled ? colour_from_samples(s, sink, col_in) : (all_plain ? colour_from_plain_ranges(s, sink, col_in, by_read) : colour_from_reader(s, sink, col_in, by_read));
+    // --pair-by-name (never next to --colour-reads or a sample: source): the name sweep and the ids ahead of the mapping sweep, and ahead of the sink, so that the
+    // lap holds the option's own work and not the set-up of the colour job
+    std::unique_ptr<PairNames> pn;
+    if (s.o.pair_by_name) {
+        pn.reset(new PairNames());
+        const auto t0 = std::chrono::steady_clock::now(); auto since = [&]() { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); };
+        if (!(all_plain ? pair_names_from_plain_ranges(s, col_in, *pn) : pair_names_from_reader(s, col_in, *pn))) return false;
+        const double t_sweep = since(); const char* where = "";
+        if (!pair_ids(s, *pn, &where)) return false;
+        if (s.knobs.trace) fprintf(stderr, "rtk_build_index: read names: sweep %.3f s (%s), ids %.3f s (%s)\n", t_sweep, all_plain ? "byte ranges on all threads" : "one reader", since() - t_sweep, where);
+        if (s.knobs.trace || col_in.size() >= 2) pair_summary(*pn, col_in.size() >= 2);
+        std::vector<uint64_t>().swap(pn->hash);
+        s.lap("read names paired");
+    }
+    std::shared_ptr<ColourSink<KM> > sink_p = std::make_shared<ColourSink<KM> >(s); ColourSink<KM>& sink = *sink_p;
+    const bool ok = all_sampled ? colour_from_samples(s, sink, col_in) : (all_plain ? colour_from_plain_ranges(s, sink, col_in, by_read, pn.get()) : colour_from_reader(s, sink, col_in, by_read, pn.get()));
     if (s.knobs.trace && (sink.q_min || sink.min_len)) { // (the same line on every route)
         fprintf(stderr, "rtk_build_index: colour filter:");
         if (sink.q_min) fprintf(stderr, " bases of the colouring reads with a quality byte below %u masked%s", static_cast<unsigned>(sink.q_min), sink.min_len ? ";" : "");

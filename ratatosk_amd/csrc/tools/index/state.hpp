@@ -38,6 +38,7 @@ struct IndexOptions {
     std::vector<std::string> graph_files;
     // --cover-edges-from FILE: the edges that fewer than min_cov_vertices colours share get two fresh ids on both ends wherever a sequence of these FASTA files (the unitigs of the k2 graph) walks over them (tools/index/cover.hpp)
     std::vector<std::string> cover_files;
+    bool pair_by_name = false; // --pair-by-name: the id of a short read is the rank of its name by first appearance over all -s files, so that mates in separate files share it (tools/index/colour.hpp; DESIGN.md section 4 [A18])
     bool graph_only = false; // --graph-only: count, table, unitigs, the unitig FASTA written, nothing else
     // what the graph is counted from, and how often a k-mer must be seen there
     const std::vector<std::string>& graph_inputs() const { return graph_files.empty() ? in_files : graph_files; }
@@ -66,6 +67,7 @@ inline int parse_options(int argc, char** argv, IndexOptions& o) {
         else if (a == "--colour-reads") o.colour_files.push_back(need("--colour-reads"));
         else if (a == "--subsample-colours") o.subsample = true;
         else if (a == "--merge-duplicates") o.merge = true;
+        else if (a == "--pair-by-name") o.pair_by_name = true;
         else if (a == "--subsample-seed") { const char* v = need("--subsample-seed"); char* end = nullptr; o.subsample_seed = strtoull(v, &end, 10); seed_given = true;
             if (*v < '0' || *v > '9' || *end) { fprintf(stderr, "rtk_build_index: --subsample-seed takes an unsigned number, not '%s'\n", v); return 2; } }
         else if (a == "--colour-min-conf") { const char* v = need("--colour-min-conf"); char* end = nullptr; o.colour_min_conf = strtod(v, &end); filter_given = "--colour-min-conf";
@@ -78,9 +80,12 @@ inline int parse_options(int argc, char** argv, IndexOptions& o) {
         else { fprintf(stderr, "rtk_build_index: unknown option %s\n", a.c_str()); return 2; }
     }
     if (o.graph_only) { // the graph and nothing else: whatever colours, annotates or takes the graph from elsewhere clashes with it
-        const char* clash = o.detect_snps ? "--snps" : !o.colour_files.empty() ? "--colour-reads" : filter_given ? filter_given : o.merge ? "--merge-duplicates" : (o.subsample || seed_given) ? "--subsample-colours" : !o.graph_files.empty() ? "--graph-from" : !o.cover_files.empty() ? "--cover-edges-from" : nullptr;
+        const char* clash = o.detect_snps ? "--snps" : !o.colour_files.empty() ? "--colour-reads" : filter_given ? filter_given : o.merge ? "--merge-duplicates" : (o.subsample || seed_given) ? "--subsample-colours" : o.pair_by_name ? "--pair-by-name" : !o.graph_files.empty() ? "--graph-from" : !o.cover_files.empty() ? "--cover-edges-from" : nullptr;
         if (clash) { fprintf(stderr, "rtk_build_index: --graph-only writes the unitig FASTA and stops: %s does not go with it\n", clash); return 2; }
     }
+    if (o.pair_by_name && !o.colour_files.empty()) { fprintf(stderr, "rtk_build_index: --pair-by-name next to --colour-reads: the long reads colour, one id each, and there is nothing to pair\n"); return 2; }
+    for (size_t f = 0; o.pair_by_name && f < o.in_files.size(); ++f) if (SampleSource::is_spec(o.in_files[f])) {
+        fprintf(stderr, "rtk_build_index: --pair-by-name with the source %s: the pairs of a sample: source are numbered by construction, and its names repeat from source to source\n", o.in_files[f].c_str()); return 2; }
     if (!o.cover_files.empty() && !o.colour_files.empty()) { fprintf(stderr, "rtk_build_index: --cover-edges-from next to --colour-reads: the low-coverage edges are covered in a first-pass index only (the reference skips the step when the long reads colour)\n"); return 2; }
     for (size_t f = 0; f < o.cover_files.size(); ++f) { FILE* fp = fopen(o.cover_files[f].c_str(), "rb"); if (!fp) { fprintf(stderr, "rtk_build_index: --cover-edges-from: cannot open %s\n", o.cover_files[f].c_str()); return 2; } fclose(fp); }
     if (!o.graph_files.empty() && min_count_given) { fprintf(stderr, "rtk_build_index: --min-count next to --graph-from: every k-mer of a graph file is a vertex (the reads of -s only colour), so there is nothing it could count\n"); return 2; }
@@ -88,7 +93,7 @@ inline int parse_options(int argc, char** argv, IndexOptions& o) {
     if (seed_given && !o.subsample) { fprintf(stderr, "rtk_build_index: --subsample-seed without --subsample-colours\n"); return 2; }
     if (filter_given && o.colour_files.empty()) { fprintf(stderr, "rtk_build_index: %s without --colour-reads\n", filter_given); return 2; }
     const bool graph_given = !o.graph_files.empty() && !o.colour_files.empty(); // (the one case without -s: the graph from a file, the colours from --colour-reads)
-    if ((o.in_files.empty() && !graph_given) || o.k < 3 || o.k > RTK_MAX_K || !(o.k & 1)) { fprintf(stderr, "usage: rtk_build_index -s reads.fq [-s ...] -o PREFIX [-k 31 (odd, <=63)] [--min-count 2] [--global-cov-factor 3.0] [--no-short-cycles] [--snps] [--fast | --gpu (k <= 63: same files, threads / the device for the heavy steps)] [--dump-input FILE] [--subsample-colours [--subsample-seed 1 (only with --subsample-colours)]: colours subsampled by coverage as the reference's index step does by default] [--merge-duplicates: read pairs that lie on the same unitigs share one colour id, as the reference's index step merges duplicated reads (no effect with --colour-reads)] [--colour-reads corrected_long_reads.fq: second-pass index, the graph comes from -s, colours and coverage from these reads [--colour-min-conf M (0 .. 1): a base of these reads whose quality is below that of confidence M colours nothing, as the reference's second-pass index does with -M (0: the '!' bases); needs FASTQ] [--colour-max-qual 40: the quality that stands for confidence 1 (-Q)] [--colour-min-len N: a read of fewer than N bases colours nothing (-C); these three only with --colour-reads]] [--graph-only: the unitig FASTA (PREFIX.index.kK.fasta.gz, the bytes of the full build) and nothing else, no .rtsk; not with --snps, --colour-reads, --merge-duplicates, --subsample-colours, --graph-from] [--graph-from unitigs.fasta.gz (may be repeated; FASTA as -s reads it): the graph is every all-A/C/G/T window of length k of these records, each once, whatever the k the file was written with (a k above the file's own: the windows of that length inside its unitigs); -s then only colours and covers, and is not needed next to --colour-reads; not with --min-count] [--cover-edges-from k2_unitigs.fasta.gz (may be repeated; FASTA, plain or gzip, of any k): every edge whose two unitigs share fewer than 2 colours gets two fresh colour ids on both unitigs wherever a sequence of the file walks over it, in the order of the file, as the reference's first-pass index covers its low-coverage edges from the k2 unitigs; the annotations see the ids, the edge bits and the coverage stay; not with --colour-reads, --graph-only]\n"); return 2; }
+    if ((o.in_files.empty() && !graph_given) || o.k < 3 || o.k > RTK_MAX_K || !(o.k & 1)) { fprintf(stderr, "usage: rtk_build_index -s reads.fq [-s ...] -o PREFIX [-k 31 (odd, <=63)] [--min-count 2] [--global-cov-factor 3.0] [--no-short-cycles] [--snps] [--fast | --gpu (k <= 63: same files, threads / the device for the heavy steps)] [--dump-input FILE] [--subsample-colours [--subsample-seed 1 (only with --subsample-colours)]: colours subsampled by coverage as the reference's index step does by default] [--merge-duplicates: read pairs that lie on the same unitigs share one colour id, as the reference's index step merges duplicated reads (no effect with --colour-reads)] [--colour-reads corrected_long_reads.fq: second-pass index, the graph comes from -s, colours and coverage from these reads [--colour-min-conf M (0 .. 1): a base of these reads whose quality is below that of confidence M colours nothing, as the reference's second-pass index does with -M (0: the '!' bases); needs FASTQ] [--colour-max-qual 40: the quality that stands for confidence 1 (-Q)] [--colour-min-len N: a read of fewer than N bases colours nothing (-C); these three only with --colour-reads]] [--graph-only: the unitig FASTA (PREFIX.index.kK.fasta.gz, the bytes of the full build) and nothing else, no .rtsk; not with --snps, --colour-reads, --merge-duplicates, --subsample-colours, --graph-from] [--graph-from unitigs.fasta.gz (may be repeated; FASTA as -s reads it): the graph is every all-A/C/G/T window of length k of these records, each once, whatever the k the file was written with (a k above the file's own: the windows of that length inside its unitigs); -s then only colours and covers, and is not needed next to --colour-reads; not with --min-count] [--cover-edges-from k2_unitigs.fasta.gz (may be repeated; FASTA, plain or gzip, of any k): every edge whose two unitigs share fewer than 2 colours gets two fresh colour ids on both unitigs wherever a sequence of the file walks over it, in the order of the file, as the reference's first-pass index covers its low-coverage edges from the k2 unitigs; the annotations see the ids, the edge bits and the coverage stay; not with --colour-reads, --graph-only] [--pair-by-name: the colour id of a short read is the rank of its NAME (the header up to the first blank, without a trailing /1 or /2) by first appearance over all -s files in the order given, as the reference numbers its pairs, so that mates share one id wherever their records lie (-s R1.fastq -s R2.fastq); without it the id is the number of name changes before the read, which pairs the mates of an interleaved file only; an interleaved file gets the same ids either way; not with --colour-reads, --graph-only, sample: sources]\n"); return 2; }
     return 0;
 }
 
