@@ -31,6 +31,8 @@ inline bool rtk_knob_load_trace() { return rtk_env_set("RTK_LOAD_TRACE"); }     
 inline uint32_t rtk_knob_mask_seg() { return static_cast<uint32_t>(rtk_env_u64("RTK_MASK_SEG", 8192)); } // u32, 8192: characters of a read per k_mask work item (rounded up to 4096s by mask_seg())
 inline int rtk_knob_seed_waves() { return rtk_env_pos_int("RTK_SEED_WAVES", 4096); } // int, 4096: waves of the per-read seed kernels
 inline bool rtk_knob_inexact_enum() { return rtk_env_is1("RTK_INEXACT_ENUM"); }    // '1': the enumerating 1-edit search instead of the signature table (A/B, tests)
+inline bool rtk_knob_inexact_shared() { return !rtk_env_eq("RTK_INEXACT_SHARED", "0"); } // '0': every window of k_inexact asks the half-k-mer index itself, instead of reading the tile's table of one look-up per read position (same results; A/B, tests)
+inline bool rtk_knob_inexact_planes() { return !rtk_env_eq("RTK_INEXACT_PLANES", "0"); } // '0': every lane of k_inexact packs its window's characters from text, instead of taking them from the tile's bit planes (same results; A/B, tests)
 inline bool rtk_knob_test_tiny_scratch() { return rtk_env_set("RTK_TEST_TINY_SCRATCH"); } // flag, test hook: attempt 0 of the seed, region and lane work areas is undersized, so that the redo paths run
 // the reference's documented ambiguities (rtk_opts_default): which reading the library takes
 inline int rtk_knob_a2_exclusive() { return rtk_env_eq("RTK_A2_XOR", "union") ? 0 : (rtk_env_eq("RTK_A2_XOR", "exclusive-ids") ? 2 : 1); } // "union" | "exclusive-ids" | (default) 1

@@ -47,7 +47,7 @@ RTK_DEV void inexact_body(const LaunchCtx* L, const BatchView& bv, int grid) {
     PoolChunk chunk; chunk.base = 0; chunk.left = 0;
     for (uint64_t t = static_cast<uint64_t>(RTK_BLOCK_ID); t < n_tiles; t += static_cast<uint64_t>(grid)) {
         if (ENUMERATE) rtk_inexact_tile(g, L->bv, t, &probes, &slots, &hits, &chunk, L->o.a2_exclusive);
-        else rtk_inexact_tile_seeded(g, L->bv, t, &probes, &slots, &hits, &chunk, L->o.a2_exclusive);
+        else rtk_inexact_tile_seeded(g, L->bv, t, &probes, &slots, &hits, &chunk, L->o.a2_exclusive, L->o.inexact_route);
     }
     // wave reduction of the per-lane probe tallies, then one atomic per wave
     unsigned long long tot = probes, tots = slots;
@@ -140,6 +140,7 @@ static OptsView opts_view(const rtk_opts* o) {
     v.colours_mode = rtk_knob_colours_route() | (rtk_knob_colours_audit() << 2); // RTK_CM_* (the selection is the same under every setting)
     v.park_eager = rtk_knob_park_eager() ? 1u : 0u;
     v.trim_store = rtk_knob_trim_store() ? 1u : 0u;
+    v.inexact_route = (rtk_knob_inexact_shared() ? 0u : RTK_IR_PER_WINDOW) | (rtk_knob_inexact_planes() ? 0u : RTK_IR_TEXT_PACK);
     v.long_read_correct = o->long_read_correct ? 1 : 0; v.max_len_weak_region2 = static_cast<uint32_t>(o->max_len_weak_region2 > 0xFFFFFFFFull ? 0xFFFFFFFFull : o->max_len_weak_region2);
     return v;
 }
