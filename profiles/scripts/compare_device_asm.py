@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Is the gfx950 device code of this tree the same as that of another commit?
 
-For a change that only renames and re-files device code.  Each of the five HIP translation units is
-compiled to device assembly (the Makefile's HIPFLAGS plus -I../../include --offload-device-only -S)
+For a change that only renames and re-files device code.  Each HIP translation unit of the library
+(the objects that the Makefile links into it) is compiled to device assembly (the Makefile's HIPFLAGS plus -I../../include --offload-device-only -S)
 from a `git archive` of the other commit and from the working tree, and the two texts are compared
 line for line after the one symbol that hashes the source text, __hip_cuid_<hash>, is replaced by a
 fixed word.  Needs hipcc and no GPU; about 35 s per unit and side.
@@ -10,21 +10,29 @@ fixed word.  Needs hipcc and no GPU; about 35 s per unit and side.
     python3 profiles/scripts/compare_device_asm.py [COMMIT] [--keep DIR] > profiles/region_names.txt
 
 COMMIT defaults to HEAD^.  With --keep the assembly stays in DIR, and the other commit's side is
-reused from there on the next call.  Prints the verdict per unit, then per kernel of the working
-tree's build the VGPR count, scratch bytes and LDS bytes, with the other commit's where they differ.
+reused from there on the next call.  Prints the verdict per unit and, for a unit that differs, the
+functions that hold the differing lines with how many each; then per kernel of the working tree's
+build the VGPR count, scratch bytes and LDS bytes, with the other commit's where they differ.
 Exit status 1 if any unit differs.
 """
 import argparse
 import concurrent.futures as cf
+import difflib
 import os
 import re
 import subprocess
 import sys
 import tempfile
 
-UNITS = ["rtk_device", "rtk_phase_long", "rtk_index", "rtk_graph_tables", "rtk_rescue"]
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 CSRC = "ratatosk_amd/csrc"
+
+
+def library_units():
+    """the HIP translation units of the library: the hip/*.o among the prerequisites of $(LIB) in the working tree's Makefile"""
+    with open(os.path.join(ROOT, CSRC, "Makefile")) as f:
+        rule = next(ln for ln in f if ln.startswith("$(LIB):"))
+    return re.findall(r"\bhip/(\w+)\.o\b", rule)
 
 
 def make_var(csrc, name):
@@ -63,6 +71,47 @@ def resources(lines):
                                 int(cur["group_segment_fixed_size"]))
             cur = {}
     return res
+
+
+def functions(lines):
+    """[(function, its lines)] in the order of the text.  A function begins at its `.type NAME,@function`; what stands in front of the first one is
+    "(head)", the metadata behind the last one "(tail)".  The number of the function inside its local labels (.LBB12_3, .Lfunc_end12) is taken
+    out, so that a function added or removed further up does not make every later one differ."""
+    out, name, cur = [], "(head)", []
+    for ln in lines:
+        m = re.match(r"\s*\.type\s+(\S+),@function", ln)
+        if m or (name not in ("(head)", "(tail)") and re.match(r"\s*\.(amdgpu_metadata|type\s+\S+,@object)", ln)):
+            out.append((name, cur))
+            name, cur = (m.group(1) if m else "(tail)"), []
+        cur.append(re.sub(r"\.(LBB|Lfunc_begin|Lfunc_end|LJTI|Ltmp)\d+", r".\1", ln))
+    out.append((name, cur))
+    return out
+
+
+def demangled(names):
+    """mangled -> name without its parameter list (c++filt when there is one, else the mangled name)"""
+    try:
+        r = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True, check=True).stdout.split("\n")
+    except (OSError, subprocess.CalledProcessError):
+        r = names
+    return {n: n if n.startswith("(") else re.sub(r"^(?:void |\(anonymous namespace\)::)*", "", d).split("(")[0] for n, d in zip(names, r)}  # "(head)", "(tail)" stay
+
+
+def differing_functions(mine, theirs):
+    """[(function, differing lines, lines here, lines there or None)] for the functions whose text is not the same on both sides"""
+    fm, ft = functions(mine), dict(functions(theirs))
+    out = []
+    for name, a in fm:
+        b = ft.pop(name, None)
+        if b is None:
+            out.append((name, len(a), len(a), None))
+        elif a != b:
+            if len(a) == len(b):
+                nd = sum(x != y for x, y in zip(a, b))
+            else:
+                nd = sum(1 for d in difflib.unified_diff(b, a, n=0, lineterm="") if d[:1] in "+-" and d[:3] not in ("+++", "---"))
+            out.append((name, nd, len(a), len(b)))
+    return out, [(n, len(b)) for n, b in ft.items()]
 
 
 def short_name(mangled):
@@ -105,10 +154,14 @@ def main():
             sys.exit("git archive %s failed" % sha)
         os.rename(part, other)
     jobs = {}
+    UNITS = library_units()
+    only_here = [u for u in UNITS if not os.path.exists(os.path.join(other, CSRC, "hip", u + ".hip"))]
     with cf.ThreadPoolExecutor(max_workers=min(len(os.sched_getaffinity(0)), 2 * len(UNITS))) as ex:
         for u in UNITS:
             theirs = os.path.join(work, "%s_%s.s" % (u, sha))
-            if not os.path.exists(theirs):
+            if u in only_here:
+                open(theirs, "w").close()
+            elif not os.path.exists(theirs):
                 jobs[(u, "theirs")] = ex.submit(assemble, other, u, theirs)
             jobs[(u, "ours")] = ex.submit(assemble, ROOT, u, os.path.join(work, u + "_tree.s"))
     warnings = {k: f.result() for k, f in jobs.items()}
@@ -124,6 +177,16 @@ def main():
         nd = sum(x != y for x, y in zip(mine, theirs)) + abs(len(mine) - len(theirs))
         print("  hip/%-22s %7d lines  %s" % (u + ".hip", len(mine),
                                               "identical" if same else "DIFFERS (%d lines, %d there)" % (nd, len(theirs))))
+        if u in only_here:
+            print("    (the other commit has no such unit)")
+        elif not same:
+            funcs, gone = differing_functions(mine, theirs)
+            names = demangled([f[0] for f in funcs] + [g[0] for g in gone])
+            print("    functions that differ (local labels compared without the function's number): %d" % (len(funcs) + len(gone)))
+            for name, n, here, there in funcs:
+                print("      %-44s %6d lines differ  (%d here, %s there)" % (names[name], n, here, "none" if there is None else there))
+            for name, there in gone:
+                print("      %-44s only there (%d lines)" % (names[name], there))
         # compiler warnings of this side that the other side does not show (known only when both were built in this call)
         if (u, "theirs") in warnings:
             known = set(warning_lines(warnings[(u, "theirs")]))

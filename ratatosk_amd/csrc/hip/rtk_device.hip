@@ -69,8 +69,7 @@ struct rtk_graph {
     void* pool_take(uint64_t bytes, uint64_t* got) {
         bytes = (bytes + 4095) / 4096 * 4096;
         // coarse size classes above 1 MiB (eight per octave, <= 12.5 % over): the buffers of consecutive tickets differ by a fraction of a per cent, and a parked buffer only serves a
-        // request it is at least as big as -- with exact sizes every second ticket of a steady run missed the pool and called hipMalloc, which stalls every stream of the device (round 6:
-        // tickets of distinct reads on the configs[4] graph, 64 instead of 51 ms per ticket)
+        // request it is at least as big as -- with exact sizes every second ticket of a steady run missed the pool and called hipMalloc, which stalls every stream of the device
         if (bytes >= (1ull << 20)) { uint64_t step = 1ull << 17; while ((step << 4) <= bytes) step <<= 1; bytes = (bytes + step - 1) / step * step; }
         { std::lock_guard<std::mutex> h(pool_lock);
           std::multimap<uint64_t, void*>::iterator it = pool.lower_bound(bytes);
@@ -96,7 +95,7 @@ struct rtk_graph {
     void* stage_take(uint64_t bytes, uint64_t* got) {
         bytes = (bytes + (1u << 20) - 1) >> 20 << 20;
         // coarse size classes: the staging buffers of consecutive tickets differ by a few per cent, and a parked buffer only serves a request it is at least as big as -- with exact
-        // sizes two of three requests of a steady run missed the pool and pinned new memory (hipHostMalloc of 67 MB: 22 ms of the worker, round 5 trace)
+        // sizes two of three requests of a steady run missed the pool and pinned new memory (tens of milliseconds of the worker each)
         if (bytes >= (32ull << 20)) bytes = (bytes + (16ull << 20) - 1) / (16ull << 20) * (16ull << 20); else if (bytes >= (4ull << 20)) bytes = (bytes + (4ull << 20) - 1) / (4ull << 20) * (4ull << 20);
         { std::lock_guard<std::mutex> h(pool_lock);
           std::multimap<uint64_t, void*>::iterator it = hpool.lower_bound(bytes);
@@ -111,7 +110,7 @@ struct rtk_graph {
     }
     // The region stage's graph-wide work areas (slot 1) as two halves: a small first-pass ticket that meets another ticket at the region stage runs its persistent
     // kernel on 2 048 waves in one half while the other half serves the next ticket -- a launch of a few Mb lasts as long as its heaviest region with most wave
-    // slots idle (round 6, tickets of the reference's size). A big ticket (or a lone one, or one whose half would be too small) takes both.
+    // slots idle (tickets of the reference's size). A big ticket (or a lone one, or one whose half would be too small) takes both.
     std::mutex rs_m; std::condition_variable rs_cv; bool rs_busy[2] = {false, false}; int rs_whole_waiting = 0;
     int region_slab_take(bool half_if_contended) { // 0 / 1: that half; 2: both
         std::unique_lock<std::mutex> lk(rs_m);
@@ -439,8 +438,8 @@ RTK_GLOBAL void k_lookup_exact(GraphView g, const char* seq, const uint64_t* rof
 #ifndef RTK_SIM
         // k <= 32: the 2-bit codes of the tile's 64 + 64 characters as bit planes (one character of each half per lane, three ballots per half: low bit, high
         // bit, is-a-base); a lane's k-mer is k bits of each plane from its own position on, reversed (the first character sits in the high bits of a code)
-        // and interleaved. Packing the k characters from text in every lane (rtk_km_from_text: four unaligned words, two 64-bit multiplies each) was ~45 % of
-        // this kernel's issue slots.
+        // and interleaved. Packing the k characters from text in every lane (rtk_km_from_text: four unaligned words, two 64-bit multiplies each) was ~45 %
+        // of this kernel's issue slots.
         RtkKm fw_t; fw_t.hi = 0; fw_t.lo = 0; bool ok_t = false; const bool planes = g.k <= 32;
         if (planes) {
             const uint64_t a0 = tile * RTK_WAVE + static_cast<uint64_t>(rtk_lane()), a1 = a0 + RTK_WAVE;
@@ -452,8 +451,7 @@ RTK_GLOBAL void k_lookup_exact(GraphView g, const char* seq, const uint64_t* rof
             const uint64_t km = k_ < 64 ? ((1ull << k_) - 1ull) : ~0ull;
             const uint64_t p0 = (sh ? ((L0a >> sh) | (L0b << (64 - sh))) : L0a) & km, p1 = (sh ? ((L1a >> sh) | (L1b << (64 - sh))) : L1a) & km, pv = (sh ? ((Va >> sh) | (Vb << (64 - sh))) : Va) & km;
             ok_t = pv == km;
-            auto spread = [](uint64_t x) { x = (x | (x << 16)) & 0x0000FFFF0000FFFFull; x = (x | (x << 8)) & 0x00FF00FF00FF00FFull; x = (x | (x << 4)) & 0x0F0F0F0F0F0F0F0Full; x = (x | (x << 2)) & 0x3333333333333333ull; return (x | (x << 1)) & 0x5555555555555555ull; };
-            fw_t.lo = (spread(rtk_brev64(p1) >> (64 - k_)) << 1) | spread(rtk_brev64(p0) >> (64 - k_));
+            fw_t.lo = (rtk_spread32(rtk_brev64(p1) >> (64 - k_)) << 1) | rtk_spread32(rtk_brev64(p0) >> (64 - k_));
         }
 #endif
         if (b < n_bases) {
@@ -483,9 +481,9 @@ RTK_GLOBAL void k_lookup_exact(GraphView g, const char* seq, const uint64_t* rof
 #endif
         }
     }
-    if (n_probes_out) { // n_probes_out[0] += k-mer queries, n_probes_out[11] += 16-byte table slots visited (RTK_CNT_PROBES_EXACT -> RTK_CNT_SLOTS_EXACT)
+    if (n_probes_out) { // n_probes_out = the RTK_CNT_PROBES_EXACT slot of the counters: += k-mer queries there, += 16-byte table slots visited at RTK_CNT_SLOTS_EXACT
         const int tot = rtk_wave_sum(static_cast<int>(probes)), tots = rtk_wave_sum(static_cast<int>(slots));
-        if (rtk_lane() == 0) { if (tot) rtk_atomic_add(reinterpret_cast<unsigned long long*>(n_probes_out), static_cast<unsigned long long>(tot)); if (tots) rtk_atomic_add(reinterpret_cast<unsigned long long*>(n_probes_out) + 11, static_cast<unsigned long long>(tots)); }
+        if (rtk_lane() == 0) { if (tot) rtk_atomic_add(reinterpret_cast<unsigned long long*>(n_probes_out), static_cast<unsigned long long>(tot)); if (tots) rtk_atomic_add(reinterpret_cast<unsigned long long*>(n_probes_out) + (RTK_CNT_SLOTS_EXACT - RTK_CNT_PROBES_EXACT), static_cast<unsigned long long>(tots)); }
     }
 }
 

@@ -10,7 +10,7 @@
 // steps ahead of their use). The sweep lasts as long as its longest pass: a level of a 10 kb read is n / 2^(l+1) + W steps for ALL its passes.
 // Passes whose band does not fit 64 lanes (band > ~4000 diagonals: the top levels of reads above ~40 kb) keep the banded row blocks.
 //
-// The driver builds the split tree level by level like the multi-wave driver of round 2 did (lists of sub-problems in read order; a round
+// The driver builds the split tree level by level (lists of sub-problems in read order; a round
 // of at most RTK_LVL_MAXN sub-problems at a time, their records in the scratch's small stack area), on one wave or -- in the multi-wave
 // kernels -- with the gangs and row blocks of a round as work items of the workgroup's waves; the leaves are traced back by all waves.
 #ifndef RTK_MYERS_LVL_H

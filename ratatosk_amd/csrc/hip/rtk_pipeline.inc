@@ -19,64 +19,6 @@ RTK_GLOBAL void k_set_ctx(LaunchCtx* out, GraphView g, OptsView o, BatchView bv,
     if (RTK_BLOCK_ID == 0 && rtk_lane() == 0) { out->g = g; out->o = o; out->bv = bv; out->rb = rb; }
 }
 
-// The per-read seed programs read the views through the launch's LaunchCtx and their work-area descriptor from LDS: a by-value copy on
-// the wave's stack is 64 interleaved copies that every field read fetches a 256-byte row of.
-#ifdef RTK_SIM
-#define RTK_SEED_SCRATCH(sc, expr) const SeedScratch sc = (expr)
-#else
-#define RTK_SEED_SCRATCH(sc, expr) __shared__ SeedScratch sc; sc = (expr); __syncthreads()
-#endif
-// One work item = one segment of `seg_w` windows of a read (`items`: read << 32 | segment, the segments of the longest reads first; built by rtk_batch_create).
-RTK_GLOBAL void k_mask(const LaunchCtx* L, BatchView bv, const uint64_t* items, uint32_t n_items, uint32_t seg_w, char* scratch, uint64_t stride, SeedScratchCfg cfg, int grid) {
-    RTK_SEED_SCRATCH(sc, seed_scratch_carve(scratch + static_cast<uint64_t>(RTK_BLOCK_ID) * stride, cfg));
-    for (uint32_t it = static_cast<uint32_t>(RTK_BLOCK_ID); it < n_items; it += static_cast<uint32_t>(grid)) {
-        const uint64_t e = rtk_u(items[it]);
-        const uint32_t r = static_cast<uint32_t>(e >> 32), seg = static_cast<uint32_t>(e & 0xFFFFFFFFull);
-        *sc.overflow = 0;
-        rtk_mask_read(L->g, L->o, L->bv, sc, r, seg * seg_w, (seg + 1u) * seg_w);
-        if (*sc.overflow && rtk_lane() == 0) rtk_atomic_or(bv.status.get() + r, 1u);
-    }
-}
-
-// 1-edit search. Two kernels so that the register budget of the variant-spelling fallback does not cap the occupancy of the seeded search.
-template <int ENUMERATE>
-RTK_DEV void inexact_body(const LaunchCtx* L, const BatchView& bv, int grid) {
-    const GraphView& g = L->g;
-    const uint64_t n_tiles = (bv.n_bases + 63) / 64;
-    unsigned long long probes = 0, slots = 0, hits = 0;
-    PoolChunk chunk; chunk.base = 0; chunk.left = 0;
-    for (uint64_t t = static_cast<uint64_t>(RTK_BLOCK_ID); t < n_tiles; t += static_cast<uint64_t>(grid)) {
-        if (ENUMERATE) rtk_inexact_tile(g, L->bv, t, &probes, &slots, &hits, &chunk, L->o.a2_exclusive);
-        else rtk_inexact_tile_seeded(g, L->bv, t, &probes, &slots, &hits, &chunk, L->o.a2_exclusive, L->o.inexact_route);
-    }
-    // wave reduction of the per-lane probe tallies, then one atomic per wave
-    unsigned long long tot = probes, tots = slots;
-#ifndef RTK_SIM
-    for (int o = 32; o > 0; o >>= 1) { tot += __shfl_xor(tot, o, 64); tots += __shfl_xor(tots, o, 64); }
-#endif
-    if (rtk_lane() == 0) { if (tot) rtk_atomic_add(bv.counters + RTK_CNT_PROBES_INEXACT, tot); if (tots) rtk_atomic_add(bv.counters + RTK_CNT_SLOTS_INEXACT, tots); if (hits) rtk_atomic_add(bv.counters + RTK_CNT_HITS_INEXACT, hits); }
-}
-// half-k-mer seeds + verification (default)
-#ifndef RTK_SIM
-#ifndef RTK_INEXACT_WPE
-#define RTK_INEXACT_WPE 6
-#endif
-__attribute__((amdgpu_waves_per_eu(RTK_INEXACT_WPE, RTK_INEXACT_WPE)))
-#endif
-RTK_GLOBAL void k_inexact(const LaunchCtx* L, BatchView bv, int grid) { inexact_body<0>(L, bv, grid); }
-// every 1-edit variant spelled and probed (RTK_INEXACT_ENUM=1 cross-check; fallback when the half-k-mer index is not built)
-RTK_GLOBAL void k_inexact_enum(const LaunchCtx* L, BatchView bv, int grid) { inexact_body<1>(L, bv, grid); }
-
-RTK_GLOBAL void k_finalize(const LaunchCtx* L, BatchView bv, char* scratch, uint64_t stride, SeedScratchCfg cfg, int grid) {
-    RTK_SEED_SCRATCH(sc, seed_scratch_carve(scratch + static_cast<uint64_t>(RTK_BLOCK_ID) * stride, cfg));
-    for (uint32_t ri = static_cast<uint32_t>(RTK_BLOCK_ID); ri < bv.n_reads; ri += static_cast<uint32_t>(grid)) {
-        const uint32_t r = bv.order[ri];
-        *sc.overflow = 0;
-        rtk_finalize_read(L->g, L->o, L->bv, sc, r);
-        if (*sc.overflow && rtk_lane() == 0) bv.status[r] |= 2u;
-    }
-}
-
 // ------------------------------------------------------------------------------------------------ batch object
 struct rtk_batch {
     rtk_graph* g = nullptr;
@@ -114,7 +56,7 @@ struct rtk_batch {
         bv.status = alloc<uint32_t>(n); bv.counters = alloc<unsigned long long>(RTK_CNT_TOTAL);
     }
     rtk_batch() { memset(&bv, 0, sizeof(bv)); memset(&stats, 0, sizeof(stats)); memset(&rb, 0, sizeof(rb)); }
-    // Round 6: a batch takes ONE buffer from the graph's pool, sized for everything it will ask for (rtk_batch_arena_bytes), and carves its ~45 arrays out of it; what does not
+    // A batch takes ONE buffer from the graph's pool, sized for everything it will ask for (rtk_batch_arena_bytes), and carves its ~45 arrays out of it; what does not
     // fit (a second set of arrays after the phasing step, grown capacities) comes from the pool one by one as before. One pool request per ticket instead of 45 -- and a miss costs
     // ONE hipMalloc, which rtk_graph_reserve_batches lets a caller pay before the correction phase (a hipMalloc stalls every stream of the device: 0.15-2.1 s per second-pass run
     // of 5.7 s went into ~165 of them, profiles/r06_pass2_trace.txt).
@@ -255,82 +197,9 @@ extern "C" int rtk_batch_create(rtk_graph* g, uint32_t n, const char* const* seq
     return RTK_OK;
 }
 
-static int seed_waves() { return rtk_knob_seed_waves(); } // waves of the per-read seed kernels (one read each at a time, longest first): 16 per CU fit (LDS); 1024 -> 4096: k_mask 1.5 -> 1.0 ms, k_finalize 4.7 -> 3.0 ms per 64 Mb, 13 GB of work areas
+#include "rtk_seed_stage.inc"
 
-// anchors of every read (stage A of the pipeline): exact scan, mask, inexact scan, filters
-static void run_seed_stage(rtk_batch* b, const OptsView& ov, int attempt) {
-    BatchView& bv = b->bv;
-    const GraphView& g = b->g->dview;
-    const rtk_stream_t st = b->stream;
-    rtk_dzero_s(bv.hitmap, 8ull * (b->n_bases / 64 + 4), st); rtk_dzero_s(bv.wdesc, 8ull * (b->n_bases + 64), st); rtk_dzero_s(bv.ipool_top, 8, st); rtk_dzero_s(bv.wk_top, 8, st); rtk_dzero_s(bv.status, 4ull * b->n, st); rtk_dzero_s(bv.counters, 8 * RTK_CNT_TOTAL, st);
-    RtkTimer t0, t1, t2, t3;
-    const int grid = default_grid();
-    t0.start(st);
-    const int xgrid = 2 * grid; // 26 VGPRs: eight waves per SIMD fit
-    rtk_launch(k_lookup_exact, xgrid, st, g, bv.seq, bv.roff, bv.n_reads, bv.n_bases, xgrid, bv.hits.get(), bv.hitmap.get(), reinterpret_cast<uint64_t*>(bv.counters + RTK_CNT_PROBES_EXACT)); // [0] queries, [+11] table slots
-    t0.stop(st);
-    SeedScratchCfg cfg;
-    cfg.set_cap = 32768u << (2 * attempt); cfg.v_cap = 32768u << (2 * attempt);
-    if (attempt == 0 && rtk_knob_test_tiny_scratch()) { cfg.set_cap = 48; cfg.v_cap = 64; } // test hook, see region_cfg
-    uint32_t max_len = 0; for (uint32_t i = 0; i < b->n; ++i) max_len = std::max<uint32_t>(max_len, static_cast<uint32_t>(b->roff[i + 1] - b->roff[i]));
-    { uint32_t q = 131072u; while (q < max_len) q <<= 1; cfg.s_cap = q + 64; } // coarse steps, see region_cfg
-    const uint64_t stride = seed_scratch_bytes(cfg);
-    int rgrid = static_cast<int>(std::min<uint32_t>(b->n, static_cast<uint32_t>(attempt ? 64 : seed_waves())));
-#ifdef RTK_SIM
-    rgrid = std::min(rgrid, 16);
-#endif
-    if (rgrid < 1) rgrid = 1;
-    int mgrid = static_cast<int>(std::min<uint32_t>(b->n_mask_items, static_cast<uint32_t>(attempt ? 64 : seed_waves()))); // k_mask: one wave per segment of a read
-#ifdef RTK_SIM
-    mgrid = std::min(mgrid, 16);
-#endif
-    if (mgrid < 1) mgrid = 1;
-    char* scratch = graph_scratch(b->g, 0, stride * std::max(rgrid, mgrid));
-    const bool second_pass = ov.long_read_correct != 0; // getSeeds keeps the exact hits only (src/Graph.cpp:100): no masked copy, no 1-edit search
-    { RegionBatch none; memset(&none, 0, sizeof(none)); rtk_launch(k_set_ctx, 1, st, b->ctx(), g, ov, bv, none); }
-    const LaunchCtx* L = b->ctx();
-    t1.start(st);
-    if (!second_pass) { // the masked copy starts as all 'N'; the segments of the reads (long reads: several waves each) open the gaps
-        rtk_dfill_s(bv.masked, 'N', b->n_bases + 64, st);
-        if (b->n_mask_items) rtk_launch(k_mask, mgrid, st, L, bv, static_cast<const uint64_t*>(b->d_mask_items), b->n_mask_items, b->mask_seg, scratch, stride, cfg, mgrid);
-    }
-    t1.stop(st);
-    t2.start(st);
-    if (!second_pass) { if (rtk_knob_inexact_enum() || g.hx_mask == 0) rtk_launch(k_inexact_enum, grid, st, L, bv, grid); else { const int sgrid = grid + grid / 2; rtk_launch(k_inexact, sgrid, st, L, bv, sgrid); } } // 76 VGPRs: six waves per SIMD (eight measured the same)
-    t2.stop(st);
-    t3.start(st);
-    rtk_launch(k_finalize, rgrid, st, L, bv, scratch, stride, cfg, rgrid);
-    t3.stop(st);
-    rtk_ssync(st);
-    b->stats.ms_lookup_exact = t0.elapsed(); b->stats.ms_mask = t1.elapsed(); b->stats.ms_lookup_inexact = t2.elapsed(); b->stats.ms_seeds = t3.elapsed();
-}
-
-static int seed_stage_checked(rtk_batch* b, const OptsView& ov) {
-    std::lock_guard<std::mutex> hold(b->g->scratch_lock[0]);
-    for (int attempt = 0; attempt < 3; ++attempt) {
-        const auto w0 = std::chrono::steady_clock::now();
-        run_seed_stage(b, ov, attempt);
-        if (rtk_knob_trace()) { unsigned long long c2[RTK_CNT_FINALIZE_SLOWEST_PHASES_END]; rtk_d2h_s(c2, b->bv.counters, sizeof(c2), b->stream);
-            fprintf(stderr, "[rtk trace] finalize, slowest read: solid %.3g junction %.3g gather %.3g classify+sort %.3g groups %.3g conflicts %.3g write %.3g cycles\n", double(c2[RTK_CNT_FINALIZE_SLOWEST_PHASES + 0]), double(c2[RTK_CNT_FINALIZE_SLOWEST_PHASES + 1]), double(c2[RTK_CNT_FINALIZE_SLOWEST_PHASES + 2]), double(c2[RTK_CNT_FINALIZE_SLOWEST_PHASES + 3]), double(c2[RTK_CNT_FINALIZE_SLOWEST_PHASES + 4]), double(c2[RTK_CNT_FINALIZE_SLOWEST_PHASES + 5]), double(c2[RTK_CNT_FINALIZE_SLOWEST_PHASES + 6])); }
-        if (rtk_knob_trace()) { unsigned long long c[RTK_CNT_FINALIZE_END]; rtk_d2h_s(c, b->bv.counters, sizeof(c), b->stream);
-            fprintf(stderr, "[rtk trace] finalize wave-cycles: solid %.3g junction %.3g gather %.3g classify+sort %.3g groups %.3g conflicts %.3g write %.3g | slowest read %.3g cycles\n", double(c[RTK_CNT_FINALIZE + 0]), double(c[RTK_CNT_FINALIZE + 1]), double(c[RTK_CNT_FINALIZE + 2]), double(c[RTK_CNT_FINALIZE + 3]), double(c[RTK_CNT_FINALIZE + 4]), double(c[RTK_CNT_FINALIZE + 5]), double(c[RTK_CNT_FINALIZE + 6]), double(c[RTK_CNT_FINALIZE_SLOWEST])); }
-        if (rtk_knob_trace()) fprintf(stderr, "[rtk trace] seeds attempt %d: %.2f ms (kernels %.2f)\n", attempt, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count(), b->stats.ms_lookup_exact + b->stats.ms_mask + b->stats.ms_lookup_inexact + b->stats.ms_seeds);
-        std::vector<uint32_t> st(b->n);
-        rtk_d2h_s(st.data(), b->bv.status, 4ull * b->n, b->stream);
-        unsigned long long cnt[RTK_CNT_SEED_READBACK]; rtk_d2h_s(cnt, b->bv.counters, sizeof(cnt), b->stream);
-        bool ovf = cnt[RTK_CNT_OVERFLOW] != 0;
-        for (uint32_t i = 0; i < b->n; ++i) if (st[i]) ovf = true;
-        if (!ovf) return RTK_OK;
-        // a scratch / pool capacity was exceeded somewhere: grow and redo the stage (still on the device)
-        if (cnt[RTK_CNT_OVERFLOW]) {
-            b->bv.ipool_cap *= 4; b->bv.ipool = b->alloc<uint64_t>(2 * b->bv.ipool_cap);
-            b->bv.wk_cap *= 4; b->bv.wk_pos = b->alloc<uint32_t>(b->bv.wk_cap); b->bv.wk_hit = b->alloc<uint64_t>(b->bv.wk_cap);
-        }
-    }
-    return rtk_fail(RTK_ERR_DEVICE, "seed stage: scratch capacity exceeded after 3 attempts");
-}
-
-// The one reader of the seed stage's output layout (BatchView, rtk_seeds.h): the anchors of read `read` of a batch whose seed stage has completed, as
+// The one reader of the seed stage's output layout (BatchView, rtk_seed_types.h): the anchors of read `read` of a batch whose seed stage has completed, as
 // (pos, unitig, dist, strand) quadruples with positions in the read's own coordinates. Read r keeps its solid positions at s_pos[roff[r] .. + n_solid[r])
 // and looks their hits up in hits[roff[r] + pos]; its weak anchors are wk_pos / wk_hit[w_off[r] .. + w_cnt[r]). Up to `cap` quadruples of each list are
 // written; the counts are always the true ones, and a list longer than `cap` is an RTK_ERR_ARG in the name of the entry `who`.

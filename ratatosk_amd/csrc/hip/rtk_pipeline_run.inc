@@ -506,9 +506,9 @@ static void region_alloc(RegionRun& R) {
 }
 
 // Which regions the lane-per-region kernel gets (known before the views go to the device): gaps under RTK_LANE_MAX_GAP bases (0 = off); none in the second pass.
-// Off by default (round 5): the kernel is byte-identical to the wave kernel on every tier but not yet faster -- a lane's program is one long dependent chain, ~5 ms per
+// Off by default: the kernel is byte-identical to the wave kernel on every tier but not yet faster -- a lane's program is one long dependent chain, ~5 ms per
 // region on one lane (DESIGN_HISTORY.md section 3.8) -- so a run opts in with RTK_LANE_MAX_GAP=128 (the bench measures both ways and reports the pair).
-// Round 6, the decision the lane kernel was waiting for: it pays from ~10^6 lane-class regions per launch upwards (break-even at 253 Mb per ticket, -5.5 % of the region stage at
+// It pays from ~10^6 lane-class regions per launch upwards (break-even at 253 Mb per ticket, -5.5 % of the region stage at
 // 989 Mb, one kernel after the other on 4 096 lane waves: DESIGN_HISTORY.md section 3.8), so a ticket of at least RTK_LANE_AUTO_BASES (512 Mi; 0 = never) bases -- `Ratatosk correct -B`
 // that large, or a caller's own -- takes it for gaps under 128 without being asked; smaller tickets (every ticket of the bench and of the CLI's default -B) never do.
 static void region_lane_class(RegionRun& R) {
@@ -939,7 +939,7 @@ extern "C" int rtk_batch_get_stats(const rtk_batch* b, rtk_stats* stats) { if (!
 // ------------------------------------------------------------------------------------------------ ticket coalescing (rtk_correct_batch)
 // The reference's workers each take a ticket of >= 1 MiB of bases (src/Common.hpp:138, src/Ratatosk.cpp:757-772) and call the per-read loop on it; a launch
 // of a ticket that small lasts as long as its longest read and its slowest region with most of the device idle (2 x 10^8 bases/s whatever the number of
-// callers, round 5). So tickets of concurrent callers are merged: a caller that arrives while a group is being gathered joins it, the group runs as ONE batch
+// callers). So tickets of concurrent callers are merged: a caller that arrives while a group is being gathered joins it, the group runs as ONE batch
 // (one pack + H2D, one set of launches, one D2H), every caller copies its own reads out of the group's pinned view. Who gathers: the first caller whose
 // ticket is still waiting when nobody else gathers. How long it gathers: until the group holds RTK_COALESCE_BASES (16 Mi) bases, else
 //  * RTK_COALESCE_WAIT_US (1 500) from its own arrival in every case -- except when it is alone (nothing queued, nothing in flight, the last group was a

@@ -149,8 +149,8 @@ RTK_HD uint64_t rtk_revcomp(uint64_t x, int k) {
     return x >> (64 - 2 * k);
 }
 
-// ---- the map of BatchView::counters (rtk_seeds.h): every slot or range that any kernel or the host uses, with who writes it. The block is cleared at the start
-// of the seed stage and of the pass-2 phasing step (rtk_pipeline.inc) and copied back once at the end of the region stage. Slots outside a range are free.
+// ---- the map of BatchView::counters (rtk_seed_types.h): every slot or range that any kernel or the host uses, with who writes it. The block is cleared at the start
+// of the seed stage (rtk_seed_stage.inc) and of the pass-2 phasing step (rtk_pipeline.inc) and copied back once at the end of the region stage. Slots outside a range are free.
 enum RtkCounterSlot {
     RTK_CNT_WINDOWS = 0, RTK_CNT_PROBES_EXACT = 1, RTK_CNT_PROBES_INEXACT = 2, RTK_CNT_HITS_INEXACT = 3, RTK_CNT_REGIONS = 4, RTK_CNT_ITEMS = 5, // seed kernels -> rtk_stats
     RTK_CNT_OVERFLOW = 6,           // seed kernels: a pool ran out (the host grows it and redoes the stage)
@@ -244,7 +244,7 @@ static_assert(RTK_CNT_FA_LINKED_END - RTK_CNT_FA_LINKED == static_cast<int>(RTK_
 static_assert(RTK_CNT_STRAND2_END - RTK_CNT_STRAND2 == static_cast<int>(RTK_RC_PARK_WALKED) - static_cast<int>(RTK_RC_STRAND2_RUN), "counter map: one slot per second-strand counter");
 static_assert(RTK_CNT_PARK_END - RTK_CNT_PARK == static_cast<int>(RTK_RC_COLOURS_SMALL) - static_cast<int>(RTK_RC_PARK_WALKED), "counter map: one slot per park counter");
 static_assert(RTK_CNT_COLOURS_END - RTK_CNT_COLOURS == static_cast<int>(RTK_RC_PARK_RESWEEPS) - static_cast<int>(RTK_RC_COLOURS_SMALL), "counter map: one slot per colour-route counter");
-// OptsView::colours_mode (rtk_seeds.h; RTK_COLOURS_ROUTE, RTK_COLOURS_AUDIT, RTK_TEST_COLOURS_FAULT of rtk_knobs.h): route in bits 0 .. 1, the audit and its test hook above
+// OptsView::colours_mode (rtk_seed_types.h; RTK_COLOURS_ROUTE, RTK_COLOURS_AUDIT, RTK_TEST_COLOURS_FAULT of rtk_knobs.h): route in bits 0 .. 1, the audit and its test hook above
 #define RTK_CM_ROUTE 3u
 #define RTK_CM_ROUTE_BITS 1u
 #define RTK_CM_ROUTE_GENERAL 2u

@@ -89,12 +89,17 @@ __device__ __forceinline__ int rtk_popc(uint64_t x) { return __popcll(x); }
 __device__ __forceinline__ int rtk_ffs(uint64_t x) { return __ffsll(static_cast<unsigned long long>(x)); }
 template <class T> __device__ __forceinline__ T rtk_atomic_add_raw(T* p, T v) { return atomicAdd(p, v); }
 __device__ __forceinline__ uint32_t rtk_atomic_or(uint32_t* p, uint32_t v) { return atomicOr(p, v); }
-__device__ __forceinline__ unsigned long long rtk_clock() { return static_cast<unsigned long long>(clock64()); } // (a build without the cycle counters was no faster: 30.93 against 30.90 ms, round 4)
+__device__ __forceinline__ unsigned long long rtk_clock() { return static_cast<unsigned long long>(clock64()); } // (a build without the cycle counters is no faster)
 __device__ __forceinline__ uint64_t rtk_brev64(uint64_t x) { return __builtin_bitreverse64(x); }
 
 #endif
 
 // 64-bit specialisations of shuffles are provided by HIP for (unsigned) long long; int8/bool go through int.
+
+RTK_DEV uint64_t rtk_spread32(uint64_t x) { // bit i of the low 32 -> bit 2 i
+    x = (x | (x << 16)) & 0x0000FFFF0000FFFFull; x = (x | (x << 8)) & 0x00FF00FF00FF00FFull; x = (x | (x << 4)) & 0x0F0F0F0F0F0F0F0Full;
+    x = (x | (x << 2)) & 0x3333333333333333ull; return (x | (x << 1)) & 0x5555555555555555ull;
+}
 
 // wave-wide reductions / scans over one value per lane
 RTK_DEV int rtk_wave_sum(int v) {

@@ -1,6 +1,6 @@
 """Bit-level identities that lane-parallel device code of round 4 rests on, restated in Python and checked against the plain rule they replace (the
 1-lane host simulator runs the plain rules, so these identities have no other CPU-side check; the gpu tier holds the kernels to the oracle):
-  * k_finalize's solid filter per 64-window block (csrc/hip/rtk_seeds.h: run starts OR-ed over a sliding window by doubling shifts) against the
+  * k_finalize's solid filter per 64-window block (csrc/hip/rtk_seed_finalize.h: run starts OR-ed over a sliding window by doubling shifts) against the
     per-window rule "dropped iff the k - 1 presence bits behind the window have a one above their first zero" (src/Graph.cpp:221-239);
   * k_lookup_exact's k-mer codes from ballot bit planes (csrc/hip/rtk_device.hip) against the character-by-character 2-bit packing;
   * the 32-bit sort key of a weak hit (variant position, base mask, kind side by side) against the 64-bit key it stands for: same order, exact round trip;

@@ -1,4 +1,4 @@
-"""k_inexact with one index look-up per read position of a tile, shared by the windows that ask for it (rtk_inexact_tile_seeded, csrc/hip/rtk_seeds.h), and
+"""k_inexact with one index look-up per read position of a tile, shared by the windows that ask for it (rtk_inexact_tile_seeded, csrc/hip/rtk_seed_seeded.h), and
 with the window codes taken from the tile's bit planes: the places where the two can go wrong, against the oracle (`op.Graph(...).seeds`). Every comparison of
 anchors is exact equality of Batch.seeds(i), under the default, RTK_INEXACT_SHARED=0, RTK_INEXACT_PLANES=0 and RTK_INEXACT_ENUM=1, at [A2] = union, exclusive and
 exclusive-ids, at k = 31, 25 and 21. One batch per k (a 9 kb genome, some 250 reads), placed so that
