@@ -281,7 +281,7 @@ int rtk_myers_batch_waves(uint32_t n, const char* const* query, const uint32_t* 
                           int32_t* dist, int32_t* n_loc, int32_t* end_locs, uint32_t cap_locs, char* cigar, uint32_t cap_cigar, int waves);
 
 /* Test-only modes of rtk_myers_batch (revision 7; one wave per problem, not rtk_myers_batch_waves / _lanes): the routes by which the region program's trim
- * and consensus share one sweep (csrc/hip/rtk_myers.h, rtk_myers_shw_by_column; csrc/hip/rtk_region.h, rtk_trim_by_column).
+ * and consensus share one sweep (csrc/hip/rtk_myers_distance.h, rtk_myers_shw_by_column; csrc/hip/rtk_region.h, rtk_trim_by_column).
  *   RTK_MYERS_MODE_SHW_BY_COLUMN: k < 0. The SHW distance of (query, target), read off the last column of ONE NW sweep of (target, query); n_loc = the number
  *     of end locations, of which end_locs holds the first (slot 0) and the last (slot n_loc - 1) only: the route does not list the others. No path.
  *   RTK_MYERS_MODE_NW_PREFIX: 0 <= k <= qlen. The NW distance and, with want_path, the path of (query[0, k), target), walked from row k of the stored NW sweep of

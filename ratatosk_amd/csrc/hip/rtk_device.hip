@@ -536,8 +536,7 @@ RTK_FN void rtk_myers_column_item(const MyersScratch& sc, const MyersProb& p, ui
         const int k = p.k; const bool from_column = p.mode == RTK_MYERS_MODE_NW_PREFIX_LAST_COLUMN, last_only = from_column || p.mode == RTK_MYERS_MODE_NW_PREFIX_LAST;
         int at = 0, last = -1;
         if (k > 0 && rtk_myers_shw_by_column(sc, q, m, t, n, iupac, from_column ? 2 : 1, k, &r, &at)) {
-            const long long W = (k + 63) >> 6;
-            if (static_cast<uint32_t>(k) <= sc.r_cap && static_cast<uint32_t>(k + n) <= sc.mv_cap && (2LL * 8 + 4) * W * n + 8LL * n < 1024 * 1024) {
+            if (static_cast<uint32_t>(k) <= sc.r_cap && static_cast<uint32_t>(k + n) <= sc.mv_cap && rtk_tb_in_memory(k, n)) {
                 if (from_column) last = rtk_myers_last_move_column(sc, k); // the trim's look at the last column of a sweep that stored no table
                 else if (last_only) last = rtk_myers_last_move(sc, k, n, n, at); // the same look at a stored table, in place of the walk
                 else rtk_myers_walk(sc, k, n, n, at, &nm);

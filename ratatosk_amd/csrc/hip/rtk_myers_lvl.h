@@ -15,6 +15,8 @@
 // kernels -- with the gangs and row blocks of a round as work items of the workgroup's waves; the leaves are traced back by all waves.
 #ifndef RTK_MYERS_LVL_H
 #define RTK_MYERS_LVL_H
+#include "rtk_myers_distance.h" // rtk_myers_column, the passes and their work items
+#include "rtk_myers_walk.h"     // rtk_myers_traceback of the leaves
 #ifndef RTK_SIM
 
 #define RTK_LVL_NODE 12   // ints per sub-problem record of a round
@@ -26,7 +28,7 @@
 // lanes of one pass of a gang: a lane must be done with word w (band + 64 columns after it started, looked at every RTK_GANG_PERIOD steps,
 // 4 steps of character prefetch) before word w + L starts, 65 L steps after word w did
 __device__ __forceinline__ int rtk_gang_lanes(int band_width, int wa) { const int l = (band_width + 63 + RTK_GANG_PERIOD + 4 + 64) / 65; return l < wa ? l : wa; }
-__device__ __forceinline__ bool rtk_hb_is_leaf(int qm, int tn) { return qm == 0 || tn == 0 || (2LL * 8 + 4) * ((qm + 63) >> 6) * tn + 8LL * tn < 1024 * 1024; } // edlib.cpp:1191-1193
+__device__ __forceinline__ bool rtk_hb_is_leaf(int qm, int tn) { return qm == 0 || tn == 0 || rtk_tb_in_memory(qm, tn); } // no further split: an empty side, or the in-memory traceback
 
 // Advance_Block (rtk_myers_step) with the outgoing delta read from one half of the delta words (the bit's half and position are per-word constants)
 __device__ __forceinline__ int rtk_gang_step64(uint64_t& Pv, uint64_t& Mv, uint64_t Eq, int hin, bool bit_hi, int bit_pos) {
@@ -273,8 +275,7 @@ __device__ __noinline__ bool rtk_myers_alignment_lvl(const MyersScratch& sc, con
                 if (bs < 0) { // only the whole problem: the optimum = the smallest left + right sum over every split point
                     int mn = 0x7fffffff;
                     for (int b0 = 0; b0 + 1 < qm; b0 += RTK_WAVE) { const int qi = b0 + lane; if (qi + 1 < qm) { const int v = rl[qi] + rr[qm - 2 - qi]; mn = v < mn ? v : mn; } }
-                    for (int o = 32; o > 0; o >>= 1) { const int v = __shfl_xor(mn, o, 64); mn = v < mn ? v : mn; }
-                    mn = rtk_u(mn);
+                    mn = rtk_u(rtk_wave_min(mn));
                     const int e0 = lh + rtk_ld(rr + (qm - 1)), e1 = rtk_ld(rl + (qm - 1)) + rh;
                     mn = e0 < mn ? e0 : mn; mn = e1 < mn ? e1 : mn;
                     if (mn > kk) { k_top = mn; redo = true; continue; } // a real score above the guess: the level again, with the band of that score
@@ -410,6 +411,38 @@ __device__ __noinline__ bool rtk_myers_alignment_lvl(const MyersScratch& sc, con
     prof.hb_total += rtk_clock() - t_all0;
     return true;
 }
+
+#ifdef RTK_MULTIWAVE
+// one leaf traceback of a leaf round, on whichever wave claimed it (its work area: st->lsc[wave]); leaves that do not fit a helper's
+// work area are left to the program wave (length stays -1)
+__device__ __noinline__ void rtk_myers_leaf_item(RtkCoop* st, int wave, int x) {
+    int32_t* const L = reinterpret_cast<int32_t*>(rtk_u(reinterpret_cast<unsigned long long>(st->llist)));
+    const char* const q = reinterpret_cast<const char*>(rtk_u(reinterpret_cast<unsigned long long>(st->lq)));
+    const char* const t = reinterpret_cast<const char*>(rtk_u(reinterpret_cast<unsigned long long>(st->lt)));
+    uint8_t* const mvs = reinterpret_cast<uint8_t*>(rtk_u(reinterpret_cast<unsigned long long>(st->lmoves)));
+    MyersScratch* const hs = reinterpret_cast<MyersScratch*>(rtk_u(reinterpret_cast<unsigned long long>(st->lsc))) + wave;
+    MyersScratch& h = *hs; RTK_ASSUME_LDS(&h);
+    const bool iupac = rtk_coop_ld(&st->liupac) != 0;
+    const int q0 = rtk_ld(L + 6 * x), qm = rtk_ld(L + 6 * x + 1), t0 = rtk_ld(L + 6 * x + 2), tn = rtk_ld(L + 6 * x + 3), off = rtk_ld(L + 6 * x + 5);
+    int len = -1;
+    const uint64_t* const need = reinterpret_cast<const uint64_t*>(rtk_u(reinterpret_cast<unsigned long long>(st->lneed)));
+    if (qm == 0 || tn == 0) { rtk_wfill(mvs + off, qm == 0 ? 2 : 1, static_cast<uint64_t>(qm + tn)); len = qm + tn; } // edlib.cpp:1171-1178
+    else if (need && rtk_need_none(need, t0, t0 + tn)) { rtk_wfill(mvs + off, 2, static_cast<uint64_t>(tn)); rtk_wfill(mvs + off + tn, 1, static_cast<uint64_t>(qm)); len = qm + tn; } // (MyersScratch::need_bm)
+    else {
+        if (rtk_fits_stored_sweep(h, qm, tn, 64u)) {
+            h.moves = mvs + off;
+            uint32_t* const nm = &st->lnm[wave];
+            if (rtk_lane() == 0) *nm = 0;
+            rtk_sync();
+            rtk_myers_traceback(h, rtk_seq(q + q0, qm), rtk_seq(t + t0, tn), iupac, nm);
+            len = static_cast<int>(rtk_u(*nm));
+            if (rtk_ld(rtk_ld(&h.overflow)) != 0) len = -1; // (cannot happen after the fit test; the program wave does it again)
+        }
+    }
+    if (rtk_lane() == 0) L[6 * x + 4] = len;
+    rtk_sync();
+}
+#endif
 
 #endif
 #endif

@@ -91,8 +91,7 @@ RTK_FN bool rtk_trim_by_column(const RCtx& c_, const char* raw_, uint32_t n_, co
     s.cnt[RTK_RC_PARK_DEFERRED] += 1; // a stored sweep that nothing has walked (yet: rtk_park_walk takes it back)
     // the conditions of rtk_myers_path's in-memory route for (corr[0, keep), raw) that the stored sweep of all of corr has not checked already
     const uint32_t keep = (out->first == -1) ? 0u : static_cast<uint32_t>(out->last + 1);
-    const long long W = (keep + 63) >> 6;
-    if (keep == 0 || keep > s.my.r_cap || keep + n > s.my.mv_cap || !((2LL * 8 + 4) * W * n + 8LL * n < 1024 * 1024)) return true;
+    if (keep == 0 || keep > s.my.r_cap || keep + n > s.my.mv_cap || !rtk_tb_in_memory(static_cast<int>(keep), n)) return true;
     const unsigned long long t1 = rtk_clock();
     TrimPark& pk = s.loc.park;
     pk.nm = 0; pk.len = keep; pk.dist = out->dist; pk.n = n; pk.gen = rtk_ld(&s.my.tb_gen); pk.pending = table ? RTK_PARK_TABLE : RTK_PARK_NO_TABLE;

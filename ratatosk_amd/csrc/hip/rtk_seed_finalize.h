@@ -4,7 +4,7 @@
 #define RTK_SEED_FINALIZE_H
 
 #include "rtk_colour_sets.h"
-#include "rtk_myers.h"
+#include "rtk_acgt.h"
 #include "rtk_seed_mask.h" // rtk_hit_bits
 #include "rtk_seed_types.h"
 #include "rtk_sets.h"

@@ -3,7 +3,7 @@
 #ifndef RTK_SEED_WINDOW_H
 #define RTK_SEED_WINDOW_H
 
-#include "rtk_myers.h"
+#include "rtk_acgt.h"
 #include "rtk_seed_types.h"
 #include "rtk_wave.h"
 

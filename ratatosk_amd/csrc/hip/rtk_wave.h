@@ -111,6 +111,15 @@ RTK_DEV int rtk_wave_sum(int v) {
 #endif
 }
 
+RTK_DEV int rtk_wave_min(int v) {
+#ifdef RTK_SIM
+    return v;
+#else
+    for (int o = 32; o > 0; o >>= 1) { const int x = __shfl_xor(v, o, 64); v = x < v ? x : v; }
+    return v;
+#endif
+}
+
 RTK_DEV int rtk_wave_excl_scan(int v, int* total) { // exclusive prefix sum across lanes
 #ifdef RTK_SIM
     *total = v; return 0;

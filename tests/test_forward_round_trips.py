@@ -12,7 +12,7 @@ a region that runs its second strand, and some still are. On the 1 Mb set at lea
 simulator) and the walks that remain make at most 0.65 of the moves of RTK_PARK_EAGER=1 (4 736 106 moves there, of which about 2.06 M belong to the parked
 paths: 0.57 expected; the margin is for the 61 regions that keep both strands). The GPU tier also holds the work counters of the wave kernels (n_expand,
 n_colour_elem, n_align, n_align_cells, the moves and the walks) to those of the simulator, set by set: both builds take the same alignment routes, the stored
-sweep that scores a terminal candidate and serves its quality string (rtk_myers_nw_and_save, csrc/hip/rtk_myers.h) included."""
+sweep that scores a terminal candidate and serves its quality string (rtk_myers_nw_and_save, csrc/hip/rtk_myers_align.h) included."""
 import pytest
 
 import test_pass2 as P2

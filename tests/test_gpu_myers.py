@@ -1,5 +1,6 @@
 """HIP Myers kernels (wave-parallel, one query word per lane) through the C ABI against the reference golden vectors
-and the oracle on seeded random problems, including row-blocked (>64 words) and Hirschberg-sized ones. Bit-exact."""
+and the oracle on seeded random problems, including row-blocked (>64 words) and Hirschberg-sized ones. Bit-exact.
+(csrc/hip/rtk_myers.h lists the aligner's headers: sweeps rtk_myers_sweep.h, row blocks rtk_myers_blocks.h, Hirschberg rtk_myers_lvl.h / rtk_myers_align.h.)"""
 import random
 
 import pytest

@@ -1,5 +1,5 @@
 """The forward trim of a gap region stores no table: its sweep keeps the delta vectors of the LAST column, and the last move of the alignment it parks is derived
-from them (csrc/hip/rtk_myers.h, rtk_myers_fast32 / rtk_myers_fast with STORE = 2 and rtk_myers_last_move_column; csrc/hip/rtk_region_align.h).
+from them (csrc/hip/rtk_myers_sweep.h, rtk_myers_fast32 / rtk_myers_fast with STORE = 2; rtk_myers_walk.h, rtk_myers_last_move_column; csrc/hip/rtk_region_align.h).
 
 Cell (keep, |raw|) of the sweep of (corrected, raw): the vertical delta is bit keep - 1 of Pv / Mv of the last column, the horizontal delta the same bit of Ph / Mh,
 and the diagonal neighbour lies one horizontal delta -- that of row keep - 1: the bit before, in the word before at a word boundary, +1 in row 0 -- to the left of the

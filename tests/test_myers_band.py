@@ -1,5 +1,5 @@
 """Ukkonen band of the big NW problems (reference: src/edlib.cpp:194-212 k doubling, :744-775 and :778-915 banded block ranges).
-The device computes only the band of k (ring schedule on one wave, banded row blocks on several: csrc/hip/rtk_myers.h); the oracle computes
+The device computes only the band of k (ring schedule on one wave, banded row blocks on several: csrc/hip/rtk_myers_band.h, rtk_myers_blocks.h); the oracle computes
 whole columns. Bounded distances with k = exact / exact - 1 / 0 / generous, unknown distances whose first guess is too small, and
 Hirschberg-sized paths must be the oracle's, bit for bit. CPU tier: the simulator (band logic, column extraction, split search);
 GPU tier: the wave schedules themselves, single wave and multi-wave workgroups."""

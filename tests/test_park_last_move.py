@@ -1,4 +1,4 @@
-"""The forward trim of a gap region keeps the LAST move of the alignment it parks, not the path (csrc/hip/rtk_myers.h, rtk_myers_last_move; csrc/hip/rtk_region_align.h,
+"""The forward trim of a gap region keeps the LAST move of the alignment it parks, not the path (csrc/hip/rtk_myers_walk.h, rtk_myers_last_move; csrc/hip/rtk_region_align.h,
 rtk_trim_by_column and rtk_park_walk).
 
 The rule that skips the second strand of a gap region asks of the parked alignment NW(corrected[0, keep), raw) only that it exists, its distance and whether its

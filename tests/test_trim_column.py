@@ -1,4 +1,4 @@
-"""The trim and the consensus of a gap region share one sweep (csrc/hip/rtk_myers.h, rtk_myers_shw_by_column; csrc/hip/rtk_region_align.h, rtk_trim_by_column).
+"""The trim and the consensus of a gap region share one sweep (csrc/hip/rtk_myers_distance.h, rtk_myers_shw_by_column; csrc/hip/rtk_region_align.h, rtk_trim_by_column).
 
 The trim's SHW alignment of (raw, corrected) is read off the LAST COLUMN of one NW sweep of (corrected, raw): equality is symmetric, so the SHW matrix is the
 transpose of that NW matrix. Row i of a stored sweep only depends on rows <= i, so the same table walked from row keep gives the consensus's NW path of
