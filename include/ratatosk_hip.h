@@ -472,6 +472,21 @@ int rtk_qv_chunk(void* job, const char* chars, uint64_t n_chars, const uint64_t*
 int rtk_qv_end(void* job, uint64_t* n_windows, uint64_t* n_found);
 uint32_t rtk_qv_span(void); /* start positions one wave takes at a time (for tests) */
 
+/* rtk_identity_*: the identity of reads to their simulated truth (rtk_identity, `correct --truth-ref --truth-tsv`; DESIGN.md section 4, [A19]; no counterpart in
+ * the reference). begin: record r of the reference = ref[rec_off[r] .. rec_off[r + 1]) (rec_off[0] = 0, ascending, n_rec + 1 entries), already upper-cased; the
+ * text is copied to HBM once and the input is not kept. max_len = the longest read or stretch a chunk may hold: it sizes the per-wave work areas; if reference,
+ * work areas and chunk buffers do not fit the free device memory the error names both byte counts. chunk (any thread, two calls run side by side): reads
+ * separated by '\n' in the layout of rtk_qv_chunk (read i = chars[starts[i] .. starts[i + 1] - 1), the last one ends at n_chars - 1; at most 64 MB and 4 M reads
+ * per call); the truth of read i is the stretch [t_start[i], t_start[i] + t_len[i]) of record rec[i], reversed and complemented (A<->T, C<->G, any other byte as
+ * it is) when rev[i] != 0 -- cut on the device from the resident reference. dist[i] = the exact unit-cost NW edit distance of read i and its truth, bytes equal
+ * iff identical (no IUPAC table, no cap). RTK_ERR_ARG, before anything is launched, for a stretch outside its record or a length above max_len. end: the number
+ * of pairs and the distance sum over all chunks; releases the job (also on error; with null outputs: only that). Appended without a new revision number: see
+ * RTK_API_REVISION. */
+int rtk_identity_begin(int device, const char* ref, uint64_t n_ref, const uint64_t* rec_off, uint32_t n_rec, uint32_t max_len, void** job);
+int rtk_identity_chunk(void* job, const char* chars, uint64_t n_chars, const uint64_t* starts, uint32_t n_reads,
+                       const uint32_t* rec, const uint64_t* t_start, const uint32_t* t_len, const unsigned char* rev, int32_t* dist);
+int rtk_identity_end(void* job, uint64_t* n_pairs, uint64_t* sum_dist);
+
 /* Stage entry for tests (revision 10): the wave-cooperative set primitives of the region stage (csrc/hip/rtk_sets.h, rtk_colours.h), one problem per wavefront
  * in ONE launch, each wave with the LDS buffer to itself as in the region kernel. Problem i: the operation op[i], two arrays of 32-bit words a[i][0 .. na[i]) and
  * b[i][0 .. nb[i]) and scalar[i]; its output words go to out_pool[out_off[i] .. out_off[i + 1]) (the caller sizes the slices), out_n[i] says how many were
@@ -522,7 +537,7 @@ const char* rtk_version(void);
  * 8: rtk_stats fields n_fa_linked_*; 9: rtk_rescue_begin / _chunk / _end; still 9: rtk_stats fields n_strand2_* and n_park_*, the test-only rtk_myers_batch mode 5, appended at the end -- a library of revision 9
  * without them leaves them as the caller set them;
  * 10: rtk_sets_batch, rtk_stats fields n_colours_*; still 10: rtk_index_colour_cov, rtk_index_colour_end_subsampled, rtk_index_subsample_events, then rtk_index_colour_merge,
- * rtk_index_colour_merge_classes, rtk_index_merge_events, then rtk_index_colour_chunk_q, then rtk_batch_fetch_seeds, then rtk_index_snp_candidates, then rtk_index_snp_plan, then rtk_index_cover_begin / _chunk / _end, then rtk_qv_begin / _chunk / _end / _span, then rtk_index_pair_ids / rtk_index_pair_plan, appended -- a library of revision 10 without them lacks the symbols, and callers look them up by name;
+ * rtk_index_colour_merge_classes, rtk_index_merge_events, then rtk_index_colour_chunk_q, then rtk_batch_fetch_seeds, then rtk_index_snp_candidates, then rtk_index_snp_plan, then rtk_index_cover_begin / _chunk / _end, then rtk_qv_begin / _chunk / _end / _span, then rtk_index_pair_ids / rtk_index_pair_plan, then rtk_identity_begin / _chunk / _end, appended -- a library of revision 10 without them lacks the symbols, and callers look them up by name;
  * then the rtk_stats field n_park_resweeps and the test-only rtk_myers_batch mode 6, which are no symbols: a library of revision 10 without them leaves the field as the
  * caller set it and answers mode 6 with RTK_ERR_ARG). */
 #define RTK_API_REVISION 10

@@ -146,6 +146,11 @@ def load_library(path=None):
         L.rtk_qv_chunk.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.rtk_qv_end.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.rtk_qv_span.argtypes = []; L.rtk_qv_span.restype = C.c_uint32
+    if hasattr(L, "rtk_identity_begin"):  # (still revision 10: appended; a library without them: identity_reads says so)
+        L.rtk_identity_begin.argtypes = [C.c_int, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
+        L.rtk_identity_chunk.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
+                                         C.POINTER(C.c_ubyte), C.POINTER(C.c_int32)]
+        L.rtk_identity_end.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     if hasattr(L, "rtk_index_pair_ids"):  # (still revision 10: appended; a library without them: index_pair_ids / index_pair_plan say so)
         L.rtk_index_pair_ids.argtypes = [C.c_int, C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
         L.rtk_index_pair_plan.argtypes = [C.c_int, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
@@ -506,6 +511,90 @@ def qv_reads(solid_kmers, seqs, k=31, device=0, max_piece=None, lib_path=None, t
     if stats is not None:
         stats["n_chunks"], stats["n_windows"], stats["n_found"] = len(chunks), n_windows.value, n_found.value
     return windows, found
+
+
+def identity_reads(ref_records, reads, truth, device=0, lib_path=None, max_chunk=None, threads=1, max_len=None, stats=None):
+    """The distances of rtk_identity (DESIGN.md section 4 [A19]) over rtk_identity_begin / _chunk / _end: ref_records = the records of the reference, reads = the
+    read sequences, truth = per read (record number, 0-based start, length, reverse strand?). Returns per read the exact unit-cost NW edit distance to its
+    stretch of the reference, reverse-complemented when the strand says so; reference and reads are upper-cased, bytes are equal iff identical. Chunks are laid
+    out as qv_reads lays them out: whole reads, max_chunk characters with their separators (default: what qv_reads takes; tests lower it to get many chunks from
+    little text; a chunk holds one read at the least). threads=2 feeds the chunks from two threads. max_len (default: the longest read or stretch) sizes the
+    device's work areas. The returned sum is checked against the device's. stats (a dict) receives n_chunks, n_pairs and sum_dist."""
+    L = load_library(lib_path)
+    if not hasattr(L, "rtk_identity_begin"):
+        raise RtkError("%s has no rtk_identity entries" % L._name)
+    if len(reads) != len(truth):
+        raise ValueError("one truth entry per read")
+    if max_chunk is None:
+        max_chunk = QV_CHUNK_CHARS
+    recs = [_b(r).upper() for r in ref_records]
+    bs = [_b(s).upper() for s in reads]
+    offs = (C.c_uint64 * (len(recs) + 1))()
+    for r, t in enumerate(recs):
+        offs[r + 1] = offs[r] + len(t)
+    text = b"".join(recs)
+    if max_len is None:
+        max_len = max([len(s) for s in bs] + [int(t[2]) for t in truth] + [1])
+    chunks, i = [], 0  # [i, j) of reads
+    while i < len(bs):
+        j, size = i, 0
+        while j < len(bs) and (j == i or size + len(bs[j]) + 1 <= max_chunk) and j - i < (2 << 20):
+            size += len(bs[j]) + 1; j += 1
+        chunks.append((i, j)); i = j
+    job = C.c_void_p()
+
+    def check(rc):
+        if rc != 0:
+            raise RtkError("rtk error %d: %s" % (rc, L.rtk_last_error().decode()))
+
+    check(L.rtk_identity_begin(device, text, len(text), offs, len(recs), max_len, C.byref(job)))
+    out = [0] * len(bs)
+
+    def run(c):
+        i, j = chunks[c]
+        n = j - i
+        starts, rec, t_start, t_len, rev = (C.c_uint64 * n)(), (C.c_uint32 * n)(), (C.c_uint64 * n)(), (C.c_uint32 * n)(), (C.c_ubyte * n)()
+        at = 0
+        for p in range(i, j):
+            starts[p - i] = at; at += len(bs[p]) + 1
+            rec[p - i], t_start[p - i], t_len[p - i], rev[p - i] = int(truth[p][0]), int(truth[p][1]), int(truth[p][2]), 1 if truth[p][3] else 0
+        chars = b"\n".join(bs[i:j]) + b"\n"
+        d = (C.c_int32 * n)()
+        check(L.rtk_identity_chunk(job, chars, len(chars), starts, n, rec, t_start, t_len, rev, d))
+        out[i:j] = list(d)
+
+    try:
+        if threads <= 1:
+            for c in range(len(chunks)):
+                run(c)
+        else:
+            import threading
+            errors = []
+
+            def feed(t):
+                try:
+                    for c in range(t, len(chunks), threads):
+                        run(c)
+                except Exception as e:  # noqa: BLE001 (handed to the caller below)
+                    errors.append(e)
+
+            th = [threading.Thread(target=feed, args=(t,)) for t in range(threads)]
+            for t in th:
+                t.start()
+            for t in th:
+                t.join()
+            if errors:
+                raise errors[0]
+    except Exception:
+        L.rtk_identity_end(job, None, None)
+        raise
+    n_pairs, sum_dist = C.c_uint64(), C.c_uint64()
+    check(L.rtk_identity_end(job, C.byref(n_pairs), C.byref(sum_dist)))
+    if (len(bs), sum(out)) != (n_pairs.value, sum_dist.value):
+        raise RtkError("rtk_identity: the chunks add up to %d pairs / distance %d, the device counted %d / %d" % (len(bs), sum(out), n_pairs.value, sum_dist.value))
+    if stats is not None:
+        stats["n_chunks"], stats["n_pairs"], stats["sum_dist"] = len(chunks), n_pairs.value, sum_dist.value
+    return out
 
 
 MODE_SHW_BY_COLUMN, MODE_NW_PREFIX, MODE_NW_PREFIX_LAST, MODE_NW_PREFIX_LAST_COLUMN = 3, 4, 5, 6  # test-only modes of myers_batch (include/ratatosk_hip.h)

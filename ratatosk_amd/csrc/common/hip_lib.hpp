@@ -37,6 +37,9 @@ struct HipLib {
     typedef int (*qv_begin_fn)(int, int, const uint64_t*, uint64_t, void**);                                                                 // rtk_qv_begin
     typedef int (*qv_chunk_fn)(void*, const char*, uint64_t, const uint64_t*, uint32_t, uint32_t*, uint32_t*);                               // rtk_qv_chunk
     typedef int (*qv_end_fn)(void*, uint64_t*, uint64_t*);                                                                                   // rtk_qv_end
+    typedef int (*identity_begin_fn)(int, const char*, uint64_t, const uint64_t*, uint32_t, uint32_t, void**);                               // rtk_identity_begin
+    typedef int (*identity_chunk_fn)(void*, const char*, uint64_t, const uint64_t*, uint32_t, const uint32_t*, const uint64_t*, const uint32_t*, const unsigned char*, int32_t*); // rtk_identity_chunk
+    typedef int (*identity_end_fn)(void*, uint64_t*, uint64_t*);                                                                             // rtk_identity_end
 
     std::string path = "libratatosk_hip.so";
     void* handle = nullptr;

@@ -274,6 +274,9 @@ extern "C" int rtk_qv_begin(int, int, const uint64_t*, uint64_t, void**) { retur
 extern "C" int rtk_qv_chunk(void*, const char*, uint64_t, const uint64_t*, uint32_t, uint32_t*, uint32_t*) { return rtk_fail(RTK_ERR_UNSUPPORTED, "rtk_qv_chunk: not part of the simulator build"); }
 extern "C" int rtk_qv_end(void*, uint64_t*, uint64_t*) { return rtk_fail(RTK_ERR_UNSUPPORTED, "rtk_qv_end: not part of the simulator build"); }
 extern "C" uint32_t rtk_qv_span(void) { return 0; } // (no k_qv here)
+extern "C" int rtk_identity_begin(int, const char*, uint64_t, const uint64_t*, uint32_t, uint32_t, void**) { return rtk_fail(RTK_ERR_UNSUPPORTED, "rtk_identity_begin: not part of the simulator build"); }
+extern "C" int rtk_identity_chunk(void*, const char*, uint64_t, const uint64_t*, uint32_t, const uint32_t*, const uint64_t*, const uint32_t*, const unsigned char*, int32_t*) { return rtk_fail(RTK_ERR_UNSUPPORTED, "rtk_identity_chunk: not part of the simulator build"); }
+extern "C" int rtk_identity_end(void*, uint64_t*, uint64_t*) { return rtk_fail(RTK_ERR_UNSUPPORTED, "rtk_identity_end: not part of the simulator build"); }
 #endif
 extern "C" int rtk_device_memory(int device, uint64_t* free_bytes, uint64_t* total_bytes) {
     if (!free_bytes || !total_bytes) return rtk_fail(RTK_ERR_ARG, "rtk_device_memory: null argument");

@@ -85,6 +85,9 @@ inline uint64_t rtk_knob_index_pair_mem(uint64_t dflt) { return std::min(dflt, r
 inline uint32_t rtk_knob_index_pair_passes() { return static_cast<uint32_t>(std::min<uint64_t>(rtk_env_u64("RTK_INDEX_PAIR_PASSES", 0), 0xFFFFFFFFull)); } // u32, 0 = as few as fit: rtk_index_pair_ids pairs in exactly this many passes over equal ranges of the hash space (clamped to 256; tests: the partitioned path on small inputs)
 inline uint64_t rtk_knob_hx_part_keys(uint64_t dflt) { return rtk_env_u64("RTK_HX_PART_KEYS", dflt); }   // u64: keys per partition when the signature table is built
 
+// ---- identity to the truth (rtk_identity.hip): read when a job begins
+inline int rtk_knob_identity_waves() { return std::min(rtk_env_pos_int("RTK_IDENTITY_WAVES", 1024), 16384); } // int <= 16384, 1024: persistent waves of k_identity per chunk in flight (two chunks: twice as many work areas)
+
 // ---- simulator only
 inline int rtk_knob_sim_devices() { return std::max(1, rtk_env_int("RTK_SIM_DEVICES", 1)); } // int, 1: pretend GPUs, so that the multi-GPU host plumbing runs on a CPU (every call)
 
@@ -96,6 +99,7 @@ inline int rtk_knob_sim_devices() { return std::max(1, rtk_env_int("RTK_SIM_DEVI
 //     RTK_INDEX_THREADS, RTK_INDEX_TRACE, RTK_INDEX_CHUNK (--gpu --cover-edges-from: characters of cover text per chunk; --pair-by-name --fast: bytes per range of a plain file)
 //   csrc/tools (rtk_rescue_reads): RTK_INDEX_CHUNK (characters of -u text per batch), RTK_INDEX_THREADS, RTK_INDEX_TRACE
 //   csrc/tools (rtk_qv): RTK_INDEX_CHUNK (characters of -l text per chunk; a longer read is cut into pieces), RTK_INDEX_THREADS, RTK_INDEX_TRACE (--gpu: also the time of k_qv alone)
+//   csrc/tools (rtk_identity): RTK_INDEX_CHUNK (characters of -l text per chunk), RTK_INDEX_THREADS, RTK_INDEX_TRACE (--gpu: also the time of k_identity alone and the tail of its launches)
 //   ratatosk_amd/api.py: RTK_LIB_OVERRIDE (another build of the library), RTK_HOST_TABLES
 
 #endif

@@ -61,6 +61,7 @@ struct Opt {
     bool k1_from_k2 = false; // --k1-from-k2: `correct -s` builds the k2 graph once (rtk_build_index --graph-only) and both indexes from its unitig file (--graph-from)
     bool pair_by_name = false; // --pair-by-name: handed to the index step whose colours come from the short reads (step 1); rtk_build_index --pair-by-name
     bool qv = false; // --qv: `correct -s` ends with rtk_qv --gpu on the -l reads and on its own output (OUT.qv.tsv; DESIGN.md section 4 [A17])
+    std::string truth_ref, truth_tsv; // --truth-ref REF.fa --truth-tsv TRUTH.tsv (both or neither): `correct -s` ends with rtk_identity --gpu on the -l reads and on its own output (OUT.identity.tsv; DESIGN.md section 4 [A19])
     bool cover_edges = false; // --cover-edges (only with --k1-from-k2): the k1 index step of `correct -s` covers its low-coverage edges from the k2 unitig file (rtk_build_index --cover-edges-from)
     bool subsample = false; std::string subsample_seed; // --subsample-colours [--subsample-seed N]: handed to both index steps of `correct -s`
     // -M / -C / -Q as given: `correct -s` hands them to the index step of the second pass (rtk_build_index --colour-min-conf / --colour-min-len / --colour-max-qual)
@@ -91,6 +92,8 @@ static void usage() {
                     "                        (rtk_build_index --colour-min-conf / --colour-min-len / --colour-max-qual). The reference applies -M 0 -C 3000 by default; here neither\n"
                     "                        applies unless given. Next to a pre-built index (-g, -d) they are ignored\n"
                     "      --qv              after the last step: the k-mer QV of the -l reads and of the output of the run against the k1-mers seen twice in the -s reads (rtk_qv --gpu, <out_prefix>.qv.tsv)\n"
+                    "      --truth-ref REF.fa --truth-tsv TRUTH.tsv  (both or neither) after the last step: the identity of the -l reads and of the output of the run to their simulated truth, the stretches\n"
+                    "                        of REF.fa that TRUTH.tsv names (rtk_simulate --lr-truth): unit-cost global edit distance per read (rtk_identity --gpu, <out_prefix>.identity.tsv)\n"
                     "  -u, --in-unmapped-short  unmapped short reads (may be repeated; or a text file of paths): those with enough k1-mers that the long reads hold and the -s reads\n"
                     "                        do not are rescued first (rtk_rescue_reads --gpu, <out_prefix>_extra_sr.fasta, removed at the end) and join the short reads of the index builds\n\n"
                     "       Ratatosk correct -1 -g <graph.fasta.gz> -d <unitig_data.rtsk> -l <long_reads> -o <out_prefix> [options]\n"
@@ -167,6 +170,8 @@ static int correct_from_short_reads(const Opt& opt, const char* argv0) {
     if (opt.in_long.empty() || opt.out.empty()) { fprintf(stderr, "Ratatosk::correct: -s, -l and -o are required\n"); return 1; }
     if (opt.cover_edges && !opt.k1_from_k2) { fprintf(stderr, "Ratatosk::correct: --cover-edges needs --k1-from-k2: the edges of the k1 graph are covered from the unitigs of the k2 graph, which is only there at that step when it is built first\n"); return 1; }
     if (opt.cover_edges && opt.pass2) { fprintf(stderr, "Ratatosk::correct: --cover-edges belongs to the k1 index step (both passes, or -1): -2 alone builds no k1 index\n"); return 1; }
+    if (opt.truth_ref.empty() != opt.truth_tsv.empty()) { fprintf(stderr, "Ratatosk::correct: --truth-ref and --truth-tsv go together: the reference and the file that says where in it each read comes from (rtk_simulate --lr-truth)\n"); return 1; }
+    if (!opt.truth_ref.empty() && (access(opt.truth_ref.c_str(), R_OK) != 0 || access(opt.truth_tsv.c_str(), R_OK) != 0)) { fprintf(stderr, "Ratatosk::correct: cannot open %s\n", access(opt.truth_ref.c_str(), R_OK) != 0 ? opt.truth_ref.c_str() : opt.truth_tsv.c_str()); return 1; }
     if (opt.pass2 && opt.in_long_raw.empty()) { fprintf(stderr, "Ratatosk::correct: -2 needs the uncorrected long reads (-L) next to the pass-1 reads (-l)\n"); return 1; }
     if (opt.k1 < 3 || opt.k1 > 31 || !(opt.k1 & 1) || opt.k2 < 3 || opt.k2 > 63 || !(opt.k2 & 1)) { fprintf(stderr, "Ratatosk::correct: k1 must be odd and <= 31, k2 odd and <= 63\n"); return 1; }
     if (!opt.min_conf_colour2.empty()) { // src/Ratatosk.cpp:378-388
@@ -276,6 +281,15 @@ static int correct_from_short_reads(const Opt& opt, const char* argv0) {
         a.push_back("-o"); a.push_back(opt.out);
         if (run_step("step 5 (k-mer QV of the reads before and after, rtk_qv)", a, v)) return 1;
     }
+    if (!opt.truth_ref.empty()) { // the reads before and after, against the stretches they were simulated from: a fresh child as well; the corrected output stays whatever becomes of it
+        const std::string result = opt.pass1 ? mid : opt.out + (opt.gzip ? ".fastq.gz" : ".fastq");
+        std::vector<std::string> a; a.push_back(dir + "/rtk_identity"); a.push_back("--gpu"); a.push_back("-r"); a.push_back(opt.truth_ref); a.push_back("-t"); a.push_back(opt.truth_tsv);
+        for (size_t i = 0; i < opt.in_long.size(); ++i) { a.push_back("-l"); a.push_back(opt.in_long[i]); }
+        a.push_back("-l"); a.push_back(result);
+        if (v) a.push_back("-v");
+        a.push_back("-o"); a.push_back(opt.out);
+        if (run_step("step 6 (identity of the reads before and after to their truth, rtk_identity)", a, v)) return 1;
+    }
     if (v) fprintf(stderr, "Ratatosk::Ratatosk(): Done. [%.1f s]\n", since());
     return 0;
 }
@@ -297,7 +311,7 @@ int main(int argc, char** argv) {
         {"correction-rounds", required_argument, 0, 'r'}, {"no-snp-correction", no_argument, 0, 'F'}, {"force-io-order", no_argument, 0, 'O'}, {"no-graph-index", no_argument, 0, 'I'},
         {"in-unmapped-short", required_argument, 0, 'u'}, {"in-accurate-long", required_argument, 0, 'a'}, {"in-short-phase", required_argument, 0, 'p'}, {"in-long-phase", required_argument, 0, 'P'}, {"force-correct-snp", no_argument, 0, 'f'},
         {"sampling", required_argument, 0, 'S'}, {"min-conf-color2", required_argument, 0, 'M'}, {"min-len-color2", required_argument, 0, 'C'},
-        {"batch-bases", required_argument, 0, 'B'}, {"strip-annotations", no_argument, 0, 1001}, {"gpus", required_argument, 0, 1002}, {"workers-per-gpu", required_argument, 0, 1003}, {"parse-only", no_argument, 0, 1004}, {"allow-tinybitmap", no_argument, 0, 1005}, {"subsample-colours", no_argument, 0, 1006}, {"subsample-seed", required_argument, 0, 1007}, {"merge-duplicates", no_argument, 0, 1008}, {"k1-from-k2", no_argument, 0, 1009}, {"cover-edges", no_argument, 0, 1010}, {"qv", no_argument, 0, 1011}, {"pair-by-name", no_argument, 0, 1012}, {"verbose", no_argument, 0, 'v'}, {0, 0, 0, 0}};
+        {"batch-bases", required_argument, 0, 'B'}, {"strip-annotations", no_argument, 0, 1001}, {"gpus", required_argument, 0, 1002}, {"workers-per-gpu", required_argument, 0, 1003}, {"parse-only", no_argument, 0, 1004}, {"allow-tinybitmap", no_argument, 0, 1005}, {"subsample-colours", no_argument, 0, 1006}, {"subsample-seed", required_argument, 0, 1007}, {"merge-duplicates", no_argument, 0, 1008}, {"k1-from-k2", no_argument, 0, 1009}, {"cover-edges", no_argument, 0, 1010}, {"qv", no_argument, 0, 1011}, {"pair-by-name", no_argument, 0, 1012}, {"truth-ref", required_argument, 0, 1013}, {"truth-tsv", required_argument, 0, 1014}, {"verbose", no_argument, 0, 'v'}, {0, 0, 0, 0}};
     int c, idx = 0;
     while ((c = getopt_long(argc - 1, argv + 1, "s:l:o:c:g:d:i:k:w:Q:m:B:L:K:W:t:r:u:a:p:P:S:M:C:GFOIf12v", lo, &idx)) != -1) {
         { // what `correct -s` hands on to its correction steps: the option as given (long options by their long name)
@@ -351,6 +365,8 @@ int main(int argc, char** argv) {
             case 1010: opt.cover_edges = true; break; // (with -g / -d, or without --k1-from-k2: refused below)
             case 1011: opt.qv = true; break; // (with -g / -d: refused below)
             case 1012: opt.pair_by_name = true; break; // (with -g / -d: refused below)
+            case 1013: opt.truth_ref = optarg; break; // (with -g / -d: refused below)
+            case 1014: opt.truth_tsv = optarg; break;
             case 's': opt.in_short.push_back(optarg); break; // (with -g / -d: ignored, said below)
             default: usage(); return 0; // the reference returns 0 on option errors too (src/Ratatosk.cpp:1018)
         }
@@ -362,6 +378,10 @@ int main(int argc, char** argv) {
     if (!opt.in_short.empty() && opt.graph.empty() && opt.udata.empty()) return correct_from_short_reads(opt, argv[0]);
     if (opt.qv) { // the set is counted from the -s reads, which a run on a pre-built index does not have
         fprintf(stderr, "Ratatosk::correct: --qv belongs to the run that builds its indexes from the short reads (correct -s SHORT -l LONG -o OUT --qv): next to a pre-built index (-g, -d) use rtk_qv -g GRAPH.fasta.gz -l READS -l OUT.fastq -k K1 -o OUT\n");
+        return 1;
+    }
+    if (!opt.truth_ref.empty() || !opt.truth_tsv.empty()) { // the step belongs to the one-command run, like --qv
+        fprintf(stderr, "Ratatosk::correct: --truth-ref / --truth-tsv belong to the run that builds its indexes from the short reads (correct -s SHORT -l LONG -o OUT --truth-ref REF.fa --truth-tsv TRUTH.tsv): next to a pre-built index (-g, -d) use rtk_identity --gpu -r REF.fa -t TRUTH.tsv -l READS -l OUT.fastq -o OUT\n");
         return 1;
     }
     if (!opt.in_unmapped.empty() && opt.graph.empty() && opt.udata.empty()) { fprintf(stderr, "Ratatosk::correct: -u needs the mapped short reads (-s) it is compared with\n"); return 1; }
